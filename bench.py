@@ -2,6 +2,7 @@
 """bench.py — spectrogram-windows/sec of the MixedNet train step on N MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs bench_outputs   # + the last timed step's arrays as .npy
     python bench.py --gpus 8                      # launches its own 8 ranks (torch.distributed.run, 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -267,6 +268,8 @@ def parse_args():
                     help="N > 1: issue the exchange through the mww_set_allreduce_hook callback into torch.distributed instead of "
                          "RCCL called from the library (mww_allreduce_init, the default)")
     ap.add_argument("--no-prefetch", action="store_true", help="draw every batch on the launching thread (default: a worker thread draws four batches ahead)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32), see dump_outputs()")
     return ap.parse_args()
 
 
@@ -278,6 +281,27 @@ def per_gpu_batch(batch, global_batch, world):
             raise SystemExit("--global-batch %d is not divisible by the %d GPUs of the job" % (global_batch, world))
         return global_batch // world
     return batch
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, eng, probs, logits, loss):
+    """--dump-outputs: what the last timed step hands its caller - per-window probabilities and logits, the batch loss, and the
+    state the step leaves behind (parameters after Adam, BN moving statistics, the step's gradient, Adam's two moments) - as
+    DIR/<name>.npy in float32.  The inputs are seeded (stores, model init, sampler streams), so two builds run with the same
+    arguments can be compared array for array.  -> {name: shape} for the JSON line."""
+    m, v, _ = eng.get_opt_state()
+    arrays = {"probabilities": probs, "logits": logits, "loss": np.array([loss]), "params": eng.get_params(),
+              "bn_state": eng.get_bn_state(), "grads": eng.get_grads(), "adam_m": m, "adam_v": v}
+    arrays = {k: np.ascontiguousarray(a, np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def _reference_loader(batch, n_samples, policy):
@@ -626,7 +650,9 @@ def main():
             tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
-        _, _, last_loss = eng.read_outputs(B)
+        probs, logits, last_loss = eng.read_outputs(B)
+        # (before anything below moves the engine on: the next steps would overwrite outputs, weights and optimizer state)
+        dumped = dump_outputs(args.dump_outputs, eng, probs, logits, last_loss) if args.dump_outputs and rank == 0 else None
 
         # ---- the launching thread's own cost per step, free of back-pressure: the mailbox ring holds eight steps, so in any run
         # longer than that the enqueue loop above is throttled to the GPU's pace (mail_begin waits for the slot's previous step)
@@ -808,6 +834,8 @@ def main():
         out["batch_sweep"] = batch_sweep
     if validation is not None:
         out["validation"] = validation
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(B, model=args.model)
     line = json.dumps(out) + "\n"

@@ -1,12 +1,17 @@
-"""oracle/data_oracle.py pinned against (a) golden vectors produced by the reference's own
-data.py and (b) the reference module itself when /root/reference is present."""
+"""oracle/data_oracle.py pinned against golden vectors produced by the reference's own data.py: (a) its batches
+(data_golden.npz) and (b) digests of its batches on the benchmark store and random cases (live_data_golden.json)."""
+import json
 import os
 import random
+import sys
 
 import numpy as np
 import pytest
 
 from oracle import data_oracle as do
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import make_golden_live_data as mgl  # noqa: E402
 
 T = 194
 POLICY = dict(freq_mix_prob=0.0, time_mask_max_size=5, time_mask_count=2, freq_mask_max_size=5, freq_mask_count=2)
@@ -103,69 +108,35 @@ def test_fixed_right_cutoff_too_large_raises():
         do.window_offset(T + 3, T, "fixed_right_cutoff", 5)
 
 
-@pytest.mark.reference
-def test_live_reference_agrees_on_benchmark_store():
-    """Same seeds, same §8(d) synthetic store -> identical batches from the reference module."""
-    from oracle import ref_data_shim as shim
+@pytest.fixture(scope="module")
+def live(golden_dir):
+    with open(os.path.join(golden_dir, "live_data_golden.json")) as fh:
+        return json.load(fh)
 
-    if not shim.available():
-        pytest.skip("reference tree not present")
-    ref = shim.load_reference_data_module()
-    import tempfile
-    from microwakeword_amd.ragged import write_ragged_store
 
-    pos, neg = do.synthetic_stores(64, 1234)
-    with tempfile.TemporaryDirectory() as tmp:
-        write_ragged_store(os.path.join(tmp, "pos", "training", "a_mmap"), pos)
-        write_ragged_store(os.path.join(tmp, "neg", "training", "a_mmap"), neg)
-        config = {"stride": 1, "window_step_ms": 10, "features": [
-            dict(type="mmap", features_dir=os.path.join(tmp, "pos"), truth=True, sampling_weight=2.0, penalty_weight=1.0, truncation_strategy="truncate_start"),
-            dict(type="mmap", features_dir=os.path.join(tmp, "neg"), truth=False, sampling_weight=10.0, penalty_weight=1.0, truncation_strategy="random")]}
-        random.seed(0); np.random.seed(0)
-        fh = ref.FeatureHandler(config)
-        rx, ry, rw = fh.get_data("training", 64, T, "default", POLICY)
+def test_live_reference_agrees_on_benchmark_store(live):
+    """Same seeds, same §8(d) synthetic store -> the batch the reference module returned (tests/golden/live_data_golden.json,
+    written by make_golden_live_data.py from the reference's own data.py), bit for bit."""
+    pos, neg = mgl.benchmark_stores()
     random.seed(0); np.random.seed(0)
     provs = [do.index_provider({"training": [pos]}, True, 2.0, 1.0, "truncate_start", 1, 0.01),
              do.index_provider({"training": [neg]}, False, 10.0, 1.0, "random", 1, 0.01)]
     x, y, w, _, _ = do.get_data(provs, "training", 64, T, "default", POLICY)
-    np.testing.assert_array_equal(x, rx)
-    np.testing.assert_array_equal(y, ry)
-    np.testing.assert_array_equal(w, rw)
+    assert [mgl.digest(a, want["dtype"]) for a, want in zip((x, y, w), live["benchmark_store"])] == live["benchmark_store"]
 
 
-@pytest.mark.reference
-def test_live_reference_fuzz():
+def test_live_reference_fuzz(live):
     """Random feature sets, policies and truncation strategies (the cases of engine_checks.random_data_case, which the
-    HIP path is tested on): the oracle and the reference's own data.py produce identical batches and leave both RNG
-    streams in the same place.  Container only (needs /root/reference)."""
-    from oracle import ref_data_shim as shim
-
-    if not shim.available():
-        pytest.skip("reference tree not present")
-    import tempfile
-
+    HIP path is tested on): the oracle produces the batches the reference's own data.py produced (digests in
+    tests/golden/live_data_golden.json) and leaves both RNG streams where it left them."""
     import engine_checks as ec
-    from microwakeword_amd.ragged import write_ragged_store
-    ref = shim.load_reference_data_module()
-    for case in range(40):
+    assert len(live["fuzz"]) == mgl.FUZZ_CASES
+    for case, gold in enumerate(live["fuzz"]):
         Tc, provs, policy, B, strategy = ec.random_data_case(case)
-        with tempfile.TemporaryDirectory() as tmp:
-            feats = []
-            for i, p in enumerate(provs):
-                write_ragged_store(os.path.join(tmp, "p%d" % i, "training", "a_mmap"), p["store"])
-                feats.append(dict(type="mmap", features_dir=os.path.join(tmp, "p%d" % i), truth=p["truth"], sampling_weight=p["sampling_weight"],
-                                  penalty_weight=p["penalty_weight"], truncation_strategy=p["truncation_strategy"],
-                                  fixed_right_cutoffs=p["fixed_right_cutoffs"]))
-            random.seed(case); np.random.seed(case)
-            fh = ref.FeatureHandler({"stride": 1, "window_step_ms": 10, "features": feats})
-            want = [fh.get_data("training", B, Tc, strategy, policy) for _ in range(2)]
-            tail = (random.random(), np.random.random())
         random.seed(case); np.random.seed(case)
         op = [do.index_provider({"training": [p["store"]]}, p["truth"], p["sampling_weight"], p["penalty_weight"],
                                 p["truncation_strategy"], 1, 0.01, p["fixed_right_cutoffs"]) for p in provs]
-        for rx, ry, rw in want:
+        for want in gold["batches"]:
             x, y, w, _, _ = do.get_data(op, "training", B, Tc, strategy, policy)
-            np.testing.assert_array_equal(x, rx, err_msg="case %d" % case)
-            np.testing.assert_array_equal(y, ry)
-            np.testing.assert_array_equal(w, rw)
-        assert tail == (random.random(), np.random.random()), case
+            assert [mgl.digest(a, d["dtype"]) for a, d in zip((x, y, w), want)] == want, "case %d" % case
+        assert [random.random(), float(np.random.random())] == gold["tail"], case

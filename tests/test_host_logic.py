@@ -417,6 +417,37 @@ def test_bench_traffic_figure_is_tied_to_the_library_it_was_measured_on(tmp_path
     assert bench.pmc_traffic("bwd_block4", "mixednet", path=str(stamped), library=str(rebuilt))[0] is None
 
 
+def test_bench_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """bench.py --dump-outputs: the outputs and state of the last timed step, one float32 .npy per array, bounded in size."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class _Eng:
+        def __init__(self, P):
+            self.P = P
+        def get_params(self): return np.arange(self.P, dtype=np.float32)
+        def get_bn_state(self): return np.full(6, 0.5, np.float32)
+        def get_grads(self): return -np.arange(self.P, dtype=np.float32)
+        def get_opt_state(self): return np.ones(self.P, np.float32), np.full(self.P, 2.0, np.float32), 7
+
+    probs, logits = np.linspace(0, 1, 8, dtype=np.float32), np.linspace(-2, 2, 8, dtype=np.float32)
+    shapes = bench.dump_outputs(str(tmp_path / "d"), _Eng(5), probs, logits, 0.25)
+    assert shapes == {"probabilities": [8], "logits": [8], "loss": [1], "params": [5], "bn_state": [6], "grads": [5], "adam_m": [5], "adam_v": [5]}
+    for name in shapes:
+        a = np.load(tmp_path / "d" / (name + ".npy"))
+        assert a.dtype == np.float32 and list(a.shape) == shapes[name]
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "logits.npy"), logits)
+    assert np.load(tmp_path / "d" / "loss.npy")[0] == 0.25
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "adam_v.npy"), np.full(5, 2.0, np.float32))
+    bench.DUMP_LIMIT_BYTES = 4 * (8 + 8 + 1 + 6 + 4 * 4) - 4    # one float short of what _Eng(4) hands over
+    with pytest.raises(SystemExit, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), _Eng(4), probs, logits, 0.25)
+    assert not (tmp_path / "big").exists()
+
+
 def test_train_model_claims_the_directory_like_the_reference(tmp_path, monkeypatch):
     """model_train_eval.py:99-128: a fresh train_dir is created, an existing one is an error unless restore_checkpoint."""
     calls = []
