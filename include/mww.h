@@ -387,6 +387,58 @@ void mww_prefetch_destroy(mww_prefetcher* p);
  * out_weights ([B], may be NULL) receive copies of what went to the device. */
 int mww_assemble_prefetched(mww_ctx* ctx, mww_prefetcher* p, float* out_labels, float* out_weights);
 
+/* ---- streaming inference and detection metrics: replaces the evaluation that follows training in the reference
+ * (model_train_eval.py:131-272 evaluate_model with --test_tflite_streaming / --test_tflite_nonstreaming;
+ * test.py:293-403 tflite_streaming_model_roc; inference.py:82-125 Model.predict_spectrogram) without TensorFlow / TFLite.
+ * A stream object borrows an existing context's device, HIP stream and uploaded feature stores (the context must outlive
+ * it).  Topology: MixedNet with a first convolution, any widths / kernels / repeat_in_block, no residual connections,
+ * spatial attention or pooled head.  Weights arrive in Keras get_weights() order (BN moving statistics included), so the
+ * same call serves the specialised-kernel and the generic-graph MixedNet contexts; BN is folded into the 1x1 weights.
+ *   MWW_STREAM_MODE_STREAM: Modes.STREAM_INTERNAL_STATE_INFERENCE - every Stream layer keeps the last R frames of its
+ *     input (zeros after create / reset; layers/stream.py:580-594), each `stride` frames fed yield one probability, the
+ *     rings carry over from track to track and from call to call; the last L mod stride frames of a track are not fed.
+ *   MWW_STREAM_MODE_NON_STREAM: the non-streaming model on the windows of `frames` rows ending at T, T + stride, ... <= L
+ *     of every track, each scored on its own (a track shorter than T gives nothing). */
+#define MWW_STREAM_MODE_STREAM 0
+#define MWW_STREAM_MODE_NON_STREAM 1
+#define MWW_STREAM_MAX_KERNELS 8
+#define MWW_STREAM_MAX_REPEAT 8
+typedef struct {
+  int32_t conv1_filters, conv1_kernel, stride;            /* --first_conv_filters, --first_conv_kernel_size, --stride */
+  int32_t n_blocks;
+  int32_t repeat[MWW_MAX_BLOCKS];                         /* --repeat_in_block */
+  int32_t n_kernels[MWW_MAX_BLOCKS];                      /* entries of each --mixconv_kernel_sizes list (ascending) */
+  int32_t kernels[MWW_MAX_BLOCKS][MWW_STREAM_MAX_KERNELS];
+  int32_t pointwise_filters[MWW_MAX_BLOCKS];              /* --pointwise_filters */
+  int32_t t_final;                                        /* T_f: frames of the final map the Dense reads */
+  int32_t frames;                                         /* T: window length of the non-streaming model (non_stream mode) */
+  int32_t mode;                                           /* MWW_STREAM_MODE_* */
+} mww_stream_desc;
+typedef struct mww_stream mww_stream;
+/* MWW_ERR_UNSUPPORTED (+ message) for a malformed description or a topology outside the list above */
+int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* desc, mww_stream** out);
+void mww_stream_destroy(mww_stream* s);
+int64_t mww_stream_num_weights(const mww_stream* s);   /* floats of the Keras-order weight vector */
+int64_t mww_stream_num_state(const mww_stream* s);     /* floats of the rings */
+int mww_stream_set_weights(mww_stream* s, const float* keras_order, int64_t n);
+int mww_stream_reset(mww_stream* s);                   /* rings back to zeros */
+int mww_stream_get_state(mww_stream* s, float* host, int64_t n);   /* conv1 ring [R1][40], per MixConv [K-1][C], head [T_f-1][C] */
+/* Runs the tracks (each a window of a resident store: pad_rows zero frames, then copy_rows store rows) in order as one call.
+ * out_offsets [n_tracks + 1] receives the first output of every track; returns the number of outputs (or an error < 0).
+ * The probabilities stay on the device (mww_stream_read, mww_stream_metrics). */
+int64_t mww_stream_run(mww_stream* s, const mww_window* tracks, int64_t n_tracks, int64_t* out_offsets);
+/* the same for one track of n_frames float32 rows in host memory */
+int64_t mww_stream_run_host(mww_stream* s, const float* frames, int64_t n_frames);
+int mww_stream_read(mww_stream* s, float* probs, float* logits, int64_t n);   /* either pointer may be NULL */
+int mww_stream_set_probs(mww_stream* s, const float* probs, int64_t n);       /* host probabilities for mww_stream_metrics */
+/* Detection metrics on the probabilities held (test.py:94-137,329-376): per track the moving average over `window`
+ * probabilities (float32, summed in order), kind 0 (ambient): cooldown false-accept counts at each float64 cutoff (cooldown
+ * starts at `cooldown`, is decremented with a floor at 0 before each value, a value > cutoff counts when it is 0 and resets
+ * it) summed over the tracks into counts[n_cutoffs]; kind 1 (positive): score = max of the moving average of the
+ * probabilities after the first `skip`.  ma_len[t]: moving-average values of track t (score is -inf when 0). */
+int mww_stream_metrics(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip,
+                       int cooldown, const double* cutoffs, int n_cutoffs, uint64_t* counts, int64_t* ma_len, float* score);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3158,3 +3158,17 @@ int mww_profile_read(mww_ctx* c, char* names, int names_cap, float* ms, int cap)
 }
 
 }  // extern "C"
+
+// ---- borrowed by tu_stream.hip (streaming evaluation, mww_stream_*): a stream object runs on its context's device and
+// HIP stream, reads the context's resident feature stores and reports errors through the same thread-local message.
+namespace mww {
+int ctx_borrow(mww_ctx* c, int* device, hipStream_t* stream, void** stores, int* dtypes, int64_t* elems, int* n_cu) {
+  if (!c) return fail(MWW_ERR_INVALID, "no context");
+  *device = c->device;
+  *stream = c->stream;
+  *n_cu = c->n_cu;
+  for (int i = 0; i < MWW_MAX_STORES; ++i) { stores[i] = c->store[i]; dtypes[i] = c->store_dtype[i]; elems[i] = c->store_elems[i]; }
+  return MWW_OK;
+}
+int set_error(int code, const char* msg) { return fail(code, msg); }
+}  // namespace mww

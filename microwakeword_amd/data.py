@@ -497,10 +497,53 @@ class FeatureHandler:
             self.engine.evaluate_windows(win, labels, bs)   # one native call: the batches are walked inside the library
         return n, labels, model.evaluation_results()
 
+    def track_windows(self, mode: str, features_length: int, only_label: Optional[float] = None):
+        """The tracks of ``get_data(mode, ..., truncation_strategy="none")`` as window descriptors of the resident stores
+        (what ``streaming.StreamingModel.predict_tracks`` runs): provider order, then ``feature_sets[mode]`` order, each
+        sample once per ``fixed_right_cutoffs`` entry; a sample of at most ``features_length`` frames is left-padded to that
+        length (fixed_length_spectrogram, data.py:97-118), a longer one is taken whole.  ``only_label``: keep the tracks of
+        that label.  Returns ``(windows, labels)``; draws nothing from any RNG."""
+        self._need_engine()
+        win, labels = [], []
+        for p in self.feature_providers:
+            if only_label is not None and p.label != float(only_label):
+                continue
+            for fi, sub in p.feature_sets[mode]:
+                length, base = p.sample_len[fi][sub], p.sample_start[fi][sub]
+                if base < 0:
+                    raise ValueError("sample (%d, %d) of %r is not resident on this rank" % (fi, sub, mode))
+                sid = p.store_id[p.feature_dtype[fi]]
+                for _ in p.fixed_right_cutoffs:   # data.py:312-321 (the cutoff does not matter for "none")
+                    win.append((sid, max(0, int(features_length) - length), length, 0, base))
+                    labels.append(p.label)
+        return np.array(win, native.WINDOW_DTYPE).reshape(-1), np.array(labels, np.float64)
+
+    def _get_data_none(self, mode: str, features_length: int):
+        """data.py:570-589 with truncation_strategy "none" (a non-training mode): a list of float32 [L_i, 40] arrays, u16
+        stores scaled by 0.0390625, samples of at most ``features_length`` frames left-padded with zeros to that length;
+        labels and weights as arrays; no shuffle, no RNG draw."""
+        data, labels, weights = [], [], []
+        for p in self.feature_providers:
+            for fi, sub in p.feature_sets[mode]:
+                spec = np.asarray(p.loaded_features[fi][sub])
+                if np.issubdtype(spec.dtype, np.uint16):
+                    spec = spec.astype(np.float32) * np.float32(0.0390625)
+                for _ in p.fixed_right_cutoffs:
+                    x = spec
+                    if x.shape[0] <= features_length:
+                        x = np.pad(x, ((features_length - x.shape[0], 0), (0, 0)), constant_values=(0, 0))
+                    data.append(x)
+                    labels.append(p.label)
+                    weights.append(p.penalty_weight)
+        return data, np.array(labels), np.array(weights)
+
     def get_data(self, mode: str, batch_size: int, features_length: int, truncation_strategy: str = "default",
                  augmentation_policy: dict = DEFAULT_POLICY):
         """Same contract as the reference (data.py:497-597): returns host arrays
-        ``(x float32 [N,T,40], labels float64 [N], weights float64 [N])``."""
+        ``(x float32 [N,T,40], labels float64 [N], weights float64 [N])``; with ``truncation_strategy="none"`` (a
+        non-training mode) x is a list of float32 [L_i, 40] arrays (data.py:570-589)."""
+        if truncation_strategy == "none" and mode != "training":
+            return self._get_data_none(mode, int(features_length))
         self._need_engine()
         eng = self.engine
         if mode == "training":
@@ -512,9 +555,6 @@ class FeatureHandler:
                 chunks.append(eng.get_batch(e - s))
             x = np.concatenate(chunks) if len(chunks) > 1 else chunks[0]
             return x, b["labels"], b["weights"]
-        if truncation_strategy == "none":
-            raise NotImplementedError("variable-length ('none') evaluation batches are produced by the reference "
-                                      "loader only for streaming TFLite tests, outside the MI355X path")
         win, labels, weights = self._eval_windows(mode, features_length, truncation_strategy)
         n = win.shape[0]
         indices = np.arange(n)

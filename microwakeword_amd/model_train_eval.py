@@ -5,8 +5,10 @@ Mirrors microwakeword/model_train_eval.py:
   * ``load_config(flags, model_module)``     :45-96   (YAML keys + derived ``summaries_dir, stride,
     spectrogram_length_final_layer, spectrogram_length, flags, training_input_shape``)
   * ``train_model(config, model, data_processor, restore_checkpoint)``   :99-128
-  * argparse surface                          :277-389 (the ``--test_*`` export flags are accepted; TFLite
-    export / streaming evaluation stay with the reference and raise here if requested)
+  * ``evaluate_model``                         :131-272 (``--test_tf_nonstreaming``, ``--test_tflite_nonstreaming``,
+    ``--test_tflite_streaming`` run natively through streaming.py, after ``--train 1`` or on an existing ``train_dir``; the
+    int8 ``*_quantized`` flags raise)
+  * argparse surface                          :277-389
 
 Data-parallel over the GPUs of one node (no reference equivalent): launched as
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 -m
@@ -162,12 +164,51 @@ def main(argv=None):
                 dist.destroy_process_group()
 
 
+def evaluate_model(flags, model_module, config, device=0):
+    """model_train_eval.py:131-272 ``evaluate_model`` on the MI355X: a fresh model loads ``<train_dir>/<use_weights>.weights.h5``
+    (its ``.npz`` twin) and is evaluated on the test sets - ``--test_tf_nonstreaming``: ``non_stream/testing_set_metrics.txt``;
+    ``--test_tflite_nonstreaming``: ``tflite_non_stream/tflite_streaming_roc.txt``; ``--test_tflite_streaming``:
+    ``tflite_stream_state_internal/tflite_streaming_roc.txt`` (streaming.py).  Nothing is exported: the streaming /
+    non-streaming forms run natively from the same weights."""
+    from . import streaming
+    model = model_module.model(flags, config["training_input_shape"], config["batch_size"], device=device)
+    model.load_weights(os.path.join(config["train_dir"], flags.use_weights + ".weights.h5"))
+    data_processor = FeatureHandler(config, engine=model.engine)
+    out = {}
+    if flags.test_tf_nonstreaming:
+        logging.info("Testing nonstreaming model")
+        out["non_stream"] = streaming.model_accuracy(config, "non_stream", model, data_processor, data_set="testing",
+                                                     accuracy_name="testing_set_metrics.txt")
+    for flag, folder, mode in ((flags.test_tflite_nonstreaming, "tflite_non_stream", "non_stream"),
+                               (flags.test_tflite_streaming, "tflite_stream_state_internal", "stream")):
+        if flag:
+            logging.info("Testing the %s model false accept per hour and false rejection rates at various cutoffs", mode)
+            sm = streaming.StreamingModel(model, config["stride"], mode)
+            out[folder] = streaming.streaming_model_roc(config, folder, sm, data_processor, data_set="testing",
+                                                        ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt")
+    return out
+
+
+def _evaluate(flags, model_module, config, device, world):
+    """rank 0 evaluates, the other ranks of a data-parallel job wait at a barrier"""
+    if not any((flags.test_tf_nonstreaming, flags.test_tflite_nonstreaming, flags.test_tflite_streaming)):
+        return None
+    from .train import process_group
+    rank, world = process_group()
+    out = evaluate_model(flags, model_module, config, device) if rank == 0 else None
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+    return out
+
+
 def _run(flags, model_module, rank, local_rank, world):
-    if any((flags.test_tf_nonstreaming, flags.test_tflite_nonstreaming, flags.test_tflite_nonstreaming_quantized,
-            flags.test_tflite_streaming, flags.test_tflite_streaming_quantized)):
-        raise NotImplementedError("model export / TFLite evaluation stays with the reference (microwakeword.utils / .test); "
-                                  "train here, then load the saved weights there (INTEGRATION.md)")
+    if flags.test_tflite_nonstreaming_quantized or flags.test_tflite_streaming_quantized:
+        raise NotImplementedError("the int8 *_quantized evaluations need the TFLite converter's calibration (reference "
+                                  "microwakeword.utils); --test_tf_nonstreaming, --test_tflite_nonstreaming and "
+                                  "--test_tflite_streaming run here")
     config = load_config(flags, model_module)
+    device = flags.device if local_rank is None else local_rank
     if flags.train:
         device = flags.device if local_rank is None else local_rank
         if world > 1 and config["batch_size"] % world:
@@ -180,9 +221,12 @@ def _run(flags, model_module, rank, local_rank, world):
         data_processor = FeatureHandler(config, engine=model.engine, shard=(rank, world) if world > 1 else None)
         if rank == 0:
             model.summary(print_fn=logging.getLogger("microwakeword_amd").info)
-        return train_model(config, model, data_processor, flags.restore_checkpoint)
+        result = train_model(config, model, data_processor, flags.restore_checkpoint)
+        _evaluate(flags, model_module, config, device, world)
+        return result
     if not os.path.isdir(config["train_dir"]):
         raise ValueError('model is not trained set "--train 1" and retrain it')
+    return _evaluate(flags, model_module, config, device, world)
 
 
 if __name__ == "__main__":

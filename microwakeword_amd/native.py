@@ -78,6 +78,18 @@ class SamplerDesc(C.Structure):
                 ("cutoff_offsets", C.POINTER(C.c_int32)), ("cutoffs", C.POINTER(C.c_int32))]
 
 
+STREAM_MAX_KERNELS = 8
+STREAM_MAX_REPEAT = 8
+STREAM_MODES = {"stream": 0, "non_stream": 1}
+
+
+class StreamDesc(C.Structure):
+    _fields_ = [("conv1_filters", C.c_int32), ("conv1_kernel", C.c_int32), ("stride", C.c_int32), ("n_blocks", C.c_int32),
+                ("repeat", C.c_int32 * MWW_MAX_BLOCKS), ("n_kernels", C.c_int32 * MWW_MAX_BLOCKS),
+                ("kernels", C.c_int32 * STREAM_MAX_KERNELS * MWW_MAX_BLOCKS), ("pointwise_filters", C.c_int32 * MWW_MAX_BLOCKS),
+                ("t_final", C.c_int32), ("frames", C.c_int32), ("mode", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)   # mww_allreduce_fn
 EXCHANGE_IN_ORDER, EXCHANGE_DEFERRED, EXCHANGE_FLUSH = 0, 1, 2
 
@@ -98,6 +110,9 @@ EXPORTS = [
     "mww_prefetch_create", "mww_prefetch_create_weighted", "mww_prefetch_acquire", "mww_prefetch_release", "mww_prefetch_rng_state", "mww_prefetch_shape",
     "mww_prefetch_destroy", "mww_assemble_prefetched",
     "mww_allreduce_unique_id", "mww_allreduce_init", "mww_allreduce_destroy", "mww_evaluate_windows",
+    "mww_stream_create", "mww_stream_destroy", "mww_stream_num_weights", "mww_stream_num_state", "mww_stream_set_weights",
+    "mww_stream_reset", "mww_stream_get_state", "mww_stream_run", "mww_stream_run_host", "mww_stream_read", "mww_stream_set_probs",
+    "mww_stream_metrics",
 ]
 
 
@@ -186,6 +201,22 @@ class NativeLib:
         L.mww_allreduce_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.mww_allreduce_destroy.argtypes = [C.c_void_p]
         L.mww_evaluate_windows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int]
+        L.mww_stream_create.argtypes = [C.c_void_p, C.POINTER(StreamDesc), C.POINTER(C.c_void_p)]
+        L.mww_stream_destroy.argtypes = [C.c_void_p]
+        L.mww_stream_destroy.restype = None
+        for f in (L.mww_stream_num_weights, L.mww_stream_num_state):
+            f.argtypes = [C.c_void_p]
+            f.restype = C.c_int64
+        for f in (L.mww_stream_set_weights, L.mww_stream_get_state, L.mww_stream_set_probs):
+            f.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64]
+        L.mww_stream_reset.argtypes = [C.c_void_p]
+        L.mww_stream_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.mww_stream_run.restype = C.c_int64
+        L.mww_stream_run_host.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64]
+        L.mww_stream_run_host.restype = C.c_int64
+        L.mww_stream_read.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64]
+        L.mww_stream_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
 
     @classmethod
     def get(cls, path: Optional[str] = None) -> "NativeLib":
@@ -566,6 +597,104 @@ class Engine:
 
 
 _METRIC_SCALARS = ("n", "correct", "tp5", "fp5", "fn5", "pos", "neg", "bce_sum")
+
+
+class Stream:
+    """``mww_stream``: streaming / non-streaming inference of a MixedNet over tracks of the resident feature stores of
+    ``engine``'s context, plus the detection metrics (include/mww.h).  ``desc``: a dict with conv1_filters, conv1_kernel,
+    stride, blocks = [(repeat, kernel sizes, pointwise filters), ...], t_final, frames, mode ("stream" / "non_stream")."""
+
+    def __init__(self, engine: "Engine", desc: dict):
+        self.engine = engine   # the context is borrowed: keep it alive
+        self.nl = engine.nl
+        d = StreamDesc()
+        d.conv1_filters, d.conv1_kernel, d.stride = int(desc["conv1_filters"]), int(desc["conv1_kernel"]), int(desc["stride"])
+        blocks = list(desc["blocks"])
+        if len(blocks) > MWW_MAX_BLOCKS:
+            raise NotImplementedError("streaming supports at most %d blocks" % MWW_MAX_BLOCKS)
+        d.n_blocks = len(blocks)
+        for i, (rep, ks, f) in enumerate(blocks):
+            ks = list(ks)
+            if len(ks) > STREAM_MAX_KERNELS:
+                raise NotImplementedError("streaming supports at most %d MixConv kernels per block" % STREAM_MAX_KERNELS)
+            d.repeat[i], d.n_kernels[i], d.pointwise_filters[i] = int(rep), len(ks), int(f)
+            for j, k in enumerate(ks):
+                d.kernels[i][j] = int(k)
+        d.t_final, d.frames, d.mode = int(desc["t_final"]), int(desc.get("frames", 0)), STREAM_MODES[desc.get("mode", "stream")]
+        h = C.c_void_p()
+        self.nl.check(self.nl.lib.mww_stream_create(engine.h, C.byref(d), C.byref(h)))
+        self.h = h
+        self.n_weights = int(self.nl.lib.mww_stream_num_weights(self.h))
+        self.n_state = int(self.nl.lib.mww_stream_num_state(self.h))
+        self.n_out = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.nl.lib.mww_stream_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, flat):
+        a = np.ascontiguousarray(flat, np.float32).reshape(-1)
+        self.nl.check(self.nl.lib.mww_stream_set_weights(self.h, _fptr(a), a.size))
+
+    def reset(self):
+        self.nl.check(self.nl.lib.mww_stream_reset(self.h))
+
+    def get_state(self):
+        a = np.zeros(self.n_state, np.float32)
+        self.nl.check(self.nl.lib.mww_stream_get_state(self.h, _fptr(a), a.size))
+        return a
+
+    def run(self, tracks: np.ndarray):
+        """tracks: WINDOW_DTYPE array -> per-track output offsets [n + 1] (probabilities stay on the device)."""
+        tr = np.ascontiguousarray(tracks, WINDOW_DTYPE)
+        off = np.zeros(tr.size + 1, np.int64)
+        n = self.nl.check(self.nl.lib.mww_stream_run(self.h, tr.ctypes.data_as(C.c_void_p), tr.size, off.ctypes.data_as(C.c_void_p)))
+        self.n_out = int(n)
+        return off
+
+    def run_host(self, frames: np.ndarray) -> int:
+        x = np.ascontiguousarray(frames, np.float32).reshape(-1, FEATURE_BINS_)
+        n = self.nl.check(self.nl.lib.mww_stream_run_host(self.h, _fptr(x), x.shape[0]))
+        self.n_out = int(n)
+        return self.n_out
+
+    def read(self, n=None, want_logits=False):
+        n = self.n_out if n is None else int(n)
+        p = np.zeros(n, np.float32)
+        z = np.zeros(n, np.float32) if want_logits else None
+        self.nl.check(self.nl.lib.mww_stream_read(self.h, _fptr(p), _fptr(z) if want_logits else None, n))
+        return (p, z) if want_logits else p
+
+    def set_probs(self, probs):
+        a = np.ascontiguousarray(probs, np.float32).reshape(-1)
+        self.nl.check(self.nl.lib.mww_stream_set_probs(self.h, _fptr(a), a.size))
+        self.n_out = a.size
+
+    def metrics(self, offsets, kind, cutoffs, window=5, skip=25, cooldown=25):
+        """-> (counts uint64 [n_cutoffs] summed over the kind-0 tracks, ma_len int64 [n], score float32 [n])"""
+        off = np.ascontiguousarray(offsets, np.int64)
+        kd = np.ascontiguousarray(kind, np.int32)
+        cut = np.ascontiguousarray(cutoffs, np.float64)
+        n = kd.size
+        if off.size != n + 1:
+            raise ValueError("offsets must have one entry more than kind")
+        counts = np.zeros(cut.size, np.uint64)
+        ma_len = np.zeros(n, np.int64)
+        score = np.zeros(n, np.float32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self.nl.check(self.nl.lib.mww_stream_metrics(self.h, vp(off), vp(kd), n, int(window), int(skip), int(cooldown), vp(cut),
+                                                     cut.size, vp(counts), vp(ma_len), vp(score)))
+        return counts, ma_len, score
+
+
+FEATURE_BINS_ = 40
 
 
 class MetricsSum:

@@ -1,0 +1,311 @@
+"""Streaming inference and the FAPH / FRR evaluation of a trained MixedNet on the MI355X - the step after training that the
+reference runs with its ``--test_*`` flags (microwakeword/model_train_eval.py:131-272 ``evaluate_model``):
+
+  * ``StreamingModel``            the model the reference converts with ``utils.convert_model_saved`` and runs through
+                                  ``inference.Model`` (inference.py:82-125 ``predict_spectrogram``), as a native
+                                  ``mww_stream`` (csrc/tu_stream.hip): ``mode="stream"`` is
+                                  Modes.STREAM_INTERNAL_STATE_INFERENCE (``--test_tflite_streaming``), ``mode="non_stream"``
+                                  the non-streaming model on every ``stride``-th window (``--test_tflite_nonstreaming``)
+  * ``false_accepts_per_hour``    test.py:94-137 ``compute_false_accepts_per_hour``
+  * ``roc_curve``                 test.py:140-204 ``generate_roc_curve`` (restated bug for bug: ``y1`` is read at
+                                  ``index - 1`` and the interpolation uses the literal 2.0)
+  * ``streaming_model_roc``       test.py:293-403 ``tflite_streaming_model_roc``
+  * ``model_accuracy``            test.py:207-290 ``tf_model_accuracy`` (``--test_tf_nonstreaming``)
+
+State carry-over, by our reading of test.py:321-324,355-365: the interpreter is created once and never reset, so the rings
+carry over from the ambient tracks (in ``get_data`` order) to the positive tracks of the test set (negatives are skipped
+without being fed).  ``streaming_model_roc`` reproduces exactly that.
+"""
+from __future__ import annotations
+
+import os
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import native
+from .layout import FEATURE_BINS, _flag, parse
+
+SCALE_U16 = np.float32(0.0390625)
+CUTOFFS = np.arange(0, 1.01, 0.01)   # test.py:331
+
+
+def stream_description(flags, t_final: int, frames: int, stride: int, mode: str) -> dict:
+    """The ``mww_stream_desc`` of a MixedNet flag set (mixednet.py:307-386).  Topologies outside the streaming kernel raise
+    NotImplementedError naming the flag."""
+    if mode not in native.STREAM_MODES:
+        raise ValueError("mode must be 'stream' or 'non_stream'")
+    pf = [int(f) for f in parse(_flag(flags, "pointwise_filters"))]
+    rep = [int(r) for r in parse(_flag(flags, "repeat_in_block"))]
+    ksz = [tuple(int(k) for k in (ks if isinstance(ks, (list, tuple)) else (ks,))) for ks in parse(_flag(flags, "mixconv_kernel_sizes"))]
+    res = list(parse(_flag(flags, "residual_connection")))
+    for lst in (rep, ksz, res):
+        if len(pf) != len(lst):
+            raise ValueError("all input lists have to be the same length")   # mixednet.py:298-305
+    unsupported = []
+    if int(_flag(flags, "first_conv_filters")) <= 0:
+        unsupported.append("first_conv_filters = 0")
+    if any(res):
+        unsupported.append("residual_connection")
+    if t_final > 1 and _flag(flags, "spatial_attention"):
+        unsupported.append("spatial_attention")
+    if t_final > 1 and _flag(flags, "pooled"):
+        unsupported.append("pooled")
+    if unsupported:
+        raise NotImplementedError("streaming evaluation does not cover MixedNet with " + ", ".join(unsupported))
+    if int(stride) != int(_flag(flags, "stride")):
+        raise ValueError("the streaming stride (%d) must be the model's --stride (%d)" % (stride, _flag(flags, "stride")))
+    return dict(conv1_filters=int(_flag(flags, "first_conv_filters")), conv1_kernel=int(_flag(flags, "first_conv_kernel_size")),
+                stride=int(stride), blocks=list(zip(rep, ksz, pf)), t_final=int(t_final), frames=int(frames), mode=mode)
+
+
+class StreamingModel:
+    """The streaming (``mode="stream"``) or non-streaming (``mode="non_stream"``) form of a trained MixedNet ``model``
+    (``microwakeword_amd.model.Model``, either kernel family), sharing the model's context: its device, HIP stream and the
+    feature stores a ``FeatureHandler`` uploaded there.  The weights are taken from ``model`` when this object is created
+    (``set_weights`` takes new ones)."""
+
+    def __init__(self, model, stride: int, mode: str = "stream"):
+        self.model = model
+        self.mode = mode
+        self.stride = int(stride)
+        lay = model.layout
+        if not hasattr(lay, "t_last") or lay.__class__.__name__ == "InceptionLayout":
+            raise NotImplementedError("streaming evaluation covers MixedNet only (streaming Inception is not implemented)")
+        self.frames = int(lay.frames)   # input_feature_slices of the non-streaming model
+        self.desc = stream_description(model.flags, lay.t_last, lay.frames, stride, mode)
+        self.native = native.Stream(model.engine, self.desc)
+        self.set_weights(model.get_weights())
+
+    def set_weights(self, weights: Sequence[np.ndarray]):
+        self.native.set_weights(np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in weights]))
+
+    def reset(self):
+        """Rings back to zeros (a freshly created interpreter)."""
+        self.native.reset()
+
+    def predict_spectrogram(self, spectrogram: np.ndarray) -> np.ndarray:
+        """inference.py:82-125: uint16 rows are scaled by 0.0390625, float64 rows cast to float32; stream mode feeds frames
+        [0, floor(L/s)*s) in chunks of s with the state carried from call to call, non-stream mode scores the windows ending
+        at T, T + s, ... <= L.  Returns the probabilities as a float32 array (the reference returns a list of the same
+        float32 values)."""
+        x = np.asarray(spectrogram)
+        if np.issubdtype(x.dtype, np.uint16):
+            x = x.astype(np.float32) * SCALE_U16
+        else:
+            x = x.astype(np.float32)
+        if x.ndim != 2 or x.shape[1] != FEATURE_BINS:
+            raise ValueError("spectrogram must be [T, %d]" % FEATURE_BINS)
+        self.native.run_host(x)
+        return self.native.read()
+
+    def predict_tracks(self, data_processor, mode: str, only_label: Optional[float] = None, features_length: Optional[int] = None):
+        """Every track of ``data_processor.get_data(mode, ..., truncation_strategy="none")`` (or only those whose label is
+        ``only_label``) in one native call over the resident stores.  Returns ``(offsets [n + 1], labels [n])``; the
+        probabilities stay on the device (``read_probabilities``, ``metrics``)."""
+        win, labels = data_processor.track_windows(mode, features_length or self.frames, only_label=only_label)
+        offsets = self.native.run(win)
+        return offsets, labels
+
+    def read_probabilities(self) -> np.ndarray:
+        return self.native.read()
+
+    def metrics(self, offsets, kind, cutoffs=CUTOFFS, sliding_window_length=5, ignore_slices_after_accept=25):
+        """Device-side detection metrics on the probabilities of the last call (see mww_stream_metrics)."""
+        return self.native.metrics(offsets, kind, cutoffs, sliding_window_length, ignore_slices_after_accept, ignore_slices_after_accept)
+
+
+# ------------------------------------------------------------------------------------------ restated post-processing
+
+def moving_average(probabilities, sliding_window_length=5) -> np.ndarray:
+    """``sliding_window_view(p, w).mean(axis=-1)`` on the float32 probabilities (test.py:349-352): float32 sums in order,
+    divided by w.  Fewer than w probabilities give an empty array (the reference raises there; callers decide)."""
+    p = np.asarray(probabilities, np.float32)
+    if p.size < sliding_window_length:
+        return np.zeros(0, np.float32)
+    return np.lib.stride_tricks.sliding_window_view(p, sliding_window_length).mean(axis=-1)
+
+
+def false_accept_counts(moving_averages: List[np.ndarray], cutoffs, ignore_slices_after_accept=25) -> np.ndarray:
+    """The false-accept counts of test.py:119-135 at each cutoff, summed over the tracks (cooldown restarted per track)."""
+    cutoffs = np.asarray(cutoffs, np.float64)
+    counts = np.zeros(cutoffs.shape[0], np.uint64)
+    for track in moving_averages:
+        cooldown = np.full(cutoffs.shape[0], ignore_slices_after_accept, np.int64)
+        for value in np.asarray(track, np.float32):
+            cooldown = np.maximum(cooldown - 1, 0)
+            hit = (cooldown == 0) & (np.float64(value) > cutoffs)
+            counts += hit.astype(np.uint64)
+            cooldown[hit] = ignore_slices_after_accept
+    return counts
+
+
+def track_hours(ma_lengths, stride=1, step_s=0.02) -> float:
+    """test.py:117: sum of len(moving_average) * stride * step_s / 3600, accumulated in track order."""
+    h = 0
+    for n in ma_lengths:
+        h += int(n) * stride * step_s / 3600.0
+    return h
+
+
+def false_accepts_per_hour(moving_averages: List[np.ndarray], cutoffs, ignore_slices_after_accept=75, stride=1, step_s=0.02):
+    """test.py:94-137 ``compute_false_accepts_per_hour``."""
+    counts = false_accept_counts(moving_averages, cutoffs, ignore_slices_after_accept)
+    return counts.astype(np.float64) / track_hours([len(t) for t in moving_averages], stride, step_s)
+
+
+def false_rejection_rates(scores, cutoffs) -> List[float]:
+    """test.py:378-383: 1 - #{score > c} / N at each cutoff."""
+    out = []
+    for cutoff in cutoffs:
+        true_accepts = sum(i > cutoff for i in scores)
+        out.append(1 - true_accepts / len(scores))
+    return out
+
+
+def roc_curve(false_accepts_per_hour, false_rejections, cutoffs, max_faph=2.0):
+    """test.py:140-204 ``generate_roc_curve``, bug for bug."""
+    if false_accepts_per_hour[0] > max_faph:
+        index_of_first_viable = 1
+        while false_accepts_per_hour[index_of_first_viable] > max_faph:
+            index_of_first_viable += 1
+        x0 = false_accepts_per_hour[index_of_first_viable - 1]
+        y0 = false_rejections[index_of_first_viable - 1]
+        x1 = false_accepts_per_hour[index_of_first_viable]
+        y1 = false_rejections[index_of_first_viable - 1]   # (sic: index - 1)
+        fnr_at_max_faph = (y0 * (x1 - 2.0) + y1 * (2.0 - x0)) / (x1 - x0)   # (sic: the literal 2.0)
+        cutoff_at_max_faph = (cutoffs[index_of_first_viable] + cutoffs[index_of_first_viable - 1]) / 2.0
+    else:
+        index_of_first_viable = 0
+        fnr_at_max_faph = false_rejections[index_of_first_viable]
+        cutoff_at_max_faph = cutoffs[index_of_first_viable]
+    xs, ys, cs = [max_faph], [fnr_at_max_faph], [cutoff_at_max_faph]
+    for index in range(index_of_first_viable, len(false_rejections)):
+        if false_accepts_per_hour[index] != xs[-1]:
+            xs.append(false_accepts_per_hour[index])
+            ys.append(false_rejections[index])
+            cs.append(cutoffs[index])
+    if xs[-1] > 0:
+        xs.append(0.0)
+        ys.append(1.0)
+        cs.append(0.0)
+    return np.flip(xs), np.flip(ys), np.flip(cs)
+
+
+def roc_text(x, y, cutoffs_at_points):
+    """The file of test.py:392-401 and its AUC (trapezoid(y, x))."""
+    from .train import _trapezoid
+    auc = _trapezoid(y, x)
+    lines = ["AUC {:.5f}".format(auc)]
+    for i in range(0, x.shape[0]):
+        lines.append("Cutoff {:.2f}: frr={:.4f}; faph={:.3f}".format(cutoffs_at_points[i], y[i], x[i]))
+    return auc, "".join(line + "\n" for line in lines)
+
+
+def evaluate_probabilities(ambient_probabilities, positive_probabilities, stride=1, step_s=0.02, sliding_window_length=5,
+                           ignore_slices_after_accept=25, cutoffs=CUTOFFS):
+    """Host restatement of test.py:340-401 on given per-track probabilities: returns dict(counts, faph, frr, x, y, cutoffs,
+    auc, text)."""
+    amb = []
+    for i, p in enumerate(ambient_probabilities):
+        ma = moving_average(p, sliding_window_length)
+        if ma.size == 0:
+            raise ValueError("ambient track %d has %d probabilities, fewer than the sliding window of %d" % (i, len(p), sliding_window_length))
+        amb.append(ma)
+    counts = false_accept_counts(amb, cutoffs, ignore_slices_after_accept)
+    faph = counts.astype(np.float64) / track_hours([a.size for a in amb], stride, step_s)
+    scores = []
+    for i, p in enumerate(positive_probabilities):
+        ma = moving_average(np.asarray(p, np.float32)[ignore_slices_after_accept:], sliding_window_length)
+        if ma.size == 0:
+            raise ValueError("positive track %d has no moving-average value after skipping %d probabilities" % (i, ignore_slices_after_accept))
+        scores.append(np.max(ma))
+    return _finish(counts, faph, scores, cutoffs)
+
+
+def _finish(counts, faph, scores, cutoffs):
+    if not scores:
+        raise ValueError("the test set has no positive track")
+    frr = false_rejection_rates(scores, cutoffs)
+    x, y, c = roc_curve(faph, frr, cutoffs)
+    auc, text = roc_text(x, y, c)
+    return dict(counts=counts, faph=faph, frr=np.asarray(frr, np.float64), scores=np.asarray(scores, np.float32), x=x, y=y,
+                cutoffs=c, auc=auc, text=text)
+
+
+def streaming_model_roc(config, folder, streaming_model: StreamingModel, data_processor, data_set="testing",
+                        ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt", sliding_window_length=5,
+                        ignore_slices_after_accept=25):
+    """test.py:293-403 ``tflite_streaming_model_roc`` on the device: the ambient tracks, then the positive tracks of
+    ``data_set``, through one stream whose state carries over (stream mode; starting from the state it has - a fresh
+    ``StreamingModel`` starts from zeros, as the reference's interpreter does), the moving averages / cooldown counts /
+    scores by the metrics kernel.  Writes ``<train_dir>/<folder>/<accuracy_name>`` and returns the AUC."""
+    stride = int(config["stride"])
+    step_s = config["window_step_ms"] / 1000
+    sm = streaming_model
+    off, _ = sm.predict_tracks(data_processor, ambient_set)
+    n_amb = off.size - 1
+    counts = np.zeros(CUTOFFS.size, np.uint64)
+    hours = 0
+    if n_amb:
+        counts, ma_len, _ = sm.metrics(off, np.zeros(n_amb, np.int32), CUTOFFS, sliding_window_length, ignore_slices_after_accept)
+        bad = np.nonzero(ma_len == 0)[0]
+        if bad.size:
+            raise ValueError("ambient track %d of %r has fewer than %d probabilities" % (bad[0], ambient_set, sliding_window_length))
+        hours = track_hours(ma_len, stride, step_s)
+    faph = counts.astype(np.float64) / hours
+    off, _ = sm.predict_tracks(data_processor, data_set, only_label=1.0)
+    n_pos = off.size - 1
+    scores = []
+    if n_pos:
+        _, ma_len, score = sm.metrics(off, np.ones(n_pos, np.int32), CUTOFFS, sliding_window_length, ignore_slices_after_accept)
+        bad = np.nonzero(ma_len == 0)[0]
+        if bad.size:
+            raise ValueError("positive track %d of %r has no moving-average value after skipping %d probabilities"
+                             % (bad[0], data_set, ignore_slices_after_accept))
+        scores = list(score)
+    res = _finish(counts, faph, scores, CUTOFFS)
+    path = os.path.join(config["train_dir"], folder)
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, accuracy_name), "wt") as fd:
+        fd.write(res["text"])
+    return res["auc"]
+
+
+def compute_metrics(true_positives, true_negatives, false_positives, false_negatives):
+    """test.py:30-70."""
+    accuracy = false_positive_rate = false_negative_rate = recall = precision = float("nan")
+    count = true_positives + true_negatives + false_positives + false_negatives
+    if count > 0:
+        accuracy = (true_positives + true_negatives) / count
+    if false_positives + true_negatives > 0:
+        false_positive_rate = false_positives / (false_positives + true_negatives)
+    if true_positives + false_negatives > 0:
+        false_negative_rate = false_negatives / (true_positives + false_negatives)
+        recall = true_positives / (true_positives + false_negatives)
+    if true_positives + false_positives > 0:
+        precision = true_positives / (true_positives + false_positives)
+    return dict(accuracy=accuracy, recall=recall, precision=precision, false_positive_rate=false_positive_rate,
+                false_negative_rate=false_negative_rate, count=count)
+
+
+def metrics_to_string(m):
+    """test.py:73-91."""
+    return ("accuracy = {accuracy:.4%}; recall = {recall:.4%}; precision = {precision:.4%}; fpr = {fpr:.4%}; fnr = {fnr:.4%}; "
+            "(N={count})").format(accuracy=m["accuracy"], recall=m["recall"], precision=m["precision"], fpr=m["false_positive_rate"],
+                                  fnr=m["false_negative_rate"], count=m["count"])
+
+
+def model_accuracy(config, folder, model, data_processor, data_set="testing", accuracy_name="testing_set_metrics.txt"):
+    """test.py:207-290 ``tf_model_accuracy``: the non-streaming model on ``get_data(data_set, truncation_strategy=
+    "truncate_start")``, p > 0.5 against the label, counted on the device (mww_evaluate_windows).  Writes
+    ``<train_dir>/<folder>/<accuracy_name>`` and returns the metric dict."""
+    _, _, _ = data_processor.evaluate_on_device(model, data_set, config["spectrogram_length"], "truncate_start")
+    raw = model.engine.metrics_raw()
+    tp, fp, fn, n = int(raw.tp5), int(raw.fp5), int(raw.fn5), int(raw.n)
+    m = compute_metrics(tp, n - tp - fp - fn, fp, fn)
+    path = os.path.join(config["train_dir"], folder)
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, accuracy_name), "wt") as fd:
+        fd.write(metrics_to_string(m))
+    return m

@@ -1,0 +1,88 @@
+"""Throughput of the streaming evaluation (csrc/tu_stream.hip) on synthetic u16 stores: N hours of ambient tracks plus
+positives through ``StreamingModel.predict_tracks`` + the metrics kernel, against the windowed alternative at the same stride
+(``Engine.evaluate_windows`` over every s-th 194-frame window of the ambient audio).  Prints one JSON line.
+
+    python tools/stream_eval_throughput.py --hours 20
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from microwakeword_amd import mixednet, native, streaming  # noqa: E402
+
+DEF = dict(pointwise_filters="48,48,48,48", residual_connection="0,0,0,0", repeat_in_block="1,1,1,1",
+           mixconv_kernel_sizes="[5],[9],[13],[21]", max_pool=0, first_conv_filters=32, first_conv_kernel_size=3,
+           spatial_attention=0, pooled=0, stride=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--hours", type=float, default=20.0)
+    ap.add_argument("--track_minutes", type=float, default=60.0)
+    ap.add_argument("--positives", type=int, default=2000)
+    ap.add_argument("--frames", type=int, default=194)
+    ap.add_argument("--window_hours", type=float, default=1.0, help="ambient hours the windowed alternative is timed on")
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    T = a.frames
+    model = mixednet.model(DEF, (T, 40), 1024, max_batch=1024, seed=3)
+    rng = np.random.default_rng(0)
+    per_track = int(a.track_minutes * 60 * 50)
+    n_amb = max(1, int(round(a.hours * 60 / a.track_minutes)))
+    amb_frames = per_track * n_amb
+    amb = rng.integers(0, 1000, size=(amb_frames, 40), dtype=np.uint16)
+    pos_len = rng.integers(80, 150, a.positives)
+    pos = rng.integers(0, 1000, size=(int(pos_len.sum()), 40), dtype=np.uint16)
+    model.engine.upload_store(0, amb.reshape(-1))
+    model.engine.upload_store(1, pos.reshape(-1))
+    amb_win = np.zeros(n_amb, native.WINDOW_DTYPE)
+    amb_win["store"], amb_win["copy_rows"], amb_win["src_elem"] = 0, per_track, np.arange(n_amb, dtype=np.int64) * per_track * 40
+    pos_win = np.zeros(a.positives, native.WINDOW_DTYPE)
+    pos_off = np.concatenate([[0], np.cumsum(pos_len)[:-1]]).astype(np.int64)
+    pos_win["store"], pos_win["pad_rows"] = 1, np.maximum(0, T - pos_len)
+    pos_win["copy_rows"], pos_win["src_elem"] = pos_len, pos_off * 40
+    sm = streaming.StreamingModel(model, 1, "stream")
+
+    def once():
+        off = sm.native.run(amb_win)
+        sm.metrics(off, np.zeros(n_amb, np.int32))
+        n = int(off[-1])
+        off = sm.native.run(pos_win)
+        sm.metrics(off, np.ones(a.positives, np.int32))
+        return n + int(off[-1])
+
+    once()   # warm-up
+    ts = []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        n_out = once()
+        ts.append(time.perf_counter() - t0)
+    t = min(ts)
+    hours = (amb_frames + int(pos_len.sum())) * 0.02 / 3600
+    # windowed alternative: every 1-frame-stride 194-frame window of `window_hours` of the ambient audio
+    nw = int(a.window_hours * 3600 * 50)
+    nw = min(nw, amb_frames - T)
+    win = np.zeros(nw, native.WINDOW_DTYPE)
+    win["store"], win["copy_rows"], win["src_elem"] = 0, T, np.arange(nw, dtype=np.int64) * 40
+    labels = np.zeros(nw, np.float32)
+    model.engine.evaluate_windows(win[:4096], labels[:4096], 1024)
+    model.engine.synchronize()
+    t0 = time.perf_counter()
+    model.engine.evaluate_windows(win, labels, 1024)
+    model.engine.synchronize()
+    tw = time.perf_counter() - t0
+    rec = {"tool": "stream_eval_throughput", "model": "mixednet default (T=%d)" % T, "stride": 1, "ambient_hours": round(amb_frames * 0.02 / 3600, 3),
+           "ambient_tracks": n_amb, "positives": a.positives, "outputs": n_out, "seconds": round(t, 4),
+           "outputs_per_s": round(n_out / t, 1), "audio_hours_per_s": round(hours / t, 3),
+           "windowed_outputs": nw, "windowed_seconds": round(tw, 4), "windowed_outputs_per_s": round(nw / tw, 1),
+           "speedup_vs_windowed": round((n_out / t) / (nw / tw), 2), "library": model.engine.nl.version()}
+    print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()
