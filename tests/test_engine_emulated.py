@@ -1,6 +1,7 @@
 """Runs the product HIP sources on the CPU under tests/hipemu (fibers + emulated wave ops) and
 checks them against oracle/.  This is a *debugging aid for the kernels' index logic* — it is not a
 product path and proves nothing about the GPU build; the real parity tests are tests/test_engine_gpu.py."""
+import collections
 import os
 
 import numpy as np
@@ -291,6 +292,7 @@ def test_conv1_x6_against_the_exact_fp32_form(emu_lib):
     the exact-fp32 MFMA form of the same kernels, incl. values over the whole uint16 range (three-slice x)."""
     ec.check_conv1_x6_against_the_f32_form(emu_lib, B=5, T=150)
     ec.check_conv1_x6_against_the_f32_form(emu_lib, B=3, T=111, raw_u16_range=True)
+    ec.check_train_steps(emu_lib, B=3, T=111, steps=1, grid=0, flags=dict(ec.DEF, conv1_x6=1, conv1_x6_fwd=1), raw_u16_range=True)
     ec.check_conv1_x6_against_the_f32_form(emu_lib, B=3, T=150, flags=dict(ec.DEF, first_conv_kernel_size=5, pointwise_filters="32,48,64,48"))
 
 
@@ -406,3 +408,59 @@ def test_block_kernels_of_the_wider_shape_table(emu_lib):
     lines = []
     m.summary(print_fn=lines.append)
     assert any(l.startswith("Kernels: specialised block kernels") for l in lines)
+
+
+# ------------------------------------------------------------------------------------------ block-table sweep (tests/block_table_sweep.py)
+def test_block_table_inventory_matches_the_shape_table(emu_lib):
+    """The inventory read back from mww_block_kernels_cover: csrc/block_launch.hip.h's table (54 first-block and 99 block shapes;
+    6 + 14 with the bf16 modes), nothing outside it, the wide backward form only for square 48 / 64 blocks, and the number of
+    instantiations per launcher that its form rules give.  The product library holds the same table."""
+    import block_table_sweep as bts
+    tabs = bts.tables(emu_lib)
+    firsts, blocks = tabs[False]
+    assert (len(firsts), len(blocks), len(tabs[True][0]), len(tabs[True][1])) == (54, 99, 6, 14)
+    assert {f[0] for f in firsts} == {3, 5} and {f[1] for f in firsts} == {32} and {f[2] for f in firsts} == {32, 48, 64}
+    assert {f[3] for f in firsts} == {3, 5, 7} and {f[4] for f in firsts} == {1, 2, 3}
+    assert {(b[0], b[1]) for b in blocks} == {(a, b) for a in (32, 48, 64) for b in (32, 48, 64)}
+    assert {b[2] for b in blocks} == set(range(3, 24, 2))
+    assert set(tabs[True][1]) == {(w, w, k) for w in (48, 64) for k in (5, 9, 11, 13, 15, 21, 23)}
+    # outside the table: width 40, a 25-tap or an even depthwise kernel, a 32-wide bf16 block
+    for bf16, widths, ks in ((False, (48, 40), (5, 9)), (False, (48, 48), (5, 25)), (False, (48, 48), (5, 10)), (True, (48, 32), (5, 9))):
+        ok, why = emu_lib.block_kernels_cover(frames=194, conv1_filters=32, conv1_kernel=3, conv1_stride=1, block_filters=widths,
+                                              block_kernel=ks, bf16=bf16)
+        assert not ok and why.startswith("block 1 "), (widths, ks, why)
+    inv = bts.inventory(emu_lib)
+    count = collections.Counter(bts.launcher_of(i) for i in inv)
+    assert count == {"fwd_first_kernel": 54 + 18 + 12, "fwd_block_kernel": 99 + 28, "bwd_first_kernel": 54 + 18 + 20,
+                     "bwd_firstw_kernel": 36 + 9, "bwd_block_kernel": 198 + 56, "bwd_blockw_kernel": 44 + 56}, count
+    wide = {tuple(int(v) for v in i.split("<")[1].split(", ")[:2]) for i in inv if i.startswith("bwd_blockw")}
+    assert wide == {(48, 48), (64, 64)}
+    assert bts.inventory(native.NativeLib.get()) == inv, "the emulated and the product library hold different shape tables"
+
+
+def test_block_table_sweep_covers_every_instantiation(emu_lib):
+    """The plan of tests/test_block_table_sweep_gpu.py launches every instantiation of the inventory, every strided first block
+    in tail mode and over two tiles; every case lands on the block kernels (in its own bf16 mode) and its id is unique."""
+    import block_table_sweep as bts
+    from microwakeword_amd import mixednet
+    missing = bts.uncovered(emu_lib)
+    assert not missing, "%d not covered:\n%s" % (len(missing), "\n".join(map(str, missing)))
+    cases = bts.plan(emu_lib)
+    assert len({c["id"] for c in cases}) == len(cases)
+    assert bts.plan(native.NativeLib.get()) == cases   # the GPU sweep's plan is this one
+    for c in cases:
+        fam = mixednet.kernel_family(bts.case_flags(c), c["T"], lib=emu_lib, bf16=c["mode"] > 0)
+        assert fam[0] == "block", (bts.describe(c), fam)
+        assert c["B"] <= 8 and c["grid"] in (0, 1, 2, 3, 5, 8)
+
+
+def test_block_table_sweep_slice(emu_lib):
+    """A fixed slice of the GPU sweep on the emulated kernels, whose LDS starts as NaN and whose buffers end at a guard page:
+    every form (narrow / wide, LAST or not, fp32 / bf16 / bf16 storage, x6 / exact conv1, a tail-mode first block) and every
+    first-block and block shape of the table at least once."""
+    import block_table_sweep as bts
+    for c in bts.emulator_slice(emu_lib):
+        try:
+            ec.check_train_steps(emu_lib, B=c["B"], T=c["T"], steps=1, grid=c["grid"], flags=bts.case_flags(c))
+        except AssertionError as e:
+            raise AssertionError("%s: %s" % (bts.describe(c), e)) from None

@@ -213,9 +213,10 @@ def test_first_block_tail_k_step_with_a_three_tap_depthwise(lib, wide):
 def test_conv1_x6_against_the_exact_fp32_form(lib):
     """Round 6: the first convolution and its weight gradient as six bf16 slice products per fp32 product (the default for
     stride-1 first convolutions; ds_read_b64_tr_b16 operands in the backward kernel) against the exact-fp32 MFMA form of the
-    same kernels (option "conv1_x6" 0): probabilities within 2e-6, gradients within 5e-6 per tensor where no ReLU decision
-    differs (engine_checks says what a flip costs), not bit-identical (the option is wired); each form against the float64 oracle
-    with its own ReLU decisions imposed.  Values over the whole uint16 range too (three-slice x), and a 5-tap first conv."""
+    same kernels (option "conv1_x6" 0): probabilities within 2e-6, gradients within 5e-6 per tensor when no ReLU decision
+    differs between the forms (every call reads both forms' decisions; engine_checks says what a flip costs), not bit-identical
+    (the option is wired); each form against the float64 oracle with its own ReLU decisions imposed.  Values over the whole uint16
+    range too (three-slice x: against the other form and against the float64 oracle), and a 5-tap first conv."""
     small = ec.check_conv1_x6_against_the_f32_form(lib, B=12, T=194)
     assert small <= 5e-6, small          # (no flip in this batch on the device; the emulated kernels agree to 1.6e-6 here)
     for form in (0, 1):
@@ -223,6 +224,9 @@ def test_conv1_x6_against_the_exact_fp32_form(lib):
         assert worst["l2_max"] <= 1e-4
     ec.check_conv1_x6_against_the_f32_form(lib, B=256, T=194)
     ec.check_conv1_x6_against_the_f32_form(lib, B=37, T=111, raw_u16_range=True)
+    # the x6 form against the float64 oracle itself on full-range uint16 inputs (x up to 2560: three significant slices)
+    worst = ec.check_train_steps(lib, B=37, T=111, steps=1, grid=0, flags=dict(ec.DEF, conv1_x6=1, conv1_x6_fwd=1), raw_u16_range=True)
+    assert worst["l2_max"] <= 1e-4
     ec.check_conv1_x6_against_the_f32_form(lib, B=64, T=150, flags=dict(ec.DEF, first_conv_kernel_size=5, pointwise_filters="32,48,64,48"))
     ec.check_conv1_x6_against_the_f32_form(lib, B=64, T=150, flags=dict(ec.DEF, pointwise_filters="64,64,64,64", mixconv_kernel_sizes="[7],[9],[13],[21]"))
 
