@@ -439,6 +439,31 @@ int mww_stream_set_probs(mww_stream* s, const float* probs, int64_t n);       /*
 int mww_stream_metrics(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip,
                        int cooldown, const double* cutoffs, int n_cutoffs, uint64_t* counts, int64_t* ma_len, float* score);
 
+/* ---- int8 quantized streaming model (the reference's --test_tflite_streaming_quantized; microwakeword_amd/quantize.py
+ * derives the parameters, INTEGRATION.md states the contract).
+ * Calibration: tensors, in order, are the input, conv1 (after ReLU), every layer of the plan (a MixConv layer's output with
+ * its groups concatenated, a 1x1 layer's output after folded BN + ReLU), the Dense logit: mww_stream_num_tensors of them.
+ * mww_stream_calibrate_host runs the float streaming model (stream mode, from the state it has, which it carries on) over
+ * n_frames host rows and writes ranges[n_tensors][2] = min, max over every position computed; the probabilities
+ * are those of mww_stream_run_host on the same frames, bit for bit. */
+int mww_stream_num_tensors(const mww_stream* s);
+int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_frames, float* ranges);
+/* Loads int8 parameters; from then on mww_stream_run / _run_host run the int8 kernel (the float weights stay for
+ * calibration) and mww_stream_reset fills every ring with its tensor's zero point.  The plan's ops, in order: conv1, every
+ * layer (MixConv: depthwise taps of all groups fused to K = max kernel taps, right-aligned; 1x1), the Dense.
+ *   weights (int8): conv1 [C1][k1*40]; MixConv [K][C]; 1x1 [Co][Ci rounded up to 4]; Dense [T_f][C_last rounded up to 4]
+ *                   (padding entries 0)
+ *   ints (int32):   per op: bias with the input zero point folded (b - zp_in * sum of the channel's weights) [cout],
+ *                   multiplier [cout], shift [cout] (TFLite QuantizeMultiplier); then the n_tensors zero points
+ *   input_scale:    the input tensor's scale (its zero point is the first of the zero points)
+ *   lut (uint8):    [256] logit q + 128 -> the uint8 output; probability = (float)u8 * (float)(1/255) */
+int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_weights, const int32_t* ints, int64_t n_ints,
+                             float input_scale, const uint8_t* lut);
+int64_t mww_stream_q8_sizes(const mww_stream* s, int64_t* n_ints);   /* int8 weights expected (n_ints: int32 entries) */
+/* uint8 outputs of the last int8 run; int8 rings (the layout of mww_stream_get_state, one byte per value) */
+int mww_stream_read_q8(mww_stream* s, uint8_t* out, int64_t n);
+int mww_stream_get_state_q8(mww_stream* s, int8_t* host, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

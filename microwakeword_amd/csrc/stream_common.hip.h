@@ -1,0 +1,384 @@
+// Shared by the float (tu_stream.hip) and the int8 (tu_stream_q8.hip) streaming kernels: the plan of a streaming MixedNet
+// (layers, weight / ring offsets, reach of every layer), the stream object, and the per-call track / segment / tile
+// tables.  Both kernels walk the same tiles and the same ring layout; only the element type and the arithmetic differ.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/mww.h"
+
+namespace mww {
+int ctx_borrow(mww_ctx* c, int* device, hipStream_t* stream, void** stores, int* dtypes, int64_t* elems, int* n_cu);
+int set_error(int code, const char* msg);
+}  // namespace mww
+
+namespace mww_stream_impl {
+
+constexpr int kStreamThreads = 256;
+constexpr int kHostStore = MWW_MAX_STORES;   // store slot of the frames mww_stream_run_host uploads
+constexpr int kTileOutputs = 256;            // outputs per tile (one head thread each)
+constexpr float kScaleU16 = 0.0390625f;      // data.py:268-269 / inference.py:93-94
+
+struct SLayer {
+  int kind;          // 0: depthwise K taps + bias (fused MixConv groups, zero leading taps); 1: 1x1 + folded BN + ReLU
+  int cin, cout, k;
+  int64_t w, b;      // offsets into the weight buffer
+  int64_t ring;      // depthwise: offset of its ring ((k - 1) x cin) in the state buffer
+  int reach;         // conv1 positions between this layer's OUTPUT and the first head input of a tile
+};
+
+struct SNet {
+  int k1, s, c1, r1, tf, c_last, n_layers, cmax;
+  int64_t w1, wd, bd;        // conv1 [k1][40][c1], dense [tf * c_last], bias
+  int64_t ring1, ring_head;  // conv1 ring [r1][40] (spectrogram rows), head ring [tf - 1][c_last]
+  int reach1;                // conv1 positions of halo in front of a tile
+  const SLayer* L;           // [n_layers], device memory (the kernel argument stays small)
+};
+
+struct SStores {
+  const void* p[MWW_MAX_STORES + 1];
+  int dtype[MWW_MAX_STORES + 1];
+};
+
+struct SCall {
+  const mww_window* trk;     // [n_trk]
+  const int64_t* trk_v0;     // [n_trk + 1] first virtual frame of each track
+  int n_trk;
+  const int64_t* seg_v0;     // segment start (virtual frame)
+  const int* seg_coff;       // conv1 index of the segment's first output
+  const int* tile_seg;
+  const int64_t* tile_m0;    // first output of the tile inside its segment
+  const int* tile_n;
+  const int64_t* tile_out0;  // global output index of the tile's first output
+  int n_tiles;
+  int use_state;             // stream mode: padded positions read the rings
+  int64_t n_out;             // outputs of the whole call (stream mode: the tile holding output n_out - 1 writes the rings)
+  const float* w;
+  const float* st_in;
+  float* st_out;
+  float* scratch;
+  int64_t scratch_per_wg;    // floats
+  int64_t buf_rows;          // rows of each activation buffer
+  float* prob;
+  float* logit;
+  float* rec;                // calibration: per-workgroup [n_tensors][2] min / max partials (NULL: not recording)
+  int n_tensors;
+};
+
+__device__ inline float frame_value(const SStores& S, const SCall& a, int64_t v, int bin) {
+  // binary search of the track holding virtual frame v
+  int lo = 0, hi = a.n_trk - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.trk_v0[mid] <= v) lo = mid; else hi = mid - 1;
+  }
+  const mww_window w = a.trk[lo];
+  const int64_t j = v - a.trk_v0[lo];
+  if (j < w.pad_rows) return 0.f;   // fixed_length_spectrogram's zero rows in front of a short clip (data.py:107-113)
+  const int64_t e = w.src_elem + (j - w.pad_rows) * MWW_FEATURE_BINS + bin;
+  if (S.dtype[w.store] == MWW_DTYPE_U16) return (float)static_cast<const unsigned short*>(S.p[w.store])[e] * kScaleU16;
+  return static_cast<const float*>(S.p[w.store])[e];
+}
+
+// int8 form (tu_stream_q8.hip): device copies of the quantized parameters; layout in include/mww.h
+struct SQ8 {
+  const int8_t* w;       // int8 weights
+  const int32_t* iv;     // per op: bias (input zero point folded), multiplier, shift [cout] each; then the tensor zero points
+  const uint8_t* lut;    // [256]: logit q + 128 -> output uint8
+  const int64_t* lw;     // [n_layers] offset of each layer's weights in w
+  const int64_t* li;     // [n_layers] offset of each layer's ints in iv
+  int64_t w1, wd, i1, id, izp;
+  float in_scale;
+  int in_zp;
+  int kp1;               // conv1 reduction length k1 * 40
+  int cpd;               // dense row pitch: C_last rounded up to 4
+  int cp;                // activation row pitch: cmax rounded up to 4
+  uint8_t* out;          // [n_out] uint8 outputs
+  const int8_t* st_in;
+  int8_t* st_out;
+  int8_t* scratch;       // global form: per-workgroup buffers
+  int use_lds;
+};
+
+}  // namespace mww_stream_impl
+
+struct mww_stream {
+  mww_ctx* ctx = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int n_cu = 256;
+  mww_stream_desc d{};
+  mww_stream_impl::SNet net{};
+  std::vector<mww_stream_impl::SLayer> layers;   // host copy of net.L
+  mww_stream_impl::SLayer* d_layers = nullptr;
+  int64_t n_weights = 0;   // Keras-order floats
+  int64_t n_dev_w = 0;     // folded device weights
+  int64_t n_state = 0;
+  int j0 = 0;              // non-stream: conv1 index of a track's first window
+  float* w = nullptr;
+  float* st[2] = {nullptr, nullptr};
+  int cur = 0;
+  bool weights_set = false;
+  // per-call device buffers, grown on demand
+  float* prob = nullptr;
+  float* logit = nullptr;
+  int64_t cap_out = 0, cap_logit = 0;
+  float* scratch = nullptr;
+  int64_t cap_scratch = 0;
+  char* tables = nullptr;
+  int64_t cap_tables = 0;
+  float* host_frames = nullptr;
+  int64_t cap_host_frames = 0;
+  int64_t n_out = 0;       // outputs held in prob (last run or set_probs)
+  // metrics
+  char* mtab = nullptr;
+  int64_t cap_mtab = 0;
+  std::vector<char> htab;   // host copy of the last call's tables
+  float* rec = nullptr;     // calibration partials
+  int64_t cap_rec = 0;
+  // int8 form (mww_stream_set_quantized): runs replace the float kernel with the int8 one
+  bool q8 = false;
+  int64_t q8_nw = 0, q8_ni = 0;
+  int8_t* q8_w = nullptr;
+  int32_t* q8_i = nullptr;
+  uint8_t* q8_lut = nullptr;
+  int64_t* q8_off = nullptr;           // [2 * n_layers]: weight offsets, then int offsets
+  std::vector<int8_t> q8_state0;       // rings at reset: each ring filled with its tensor's zero point
+  int8_t* q8_st[2] = {nullptr, nullptr};
+  int q8_cur = 0;
+  float q8_in_scale = 1.f;
+  int q8_in_zp = 0;
+  int64_t q8_w1 = 0, q8_wd = 0, q8_i1 = 0, q8_id = 0, q8_izp = 0;
+  uint8_t* q8_out = nullptr;
+  int64_t cap_q8_out = 0;
+  int8_t* q8_scratch = nullptr;
+  int64_t cap_q8_scratch = 0;
+};
+
+namespace mww_stream_impl {
+
+#define SCHK(expr)                                                                                      \
+  do {                                                                                                  \
+    hipError_t e_ = (expr);                                                                             \
+    if (e_ != hipSuccess) return mww::set_error(MWW_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
+  } while (0)
+
+inline int unsupported(const std::string& m) { return mww::set_error(MWW_ERR_UNSUPPORTED, m.c_str()); }
+
+template <class T>
+inline int grow(T** p, int64_t* cap, int64_t n) {
+  if (n <= *cap) return MWW_OK;
+  if (*p) SCHK(hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  SCHK(hipMalloc((void**)p, (size_t)n * sizeof(T) + 64));
+  *cap = n;
+  return MWW_OK;
+}
+
+// topology + weight / state layout from the description; Keras-order size in *keras
+inline int plan(const mww_stream_desc& d, SNet& net, std::vector<SLayer>& layers, int64_t* keras, int64_t* dev_w, int64_t* state, int* j0) {
+  std::memset(&net, 0, sizeof(net));
+  layers.assign((size_t)2 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT, SLayer{});
+  if (d.mode != MWW_STREAM_MODE_STREAM && d.mode != MWW_STREAM_MODE_NON_STREAM) return unsupported("mode must be stream or non_stream");
+  if (d.conv1_filters <= 0 || d.conv1_kernel <= 0 || d.stride <= 0)
+    return unsupported("streaming needs a first convolution (first_conv_filters > 0, kernel and stride > 0)");
+  if (d.n_blocks <= 0 || d.n_blocks > MWW_MAX_BLOCKS) return unsupported("n_blocks must be 1..8");
+  if (d.t_final <= 0) return unsupported("t_final must be positive");
+  net.k1 = d.conv1_kernel;
+  net.s = d.stride;
+  net.c1 = d.conv1_filters;
+  net.r1 = d.conv1_kernel > d.stride ? d.conv1_kernel - d.stride : 0;
+  net.tf = d.t_final;
+  int64_t kw = (int64_t)net.k1 * MWW_FEATURE_BINS * net.c1, dw = kw, st = 0;
+  net.w1 = 0;
+  net.ring1 = st;
+  st += (int64_t)net.r1 * MWW_FEATURE_BINS;
+  int c = net.c1, cmax = net.c1, nl = 0, sum_r = 0;
+  for (int b = 0; b < d.n_blocks; ++b) {
+    const int nk = d.n_kernels[b], f = d.pointwise_filters[b];
+    if (nk <= 0 || nk > MWW_STREAM_MAX_KERNELS) return unsupported("block " + std::to_string(b) + ": 1..8 MixConv kernels");
+    if (d.repeat[b] <= 0 || d.repeat[b] > MWW_STREAM_MAX_REPEAT) return unsupported("block " + std::to_string(b) + ": repeat must be 1..4");
+    if (f <= 0 || f > 1024) return unsupported("block " + std::to_string(b) + ": pointwise filters must be 1..1024");
+    int K = 0;
+    for (int g = 0; g < nk; ++g) {
+      if (d.kernels[b][g] <= 0) return unsupported("block " + std::to_string(b) + ": kernel sizes must be positive");
+      if (g && d.kernels[b][g] < d.kernels[b][g - 1]) return unsupported("mixconv kernel sizes must be ascending (alignment uses the last one)");
+      K = d.kernels[b][g] > K ? d.kernels[b][g] : K;
+    }
+    for (int r = 0; r < d.repeat[b]; ++r) {
+      if (K > 1) {   // MixConv: depthwise groups (+ bias) fused to one [K][C] table, own ring of K - 1 frames
+        if (nk > c) return unsupported("more MixConv groups than channels");
+        SLayer& L = layers[nl++];
+        L.kind = 0; L.cin = c; L.cout = c; L.k = K;
+        L.w = dw; dw += (int64_t)K * c;
+        L.b = dw; dw += c;
+        L.ring = st; st += (int64_t)(K - 1) * c;
+        for (int g = 0; g < nk; ++g) kw += (int64_t)d.kernels[b][g] * (c / nk + (g == 0 ? c % nk : 0)) + (c / nk + (g == 0 ? c % nk : 0));
+        sum_r += K - 1;
+      }
+      SLayer& P = layers[nl++];
+      P.kind = 1; P.cin = c; P.cout = f; P.k = 1;
+      P.w = dw; dw += (int64_t)c * f;
+      P.b = dw; dw += f;
+      kw += (int64_t)c * f + 4 * f;   // kernel, gamma, beta, moving mean, moving variance
+      c = f;
+      cmax = c > cmax ? c : cmax;
+    }
+  }
+  net.n_layers = nl;
+  net.c_last = c;
+  net.cmax = cmax;
+  net.wd = dw; dw += (int64_t)net.tf * c;
+  net.bd = dw; dw += 1;
+  kw += (int64_t)net.tf * c + 1;
+  net.ring_head = st;
+  st += (int64_t)(net.tf - 1) * c;
+  // reach: conv1 positions between a layer's output and the first head input of a tile
+  int reach = net.tf - 1;
+  for (int l = nl - 1; l >= 0; --l) {
+    layers[l].reach = reach;
+    if (layers[l].kind == 0) reach += layers[l].k - 1;
+  }
+  layers.resize((size_t)nl);
+  net.reach1 = reach;
+  *j0 = 0;
+  if (d.mode == MWW_STREAM_MODE_NON_STREAM) {
+    if (d.frames < net.k1) return unsupported("non_stream mode needs frames >= the first convolution's kernel");
+    const int n1 = (d.frames - net.k1) / net.s + 1;
+    if (n1 - sum_r != net.tf)
+      return unsupported("t_final " + std::to_string(net.tf) + " does not match a " + std::to_string(d.frames) + "-frame window (" +
+                         std::to_string(n1 - sum_r) + " final frames)");
+    *j0 = n1 - 1;
+  }
+  *keras = kw;
+  *dev_w = dw;
+  *state = st;
+  return MWW_OK;
+}
+
+// Per-call tables of a track list (tracks, virtual frame offsets, segments, tiles) uploaded to s->tables, the output
+// buffers grown, and the kernel arguments filled.  Returns the number of outputs (0: nothing to launch) or an error < 0.
+inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk, int64_t* out_off, int64_t n_host_frames,
+                            SStores& S, SCall& a, int* grid_out) {
+  if (n_trk < 0 || n_trk > INT32_MAX || (n_trk && !trk) || !out_off) return mww::set_error(MWW_ERR_INVALID, "bad track list");
+  S = SStores{};
+  void* stores[MWW_MAX_STORES];
+  int dt[MWW_MAX_STORES];
+  int64_t el[MWW_MAX_STORES];
+  int dev;
+  hipStream_t hs;
+  int ncu;
+  int rc = mww::ctx_borrow(s->ctx, &dev, &hs, stores, dt, el, &ncu);
+  if (rc) return rc;
+  for (int i = 0; i < MWW_MAX_STORES; ++i) { S.p[i] = stores[i]; S.dtype[i] = dt[i]; }
+  S.p[kHostStore] = s->host_frames;
+  S.dtype[kHostStore] = MWW_DTYPE_F32;
+  const SNet& net = s->net;
+  const bool stream_mode = s->d.mode == MWW_STREAM_MODE_STREAM;
+  const int T = s->d.frames;
+  // per track: frames fed and outputs (predict_spectrogram: chunks of s, trailing L mod s frames never fed; non-stream:
+  // windows ending at T, T + s, ... <= L)
+  std::vector<int64_t> v0((size_t)n_trk + 1, 0);
+  out_off[0] = 0;
+  for (int64_t t = 0; t < n_trk; ++t) {
+    const mww_window& w = trk[t];
+    if (w.pad_rows < 0 || w.copy_rows < 0) return mww::set_error(MWW_ERR_INVALID, "negative track rows");
+    if (w.store >= 0) {
+      if (w.store >= MWW_MAX_STORES || !stores[w.store]) return mww::set_error(MWW_ERR_INVALID, "track refers to a store that was not uploaded");
+      if (w.src_elem < 0 || w.src_elem + (int64_t)w.copy_rows * MWW_FEATURE_BINS > el[w.store])
+        return mww::set_error(MWW_ERR_INVALID, "track reads past the end of its store");
+    } else if (w.src_elem < 0 || w.src_elem + (int64_t)w.copy_rows * MWW_FEATURE_BINS > n_host_frames * MWW_FEATURE_BINS) {
+      return mww::set_error(MWW_ERR_INVALID, "track reads past the host frames");
+    }
+    const int64_t L = (int64_t)w.pad_rows + w.copy_rows;
+    int64_t n_o;
+    if (stream_mode) {
+      n_o = L / net.s;
+      v0[t + 1] = v0[t] + n_o * net.s;
+    } else {
+      n_o = L >= T ? (L - T) / net.s + 1 : 0;
+      v0[t + 1] = v0[t] + L;
+    }
+    out_off[t + 1] = out_off[t] + n_o;
+  }
+  const int64_t n_out = n_trk ? out_off[n_trk] : 0;
+  s->n_out = n_out;
+  if (n_out == 0) return 0;
+  // segments and tiles
+  std::vector<int64_t> seg_v0, tile_m0, tile_out0;
+  std::vector<int> seg_coff, tile_seg, tile_n;
+  auto add_tiles = [&](int sg, int64_t n, int64_t out0) {
+    for (int64_t m = 0; m < n; m += kTileOutputs) {
+      tile_seg.push_back(sg);
+      tile_m0.push_back(m);
+      tile_n.push_back((int)(n - m < kTileOutputs ? n - m : kTileOutputs));
+      tile_out0.push_back(out0 + m);
+    }
+  };
+  if (stream_mode) {
+    seg_v0.push_back(0);
+    seg_coff.push_back(0);
+    add_tiles(0, n_out, 0);
+  } else {
+    for (int64_t t = 0; t < n_trk; ++t) {
+      const int64_t n = out_off[t + 1] - out_off[t];
+      if (!n) continue;
+      seg_v0.push_back(v0[t]);
+      seg_coff.push_back(s->j0);
+      add_tiles((int)seg_v0.size() - 1, n, out_off[t]);
+    }
+  }
+  const int n_tiles = (int)tile_seg.size();
+  const int n_seg = (int)seg_v0.size();
+  // one table upload: tracks, v0, segments, tiles
+  auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+  const int64_t o_trk = 0, o_v0 = al(o_trk + n_trk * (int64_t)sizeof(mww_window)), o_sv0 = al(o_v0 + (n_trk + 1) * 8),
+                o_sco = al(o_sv0 + n_seg * 8), o_tsg = al(o_sco + n_seg * 4), o_tm0 = al(o_tsg + n_tiles * 4),
+                o_tn = al(o_tm0 + n_tiles * 8), o_to0 = al(o_tn + n_tiles * 4), bytes = al(o_to0 + n_tiles * 8);
+  std::vector<char>& tab = s->htab;   // kept until the next call: the upload below is asynchronous
+  tab.assign((size_t)bytes, 0);
+  std::memcpy(&tab[o_trk], trk, (size_t)n_trk * sizeof(mww_window));
+  for (int64_t t = 0; t < n_trk; ++t)
+    if (trk[t].store < 0) reinterpret_cast<mww_window*>(&tab[o_trk])[t].store = kHostStore;
+  std::memcpy(&tab[o_v0], v0.data(), (size_t)(n_trk + 1) * 8);
+  std::memcpy(&tab[o_sv0], seg_v0.data(), (size_t)n_seg * 8);
+  std::memcpy(&tab[o_sco], seg_coff.data(), (size_t)n_seg * 4);
+  std::memcpy(&tab[o_tsg], tile_seg.data(), (size_t)n_tiles * 4);
+  std::memcpy(&tab[o_tm0], tile_m0.data(), (size_t)n_tiles * 8);
+  std::memcpy(&tab[o_tn], tile_n.data(), (size_t)n_tiles * 4);
+  std::memcpy(&tab[o_to0], tile_out0.data(), (size_t)n_tiles * 8);
+  SCHK(hipSetDevice(s->device));
+  if ((rc = grow(&s->tables, &s->cap_tables, bytes))) return rc;
+  if ((rc = grow(&s->prob, &s->cap_out, n_out))) return rc;
+  if ((rc = grow(&s->logit, &s->cap_logit, n_out))) return rc;
+  *grid_out = n_tiles < 2 * s->n_cu ? n_tiles : 2 * s->n_cu;
+  SCHK(hipMemcpyAsync(s->tables, tab.data(), (size_t)bytes, hipMemcpyHostToDevice, s->stream));
+  a = SCall{};
+  a.trk = reinterpret_cast<const mww_window*>(s->tables + o_trk);
+  a.trk_v0 = reinterpret_cast<const int64_t*>(s->tables + o_v0);
+  a.n_trk = (int)n_trk;
+  a.seg_v0 = reinterpret_cast<const int64_t*>(s->tables + o_sv0);
+  a.seg_coff = reinterpret_cast<const int*>(s->tables + o_sco);
+  a.tile_seg = reinterpret_cast<const int*>(s->tables + o_tsg);
+  a.tile_m0 = reinterpret_cast<const int64_t*>(s->tables + o_tm0);
+  a.tile_n = reinterpret_cast<const int*>(s->tables + o_tn);
+  a.tile_out0 = reinterpret_cast<const int64_t*>(s->tables + o_to0);
+  a.n_tiles = n_tiles;
+  a.use_state = stream_mode ? 1 : 0;
+  a.n_out = n_out;
+  a.w = s->w;
+  a.st_in = s->st[s->cur];
+  a.st_out = s->st[s->cur ^ 1];
+  a.buf_rows = kTileOutputs + net.reach1;
+  a.prob = s->prob;
+  a.logit = s->logit;
+  return n_out;
+}
+
+}  // namespace mww_stream_impl

@@ -20,86 +20,51 @@
 // state, so no tile reads a ring another tile writes).  Every sum runs in a fixed order: no atomics, runs are bit-identical.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
+#include "stream_common.hip.h"
 
-#include "../../include/mww.h"
+using namespace mww_stream_impl;
 
 namespace mww {
-int ctx_borrow(mww_ctx* c, int* device, hipStream_t* stream, void** stores, int* dtypes, int64_t* elems, int* n_cu);
-int set_error(int code, const char* msg);
+int64_t stream_q8_launch(mww_stream* s, const mww_stream_impl::SStores& S, mww_stream_impl::SCall& a, int grid);
+int stream_q8_reset(mww_stream* s);
+void stream_q8_free(mww_stream* s);
 }  // namespace mww
 
 namespace {
 
-constexpr int kStreamThreads = 256;
-constexpr int kHostStore = MWW_MAX_STORES;   // store slot of the frames mww_stream_run_host uploads
-constexpr int kTileOutputs = 256;            // outputs per tile (one head thread each)
-constexpr float kScaleU16 = 0.0390625f;      // data.py:268-269 / inference.py:93-94
-
-struct SLayer {
-  int kind;          // 0: depthwise K taps + bias (fused MixConv groups, zero leading taps); 1: 1x1 + folded BN + ReLU
-  int cin, cout, k;
-  int64_t w, b;      // offsets into the weight buffer
-  int64_t ring;      // depthwise: offset of its ring ((k - 1) x cin) in the state buffer
-  int reach;         // conv1 positions between this layer's OUTPUT and the first head input of a tile
-};
-
-struct SNet {
-  int k1, s, c1, r1, tf, c_last, n_layers, cmax;
-  int64_t w1, wd, bd;        // conv1 [k1][40][c1], dense [tf * c_last], bias
-  int64_t ring1, ring_head;  // conv1 ring [r1][40] (spectrogram rows), head ring [tf - 1][c_last]
-  int reach1;                // conv1 positions of halo in front of a tile
-  const SLayer* L;           // [n_layers], device memory (the kernel argument stays small)
-};
-
-struct SStores {
-  const void* p[MWW_MAX_STORES + 1];
-  int dtype[MWW_MAX_STORES + 1];
-};
-
-struct SCall {
-  const mww_window* trk;     // [n_trk]
-  const int64_t* trk_v0;     // [n_trk + 1] first virtual frame of each track
-  int n_trk;
-  const int64_t* seg_v0;     // segment start (virtual frame)
-  const int* seg_coff;       // conv1 index of the segment's first output
-  const int* tile_seg;
-  const int64_t* tile_m0;    // first output of the tile inside its segment
-  const int* tile_n;
-  const int64_t* tile_out0;  // global output index of the tile's first output
-  int n_tiles;
-  int use_state;             // stream mode: padded positions read the rings
-  int64_t n_out;             // outputs of the whole call (stream mode: the tile holding output n_out - 1 writes the rings)
-  const float* w;
-  const float* st_in;
-  float* st_out;
-  float* scratch;
-  int64_t scratch_per_wg;    // floats
-  int64_t buf_rows;          // rows of each activation buffer
-  float* prob;
-  float* logit;
-};
-
-__device__ inline float frame_value(const SStores& S, const SCall& a, int64_t v, int bin) {
-  // binary search of the track holding virtual frame v
-  int lo = 0, hi = a.n_trk - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.trk_v0[mid] <= v) lo = mid; else hi = mid - 1;
+// Calibration (REC): every thread keeps the min / max of the values it computes for the current tensor; the block folds
+// them in thread order into its running [n_tensors] min / max, written once per workgroup at the end.
+__device__ inline void rec_fold(float lmin, float lmax, int t, float* red, float* rmin, float* rmax) {
+  const int tid = threadIdx.x;
+  red[tid] = lmin;
+  red[kStreamThreads + tid] = lmax;
+  __syncthreads();
+  if (tid == 0) {
+    float lo = rmin[t], hi = rmax[t];
+    for (int i = 0; i < kStreamThreads; ++i) {
+      lo = fminf(lo, red[i]);
+      hi = fmaxf(hi, red[kStreamThreads + i]);
+    }
+    rmin[t] = lo;
+    rmax[t] = hi;
   }
-  const mww_window w = a.trk[lo];
-  const int64_t j = v - a.trk_v0[lo];
-  if (j < w.pad_rows) return 0.f;   // fixed_length_spectrogram's zero rows in front of a short clip (data.py:107-113)
-  const int64_t e = w.src_elem + (j - w.pad_rows) * MWW_FEATURE_BINS + bin;
-  if (S.dtype[w.store] == MWW_DTYPE_U16) return (float)static_cast<const unsigned short*>(S.p[w.store])[e] * kScaleU16;
-  return static_cast<const float*>(S.p[w.store])[e];
+  __syncthreads();
 }
 
+constexpr int kMaxTensors = 3 + 2 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT;
+
+template <bool REC>
 __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net, SStores S, SCall a) {
   const int tid = threadIdx.x;
+  __shared__ float red[REC ? 2 * kStreamThreads : 1], rmin[REC ? kMaxTensors : 1], rmax[REC ? kMaxTensors : 1];
+  float lmin = INFINITY, lmax = -INFINITY;
+  if (REC) {
+    for (int t = tid; t < a.n_tensors; t += kStreamThreads) {
+      rmin[t] = INFINITY;
+      rmax[t] = -INFINITY;
+    }
+    __syncthreads();
+  }
   float* G = a.scratch + (int64_t)blockIdx.x * a.scratch_per_wg;            // gathered padded input rows [.][40]
   float* B0 = G + ((a.buf_rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS;   // two activation buffers [rows][cmax]
   float* B1 = B0 + a.buf_rows * net.cmax;
@@ -135,8 +100,17 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
       float acc = 0.f;
       for (int r = 0; r < net.k1 * MWW_FEATURE_BINS; ++r) acc = fmaf(g[r], w[(int64_t)r * net.c1], acc);
       B0[i * net.cmax + co] = acc > 0.f ? acc : 0.f;
+      if (REC) {
+        lmin = fminf(lmin, B0[i * net.cmax + co]);
+        lmax = fmaxf(lmax, B0[i * net.cmax + co]);
+      }
     }
     __syncthreads();
+    if (REC) {
+      rec_fold(lmin, lmax, 1, red, rmin, rmax);
+      lmin = INFINITY;
+      lmax = -INFINITY;
+    }
     float* in = B0;
     float* out = B1;
     int64_t in_lo = lo;
@@ -158,6 +132,10 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
             acc = fmaf(a.w[L.w + (int64_t)j * C + c], x, acc);
           }
           out[(i - o_lo) * net.cmax + c] = acc;
+          if (REC) {
+            lmin = fminf(lmin, acc);
+            lmax = fmaxf(lmax, acc);
+          }
         }
         if (last) {   // this layer's ring after the call: its input at positions [N - R, N)
           for (int idx = tid; idx < R * C; idx += kStreamThreads) {
@@ -176,9 +154,18 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
           float acc = a.w[L.b + co];
           for (int ci = 0; ci < Ci; ++ci) acc = fmaf(x[ci], w[(int64_t)ci * Co], acc);
           out[(i - o_lo) * net.cmax + co] = acc > 0.f ? acc : 0.f;
+          if (REC) {
+            lmin = fminf(lmin, out[(i - o_lo) * net.cmax + co]);
+            lmax = fmaxf(lmax, out[(i - o_lo) * net.cmax + co]);
+          }
         }
       }
       __syncthreads();
+      if (REC) {
+        rec_fold(lmin, lmax, 2 + l, red, rmin, rmax);
+        lmin = INFINITY;
+        lmax = -INFINITY;
+      }
       float* t = in;
       in = out;
       out = t;
@@ -204,6 +191,15 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
       const int64_t g = a.tile_out0[tile] + o;
       a.logit[g] = acc;
       a.prob[g] = 1.f / (1.f + expf(-acc));
+      if (REC) {
+        lmin = fminf(lmin, acc);
+        lmax = fmaxf(lmax, acc);
+      }
+    }
+    if (REC) {
+      rec_fold(lmin, lmax, 2 + net.n_layers, red, rmin, rmax);
+      lmin = INFINITY;
+      lmax = -INFINITY;
     }
     if (last) {
       for (int idx = tid; idx < (TF - 1) * C; idx += kStreamThreads) {
@@ -214,6 +210,11 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
     }
     __syncthreads();   // the next tile reuses the scratch
   }
+  if (REC)
+    for (int t = tid; t < a.n_tensors; t += kStreamThreads) {
+      a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2] = rmin[t];
+      a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2 + 1] = rmax[t];
+    }
 }
 
 // Detection metrics (test.py:94-137 compute_false_accepts_per_hour, :329-376).  One workgroup per track: thread j < n_cut
@@ -274,143 +275,6 @@ __global__ void stream_counts_sum_kernel(const unsigned long long* counts, int n
 
 }  // namespace
 
-struct mww_stream {
-  mww_ctx* ctx = nullptr;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int n_cu = 256;
-  mww_stream_desc d{};
-  SNet net{};
-  std::vector<SLayer> layers;   // host copy of net.L
-  SLayer* d_layers = nullptr;
-  int64_t n_weights = 0;   // Keras-order floats
-  int64_t n_dev_w = 0;     // folded device weights
-  int64_t n_state = 0;
-  int j0 = 0;              // non-stream: conv1 index of a track's first window
-  float* w = nullptr;
-  float* st[2] = {nullptr, nullptr};
-  int cur = 0;
-  bool weights_set = false;
-  // per-call device buffers, grown on demand
-  float* prob = nullptr;
-  float* logit = nullptr;
-  int64_t cap_out = 0, cap_logit = 0;
-  float* scratch = nullptr;
-  int64_t cap_scratch = 0;
-  char* tables = nullptr;
-  int64_t cap_tables = 0;
-  float* host_frames = nullptr;
-  int64_t cap_host_frames = 0;
-  int64_t n_out = 0;       // outputs held in prob (last run or set_probs)
-  // metrics
-  char* mtab = nullptr;
-  int64_t cap_mtab = 0;
-};
-
-namespace {
-
-#define SCHK(expr)                                                                                      \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return mww::set_error(MWW_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-int unsupported(const std::string& m) { return mww::set_error(MWW_ERR_UNSUPPORTED, m.c_str()); }
-
-template <class T>
-int grow(T** p, int64_t* cap, int64_t n) {
-  if (n <= *cap) return MWW_OK;
-  if (*p) SCHK(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  SCHK(hipMalloc((void**)p, (size_t)n * sizeof(T) + 64));
-  *cap = n;
-  return MWW_OK;
-}
-
-// topology + weight / state layout from the description; Keras-order size in *keras
-int plan(const mww_stream_desc& d, SNet& net, std::vector<SLayer>& layers, int64_t* keras, int64_t* dev_w, int64_t* state, int* j0) {
-  std::memset(&net, 0, sizeof(net));
-  layers.assign((size_t)2 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT, SLayer{});
-  if (d.mode != MWW_STREAM_MODE_STREAM && d.mode != MWW_STREAM_MODE_NON_STREAM) return unsupported("mode must be stream or non_stream");
-  if (d.conv1_filters <= 0 || d.conv1_kernel <= 0 || d.stride <= 0)
-    return unsupported("streaming needs a first convolution (first_conv_filters > 0, kernel and stride > 0)");
-  if (d.n_blocks <= 0 || d.n_blocks > MWW_MAX_BLOCKS) return unsupported("n_blocks must be 1..8");
-  if (d.t_final <= 0) return unsupported("t_final must be positive");
-  net.k1 = d.conv1_kernel;
-  net.s = d.stride;
-  net.c1 = d.conv1_filters;
-  net.r1 = d.conv1_kernel > d.stride ? d.conv1_kernel - d.stride : 0;
-  net.tf = d.t_final;
-  int64_t kw = (int64_t)net.k1 * MWW_FEATURE_BINS * net.c1, dw = kw, st = 0;
-  net.w1 = 0;
-  net.ring1 = st;
-  st += (int64_t)net.r1 * MWW_FEATURE_BINS;
-  int c = net.c1, cmax = net.c1, nl = 0, sum_r = 0;
-  for (int b = 0; b < d.n_blocks; ++b) {
-    const int nk = d.n_kernels[b], f = d.pointwise_filters[b];
-    if (nk <= 0 || nk > MWW_STREAM_MAX_KERNELS) return unsupported("block " + std::to_string(b) + ": 1..8 MixConv kernels");
-    if (d.repeat[b] <= 0 || d.repeat[b] > MWW_STREAM_MAX_REPEAT) return unsupported("block " + std::to_string(b) + ": repeat must be 1..4");
-    if (f <= 0 || f > 1024) return unsupported("block " + std::to_string(b) + ": pointwise filters must be 1..1024");
-    int K = 0;
-    for (int g = 0; g < nk; ++g) {
-      if (d.kernels[b][g] <= 0) return unsupported("block " + std::to_string(b) + ": kernel sizes must be positive");
-      if (g && d.kernels[b][g] < d.kernels[b][g - 1]) return unsupported("mixconv kernel sizes must be ascending (alignment uses the last one)");
-      K = d.kernels[b][g] > K ? d.kernels[b][g] : K;
-    }
-    for (int r = 0; r < d.repeat[b]; ++r) {
-      if (K > 1) {   // MixConv: depthwise groups (+ bias) fused to one [K][C] table, own ring of K - 1 frames
-        if (nk > c) return unsupported("more MixConv groups than channels");
-        SLayer& L = layers[nl++];
-        L.kind = 0; L.cin = c; L.cout = c; L.k = K;
-        L.w = dw; dw += (int64_t)K * c;
-        L.b = dw; dw += c;
-        L.ring = st; st += (int64_t)(K - 1) * c;
-        for (int g = 0; g < nk; ++g) kw += (int64_t)d.kernels[b][g] * (c / nk + (g == 0 ? c % nk : 0)) + (c / nk + (g == 0 ? c % nk : 0));
-        sum_r += K - 1;
-      }
-      SLayer& P = layers[nl++];
-      P.kind = 1; P.cin = c; P.cout = f; P.k = 1;
-      P.w = dw; dw += (int64_t)c * f;
-      P.b = dw; dw += f;
-      kw += (int64_t)c * f + 4 * f;   // kernel, gamma, beta, moving mean, moving variance
-      c = f;
-      cmax = c > cmax ? c : cmax;
-    }
-  }
-  net.n_layers = nl;
-  net.c_last = c;
-  net.cmax = cmax;
-  net.wd = dw; dw += (int64_t)net.tf * c;
-  net.bd = dw; dw += 1;
-  kw += (int64_t)net.tf * c + 1;
-  net.ring_head = st;
-  st += (int64_t)(net.tf - 1) * c;
-  // reach: conv1 positions between a layer's output and the first head input of a tile
-  int reach = net.tf - 1;
-  for (int l = nl - 1; l >= 0; --l) {
-    layers[l].reach = reach;
-    if (layers[l].kind == 0) reach += layers[l].k - 1;
-  }
-  layers.resize((size_t)nl);
-  net.reach1 = reach;
-  *j0 = 0;
-  if (d.mode == MWW_STREAM_MODE_NON_STREAM) {
-    if (d.frames < net.k1) return unsupported("non_stream mode needs frames >= the first convolution's kernel");
-    const int n1 = (d.frames - net.k1) / net.s + 1;
-    if (n1 - sum_r != net.tf)
-      return unsupported("t_final " + std::to_string(net.tf) + " does not match a " + std::to_string(d.frames) + "-frame window (" +
-                         std::to_string(n1 - sum_r) + " final frames)");
-    *j0 = n1 - 1;
-  }
-  *keras = kw;
-  *dev_w = dw;
-  *state = st;
-  return MWW_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* d, mww_stream** out) {
@@ -446,8 +310,9 @@ void mww_stream_destroy(mww_stream* s) {
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (void* p : {(void*)s->w, (void*)s->st[0], (void*)s->st[1], (void*)s->prob, (void*)s->logit, (void*)s->scratch,
-                  (void*)s->tables, (void*)s->host_frames, (void*)s->mtab, (void*)s->d_layers})
+                  (void*)s->tables, (void*)s->host_frames, (void*)s->mtab, (void*)s->d_layers, (void*)s->rec})
     if (p) (void)hipFree(p);
+  mww::stream_q8_free(s);
   delete s;
 }
 
@@ -513,7 +378,7 @@ int mww_stream_reset(mww_stream* s) {
   SCHK(hipSetDevice(s->device));
   SCHK(hipMemsetAsync(s->st[s->cur], 0, (size_t)(s->n_state + 1) * sizeof(float), s->stream));
   SCHK(hipStreamSynchronize(s->stream));
-  return MWW_OK;
+  return s->q8 ? mww::stream_q8_reset(s) : MWW_OK;
 }
 
 int mww_stream_get_state(mww_stream* s, float* h, int64_t n) {
@@ -524,131 +389,38 @@ int mww_stream_get_state(mww_stream* s, float* h, int64_t n) {
   return MWW_OK;
 }
 
-static int64_t run_tracks(mww_stream* s, const mww_window* trk, int64_t n_trk, int64_t* out_off, const float* host_frames,
-                          int64_t n_host_frames) {
-  if (!s->weights_set) return mww::set_error(MWW_ERR_STATE, "mww_stream_set_weights first");
-  if (n_trk < 0 || n_trk > INT32_MAX || (n_trk && !trk) || !out_off) return mww::set_error(MWW_ERR_INVALID, "bad track list");
-  SStores S{};
-  void* stores[MWW_MAX_STORES];
-  int dt[MWW_MAX_STORES];
-  int64_t el[MWW_MAX_STORES];
-  int dev;
-  hipStream_t hs;
-  int ncu;
-  int rc = mww::ctx_borrow(s->ctx, &dev, &hs, stores, dt, el, &ncu);
-  if (rc) return rc;
-  for (int i = 0; i < MWW_MAX_STORES; ++i) { S.p[i] = stores[i]; S.dtype[i] = dt[i]; }
-  S.p[kHostStore] = s->host_frames;
-  S.dtype[kHostStore] = MWW_DTYPE_F32;
+// one call over a track list: the int8 kernel once int8 parameters are loaded (except for calibration), else the float one
+static int64_t run_tracks(mww_stream* s, const mww_window* trk, int64_t n_trk, int64_t* out_off, int64_t n_host_frames,
+                          float* rec = nullptr) {
+  if (!s->weights_set && !s->q8) return mww::set_error(MWW_ERR_STATE, "mww_stream_set_weights first");
+  if (rec && s->d.mode != MWW_STREAM_MODE_STREAM) return mww::set_error(MWW_ERR_STATE, "calibration runs a stream-mode object");
+  if (rec && !s->weights_set) return mww::set_error(MWW_ERR_STATE, "calibration runs the float weights: mww_stream_set_weights first");
+  SStores S;
+  SCall a;
+  int grid = 0;
+  const int64_t n_out = prepare_call(s, trk, n_trk, out_off, n_host_frames, S, a, &grid);
+  if (n_out <= 0) return n_out;
+  if (s->q8 && !rec) return mww::stream_q8_launch(s, S, a, grid);
   const SNet& net = s->net;
-  const bool stream_mode = s->d.mode == MWW_STREAM_MODE_STREAM;
-  const int T = s->d.frames;
-  // per track: frames fed and outputs (predict_spectrogram: chunks of s, trailing L mod s frames never fed; non-stream:
-  // windows ending at T, T + s, ... <= L)
-  std::vector<int64_t> v0((size_t)n_trk + 1, 0);
-  out_off[0] = 0;
-  for (int64_t t = 0; t < n_trk; ++t) {
-    const mww_window& w = trk[t];
-    const int sid = w.store < 0 ? kHostStore : w.store;
-    if (w.pad_rows < 0 || w.copy_rows < 0) return mww::set_error(MWW_ERR_INVALID, "negative track rows");
-    if (w.store >= 0) {
-      if (w.store >= MWW_MAX_STORES || !stores[w.store]) return mww::set_error(MWW_ERR_INVALID, "track refers to a store that was not uploaded");
-      if (w.src_elem < 0 || w.src_elem + (int64_t)w.copy_rows * MWW_FEATURE_BINS > el[w.store])
-        return mww::set_error(MWW_ERR_INVALID, "track reads past the end of its store");
-    } else if (w.src_elem < 0 || w.src_elem + (int64_t)w.copy_rows * MWW_FEATURE_BINS > n_host_frames * MWW_FEATURE_BINS) {
-      return mww::set_error(MWW_ERR_INVALID, "track reads past the host frames");
-    }
-    (void)sid;
-    const int64_t L = (int64_t)w.pad_rows + w.copy_rows;
-    int64_t n_o;
-    if (stream_mode) {
-      n_o = L / net.s;
-      v0[t + 1] = v0[t] + n_o * net.s;
-    } else {
-      n_o = L >= T ? (L - T) / net.s + 1 : 0;
-      v0[t + 1] = v0[t] + L;
-    }
-    out_off[t + 1] = out_off[t] + n_o;
-  }
-  const int64_t n_out = n_trk ? out_off[n_trk] : 0;
-  s->n_out = n_out;
-  if (n_out == 0) return 0;
-  // segments and tiles
-  std::vector<int64_t> seg_v0, tile_m0, tile_out0;
-  std::vector<int> seg_coff, tile_seg, tile_n;
-  auto add_tiles = [&](int sg, int64_t n, int64_t out0) {
-    for (int64_t m = 0; m < n; m += kTileOutputs) {
-      tile_seg.push_back(sg);
-      tile_m0.push_back(m);
-      tile_n.push_back((int)(n - m < kTileOutputs ? n - m : kTileOutputs));
-      tile_out0.push_back(out0 + m);
-    }
-  };
-  if (stream_mode) {
-    seg_v0.push_back(0);
-    seg_coff.push_back(0);
-    add_tiles(0, n_out, 0);
-  } else {
-    for (int64_t t = 0; t < n_trk; ++t) {
-      const int64_t n = out_off[t + 1] - out_off[t];
-      if (!n) continue;
-      seg_v0.push_back(v0[t]);
-      seg_coff.push_back(s->j0);
-      add_tiles((int)seg_v0.size() - 1, n, out_off[t]);
-    }
-  }
-  const int n_tiles = (int)tile_seg.size();
-  const int n_seg = (int)seg_v0.size();
-  // one table upload: tracks, v0, segments, tiles
-  auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-  const int64_t o_trk = 0, o_v0 = al(o_trk + n_trk * (int64_t)sizeof(mww_window)), o_sv0 = al(o_v0 + (n_trk + 1) * 8),
-                o_sco = al(o_sv0 + n_seg * 8), o_tsg = al(o_sco + n_seg * 4), o_tm0 = al(o_tsg + n_tiles * 4),
-                o_tn = al(o_tm0 + n_tiles * 8), o_to0 = al(o_tn + n_tiles * 4), bytes = al(o_to0 + n_tiles * 8);
-  std::vector<char> tab((size_t)bytes, 0);
-  std::memcpy(&tab[o_trk], trk, (size_t)n_trk * sizeof(mww_window));
-  for (int64_t t = 0; t < n_trk; ++t)
-    if (trk[t].store < 0) reinterpret_cast<mww_window*>(&tab[o_trk])[t].store = kHostStore;
-  std::memcpy(&tab[o_v0], v0.data(), (size_t)(n_trk + 1) * 8);
-  std::memcpy(&tab[o_sv0], seg_v0.data(), (size_t)n_seg * 8);
-  std::memcpy(&tab[o_sco], seg_coff.data(), (size_t)n_seg * 4);
-  std::memcpy(&tab[o_tsg], tile_seg.data(), (size_t)n_tiles * 4);
-  std::memcpy(&tab[o_tm0], tile_m0.data(), (size_t)n_tiles * 8);
-  std::memcpy(&tab[o_tn], tile_n.data(), (size_t)n_tiles * 4);
-  std::memcpy(&tab[o_to0], tile_out0.data(), (size_t)n_tiles * 8);
-  SCHK(hipSetDevice(s->device));
-  if ((rc = grow(&s->tables, &s->cap_tables, bytes))) return rc;
-  if ((rc = grow(&s->prob, &s->cap_out, n_out))) return rc;
-  if ((rc = grow(&s->logit, &s->cap_logit, n_out))) return rc;
-  const int grid = n_tiles < 2 * s->n_cu ? n_tiles : 2 * s->n_cu;
-  const int64_t rows = kTileOutputs + net.reach1;
-  const int64_t per_wg = al(((rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS + 2 * rows * net.cmax);
-  if ((rc = grow(&s->scratch, &s->cap_scratch, per_wg * grid))) return rc;
-  SCHK(hipMemcpyAsync(s->tables, tab.data(), (size_t)bytes, hipMemcpyHostToDevice, s->stream));
-  SCall a{};
-  a.trk = reinterpret_cast<const mww_window*>(s->tables + o_trk);
-  a.trk_v0 = reinterpret_cast<const int64_t*>(s->tables + o_v0);
-  a.n_trk = (int)n_trk;
-  a.seg_v0 = reinterpret_cast<const int64_t*>(s->tables + o_sv0);
-  a.seg_coff = reinterpret_cast<const int*>(s->tables + o_sco);
-  a.tile_seg = reinterpret_cast<const int*>(s->tables + o_tsg);
-  a.tile_m0 = reinterpret_cast<const int64_t*>(s->tables + o_tm0);
-  a.tile_n = reinterpret_cast<const int*>(s->tables + o_tn);
-  a.tile_out0 = reinterpret_cast<const int64_t*>(s->tables + o_to0);
-  a.n_tiles = n_tiles;
-  a.use_state = stream_mode ? 1 : 0;
-  a.n_out = n_out;
+  const int64_t rows = a.buf_rows;
+  const int64_t per_wg = (((rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS + 2 * rows * net.cmax + 255) & ~(int64_t)255;
+  int rc = grow(&s->scratch, &s->cap_scratch, per_wg * grid);
+  if (rc) return rc;
   a.w = s->w;
   a.st_in = s->st[s->cur];
   a.st_out = s->st[s->cur ^ 1];
   a.scratch = s->scratch;
   a.scratch_per_wg = per_wg;
-  a.buf_rows = rows;
-  a.prob = s->prob;
-  a.logit = s->logit;
-  hipLaunchKernelGGL(stream_forward_kernel, dim3(grid), dim3(kStreamThreads), 0, s->stream, net, S, a);
+  if (rec) {
+    a.n_tensors = net.n_layers + 3;
+    a.rec = rec;
+    hipLaunchKernelGGL(stream_forward_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, s->stream, net, S, a);
+  } else {
+    hipLaunchKernelGGL(stream_forward_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, s->stream, net, S, a);
+  }
   SCHK(hipGetLastError());
-  SCHK(hipStreamSynchronize(s->stream));   // the host tables above are released on return
-  if (stream_mode) s->cur ^= 1;            // the rings this call wrote are the state of the next one
+  SCHK(hipStreamSynchronize(s->stream));
+  if (s->d.mode == MWW_STREAM_MODE_STREAM) s->cur ^= 1;   // the rings this call wrote are the state of the next one
   return n_out;
 }
 
@@ -656,7 +428,7 @@ int64_t mww_stream_run(mww_stream* s, const mww_window* tracks, int64_t n_tracks
   if (!s) return mww::set_error(MWW_ERR_INVALID, "null stream");
   for (int64_t t = 0; t < n_tracks; ++t)
     if (tracks[t].store < 0) return mww::set_error(MWW_ERR_INVALID, "track refers to a store that was not uploaded");
-  return run_tracks(s, tracks, n_tracks, out_offsets, nullptr, 0);
+  return run_tracks(s, tracks, n_tracks, out_offsets, 0);
 }
 
 int64_t mww_stream_run_host(mww_stream* s, const float* frames, int64_t n_frames) {
@@ -669,7 +441,45 @@ int64_t mww_stream_run_host(mww_stream* s, const float* frames, int64_t n_frames
   w.store = -1;
   w.copy_rows = (int32_t)n_frames;
   int64_t off[2];
-  return run_tracks(s, &w, 1, off, frames, n_frames);
+  return run_tracks(s, &w, 1, off, n_frames);
+}
+
+int mww_stream_num_tensors(const mww_stream* s) { return s ? s->net.n_layers + 3 : 0; }
+
+int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_frames, float* ranges) {
+  if (!s || !ranges || (n_frames && !frames) || n_frames < 0 || n_frames > INT32_MAX) return mww::set_error(MWW_ERR_INVALID, "bad frames");
+  const int nt = s->net.n_layers + 3;
+  for (int t = 0; t < nt; ++t) {
+    ranges[2 * t] = INFINITY;
+    ranges[2 * t + 1] = -INFINITY;
+  }
+  // the input tensor: every frame fed (chunks of s; the trailing L mod s frames are not), in order
+  const int64_t fed = n_frames / s->net.s * s->net.s;
+  for (int64_t i = 0; i < fed * MWW_FEATURE_BINS; ++i) {
+    ranges[0] = fminf(ranges[0], frames[i]);
+    ranges[1] = fmaxf(ranges[1], frames[i]);
+  }
+  SCHK(hipSetDevice(s->device));
+  int rc = grow(&s->host_frames, &s->cap_host_frames, (n_frames + 1) * MWW_FEATURE_BINS);
+  if (!rc) rc = grow(&s->rec, &s->cap_rec, (int64_t)2 * s->n_cu * nt * 2);
+  if (rc) return rc;
+  if (n_frames) SCHK(hipMemcpyAsync(s->host_frames, frames, (size_t)n_frames * MWW_FEATURE_BINS * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  mww_window w{};
+  w.store = -1;
+  w.copy_rows = (int32_t)n_frames;
+  int64_t off[2];
+  const int64_t n_out = run_tracks(s, &w, 1, off, n_frames, s->rec);
+  if (n_out <= 0) return (int)n_out;
+  const int64_t n_tiles = (n_out + kTileOutputs - 1) / kTileOutputs;
+  const int grid = (int)(n_tiles < 2 * s->n_cu ? n_tiles : 2 * s->n_cu);
+  std::vector<float> part((size_t)grid * nt * 2);
+  SCHK(hipMemcpy(part.data(), s->rec, part.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (int g = 0; g < grid; ++g)   // fixed order
+    for (int t = 1; t < nt; ++t) {
+      ranges[2 * t] = fminf(ranges[2 * t], part[((size_t)g * nt + t) * 2]);
+      ranges[2 * t + 1] = fmaxf(ranges[2 * t + 1], part[((size_t)g * nt + t) * 2 + 1]);
+    }
+  return MWW_OK;
 }
 
 int mww_stream_read(mww_stream* s, float* probs, float* logits, int64_t n) {

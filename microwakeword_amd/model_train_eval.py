@@ -131,6 +131,9 @@ def build_parser():
     parser.add_argument("--test_tflite_nonstreaming_quantized", type=int, default=0)
     parser.add_argument("--test_tflite_streaming", type=int, default=0)
     parser.add_argument("--test_tflite_streaming_quantized", type=int, default=0)
+    parser.add_argument("--quantized_backend", type=str, default="tflite", choices=("tflite", "native"),
+                        help="native: run --test_tflite_streaming_quantized on the int8 kernel here, calibrated and quantized "
+                             "by a restatement of TFLite's int8 arithmetic (not TFLite itself)")
     parser.add_argument("--restore_checkpoint", type=int, default=0)
     parser.add_argument("--use_weights", type=str, default="best_weights")
     parser.add_argument("--verbosity", type=str, default="INFO")
@@ -168,7 +171,10 @@ def evaluate_model(flags, model_module, config, device=0):
     """model_train_eval.py:131-272 ``evaluate_model`` on the MI355X: a fresh model loads ``<train_dir>/<use_weights>.weights.h5``
     (its ``.npz`` twin) and is evaluated on the test sets - ``--test_tf_nonstreaming``: ``non_stream/testing_set_metrics.txt``;
     ``--test_tflite_nonstreaming``: ``tflite_non_stream/tflite_streaming_roc.txt``; ``--test_tflite_streaming``:
-    ``tflite_stream_state_internal/tflite_streaming_roc.txt`` (streaming.py).  Nothing is exported: the streaming /
+    ``tflite_stream_state_internal/tflite_streaming_roc.txt`` (streaming.py); ``--test_tflite_streaming_quantized`` with
+    ``--quantized_backend native``: calibration and int8 quantization (quantize.py), the parameters in
+    ``tflite_stream_state_internal_quant/stream_state_internal_quant.npz`` and the ROC of the int8 streaming model in
+    ``tflite_stream_state_internal_quant/tflite_streaming_roc.txt``.  No TFLite file is written: the streaming /
     non-streaming forms run natively from the same weights."""
     from . import streaming
     model = model_module.model(flags, config["training_input_shape"], config["batch_size"], device=device)
@@ -186,12 +192,27 @@ def evaluate_model(flags, model_module, config, device=0):
             sm = streaming.StreamingModel(model, config["stride"], mode)
             out[folder] = streaming.streaming_model_roc(config, folder, sm, data_processor, data_set="testing",
                                                         ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt")
+    if getattr(flags, "test_tflite_streaming_quantized", 0):
+        from . import quantize
+        folder = "tflite_stream_state_internal_quant"
+        logging.info("Testing the quantized streaming model: calibrated and quantized by a restatement of TFLite's int8 "
+                     "arithmetic (quantize.py, INTEGRATION.md), not by TFLite")
+        ranges = quantize.calibrate(model, data_processor, config)
+        qm = quantize.quantize(model, ranges)
+        path = os.path.join(config["train_dir"], folder)
+        os.makedirs(path, exist_ok=True)
+        qm.save(os.path.join(path, "stream_state_internal_quant.npz"))
+        logging.info("int8 parameters:\n%s", qm.summary())
+        qsm = streaming.QuantizedStreamingModel(qm, config["stride"], "stream", context=model)
+        out[folder] = streaming.streaming_model_roc(config, folder, qsm, data_processor, data_set="testing",
+                                                    ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt")
     return out
 
 
 def _evaluate(flags, model_module, config, device, world):
     """rank 0 evaluates, the other ranks of a data-parallel job wait at a barrier"""
-    if not any((flags.test_tf_nonstreaming, flags.test_tflite_nonstreaming, flags.test_tflite_streaming)):
+    if not any((flags.test_tf_nonstreaming, flags.test_tflite_nonstreaming, flags.test_tflite_streaming,
+                getattr(flags, "test_tflite_streaming_quantized", 0))):
         return None
     from .train import process_group
     rank, world = process_group()
@@ -203,10 +224,16 @@ def _evaluate(flags, model_module, config, device, world):
 
 
 def _run(flags, model_module, rank, local_rank, world):
-    if flags.test_tflite_nonstreaming_quantized or flags.test_tflite_streaming_quantized:
-        raise NotImplementedError("the int8 *_quantized evaluations need the TFLite converter's calibration (reference "
-                                  "microwakeword.utils); --test_tf_nonstreaming, --test_tflite_nonstreaming and "
-                                  "--test_tflite_streaming run here")
+    if flags.test_tflite_nonstreaming_quantized or (flags.test_tflite_streaming_quantized and flags.quantized_backend != "native"):
+        msg = ("the int8 *_quantized evaluations need the TFLite converter's calibration (reference "
+               "microwakeword.utils); --test_tf_nonstreaming, --test_tflite_nonstreaming and "
+               "--test_tflite_streaming run here. --test_tflite_streaming_quantized also runs here with --quantized_backend "
+               "native, on a restatement of TFLite's int8 arithmetic (not TFLite itself)")
+        if flags.test_tflite_nonstreaming_quantized:
+            msg += ("; --test_tflite_nonstreaming_quantized has no such restatement: the reference's calibration generator "
+                    "yields stride-row chunks, which do not fit the non-streaming model's T-row input, so there is no "
+                    "well-defined calibration to restate")
+        raise NotImplementedError(msg)
     config = load_config(flags, model_module)
     device = flags.device if local_rank is None else local_rank
     if flags.train:

@@ -112,7 +112,8 @@ EXPORTS = [
     "mww_allreduce_unique_id", "mww_allreduce_init", "mww_allreduce_destroy", "mww_evaluate_windows",
     "mww_stream_create", "mww_stream_destroy", "mww_stream_num_weights", "mww_stream_num_state", "mww_stream_set_weights",
     "mww_stream_reset", "mww_stream_get_state", "mww_stream_run", "mww_stream_run_host", "mww_stream_read", "mww_stream_set_probs",
-    "mww_stream_metrics",
+    "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
+    "mww_stream_read_q8", "mww_stream_get_state_q8",
 ]
 
 
@@ -217,6 +218,13 @@ class NativeLib:
         L.mww_stream_read.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64]
         L.mww_stream_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mww_stream_num_tensors.argtypes = [C.c_void_p]
+        L.mww_stream_calibrate_host.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float)]
+        L.mww_stream_set_quantized.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
+        L.mww_stream_q8_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.mww_stream_q8_sizes.restype = C.c_int64
+        L.mww_stream_read_q8.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.mww_stream_get_state_q8.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
 
     @classmethod
     def get(cls, path: Optional[str] = None) -> "NativeLib":
@@ -626,6 +634,7 @@ class Stream:
         self.h = h
         self.n_weights = int(self.nl.lib.mww_stream_num_weights(self.h))
         self.n_state = int(self.nl.lib.mww_stream_num_state(self.h))
+        self.stride = int(d.stride)
         self.n_out = 0
 
     def close(self):
@@ -692,6 +701,43 @@ class Stream:
         self.nl.check(self.nl.lib.mww_stream_metrics(self.h, vp(off), vp(kd), n, int(window), int(skip), int(cooldown), vp(cut),
                                                      cut.size, vp(counts), vp(ma_len), vp(score)))
         return counts, ma_len, score
+
+    # ---- int8 form (include/mww.h, mww_stream_set_quantized)
+    def num_tensors(self) -> int:
+        return int(self.nl.check(self.nl.lib.mww_stream_num_tensors(self.h)))
+
+    def calibrate_host(self, frames: np.ndarray) -> np.ndarray:
+        """float stream-mode run over host frames recording every tensor's range -> float32 [n_tensors, 2] (min, max)"""
+        x = np.ascontiguousarray(frames, np.float32).reshape(-1, FEATURE_BINS_)
+        r = np.zeros((self.num_tensors(), 2), np.float32)
+        self.nl.check(self.nl.lib.mww_stream_calibrate_host(self.h, _fptr(x), x.shape[0], _fptr(r)))
+        self.n_out = x.shape[0] // self.stride
+        return r
+
+    def q8_sizes(self):
+        ni = C.c_int64()
+        nw = self.nl.check(self.nl.lib.mww_stream_q8_sizes(self.h, C.byref(ni)))
+        return int(nw), int(ni.value)
+
+    def set_quantized(self, weights, ints, input_scale, lut):
+        w = np.ascontiguousarray(weights, np.int8).reshape(-1)
+        iv = np.ascontiguousarray(ints, np.int32).reshape(-1)
+        lt = np.ascontiguousarray(lut, np.uint8).reshape(-1)
+        if lt.size != 256:
+            raise ValueError("the logistic table has 256 entries")
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self.nl.check(self.nl.lib.mww_stream_set_quantized(self.h, vp(w), w.size, vp(iv), iv.size, float(input_scale), vp(lt)))
+
+    def read_q8(self, n=None) -> np.ndarray:
+        n = self.n_out if n is None else int(n)
+        out = np.zeros(n, np.uint8)
+        self.nl.check(self.nl.lib.mww_stream_read_q8(self.h, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def get_state_q8(self) -> np.ndarray:
+        a = np.zeros(self.n_state, np.int8)
+        self.nl.check(self.nl.lib.mww_stream_get_state_q8(self.h, a.ctypes.data_as(C.c_void_p), a.size))
+        return a
 
 
 FEATURE_BINS_ = 40

@@ -115,6 +115,43 @@ class StreamingModel:
         return self.native.metrics(offsets, kind, cutoffs, sliding_window_length, ignore_slices_after_accept, ignore_slices_after_accept)
 
 
+class QuantizedStreamingModel(StreamingModel):
+    """The int8 quantized streaming model (``--test_tflite_streaming_quantized``) on the int8 kernel
+    (csrc/tu_stream_q8.hip), with the methods of ``StreamingModel``: ``model_or_file`` is a ``quantize.QuantizedModel`` or
+    the path of its ``.npz``; ``context`` is the float MixedNet ``Model`` whose context (device, HIP stream, resident
+    feature stores) the stream borrows.  Probabilities are ``uint8 / 255`` in float32 (``read_q8`` gives the uint8
+    outputs), in the same device buffer the metrics kernel reads."""
+
+    def __init__(self, model_or_file, stride: int, mode: str = "stream", context=None):
+        from .quantize import QuantizedModel
+        q = model_or_file if isinstance(model_or_file, QuantizedModel) else QuantizedModel.load(model_or_file)
+        if context is None:
+            raise ValueError("QuantizedStreamingModel needs the float model whose context it shares (context=...)")
+        if mode not in native.STREAM_MODES:
+            raise ValueError("mode must be 'stream' or 'non_stream'")
+        if int(stride) != int(q.desc["stride"]):
+            raise ValueError("the streaming stride (%d) must be the quantized model's stride (%d)" % (stride, q.desc["stride"]))
+        self.model = context
+        self.quantized = q
+        self.mode = mode
+        self.stride = int(stride)
+        self.frames = int(q.desc["frames"])
+        self.desc = dict(q.desc, mode=mode)
+        self.native = native.Stream(context.engine, self.desc)
+        self.native.set_quantized(*q.packed())
+
+    def set_weights(self, weights):
+        raise NotImplementedError("a quantized streaming model takes new parameters from quantize.quantize")
+
+    def read_q8(self) -> np.ndarray:
+        """uint8 outputs of the last call"""
+        return self.native.read_q8()
+
+    def get_state_q8(self) -> np.ndarray:
+        """int8 rings (the layout of Stream.get_state)"""
+        return self.native.get_state_q8()
+
+
 # ------------------------------------------------------------------------------------------ restated post-processing
 
 def moving_average(probabilities, sliding_window_length=5) -> np.ndarray:

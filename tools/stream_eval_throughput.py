@@ -3,6 +3,8 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
 (``Engine.evaluate_windows`` over every s-th 194-frame window of the ambient audio).  Prints one JSON line.
 
     python tools/stream_eval_throughput.py --hours 20
+    python tools/stream_eval_throughput.py --hours 20 --quantized   # the int8 model (csrc/tu_stream_q8.hip); also times
+                                                                    # the calibration pass (500 spectrograms) + quantization
 """
 import argparse
 import json
@@ -13,7 +15,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from microwakeword_amd import mixednet, native, streaming  # noqa: E402
+from microwakeword_amd import mixednet, native, quantize, streaming  # noqa: E402
 
 DEF = dict(pointwise_filters="48,48,48,48", residual_connection="0,0,0,0", repeat_in_block="1,1,1,1",
            mixconv_kernel_sizes="[5],[9],[13],[21]", max_pool=0, first_conv_filters=32, first_conv_kernel_size=3,
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--frames", type=int, default=194)
     ap.add_argument("--window_hours", type=float, default=1.0, help="ambient hours the windowed alternative is timed on")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--quantized", action="store_true", help="time the int8 streaming model instead of the float one")
     a = ap.parse_args()
     T = a.frames
     model = mixednet.model(DEF, (T, 40), 1024, max_batch=1024, seed=3)
@@ -47,6 +50,20 @@ def main():
     pos_win["store"], pos_win["pad_rows"] = 1, np.maximum(0, T - pos_len)
     pos_win["copy_rows"], pos_win["src_elem"] = pos_len, pos_off * 40
     sm = streaming.StreamingModel(model, 1, "stream")
+    extra = {}
+    if a.quantized:
+        # the calibration pass of --test_tflite_streaming_quantized: 500 spectrograms of T frames, chunks of s = 1
+        cal = rng.integers(0, 1000, size=(quantize.CALIBRATION_SAMPLES * (T - 1), 40)).astype(np.float32) * streaming.SCALE_U16
+        sm.native.calibrate_host(cal[:1000])   # warm-up
+        cs = []
+        for _ in range(a.reps):
+            c = streaming.StreamingModel(model, 1, "stream")
+            t0 = time.perf_counter()
+            ranges = c.native.calibrate_host(cal)
+            qm = quantize.quantize(model, ranges)
+            cs.append(time.perf_counter() - t0)
+        sm = streaming.QuantizedStreamingModel(qm, 1, "stream", context=model)
+        extra = {"quantized": "int8", "calibration_frames": int(cal.shape[0]), "calibration_seconds": round(min(cs), 4)}
 
     def once():
         off = sm.native.run(amb_win)
@@ -76,7 +93,7 @@ def main():
     model.engine.evaluate_windows(win, labels, 1024)
     model.engine.synchronize()
     tw = time.perf_counter() - t0
-    rec = {"tool": "stream_eval_throughput", "model": "mixednet default (T=%d)" % T, "stride": 1, "ambient_hours": round(amb_frames * 0.02 / 3600, 3),
+    rec = {"tool": "stream_eval_throughput", "model": "mixednet default (T=%d)" % T, **extra, "stride": 1, "ambient_hours": round(amb_frames * 0.02 / 3600, 3),
            "ambient_tracks": n_amb, "positives": a.positives, "outputs": n_out, "seconds": round(t, 4),
            "outputs_per_s": round(n_out / t, 1), "audio_hours_per_s": round(hours / t, 3),
            "windowed_outputs": nw, "windowed_seconds": round(tw, 4), "windowed_outputs_per_s": round(nw / tw, 1),
