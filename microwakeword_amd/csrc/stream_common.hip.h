@@ -203,7 +203,7 @@ inline int plan(const mww_stream_desc& d, SNet& net, std::vector<SLayer>& layers
   for (int b = 0; b < d.n_blocks; ++b) {
     const int nk = d.n_kernels[b], f = d.pointwise_filters[b];
     if (nk <= 0 || nk > MWW_STREAM_MAX_KERNELS) return unsupported("block " + std::to_string(b) + ": 1..8 MixConv kernels");
-    if (d.repeat[b] <= 0 || d.repeat[b] > MWW_STREAM_MAX_REPEAT) return unsupported("block " + std::to_string(b) + ": repeat must be 1..4");
+    if (d.repeat[b] <= 0 || d.repeat[b] > MWW_STREAM_MAX_REPEAT) return unsupported("block " + std::to_string(b) + ": repeat must be 1..8");
     if (f <= 0 || f > 1024) return unsupported("block " + std::to_string(b) + ": pointwise filters must be 1..1024");
     int K = 0;
     for (int g = 0; g < nk; ++g) {

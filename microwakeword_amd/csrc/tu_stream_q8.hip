@@ -297,6 +297,16 @@ int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_wei
   const SNet& net = s->net;
   for (int64_t t = 0; t < net.n_layers + 3; ++t)
     if (ints[izp + t] < -128 || ints[izp + t] > 127) return mww::set_error(MWW_ERR_INVALID, "zero points must lie in [-128, 127]");
+  // q8_requant shifts by at most 31 bits either way: QuantizeMultiplier emits shifts in [-31, 30] and multipliers >= 0,
+  // anything else (from a hand-made .npz) would reach x >> e with e >= 32 on the device
+  auto bad_requant = [&](int64_t at, int64_t cout) {
+    for (int64_t c = 0; c < cout; ++c)
+      if (ints[at + cout + c] < 0 || ints[at + 2 * cout + c] < -31 || ints[at + 2 * cout + c] > 30) return true;
+    return false;
+  };
+  bool bad = bad_requant(i1, net.c1) || bad_requant(id, 1);
+  for (size_t l = 0; l < s->layers.size() && !bad; ++l) bad = bad_requant(li[l], s->layers[l].cout);
+  if (bad) return mww::set_error(MWW_ERR_INVALID, "requantization multipliers must be >= 0 and shifts lie in [-31, 30]");
   mww::stream_q8_free(s);
   // rings at reset: real zero, i.e. each ring's tensor zero point (conv1: the input, MixConv: its input, head: the last map)
   std::vector<int8_t> st0((size_t)s->n_state + 4, 0);

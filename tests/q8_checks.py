@@ -28,13 +28,15 @@ def make_quantized(lib, flags, T, cal_frames=400, seed=42):
     return om, model, quantize.quantize(model, ranges)
 
 
-def synthetic_quantized(desc, seed=0):
+def synthetic_quantized(desc, seed=0, ranges=None):
     """a QuantizedModel of any stream description from random Keras-order weights and fixed ranges (topologies no float
-    engine instantiates, e.g. tiles too large for LDS); run it with the context of any float model"""
+    engine instantiates, e.g. tiles too large for LDS); run it with the context of any float model.  ``ranges``
+    [n_tensors, 2] replaces the fixed ranges (which leave odd topologies with a near-constant logit: see check_spread)."""
+    fixed = ranges is None
     rng = np.random.default_rng(seed)
     k1, c = int(desc["conv1_kernel"]), int(desc["conv1_filters"])
     w = [rng.normal(0, 0.1, (k1, 1, 40, c))]
-    ranges = [(0.0, 26.0), (0.0, 4.0)]
+    fixed_ranges, ranges = ranges, [(0.0, 26.0), (0.0, 4.0)]
     for kind, _, _, ks, ci, co in quantize.plan_ops(desc):
         if kind == "mix":
             for gc, k in zip(quantize.split_channels(ci, len(ks)), ks):
@@ -47,7 +49,45 @@ def synthetic_quantized(desc, seed=0):
     c_last = int(desc["blocks"][-1][2])
     w += [rng.normal(0, 0.05, (int(desc["t_final"]) * c_last, 1)), rng.normal(0, 0.1, 1)]
     ranges.append((-8.0, 8.0))
+    if not fixed:
+        ranges = fixed_ranges
     return quantize.quantize_weights(desc, w, np.array(ranges, np.float32))
+
+
+SPREAD_MIN_DISTINCT, SPREAD_MAX_SHARE, SPREAD_MAX_CLAMPED = 32, 0.5, 0.9
+
+
+def spread(qm, frames):
+    """(distinct int8 logits, share of the most frequent one, largest share of a ring-feeding tensor's values at a clamp
+    value) of the ORACLE over ``frames`` from reset - what an int8 comparison on these inputs can see at all"""
+    trace = []
+    _, logit, _ = qo.whole_sequence(qm, frames, trace=trace)
+    vals, counts = np.unique(logit, return_counts=True)
+    clamped = 0.0
+    for relu, zp, a in trace:
+        if a.size:
+            lo = max(-128, zp) if relu else -128
+            clamped = max(clamped, float(np.mean((a == lo) | (a == 127))))
+    return int(vals.size), float(counts.max() / max(1, logit.size)), clamped
+
+
+def check_spread(qm, frames, what=""):
+    """a condition on the INPUTS of an int8 comparison, from the oracle alone: at least 32 distinct logits, none more
+    than half of the time, no ring-feeding tensor more than 90 % at its clamp values"""
+    distinct, share, clamped = spread(qm, frames)
+    assert distinct >= SPREAD_MIN_DISTINCT and share <= SPREAD_MAX_SHARE and clamped <= SPREAD_MAX_CLAMPED, (
+        what, "distinct logits %d, most frequent %.3f, clamped %.3f" % (distinct, share, clamped))
+    return distinct, share, clamped
+
+
+def check_logits(qsm, ref_lq, what):
+    """the kernel's int8 logit (float32 in the logit buffer) equals the oracle's: the uint8 output is a many-to-one table
+    of it (a handful of distinct outputs from tens of logits), so this is where a Dense / requantization error shows"""
+    lq = qsm.native.read(want_logits=True)[1]
+    ref = np.asarray(ref_lq, np.float32)
+    assert lq.shape == ref.shape, (what, lq.shape, ref.shape)
+    assert np.array_equal(lq, ref), "%s: %d of %d int8 logits differ (largest difference %g)" % (
+        what, int(np.sum(lq != ref)), lq.size, float(np.abs(lq - ref).max()))
 
 
 def _check_probs(qsm, u8):
@@ -56,8 +96,8 @@ def _check_probs(qsm, u8):
 
 
 def check_q8_stream_parity(lib, flags, T, calls, seed=0, qm=None, model=None):
-    """``calls``: (lengths, pads) run as successive mww_stream_run calls on one int8 stream; uint8 outputs and int8 rings
-    after every call equal the oracle's.  Returns (model, qm, per-call uint8 outputs)."""
+    """``calls``: (lengths, pads) run as successive mww_stream_run calls on one int8 stream; uint8 outputs, int8 logits
+    and int8 rings after every call equal the oracle's.  Returns (model, qm, per-call uint8 outputs)."""
     if qm is None:
         _, model, qm = make_quantized(lib, flags, T)
     s = int(flags["stride"])
@@ -71,9 +111,10 @@ def check_q8_stream_parity(lib, flags, T, calls, seed=0, qm=None, model=None):
         for t in range(len(lengths)):
             assert off[t + 1] - off[t] == lengths[t] // s
         fed += [f[:(len(f) // s) * s] for f in tr.frames]
-        ref_u8, _, ref_st = qo.whole_sequence(qm, np.concatenate(fed + [np.zeros((0, 40), np.float32)], 0))
+        ref_u8, ref_lq, ref_st = qo.whole_sequence(qm, np.concatenate(fed + [np.zeros((0, 40), np.float32)], 0))
         assert np.array_equal(u8, ref_u8[ref_u8.size - u8.size:]), "call %d: %d of %d outputs differ" % (
             ci, int(np.sum(u8 != ref_u8[ref_u8.size - u8.size:])), u8.size)
+        check_logits(qsm, ref_lq[ref_lq.size - u8.size:], "call %d" % ci)
         assert np.array_equal(qsm.get_state_q8(), ref_st), "call %d: rings differ" % ci
         _check_probs(qsm, u8)
         outs.append(u8)
@@ -87,8 +128,12 @@ def check_q8_non_stream(lib, flags, T, lengths, pads, seed=0, qm=None, model=Non
     tr = sc.Tracks(model, lengths, pads, seed=seed)
     off = qsm.native.run(tr.win)
     u8 = qsm.read_q8()
+    lq = []
     for t, f in enumerate(tr.frames):
-        assert np.array_equal(u8[off[t]:off[t + 1]], qo.non_stream(qm, f, T)), "track %d" % t
+        ref_u8, ref_lq = qo.non_stream(qm, f, T, want_logits=True)
+        assert np.array_equal(u8[off[t]:off[t + 1]], ref_u8), "track %d" % t
+        lq.append(ref_lq)
+    check_logits(qsm, np.concatenate(lq + [np.zeros(0, np.int8)]), "non_stream")
     _check_probs(qsm, u8)
     return qsm, tr, off, u8
 

@@ -45,9 +45,38 @@ def mbqm(x, M, shift):
     return rdpot(srdhm(wrap32(np.asarray(x, np.int64) << left), M), right)
 
 
+BRANCHES = None   # a set while ``record_branches`` is active: the requantization / input branches the ORACLE took
+
+
+class record_branches:
+    """``with record_branches() as seen:`` collects the names of the branches every ``requant`` / ``quantize_input`` of
+    this module takes inside the block (the oracle is instrumented, never the kernel): rq-left-shift, rq-right-shift>=16,
+    rq-shift=-31, rq-shift=+30, rq-clamp-low-relu, rq-clamp-low-norelu, rq-clamp-127, rq-zp-out=-128 / 0 / 127,
+    in-sat-low, in-sat-high."""
+
+    def __enter__(self):
+        global BRANCHES
+        self.prev, BRANCHES = BRANCHES, set()
+        return BRANCHES
+
+    def __exit__(self, *exc):
+        global BRANCHES
+        BRANCHES = self.prev
+        return False
+
+
 def requant(acc, op, zp_out, relu):
     lo = max(-128, zp_out) if relu else -128
-    return np.clip(mbqm(acc, op["multiplier"], op["shift"]) + zp_out, lo, 127).astype(np.int64)
+    v = mbqm(acc, op["multiplier"], op["shift"]) + zp_out
+    if BRANCHES is not None and np.size(acc):
+        sh = np.asarray(op["shift"], np.int64)
+        for name, hit in (("rq-left-shift", np.any(sh > 0)), ("rq-right-shift>=16", np.any(sh <= -16)),
+                          ("rq-shift=-31", np.any(sh == -31)), ("rq-shift=+30", np.any(sh == 30)),
+                          ("rq-clamp-low-relu" if relu else "rq-clamp-low-norelu", np.any(v < lo)),
+                          ("rq-clamp-127", np.any(v > 127)), ("rq-zp-out=%d" % zp_out, zp_out in (-128, 0, 127))):
+            if hit:
+                BRANCHES.add(name)
+    return np.clip(v, lo, 127).astype(np.int64)
 
 
 def imatmul(a, b):
@@ -58,6 +87,11 @@ def imatmul(a, b):
 def quantize_input(x, scale, zp):
     """float32(x / scale) + float32(zp), truncated, saturated"""
     t = np.asarray(x, np.float32) / np.float32(scale) + np.float32(zp)
+    if BRANCHES is not None and t.size:
+        if np.any(np.trunc(t) < -128):
+            BRANCHES.add("in-sat-low")
+        if np.any(np.trunc(t) > 127):
+            BRANCHES.add("in-sat-high")
     return np.clip(np.trunc(t), -128, 127).astype(np.int64)
 
 
@@ -118,9 +152,10 @@ class Q:
         return u8, u8.astype(np.float32) * INV255
 
 
-def whole_sequence(qm, frames):
+def whole_sequence(qm, frames, trace=None):
     """From reset over the fed frames [0, floor(L/s)*s) -> (uint8 [n], int8 logits [n], rings int8 flat in the layout of
-    mww_stream_get_state after the call)"""
+    mww_stream_get_state after the call).  ``trace``: a list that receives (relu, zero point, values) of every activation
+    tensor that feeds a ring (each MixConv's input, the head's input)."""
     q = Q(qm)
     F = (len(frames) // q.s) * q.s
     n = F // q.s
@@ -132,7 +167,11 @@ def whole_sequence(qm, frames):
             R = op["weights"].shape[0] - 1
             a = np.concatenate([np.full((R, a.shape[1]), q.zp[1 + li], np.int64), a], 0)
             rings.append(a[a.shape[0] - R:].reshape(-1))
+            if trace is not None:   # a MixConv input is conv1's or a pointwise layer's output (ReLU) unless a MixConv precedes it
+                trace.append((li == 0 or q.layers[li - 1]["kind"] == "pw", q.zp[1 + li], a[R:]))
         a = q.layer(li, a)
+    if trace is not None:
+        trace.append((True, q.zp[1 + len(q.layers)], a))
     h = np.concatenate([np.full((q.tf - 1, a.shape[1]), q.zp[1 + len(q.layers)], np.int64), a], 0)
     if q.tf > 1:
         rings.append(h[h.shape[0] - (q.tf - 1):].reshape(-1))
@@ -191,15 +230,16 @@ class StepStreamQ8:
         return self.q.output(logit)[0]
 
 
-def non_stream(qm, frames, T):
-    """the non-streaming model (no rings) on the windows ending at T, T + s, ... <= L -> uint8"""
+def non_stream(qm, frames, T, want_logits=False):
+    """the non-streaming model (no rings) on the windows ending at T, T + s, ... <= L -> uint8 (and the int8 logits)"""
     q = Q(qm)
     L = len(frames)
     if L < T:
-        return np.zeros(0, np.uint8)
+        return (np.zeros(0, np.uint8), np.zeros(0, np.int8)) if want_logits else np.zeros(0, np.uint8)
     a = q.conv1(quantize_input(np.asarray(frames, np.float32), q.scale0, q.zp[0]))
     for li in range(len(q.layers)):
         a = q.layer(li, a)
     logit = q.head(a)
     n = (L - T) // q.s + 1
-    return q.output(logit[:n])[0]
+    u8 = q.output(logit[:n])[0]
+    return (u8, logit[:n].astype(np.int8)) if want_logits else u8

@@ -69,6 +69,31 @@ def stream_reference(om, flags, frames_list):
     return out
 
 
+def flags_of(desc):
+    """the MixedNet flag set of a stream description (any the streaming plan accepts)"""
+    return dict(ec.DEF, first_conv_filters=int(desc["conv1_filters"]), first_conv_kernel_size=int(desc["conv1_kernel"]),
+                stride=int(desc["stride"]), pointwise_filters="".join("%d," % f for _, _, f in desc["blocks"]),
+                repeat_in_block="".join("%d," % r for r, _, _ in desc["blocks"]),
+                mixconv_kernel_sizes="".join("[%s]," % ",".join(str(int(k)) for k in ks) for _, ks, _ in desc["blocks"]),
+                residual_connection="".join("0," for _ in desc["blocks"]))   # trailing commas: one block stays a list
+
+
+def frames_of(desc):
+    """window length T of the non-streaming model whose final map has desc["t_final"] frames ((T - k1) % stride == 0)"""
+    sum_r = sum(int(r) * (max(ks) - 1) for r, ks, _ in desc["blocks"])
+    return (int(desc["t_final"]) + sum_r - 1) * int(desc["stride"]) + int(desc["conv1_kernel"])
+
+
+_CONTEXT = {}
+
+
+def context_model(lib):
+    """one small float model per library: native.Stream(model.engine, desc) runs any description in its context"""
+    if id(lib) not in _CONTEXT:
+        _CONTEXT[id(lib)] = (lib, make_model(lib, ec.DEF, 52)[1])
+    return _CONTEXT[id(lib)][1]
+
+
 def _compare(got_p, got_z, ref_z, what):
     ref_z = np.asarray(ref_z, np.float64)
     assert got_p.shape == ref_z.shape, (what, got_p.shape, ref_z.shape)
@@ -77,10 +102,30 @@ def _compare(got_p, got_z, ref_z, what):
         assert np.abs(got_p - so.sigmoid(ref_z)).max() <= PROB_TOL, (what, np.abs(got_p - so.sigmoid(ref_z)).max())
 
 
+def compare_state(got, ref, net, what):
+    """``mww_stream_get_state`` against the oracle's rings: the conv1 ring is a copy of input frames (exact), every other
+    ring holds plain activations (FWD_TOL).  Returns the largest activation-ring error."""
+    got, ref = np.asarray(got), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    n1 = net.r1 * 40
+    assert np.array_equal(got[:n1], ref[:n1].astype(np.float32)), (what, "conv1 ring differs")
+    err = float(np.abs(got[n1:] - ref[n1:]).max()) if got.size > n1 else 0.0
+    if not err <= ec.FWD_TOL:   # (a NaN fails too) name the first ring that is off: it localises the layer
+        at, names = n1, ["mixconv %d" % i for i in range(len(net.ring_sizes()) - 2)] + ["head"]
+        for name, n in zip(names, net.ring_sizes_flat()[1:]):
+            e = float(np.abs(got[at:at + n] - ref[at:at + n]).max()) if n else 0.0
+            assert e <= ec.FWD_TOL, (what, "ring of " + name, e)
+            at += n
+        raise AssertionError((what, "rings", err))
+    return err
+
+
 def check_stream_parity(lib, flags, T, calls, seed=0):
-    """``calls``: list of (lengths, pads) run as successive mww_stream_run calls on one stream (state carried)."""
+    """``calls``: list of (lengths, pads) run as successive mww_stream_run calls on one stream (state carried); the
+    rings after every call are held to the oracle's as well."""
     om, model = make_model(lib, flags, T)
     sm = streaming.StreamingModel(model, int(flags["stride"]), "stream")
+    net, s = so.Net(flags, om), int(flags["stride"])
     all_frames, got = [], []
     for ci, (lengths, pads) in enumerate(calls):
         tr = Tracks(model, lengths, pads, seed=seed + ci, store_ids=(2 * ci, 2 * ci + 1))
@@ -91,6 +136,8 @@ def check_stream_parity(lib, flags, T, calls, seed=0):
             assert off[t + 1] - off[t] == lengths[t] // int(flags["stride"])
             got.append((p[off[t]:off[t + 1]], z[off[t]:off[t + 1]]))
         all_frames += tr.frames
+        fed = np.concatenate([f[:(len(f) // s) * s] for f in all_frames] + [np.zeros((0, 40), np.float32)], 0)
+        compare_state(sm.native.get_state(), so.whole_sequence(net, fed, rings=True)[1], net, "state after call %d" % ci)
     ref = stream_reference(om, flags, all_frames)
     for i, ((p, z), r) in enumerate(zip(got, ref)):
         _compare(p, z, r, "track %d" % i)

@@ -9,6 +9,9 @@ Keras-order weights of ``oracle.model_oracle.OracleModel``.
   * ``whole_sequence``  the vectorised form: each Stream layer's input left-padded with its R state frames, every layer
                      valid and right-aligned, the Dense at every position of the final map.
   * ``non_stream_windows``  the non-streaming model on the windows ending at T, T + s, ... <= L.
+``Net(..., dtype=np.float32)`` runs the same restatement in float32 (its distance from the float64 form is the rounding a
+float32 implementation of these sums carries: tests/stream_sweep.py conditions its inputs on it).  ``StepStream.state()`` and
+``whole_sequence(..., rings=True)`` give the rings in the layout of mww_stream_get_state.
 """
 from __future__ import annotations
 
@@ -20,9 +23,10 @@ BN_EPS = 1e-3
 
 
 class Net:
-    def __init__(self, flags, om):
+    def __init__(self, flags, om, dtype=np.float64):
         self.flags = flags
-        w = {v.name: np.asarray(v.value, np.float64) for v in om.vars}
+        self.dtype = np.dtype(dtype)
+        w = {v.name: np.asarray(v.value, self.dtype) for v in om.vars}
         self.w = w
         self.k1, self.s = int(flags["first_conv_kernel_size"]), int(flags["stride"])
         self.r1 = max(0, self.k1 - self.s)
@@ -46,7 +50,7 @@ class Net:
         k = self.w["conv1.kernel"][:, 0]   # [k1, 40, C1]
         m = (mem.shape[0] - self.k1) // self.s + 1
         if m <= 0:
-            return np.zeros((0, k.shape[2]))
+            return np.zeros((0, k.shape[2]), self.dtype)
         win = np.lib.stride_tricks.sliding_window_view(mem, self.k1, axis=0)[::self.s][:m]   # [m, 40, k1]
         return np.maximum(np.einsum("mbk,kbc->mc", win, k), 0)
 
@@ -70,10 +74,20 @@ class Net:
         y = x @ self.w[p + ".pw.kernel"][0, 0]
         g, b = self.w[p + ".bn.gamma"], self.w[p + ".bn.beta"]
         mu, var = self.w[p + ".bn.moving_mean"], self.w[p + ".bn.moving_variance"]
-        return np.maximum((y - mu) / np.sqrt(var + BN_EPS) * g + b, 0)
+        return np.maximum((y - mu) / np.sqrt(var + self.dtype.type(BN_EPS)) * g + b, 0)
 
     def ring_sizes(self):
         return [self.r1] + [max(ks) - 1 for kind, _, ks in self.layers if kind == "mix"] + [self.tf - 1]
+
+    def ring_sizes_flat(self):
+        """elements of every ring in state order: conv1 [r1, 40], each MixConv [K - 1, C_in], the head [tf - 1, C_last]"""
+        out, c = [self.r1 * 40], self.w["conv1.kernel"].shape[3]
+        for kind, p, ks in self.layers:
+            if kind == "mix":
+                out.append((max(ks) - 1) * c)
+            else:
+                c = self.w[p + ".pw.kernel"].shape[3]
+        return out + [(self.tf - 1) * self.c_last]
 
 
 class StepStream:
@@ -85,19 +99,25 @@ class StepStream:
 
     def reset(self):
         n = self.net
-        self.ring1 = np.zeros((n.r1, 40))
+        self.ring1 = np.zeros((n.r1, 40), n.dtype)
         self.rings = {}
         c = n.w["conv1.kernel"].shape[3]
         for kind, p, ks in n.layers:
             if kind == "mix":
-                self.rings[p] = np.zeros((max(ks) - 1, c))
+                self.rings[p] = np.zeros((max(ks) - 1, c), n.dtype)
             else:
                 c = n.w[p + ".pw.kernel"].shape[3]
-        self.hring = np.zeros((n.tf - 1, n.c_last))
+        self.hring = np.zeros((n.tf - 1, n.c_last), n.dtype)
+
+    def state(self):
+        """the rings, flat, in the layout of mww_stream_get_state: conv1, every MixConv in layer order, the head"""
+        n = self.net
+        parts = [self.ring1.reshape(-1)] + [self.rings[p].reshape(-1) for kind, p, _ in n.layers if kind == "mix"]
+        return np.concatenate(parts + [self.hring.reshape(-1)])
 
     def step(self, chunk):
         n = self.net
-        mem = np.concatenate([self.ring1, chunk], 0)
+        mem = np.concatenate([self.ring1, np.asarray(chunk, n.dtype)], 0)
         if n.r1:
             self.ring1 = mem[-n.r1:]
         x = n.conv1(mem)
@@ -122,22 +142,33 @@ class StepStream:
         return np.array([self.step(frames[i:i + s]) for i in range(0, (len(frames) // s) * s, s)])
 
 
-def whole_sequence(net: Net, frames, state=None):
-    """Vectorised streaming form from zero state over the fed frames [0, floor(L/s)*s) -> logits [floor(L/s)]."""
-    s = net.s
+def whole_sequence(net: Net, frames, state=None, rings=False):
+    """Vectorised streaming form from zero state over the fed frames [0, floor(L/s)*s) -> logits [floor(L/s)]; with
+    ``rings`` also the state after those frames (the last R rows of every Stream layer's padded input, flat, in the layout
+    of mww_stream_get_state)."""
+    s, dt = net.s, net.dtype
     F = (len(frames) // s) * s
-    x = np.concatenate([np.zeros((net.r1, 40)), np.asarray(frames[:F], np.float64)], 0)
+    if F == 0:
+        z = np.zeros(0, dt)
+        return (z, np.zeros(sum(net.ring_sizes_flat()), dt)) if rings else z
+    x = np.concatenate([np.zeros((net.r1, 40), dt), np.asarray(frames[:F], dt)], 0)
+    st = [x[x.shape[0] - net.r1:].reshape(-1)]
     a = net.conv1(x)
     for kind, p, ks in net.layers:
         if kind == "mix":
-            a = net.mix(p, ks, np.concatenate([np.zeros((max(ks) - 1, a.shape[1])), a], 0))
+            R = max(ks) - 1
+            a = np.concatenate([np.zeros((R, a.shape[1]), dt), a], 0)
+            st.append(a[a.shape[0] - R:].reshape(-1))
+            a = net.mix(p, ks, a)
         else:
             a = net.pw(p, a)
-    h = np.concatenate([np.zeros((net.tf - 1, a.shape[1])), a], 0)
+    h = np.concatenate([np.zeros((net.tf - 1, a.shape[1]), dt), a], 0)
+    st.append(h[h.shape[0] - (net.tf - 1):].reshape(-1))
     n = F // s
     W = net.wd.reshape(net.tf, -1)
     win = np.lib.stride_tricks.sliding_window_view(h, net.tf, axis=0)[:n]   # [n, C, tf]
-    return np.einsum("nct,tc->n", win, W) + net.bd
+    z = np.einsum("nct,tc->n", win, W) + net.bd
+    return (z, np.concatenate(st)) if rings else z
 
 
 def non_stream_windows(om, frames, T, s):
