@@ -1,0 +1,963 @@
+// The conv/BN graph engine of libmww_hip.so (Inception, and every MixedNet off the block kernels' shape table): validation and
+// planning of a mww_convnet_desc, LDS sizing, and the forward / backward launch sequences.  The convolution kernels are
+// instantiated and launched in tu_graph.hip (graph_launch.hip.h); the small non-template kernels are defined there too
+// and launched from here.
+#define MWW_BLOCK_TU 1        // the non-template kernels of the block-kernel headers belong to mww_lib.hip,
+#define MWW_GRAPH_HOST_TU 1   // those of the graph kernel headers to tu_graph.hip
+#include <cstring>
+
+#include "engine.hip.h"
+#include "graph_launch.hip.h"
+
+namespace mww {
+
+static_assert(kGMaxSrc == MWW_MAX_OP_SOURCES, "GOp holds MWW_MAX_OP_SOURCES sources");
+
+namespace {
+
+bool g_width_supported(int n) {
+#define X(N) if (n == N) return true;
+  MWW_G_WIDTHS(X)
+#undef X
+  return false;
+}
+
+// Dynamic LDS of the MFMA graph kernels (kernels_graph.hip.h) for an op whose tiles hold rin input rows / rout output rows
+// (forward naming; the whole window, or a frame chunk of a 1x1 op): weights [k][cin4][NCW] zero-padded to whole k-steps /
+// filter tiles; gconv_body's publish scratch aliases the first 2 * kThreads floats, its MODE 1 keeps the statistics pairs of
+// the second and third source behind the tiles.
+size_t g_up16(int v) { return (size_t)((v + 15) / 16 * 16); }
+size_t g_lds_fwd(const GOp& o, int rin, int rout) {
+  return g_lds_body((size_t)o.k * g_up4(o.cin) * g_up16(o.cout) + (size_t)rin * (o.cin | 1) + (size_t)rout * (o.cout | 1), 0);
+}
+size_t g_lds_dx(const GOp& o, int rows_dp_padded, int rows_dx) {
+  return g_lds_body((size_t)o.k * g_up4(o.cout) * g_up16(o.cin) + (size_t)rows_dp_padded * (o.cout | 1) + (size_t)rows_dx * (o.cin | 1), o.n_src - 1);
+}
+size_t g_lds_wg(const GOp& o, int rin, int rout) {
+  const int tasks = o.k * o.cin, mt = (tasks + 15) / 16, nt = (o.cout + 15) / 16;
+  size_t b = (((size_t)rin * (o.cin | 1) + 6) / 4 * 4 + g_up4(rout) * (size_t)gwg_dp_pitch(o.cout)) * sizeof(float);
+  if (gwg_kparts(tasks) > 1) b = std::max(b, (size_t)gwg_kparts(tasks) * mt * nt * 256 * sizeof(float));   // scratch of the sum over the frame parts
+  return b;
+}
+
+// Frame chunks ("graph_frame_chunks"; kernels_graph.hip.h, CH instantiations): S work items of Tc output frames per window -
+// the 1x1 ops in all three roles, ops with k > 1 in the forward convolution and in a weight gradient that has no data
+// gradient next to it (the stem).  0 = whole windows (the default: the chunked kernels are covered by the parity tests but have not been timed
+// on the GPU yet), 1 = as many chunks (<= 4) as it takes for the launch's tiles to fit four times per CU, 2..4 = that many.
+// Only with the statistics hand-over (such graphs have no residual branches, which the chunked data gradient does not
+// handle) and never for twin launches.
+// input frames (with halo) of a chunk of t output frames
+int g_chunk_in(const GOp& o, int t) { return (t - 1) * o.stride + (o.k - 1) * o.dil + 1; }
+
+int g_chunks(const mww_ctx* c, const GOp& o, bool inl, bool backward, int* Tc) {
+  *Tc = o.tout;
+  // the data gradient is only chunked without a halo (k = 1); forward convolution and a weight gradient on its own take any k
+  if (!inl || c->g_chunks == 0 || o.kind != MWW_OP_CONV || o.tout < 32 || (backward && o.needs_dx && o.k != 1)) return 1;
+  int S = c->g_chunks;
+  if (S == 1) {
+    for (S = 1; S < 4; ++S) {
+      const int t = (o.tout + S - 1) / S, ti = g_chunk_in(o, t);
+      const size_t lds = backward ? std::max(g_lds_wg(o, ti, t), o.needs_dx ? g_lds_dx(o, t, t) : 0) : g_lds_fwd(o, ti, t);
+      if (lds + 3072 <= 40960) break;
+    }
+  }
+  S = std::min(S, 4);
+  *Tc = (o.tout + S - 1) / S;
+  return (S - 1) * *Tc < o.tout ? S : 1;   // (every chunk non-empty)
+}
+
+}  // namespace
+
+int g_planes(const mww_ctx* c, const GOp& o) { return (c->g_planar && o.planes > 1) ? o.planes : 1; }
+long long g_pstride(const mww_ctx* c, const GOp& o) { return (long long)c->d.max_batch * o.tout * o.pc + kPlanePad; }
+
+namespace {
+
+// the static shape of op `o`, or 0
+int g_shape_id(const mww_ctx* c, const GOp& o) {
+  if (!c->g_static || o.kind != MWW_OP_CONV || o.dil != 1 || o.stride != 1 || o.res_src >= 0 || o.n_src < 1) return 0;
+  if (o.tin > kGTmax || o.tout > kGTmax) return 0;   // a window's rows travel in a fixed set of registers (GSliceRegs)
+  int C[kGMaxSrc] = {0, 0, 0}, L[kGMaxSrc] = {0, 0, 0};
+  for (int i = 0; i < o.n_src; ++i) {
+    if (o.src[i] < 0) {
+      C[i] = L[i] = MWW_FEATURE_BINS;
+    } else {
+      const GOp& pr = c->G[o.src[i]];
+      if (pr.res_src >= 0) return 0;
+      C[i] = o.scn[i];
+      L[i] = g_planes(c, pr) > 1 ? o.scn[i] : pr.cout;   // (a plane of a planar producer is a whole tensor of its own)
+    }
+    const int v = ((C[i] | L[i]) & 3) == 0 ? 4 : (((C[i] | L[i]) & 1) == 0 ? 2 : 1);
+    if (o.src[i] >= 0 && L[i] != C[i] && o.sc0[i] % v) return 0;   // the slice must start on the vector width the static staging uses
+  }
+#define X(ID, K, N, C0, L0, C1, L1, C2, L2)                                                                     \
+  if (o.k == K && o.n_src == N && C[0] == C0 && L[0] == L0 && C[1] == C1 && L[1] == L1 && C[2] == C2 && L[2] == L2) return ID;
+  MWW_G_SHAPES(X)
+#undef X
+  return 0;
+}
+
+}  // namespace
+
+// The stem of a conv/BN graph can read a descriptor-only batch in place ("fused_input", kernels_graph.hip.h XG): exactly one
+// op reads the spectrogram, as its only source, and its shape has a gathering instantiation.
+bool g_stem_gathers(const mww_ctx* c) {
+  if (!c->generic || !c->fused_input || c->d.frames > kGXRows) return false;
+  int readers = 0, stem = -1;
+  for (size_t i = 0; i < c->G.size(); ++i)
+    for (int s = 0; s < c->G[i].n_src; ++s)
+      if (c->G[i].src[s] < 0) {
+        ++readers;
+        stem = (int)i;
+      }
+  if (readers != 1) return false;
+  const GOp& o = c->G[stem];
+  if (o.n_src != 1 || o.toff[0] != 0 || o.tin != c->d.frames) return false;
+  const int shape = g_shape_id(c, o);
+#define XS(ID, N) if (shape == ID && o.cout == N) return true;
+  MWW_G_SHAPE_XG(XS)
+#undef XS
+  return false;
+}
+
+namespace {
+
+bool g_reads_lazy_x(const mww_ctx* c, const GSrc* src, int n) {
+  if (!c->x_lazy) return false;
+  for (int i = 0; i < n; ++i)
+    if (src[i].p == c->x) return true;
+  return false;
+}
+
+GLaunch g_launch_ctx(mww_ctx* c) { return GLaunch{c->stream, c->n_cu, c->g_dgrad_share, &c->g_occ}; }
+
+// result of a launcher of graph_launch.hip.h -> MWW_* code
+int g_rc(int r, const char* no_kernel = "conv width not instantiated") {
+  if (r == 0) return MWW_OK;
+  if (r == kGNoKernel) return fail(MWW_ERR_UNSUPPORTED, no_kernel);
+  return fail(MWW_ERR_HIP, std::string("hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)r));
+}
+
+// forward convolution (ch: the frame-chunk instantiations, a.S > 1)
+int launch_gconv(mww_ctx* c, bool ch, int nc, const GConvArgs& a, const GridPick& pk, size_t lds, int shape = 0) {
+  if (g_reads_lazy_x(c, a.src, a.n_src)) {
+    // descriptor-only batch: the gathering instantiation if there is one and the grid leaves every workgroup at most
+    // kXMaxSamples windows; else x is written out first
+    const int r = ch ? kGNoKernel : k_launch_gconv_xg(g_launch_ctx(c), nc, a, x_gather(c), pk, lds, shape);
+    if (r != kGNoKernel) return g_rc(r);
+    int rcx = materialise_x(c);
+    if (rcx) return rcx;
+  }
+  return g_rc(k_launch_gconv(g_launch_ctx(c), ch, nc, a, pk, lds, shape));
+}
+
+int launch_gwgrad(mww_ctx* c, bool ch, int nc, const GWgradArgs& a, const GridPick& pk, size_t lds, int shape = 0) {
+  if (g_reads_lazy_x(c, a.src, a.n_src)) {   // (as in launch_gconv)
+    const int r = ch ? kGNoKernel : k_launch_gwgrad_xg(g_launch_ctx(c), nc, a, x_gather(c), pk, lds, shape);
+    if (r != kGNoKernel) return g_rc(r);
+    int rcx = materialise_x(c);
+    if (rcx) return rcx;
+  }
+  return g_rc(k_launch_gwgrad(g_launch_ctx(c), ch, nc, a, pk, lds, shape));
+}
+
+float* gbn_slot(GOp& o, int i) { return o.bn + (size_t)i * o.cout; }
+
+// source i of op `oi` as the kernels see it; `backward` adds the gradient routing flags
+GSrc g_make_src(mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
+  GOp& o = c->G[oi];
+  GSrc s;
+  memset(&s, 0, sizeof(s));
+  s.toff = o.toff[i];
+  if (o.src[i] < 0) {
+    s.p = c->x;
+    s.T = c->d.frames;
+    s.C = s.ld = s.sld = MWW_FEATURE_BINS;
+    s.flags = GSRC_IDENTITY;
+    return s;
+  }
+  GOp& pr = c->G[o.src[i]];
+  s.p = pr.p;
+  if (pr.norm == MWW_NORM_BN) {
+    s.scale = gbn_slot(pr, BN_SCALE);
+    s.shift = gbn_slot(pr, BN_SHIFT);
+    s.mean = gbn_slot(pr, BN_MEAN);
+    s.rstd = gbn_slot(pr, BN_RSTD);
+  } else {   // a bias (or nothing) instead of a BN: y = p * 1 + bias
+    s.scale = c->ones;
+    s.shift = pr.norm == MWW_NORM_BIAS ? c->params + pr.o_beta : c->zeros;
+    s.mean = c->zeros;
+    s.rstd = c->ones;
+  }
+  s.g = pr.g;
+  s.gstat_part = pr.gstat_part;
+  s.T = pr.tout;
+  s.C = o.scn[i];
+  s.ld = s.sld = pr.cout;
+  s.c0 = s.scb = o.sc0[i];
+  if (g_planes(c, pr) > 1) {
+    // the producer's tensors are planar and this slice is one of the planes: whole rows of C channels, BN arrays at the plane
+    const long long off = (long long)(o.sc0[i] / pr.pc) * g_pstride(c, pr);
+    s.p += off;
+    s.g += off;
+    s.scale += s.c0;
+    s.shift += s.c0;
+    s.mean += s.c0;
+    s.rstd += s.c0;
+    s.ld = s.C;
+    s.c0 = 0;
+  }
+  if (pr.act == MWW_ACT_LINEAR) s.flags |= GSRC_LINEAR;
+  if (pr.res_src >= 0) {
+    GOp& rr = c->G[pr.res_src];
+    s.rp = rr.p;
+    s.rscale = gbn_slot(rr, BN_SCALE);
+    s.rshift = gbn_slot(rr, BN_SHIFT);
+    s.rT = rr.tout;
+    s.rdrop = pr.res_drop;
+  }
+  if (backward) s.flags |= GSRC_GRAD | (o.src_first[i] ? 0 : GSRC_ACCUM) | (o.src_last[i] ? GSRC_STATS : 0);
+  if (backward && inl && o.src_last[i]) {   // the slice's backward sums go to the producer's accumulator rows
+    s.gacc.acc = pr.gacc[c->gpar];
+    s.gacc.clear = pr.gacc[c->gpar ^ 1];
+    pr.gacc_cur = s.gacc.acc;
+  }
+  return s;
+}
+
+GBnBwd g_make_bnbwd(mww_ctx* c, GOp& o) {
+  GBnBwd y;
+  memset(&y, 0, sizeof(y));
+  y.g = o.g;
+  y.p = o.p;
+  if (o.norm != MWW_NORM_BN) {   // dp = g
+    y.mean = c->zeros; y.rstd = c->ones; y.c1 = c->ones; y.mg = c->zeros; y.mgx = c->zeros;
+  } else {
+    y.mean = gbn_slot(o, BN_MEAN); y.rstd = gbn_slot(o, BN_RSTD); y.c1 = gbn_slot(o, BN_C1); y.mg = gbn_slot(o, BN_MG); y.mgx = gbn_slot(o, BN_MGX);
+  }
+  y.planes = g_planes(c, o);
+  y.pc = o.pc;
+  y.pstride = g_pstride(c, o);
+  return y;
+}
+
+GDwArgs g_make_dw(mww_ctx* c, int oi, int B, bool backward, bool inl = false) {
+  GOp& o = c->G[oi];
+  GDwArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = g_make_src(c, oi, 0, backward, inl);
+  a.w = c->params + o.o_w;
+  a.k = o.k;
+  a.C = o.cout;
+  a.B = B;
+  a.Tin = o.tin;
+  a.Tout = o.tout;
+  a.out = o.p;
+  a.y = g_make_bnbwd(c, o);
+  a.grad_part = o.grad_part;
+  return a;
+}
+
+}  // namespace
+
+int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) {
+  if (c->x_lazy && !g_stem_gathers(c)) {   // (an option changed since the batch was assembled)
+    int rcx = materialise_x(c);
+    if (rcx) return rcx;
+  }
+  Launcher lp{c};
+  const int n = (int)c->G.size();
+  const int gg = std::min(B, c->grid_g);
+  // statistics hand-over instead of finalize launches (kernels_graph.hip.h)
+  const bool inl = training && c->bn_inline && c->g_inline_ok && !(c->hook && c->sync_bn) && !c->profile_split;
+  const bool pick = inl && c->grid_g_auto;   // per-launch grids (g_role_grid)
+  auto leader = [&](int oi) { return (oi > 0 && c->G[oi - 1].twin_next) ? oi - 1 : oi; };   // first op of the launch op oi rides in
+  auto fold_of = [&](int pi, bool publish) {
+    GOp& pr = c->G[pi];
+    GFoldFwd f;
+    memset(&f, 0, sizeof(f));
+    f.acc = pr.facc_cur;
+    f.C = pr.cout;
+    f.groups = pr.groups;
+    f.inv_n = 1.0f / ((float)B * (float)pr.tout * (float)(pr.groups > 1 ? pr.cout / pr.groups : 1));
+    f.publish = publish ? 1 : 0;
+    f.update_moving = update_moving ? 1 : 0;
+    f.gamma = c->params + pr.o_gamma;
+    f.beta = c->params + pr.o_beta;
+    f.moving_mean = c->bn_state + pr.o_mm;
+    f.moving_var = c->bn_state + pr.o_mv;
+    f.scale = gbn_slot(pr, BN_SCALE);
+    f.shift = gbn_slot(pr, BN_SHIFT);
+    f.mean = gbn_slot(pr, BN_MEAN);
+    f.rstd = gbn_slot(pr, BN_RSTD);
+    return f;
+  };
+  for (int i = 0; i < n; ++i) {
+    GOp& o = c->G[i];
+    if (!training && o.norm == MWW_NORM_BN) {
+      GBnEvalArgs e{c->params + o.o_gamma, c->params + o.o_beta, c->bn_state + o.o_mm, c->bn_state + o.o_mv,
+                    gbn_slot(o, BN_SCALE), gbn_slot(o, BN_SHIFT), o.cout, o.groups};
+      lp.begin("bn_eval_prepare", i);
+      hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, c->stream, e);
+      lp.end();
+    }
+    if (o.kind == MWW_OP_DEPTHWISE) {
+      GDwArgs dw = g_make_dw(c, i, B, false);
+      if (inl && o.src[0] >= 0 && c->G[o.src[0]].norm == MWW_NORM_BN && c->G[o.src[0]].first_consumer == i)
+        dw.fold = fold_of(o.src[0], true);
+      lp.begin("dw_fwd", i);
+      // (no statistics leave this launch: its grid is free to follow its occupancy even without the hand-over)
+      const int rc = g_rc(k_launch_gdw(g_launch_ctx(c), 0, dw, GridPick{c->grid_g_auto ? 0 : gg, B, 1, c->g_cap_fwd, nullptr}, o.lds_fwd));
+      lp.end();
+      if (rc) return rc;
+      continue;
+    }
+    auto fwd_args = [&](int oi) {
+      GOp& q = c->G[oi];
+      GConvArgs a;
+      memset(&a, 0, sizeof(a));
+      a.n_src = q.n_src;
+      for (int s = 0; s < q.n_src; ++s) a.src[s] = g_make_src(c, oi, s, false);
+      a.w = c->params + q.o_w;
+      a.k = q.k;
+      a.dil = q.dil;
+      a.cin = q.cin;
+      a.stride = q.stride;
+      a.B = B;
+      a.Tin = q.tin;
+      a.Tout = q.tout;
+      a.out = q.p;
+      a.out_planes = g_planes(c, q);
+      a.out_pc = q.pc;
+      a.out_pstride = g_pstride(c, q);
+      a.stat_part = (training && q.norm == MWW_NORM_BN) ? q.stat_part : nullptr;
+      if (inl) {
+        a.sacc.acc = q.facc[c->fpar];
+        a.sacc.clear = q.facc[c->fpar ^ 1];
+        q.facc_cur = a.sacc.acc;
+        for (int s = 0; s < q.n_src; ++s) {
+          const int pi = q.src[s];
+          if (pi < 0 || c->G[pi].norm != MWW_NORM_BN) continue;   // (no statistics to fold)
+          const int fc = c->G[pi].first_consumer;
+          if (leader(oi) != leader(fc)) continue;   // a later launch: the arrays were published by the first one
+          bool first_ref = true;
+          for (int s2 = 0; s2 < s; ++s2) first_ref = first_ref && q.src[s2] != pi;
+          a.fold[s] = fold_of(pi, oi == fc && first_ref);
+        }
+      }
+      return a;
+    };
+    auto fin_args = [&](int oi, const StatSource& ss) {
+      GOp& q = c->G[oi];
+      return GBnFwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
+                        c->params + q.o_gamma, c->params + q.o_beta, c->bn_state + q.o_mm, c->bn_state + q.o_mv,
+                        gbn_slot(q, BN_SCALE), gbn_slot(q, BN_SHIFT), gbn_slot(q, BN_MEAN), gbn_slot(q, BN_RSTD), update_moving ? 1 : 0};
+    };
+    const bool sync = c->hook && c->sync_bn;
+    if (o.twin_next && !sync && !c->profile_split) {
+      // twins: one convolution launch and one finalize launch for the pair
+      GOp& o2 = c->G[i + 1];
+      if (!training) {
+        GBnEvalArgs e{c->params + o2.o_gamma, c->params + o2.o_beta, c->bn_state + o2.o_mm, c->bn_state + o2.o_mv,
+                      gbn_slot(o2, BN_SCALE), gbn_slot(o2, BN_SHIFT), o2.cout, o2.groups};
+        hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, c->stream, e);
+      }
+      const GConvArgs fa0 = fwd_args(i), fa1 = fwd_args(i + 1);
+      lp.begin("conv_fwd2_", i);
+      const bool split2 = inl && c->g_role_split;
+      const int r2 = k_launch_gfwd2(g_launch_ctx(c), o.cout, fa0, fa1, GridPick{pick ? 0 : (split2 ? std::max(1, gg / 2) : gg), B, split2 ? 2 : 1, c->g_cap_fwd, nullptr},
+                                    std::max(o.lds_fwd, o2.lds_fwd), g_shape_id(c, o) == g_shape_id(c, o2) ? g_shape_id(c, o) : 0);
+      lp.end();
+      if (r2 != kGNoKernel) {
+        if (r2) return g_rc(r2);
+        if (training && !inl) {
+          const float inv_n = 1.0f / ((float)B * (float)o.tout * (float)(o.groups > 1 ? o.cout / o.groups : 1));
+          StatSource s0{o.stat_part, gg, inv_n, 1.0f}, s1{o2.stat_part, gg, inv_n, 1.0f};
+          const GBnFwdArgs f0 = fin_args(i, s0), f1 = fin_args(i + 1, s1);
+          const int n0 = o.slots;
+          lp.begin("bn_fwd_finalize2_", i);
+          hipLaunchKernelGGL(gbn_fwd_finalize2_kernel, dim3(o.slots + o2.slots), dim3(kThreads), 0, c->stream, f0, f1, n0);
+          lp.end();
+        }
+        ++i;   // the twin is done
+        continue;
+      }
+      if (c->profile) {   // width not instantiated: nothing was launched, fall through to the single-op route
+        (void)hipEventDestroy(c->prof.back().a);
+        (void)hipEventDestroy(c->prof.back().b);
+        c->prof.pop_back();
+      }
+    }
+    GConvArgs fa = fwd_args(i);
+    int Tc = 0;
+    const int S = g_chunks(c, o, inl, false, &Tc);
+    lp.begin("conv_fwd", i);
+    int rc;
+    if (S > 1) {
+      fa.S = S;
+      fa.Tc = Tc;
+      rc = launch_gconv(c, true, o.cout, fa, GridPick{pick ? 0 : gg, B * S, 1, c->g_cap_fwd, nullptr}, g_lds_fwd(o, g_chunk_in(o, Tc), Tc));
+    } else {
+      rc = launch_gconv(c, false, o.cout, fa, GridPick{pick ? 0 : gg, B, 1, c->g_cap_fwd, nullptr}, o.lds_fwd, g_shape_id(c, o));
+    }
+    lp.end();
+    if (rc) return rc;
+    if (training && o.norm == MWW_NORM_BN && !inl) {
+      const int members = o.groups > 1 ? o.cout / o.groups : 1;
+      StatSource ss;
+      int rcs = exchange_stats(c, lp, "bn_stat_exchange", i, o.stat_part, gg, o.cout, 0,
+                               1.0f / ((float)B * (float)o.tout * (float)members), &ss);
+      if (rcs) return rcs;
+      const GBnFwdArgs f = fin_args(i, ss);
+      lp.begin("bn_fwd_finalize", i);
+      hipLaunchKernelGGL(gbn_fwd_finalize_kernel, dim3(o.slots), dim3(kThreads), 0, c->stream, f);
+      lp.end();
+    }
+  }
+  GOp& lo = c->G[n - 1];
+  const bool drop = loss && c->dropout > 0.f;   // Dropout is active in the train step only (Keras training=True)
+  const bool gen_inline = drop && !c->keep_explicit && !c->head2;   // ghead_kernel draws the mask itself
+  if (drop && !c->keep_explicit && !gen_inline) {
+    const long long ne = (long long)B * c->t_last * c->c_last;
+    DropoutMaskArgs dm{c->keep, ne, c->dropout_seed, reinterpret_cast<const unsigned*>(mail_hyper(c)) + 2, c->dropout};
+    lp.begin("dropout_mask");
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, dm);
+    lp.end();
+  }
+  const int ghead = std::min(B, c->grid_head);
+  GHeadArgs h;
+  memset(&h, 0, sizeof(h));
+  h.p = lo.p;
+  h.scale = gbn_slot(lo, BN_SCALE);
+  h.shift = gbn_slot(lo, BN_SHIFT);
+  h.mean = gbn_slot(lo, BN_MEAN);
+  h.rstd = gbn_slot(lo, BN_RSTD);
+  h.wd = c->params + c->o_dense_w;
+  h.bd = c->params + c->o_dense_b;
+  h.y = (loss || metrics) ? c->y_cur : nullptr;
+  h.sw = c->sw_cur;
+  h.keep = (drop && !gen_inline) ? c->keep : nullptr;
+  if (gen_inline) {
+    h.keep_gen = c->keep;
+    h.seed = c->dropout_seed;
+    h.counter = reinterpret_cast<const unsigned*>(mail_hyper(c)) + 2;
+    h.rate = c->dropout;
+  }
+  h.z = c->z;
+  h.prob = c->prob;
+  h.dz = c->dz;
+  h.loss_part = c->loss_part;
+  h.g = lo.g;
+  h.gstat_part = lo.gstat_part;
+  h.B = B;
+  h.T = lo.tout;
+  h.C = lo.cout;
+  h.inv_b = 1.0f / (float)B;
+  h.training = (loss ? kHeadTraining : 0) | (c->bce_clipped ? kHeadClippedLoss : 0);
+  if (inl) {
+    h.fold = fold_of(n - 1, true);   // the head is the first (and only) consumer of the last op
+    c->fpar ^= 1;
+    if (loss) {
+      h.gacc.acc = lo.gacc[c->gpar];
+      h.gacc.clear = lo.gacc[c->gpar ^ 1];
+      lo.gacc_cur = h.gacc.acc;
+    }
+  }
+  if (lo.res_src >= 0) {
+    GOp& rr = c->G[lo.res_src];
+    h.rp = rr.p;
+    h.rscale = gbn_slot(rr, BN_SCALE);
+    h.rshift = gbn_slot(rr, BN_SHIFT);
+    h.rT = rr.tout;
+    h.rdrop = lo.res_drop;
+  }
+  if (c->head2) {
+    GHead2Args h2;
+    h2.h = h;
+    h2.watt = c->head_att ? c->params + c->o_att : nullptr;
+    h2.pool = c->head_pool;
+    h2.hact = c->hact;
+    h2.watt_part = c->watt_part;
+    if (c->lds_head2 > 64 * 1024)
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ghead_att_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_head2));
+    lp.begin("head");
+    hipLaunchKernelGGL(ghead_att_kernel, dim3(ghead), dim3(kThreads), c->lds_head2, c->stream, h2);
+    lp.end();
+    // the dense layer sees hact (already activated): identity "BN" for the dense-weight gradient
+    return enqueue_side_work(c, B, metrics, loss, c->hact, c->ones, c->zeros, nullptr);
+  }
+  lp.begin("head");
+  hipLaunchKernelGGL(ghead_kernel, dim3(ghead), dim3(kThreads), 0, c->stream, h);
+  lp.end();
+  return enqueue_side_work(c, B, metrics, loss, lo.p, gbn_slot(lo, BN_SCALE), gbn_slot(lo, BN_SHIFT), drop ? c->keep : nullptr);
+}
+
+int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
+  Launcher lp{c};
+  const int n = (int)c->G.size();
+  const int gg = std::min(B, c->grid_g);
+  const int ghead = std::min(B, c->grid_head);
+  GradReduceArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  // statistics hand-over: the op's own backward launch folds (sum g, sum g*xhat) from the accumulator rows its consumers
+  // (or the head) added to; the weight-gradient role publishes c1 / mg / mgx / dgamma / dbeta
+  const bool inl = c->bn_inline && c->g_inline_ok && !(c->hook && c->sync_bn) && !c->profile_split;
+  auto bfold = [&](GOp& q, bool publish) {
+    GFoldBwd f;
+    memset(&f, 0, sizeof(f));
+    if (!inl || q.norm != MWW_NORM_BN) return f;
+    f.acc = q.gacc_cur;
+    f.groups = q.groups;
+    f.inv_n = 1.0f / ((float)B * (float)q.tout * (float)(q.groups > 1 ? q.cout / q.groups : 1));
+    f.dscale = 1.0f;
+    f.publish = publish ? 1 : 0;
+    f.gamma = c->params + q.o_gamma;
+    f.c1 = gbn_slot(q, BN_C1);
+    f.mg = gbn_slot(q, BN_MG);
+    f.mgx = gbn_slot(q, BN_MGX);
+    f.dgamma = c->grads + q.o_gamma;
+    f.dbeta = c->grads + q.o_beta;
+    return f;
+  };
+  auto bwd_fin_args = [&](int oi, const StatSource& ss) {
+    GOp& q = c->G[oi];
+    return GBnBwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
+                      c->params + q.o_gamma, gbn_slot(q, BN_RSTD), gbn_slot(q, BN_C1), gbn_slot(q, BN_MG), gbn_slot(q, BN_MGX),
+                      c->grads + q.o_gamma, c->grads + q.o_beta, ss.dscale, 0};
+  };
+  auto wgrad_args = [&](int oi) {
+    GOp& q = c->G[oi];
+    GWgradArgs w;
+    memset(&w, 0, sizeof(w));
+    w.n_src = q.n_src;
+    for (int s = 0; s < q.n_src; ++s) w.src[s] = g_make_src(c, oi, s, false);
+    w.y = g_make_bnbwd(c, q);
+    w.y.fold = bfold(q, true);
+    w.k = q.k;
+    w.dil = q.dil;
+    w.cin = q.cin;
+    w.stride = q.stride;
+    w.B = B;
+    w.Tin = q.tin;
+    w.Tout = q.tout;
+    w.grad_part = q.grad_part;
+    return w;
+  };
+  auto dgrad_args = [&](int oi) {
+    GOp& q = c->G[oi];
+    GConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_src = q.n_src;
+    for (int s = 0; s < q.n_src; ++s) a.src[s] = g_make_src(c, oi, s, true, inl);
+    a.w = c->params + q.o_w;   // (the data-gradient kernel reads them transposed / tap-reversed in place)
+    a.k = q.k;
+    a.dil = q.dil;
+    a.cin = q.cout;
+    a.stride = 1;
+    a.B = B;
+    a.Tin = q.tout;
+    a.Tout = q.tin;
+    a.y = g_make_bnbwd(c, q);
+    a.y.fold = bfold(q, false);
+    return a;
+  };
+  const bool split = inl && c->g_role_split;
+  const bool pick = inl && c->grid_g_auto;   // per-launch grids (g_role_grid)
+  const int gg2 = split ? std::max(1, gg / 2) : gg, gg4 = split ? std::max(1, gg / 4) : gg;
+  auto add_segment = [&](int oi, int rows) {
+    GOp& q = c->G[oi];
+    GradSegment s;
+    s.part = q.grad_part;
+    s.G = rows;
+    s.stride = q.k * q.cin * q.cout;
+    s.n = s.stride;
+    s.dst = (int)q.o_w;
+    ga.seg[ga.nseg++] = s;
+  };
+  const bool sync = c->hook && c->sync_bn;
+  for (int i = n - 1; i >= 0; --i) {
+    GOp& o = c->G[i];
+    const int members = o.groups > 1 ? o.cout / o.groups : 1;
+    if (i > 0 && c->G[i - 1].twin_next && !sync && !c->profile_split) {
+      // twins (i-1, i): one finalize launch and one four-role backward launch for the pair
+      GOp& o1 = c->G[i - 1];
+      const float inv_n = 1.0f / ((float)B * (float)o.tout * (float)members);
+      StatSource s0{o.gstat_part, gg, inv_n, 1.0f}, s1{o1.gstat_part, gg, inv_n, 1.0f};
+      const GBnBwdArgs bf0 = bwd_fin_args(i, s0), bf1 = bwd_fin_args(i - 1, s1);
+      const GWgradArgs w0 = wgrad_args(i), w1 = wgrad_args(i - 1);
+      const GConvArgs d0 = dgrad_args(i), d1 = dgrad_args(i - 1);
+      const int n0 = o.slots;
+      lp.begin("conv_bwd2_", i);
+      if (!inl) hipLaunchKernelGGL(gbn_bwd_finalize2_kernel, dim3(o.slots + o1.slots), dim3(kThreads), 0, c->stream, bf0, bf1, n0);
+      int rows = gg4;
+      const int r2 = k_launch_gbwd2(g_launch_ctx(c), o.cout, w0, d0, w1, d1, GridPick{pick ? 0 : gg4, B, split ? 4 : 1, c->g_cap_bwd, &rows},
+                                   std::max(std::max(o.lds_wg, o.lds_dx), std::max(o1.lds_wg, o1.lds_dx)),
+                                   g_shape_id(c, o) == g_shape_id(c, o1) ? g_shape_id(c, o) : 0);
+      lp.end();
+      if (r2) return g_rc(r2, "twin ops without a fused backward instantiation");
+      add_segment(i, rows);
+      add_segment(i - 1, rows);
+      --i;
+      continue;
+    }
+    if (!o.adders.empty()) {
+      GResGatherArgs ra;
+      memset(&ra, 0, sizeof(ra));
+      ra.n = (int)o.adders.size();
+      for (int q = 0; q < ra.n; ++q) {
+        GOp& x = c->G[o.adders[q]];
+        ra.gx[q] = x.g;
+        ra.Tx[q] = x.tout;
+        ra.drop[q] = x.res_drop;
+      }
+      ra.p = o.p;
+      ra.mean = gbn_slot(o, BN_MEAN);
+      ra.rstd = gbn_slot(o, BN_RSTD);
+      ra.g = o.g;
+      ra.gstat_part = o.gstat_part;
+      ra.B = B;
+      ra.T = o.tout;
+      ra.C = o.cout;
+      lp.begin("residual_gather", i);
+      hipLaunchKernelGGL(gres_gather_kernel, dim3(gg), dim3(kThreads), 0, c->stream, ra);
+      lp.end();
+    }
+    if (o.norm == MWW_NORM_BN && !inl) {
+      StatSource ss;
+      int rcs = exchange_stats(c, lp, "bn_gstat_exchange", i, o.gstat_part, i == n - 1 ? ghead : gg, o.cout, 1,
+                               1.0f / ((float)B * (float)o.tout * (float)members), &ss);
+      if (rcs) return rcs;
+      GBnBwdArgs f{ss.part, ss.G, o.cout, o.groups, ss.inv_n,
+                   c->params + o.o_gamma, gbn_slot(o, BN_RSTD), gbn_slot(o, BN_C1), gbn_slot(o, BN_MG), gbn_slot(o, BN_MGX),
+                   c->grads + o.o_gamma, c->grads + o.o_beta, ss.dscale, 0};
+      lp.begin("bn_bwd_finalize", i);
+      hipLaunchKernelGGL(gbn_bwd_finalize_kernel, dim3(o.slots), dim3(kThreads), 0, c->stream, f);
+      lp.end();
+    } else if (o.norm == MWW_NORM_BIAS && !inl) {
+      // d bias = sum of the output gradient = the first statistic the consumers already accumulated
+      GBnBwdArgs f{o.gstat_part, gg, o.cout, 1, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->grads + o.o_beta, 1.0f, 1};
+      lp.begin("bias_grad", i);
+      hipLaunchKernelGGL(gbn_bwd_finalize_kernel, dim3(o.cout), dim3(kThreads), 0, c->stream, f);
+      lp.end();
+    }
+    if (o.kind == MWW_OP_DEPTHWISE) {
+      GDwArgs dw = g_make_dw(c, i, B, true, inl);
+      if (inl && o.norm == MWW_NORM_BIAS) {   // the rows this op's consumer added (sum g, ..) to: folded by the weight-gradient launch
+        dw.bias_acc = o.gacc_cur;
+        dw.dbeta = c->grads + o.o_beta;
+      }
+      lp.begin("dw_wgrad", i);
+      int gwg = 0;   // (its partial rows are its own)
+      int rc = g_rc(k_launch_gdw_wgrad(g_launch_ctx(c), dw, GridPick{c->grid_g_auto ? 0 : gg, B, 1, c->g_cap_bwd, &gwg}, o.lds_wg));
+      lp.end();
+      if (rc) return rc;
+      if (o.needs_dx) {
+        lp.begin("dw_dgrad", i);
+        // (partial statistics rows are shared without the hand-over)
+        rc = g_rc(k_launch_gdw(g_launch_ctx(c), 1, dw, GridPick{pick ? 0 : gg, B, 1, c->g_cap_bwd, nullptr}, o.lds_dx));
+        lp.end();
+        if (rc) return rc;
+      }
+      GradSegment s;
+      s.part = o.grad_part;
+      s.G = gwg;
+      s.stride = o.k * o.cout;
+      s.n = s.stride;
+      s.dst = (int)o.o_w;
+      ga.seg[ga.nseg++] = s;
+      continue;
+    }
+    GWgradArgs w;
+    memset(&w, 0, sizeof(w));
+    w.n_src = o.n_src;
+    for (int s = 0; s < o.n_src; ++s) w.src[s] = g_make_src(c, i, s, false);
+    w.y = g_make_bnbwd(c, o);
+    w.y.fold = bfold(o, true);
+    w.k = o.k;
+    w.dil = o.dil;
+    w.cin = o.cin;
+    w.stride = o.stride;
+    w.B = B;
+    w.Tin = o.tin;
+    w.Tout = o.tout;
+    w.grad_part = o.grad_part;
+    GConvArgs a;
+    memset(&a, 0, sizeof(a));
+    if (o.needs_dx) {
+      a.n_src = o.n_src;
+      for (int s = 0; s < o.n_src; ++s) a.src[s] = g_make_src(c, i, s, true, inl);
+      a.w = c->params + o.o_w;
+      a.k = o.k;
+      a.dil = o.dil;
+      a.cin = o.cout;
+      a.stride = 1;
+      a.B = B;
+      a.Tin = o.tout;
+      a.Tout = o.tin;
+      a.y = g_make_bnbwd(c, o);
+      a.y.fold = bfold(o, false);
+    }
+    bool fused = false;
+    int rows = gg;
+    int Tc = 0;
+    const int S = g_chunks(c, o, inl, true, &Tc);   // frame chunks (1x1 ops): S work items per window for both roles
+    size_t lds_wg = o.lds_wg, lds_dx = o.lds_dx;
+    if (S > 1) {
+      w.S = a.S = S;
+      w.Tc = a.Tc = Tc;
+      lds_wg = g_lds_wg(o, g_chunk_in(o, Tc), Tc);
+      lds_dx = o.needs_dx ? g_lds_dx(o, Tc, Tc) : 0;
+    }
+    const int items = B * S;
+    if (o.needs_dx && !c->profile_split) {
+      lp.begin("conv_bwd", i);
+      const GridPick pkf{pick ? 0 : gg2, items, split ? 2 : 1, c->g_cap_bwd, &rows};
+      const int rf = k_launch_gbwd(g_launch_ctx(c), S > 1, o.cout, o.cin, w, a, pkf, std::max(lds_wg, lds_dx), g_shape_id(c, o));
+      lp.end();
+      if (rf > 0) return g_rc(rf);
+      fused = rf == 0;
+      if (!fused && c->profile) {   // nothing was launched: drop the empty profile entry
+        (void)hipEventDestroy(c->prof.back().a);
+        (void)hipEventDestroy(c->prof.back().b);
+        c->prof.pop_back();
+      }
+    }
+    if (!fused) {
+      lp.begin("conv_wgrad", i);
+      const GridPick pkw{pick ? 0 : gg, items, 1, c->g_cap_bwd, &rows};
+      int rc = launch_gwgrad(c, S > 1, o.cout, w, pkw, lds_wg, g_shape_id(c, o));
+      lp.end();
+      if (rc) return rc;
+      if (o.needs_dx) {
+        lp.begin("conv_dgrad", i);
+        const GridPick pkd{pick ? 0 : gg, items, 1, c->g_cap_bwd, nullptr};
+        rc = g_rc(k_launch_gdgrad(g_launch_ctx(c), S > 1, o.cin, a, pkd, lds_dx));
+        lp.end();
+        if (rc) return rc;
+      }
+    }
+    GradSegment s;
+    s.part = o.grad_part;
+    s.G = rows;
+    s.stride = o.k * o.cin * o.cout;
+    s.n = s.stride;
+    s.dst = (int)o.o_w;
+    ga.seg[ga.nseg++] = s;
+  }
+  if (c->head2 && c->head_att) {
+    GradSegment s;
+    s.part = c->watt_part;
+    s.G = ghead;
+    s.stride = 8;
+    s.n = 8;
+    s.dst = (int)c->o_att;
+    ga.seg[ga.nseg++] = s;
+  }
+  if (inl) c->gpar ^= 1;
+  return enqueue_grad_assembly(c, B, ga, fuse_adam);
+}
+
+int g_plan_convnet(const mww_convnet_desc& d, GPlan* plan) {
+  if (d.n_ops < 1 || d.n_ops > MWW_MAX_GRAPH_OPS) return fail(MWW_ERR_INVALID, "n_ops out of range");
+  if (d.max_batch <= 0 || d.frames <= 0) return fail(MWW_ERR_INVALID, "frames and max_batch must be positive");
+  if (!(d.dropout >= 0.f && d.dropout < 1.f)) return fail(MWW_ERR_INVALID, "dropout rate must be in [0, 1)");
+  std::vector<GOp>& ops = plan->ops;
+  ops.assign(d.n_ops, GOp());
+  std::vector<int> n_consumers(d.n_ops, 0);
+  int64_t off = 0, soff = 0;
+  for (int i = 0; i < d.n_ops; ++i) {
+    const mww_conv_bn_op& s = d.ops[i];
+    GOp& o = ops[i];
+    const std::string tag = "op " + std::to_string(i) + ": ";
+    if (s.n_src < 1 || s.n_src > MWW_MAX_OP_SOURCES) return fail(MWW_ERR_INVALID, tag + "1..3 sources");
+    if (s.kernel < 1 || s.dilation < 1 || s.filters < 1 || s.bn_groups < 1) return fail(MWW_ERR_INVALID, tag + "bad kernel / dilation / filters / groups");
+    if (s.filters % s.bn_groups) return fail(MWW_ERR_INVALID, tag + "filters must be a multiple of the sub-spectral groups");
+    if (s.kind != MWW_OP_CONV && s.kind != MWW_OP_DEPTHWISE) return fail(MWW_ERR_INVALID, tag + "unknown op kind");
+    if (s.norm < MWW_NORM_BN || s.norm > MWW_NORM_NONE || (s.act != MWW_ACT_RELU && s.act != MWW_ACT_LINEAR)) return fail(MWW_ERR_INVALID, tag + "unknown norm / activation");
+    o.res_src = s.residual > 0 ? s.residual - 1 : -1;
+    o.res_drop = s.residual_drop;
+    o.kind = s.kind;
+    o.stride = s.stride > 1 ? s.stride : 1;
+    o.norm = s.norm;
+    o.act = s.act;
+    o.n_src = s.n_src;
+    o.k = s.kernel;
+    o.dil = s.dilation;
+    o.cout = s.filters;
+    o.groups = s.bn_groups;
+    o.slots = s.norm == MWW_NORM_BN ? (s.bn_groups > 1 ? s.bn_groups : s.filters) : 0;
+    o.cin = 0;
+    o.tin = -1;
+    for (int j = 0; j < s.n_src; ++j) {
+      const int src = s.src[j];
+      if (src < -1 || src >= i) return fail(MWW_ERR_INVALID, tag + "sources must be earlier ops (or -1 for the spectrogram)");
+      for (int j2 = 0; j2 < j; ++j2)
+        if (s.src[j2] == src) return fail(MWW_ERR_UNSUPPORTED, tag + "the same source twice");
+      if (s.src_drop[j] < 0) return fail(MWW_ERR_INVALID, tag + "negative frame drop");
+      const int T = src < 0 ? d.frames : ops[src].tout, Cfull = src < 0 ? MWW_FEATURE_BINS : ops[src].cout;
+      const int c0 = s.src_cn[j] > 0 ? s.src_c0[j] : 0, C = s.src_cn[j] > 0 ? s.src_cn[j] : Cfull;
+      if (c0 < 0 || c0 + C > Cfull || (src < 0 && C != Cfull)) return fail(MWW_ERR_INVALID, tag + "bad channel slice");
+      const int rows = T - s.src_drop[j];
+      if (o.tin >= 0 && rows != o.tin) return fail(MWW_ERR_INVALID, tag + "sources are not aligned to the same number of frames");
+      o.tin = rows;
+      o.cin += C;
+      o.src[j] = src;
+      o.toff[j] = s.src_drop[j];
+      o.sc0[j] = c0;
+      o.scn[j] = C;
+      if (src >= 0) {
+        o.needs_dx = true;
+        n_consumers[src]++;
+      }
+    }
+    const int span = o.tin - (o.k - 1) * o.dil;
+    if (span <= 0) return fail(MWW_ERR_INVALID, tag + "spectrogram too short for the kernel sizes");
+    o.tout = (span - 1) / o.stride + 1;
+    if (o.stride > 1 && o.needs_dx) return fail(MWW_ERR_UNSUPPORTED, tag + "a time stride is only implemented for ops fed by the spectrogram");
+    const int pad = (o.k - 1) * o.dil;
+    if (o.kind == MWW_OP_DEPTHWISE) {
+      if (o.n_src != 1 || o.cin != o.cout || o.dil != 1 || o.stride != 1) return fail(MWW_ERR_INVALID, tag + "a depthwise op has one source with as many channels as filters, no dilation, no stride");
+      if (o.norm == MWW_NORM_BN) return fail(MWW_ERR_UNSUPPORTED, tag + "depthwise + BatchNorm is not implemented (bias or nothing)");
+      if (o.cout > kThreads || o.k * o.cout > kGDwTasks * kThreads) return fail(MWW_ERR_UNSUPPORTED, tag + "depthwise op too large (channels <= 256, taps x channels <= 2048)");
+      // tap blocks of 8 with zero weights, kGDwTail zero rows behind every staged window (kernels_graph.hip.h)
+      const size_t pi = (size_t)(o.cout | 1), wsz = (size_t)gdw_kpad(o.k) * o.cout;
+      o.lds_fwd = (wsz + (size_t)(o.tin + kGDwTail) * pi) * sizeof(float);
+      o.lds_dx = o.needs_dx ? (wsz + (size_t)(o.tout + 2 * pad + kGDwTail) * pi) * sizeof(float) : 0;
+      o.lds_wg = std::max((size_t)(o.tin + kGDwTail) * pi + (size_t)(o.tout + kGDwJ) * pi, (size_t)2 * kThreads * kGDwJ) * sizeof(float);   // (.. or the scratch of the final sum)
+    } else {
+      if (!g_width_supported(o.cout)) return fail(MWW_ERR_UNSUPPORTED, tag + "filter count not instantiated (8,10,12,16,20,24,30,32,36,40,48,60,64)");
+      if (o.needs_dx && !g_width_supported(o.cin)) return fail(MWW_ERR_UNSUPPORTED, tag + "input channel count not instantiated");
+      if (o.k * o.cin > kThreads) return fail(MWW_ERR_UNSUPPORTED, tag + "kernel x input channels exceeds 256");
+      o.lds_fwd = g_lds_fwd(o, o.tin, o.tout);   // (g_lds_*: the LDS tiles of the MFMA kernels)
+      o.lds_dx = o.needs_dx ? g_lds_dx(o, o.tout + 2 * pad, o.tin) : 0;
+      o.lds_wg = g_lds_wg(o, o.tin, o.tout);
+    }
+    if (std::max(o.lds_fwd, std::max(o.lds_dx, o.lds_wg)) > kMaxDynLds) return fail(MWW_ERR_UNSUPPORTED, tag + "window does not fit the LDS tile");
+    o.o_w = off; off += o.kind == MWW_OP_DEPTHWISE ? (int64_t)o.k * o.cout : (int64_t)o.k * o.cin * o.cout;
+    if (o.norm == MWW_NORM_BN) {
+      o.o_gamma = off; off += o.slots;
+      o.o_beta = off; off += o.slots;
+      o.o_mm = soff; soff += o.slots;
+      o.o_mv = soff; soff += o.slots;
+    } else if (o.norm == MWW_NORM_BIAS) {
+      o.o_beta = off; off += o.cout;
+    }
+  }
+  for (int i = 0; i < d.n_ops; ++i) {
+    GOp& o = ops[i];
+    if (o.res_src < 0) continue;
+    const std::string tag = "op " + std::to_string(i) + ": ";
+    if (o.res_src >= i) return fail(MWW_ERR_INVALID, tag + "the residual op must come earlier");
+    GOp& r = ops[o.res_src];
+    if (r.kind != MWW_OP_CONV || r.norm != MWW_NORM_BN || r.act != MWW_ACT_LINEAR || o.norm != MWW_NORM_BN)
+      return fail(MWW_ERR_UNSUPPORTED, tag + "a residual is a conv + BatchNorm + linear op added to a BatchNorm output");
+    if (r.cout != o.cout || o.res_drop < 0 || r.tout - o.res_drop != o.tout) return fail(MWW_ERR_INVALID, tag + "residual shape does not match");
+    if (n_consumers[o.res_src] != 0) return fail(MWW_ERR_UNSUPPORTED, tag + "a residual op cannot also be a regular source");
+    if ((int)r.adders.size() >= kGMaxAdders) return fail(MWW_ERR_UNSUPPORTED, tag + "too many ops add the same residual");
+    r.adders.push_back(i);
+    for (int i2 = i + 1; i2 < d.n_ops; ++i2)
+      for (int j2 = 0; j2 < ops[i2].n_src; ++j2)
+        if (ops[i2].src[j2] == i && ops[i2].scn[j2] != o.cout) return fail(MWW_ERR_UNSUPPORTED, tag + "an op with a residual must be read whole (no channel slice)");
+  }
+  for (int i = 0; i + 1 < d.n_ops; ++i)
+    if (n_consumers[i] == 0 && ops[i].adders.empty()) return fail(MWW_ERR_INVALID, "op " + std::to_string(i) + " has no consumer");
+  // twins: consecutive, mutually independent convolutions of one shape (Inception's second-level k x 1 convs of
+  // branch 2 and branch 3) share their forward, finalize and backward launches
+  auto twin_width = [](int n) {
+#define X(N) if (n == N) return true;
+    MWW_G_TWIN_WIDTHS(X)
+#undef X
+    return false;
+  };
+  for (int i = 0; i + 2 < d.n_ops; ++i) {
+    GOp &a = ops[i], &b = ops[i + 1];
+    const bool same = a.kind == MWW_OP_CONV && b.kind == MWW_OP_CONV && a.k == b.k && a.dil == b.dil && a.cin == b.cin && a.cout == b.cout &&
+                      a.groups == b.groups && a.norm == MWW_NORM_BN && b.norm == MWW_NORM_BN && a.act == b.act && a.stride == 1 &&
+                      b.stride == 1 && a.tin == b.tin && a.n_src == 1 && b.n_src == 1 && a.src[0] >= 0 && b.src[0] >= 0 &&
+                      b.src[0] != i && a.res_src < 0 && b.res_src < 0 && a.adders.empty() && b.adders.empty() && a.cin == a.cout &&
+                      twin_width(a.cout);
+    // twins run concurrently inside one launch: they must not route gradient into the same channels of one producer
+    // (store vs accumulate would race; e.g. the unfused 1x1 branch heads of an Inception block with sub-spectral groups)
+    const bool shared = a.src[0] == b.src[0] && a.sc0[0] < b.sc0[0] + b.cin && b.sc0[0] < a.sc0[0] + a.cin;
+    if (same && !shared && (i == 0 || !ops[i - 1].twin_next)) a.twin_next = true;
+  }
+  // gradient routing: per producer, the slices its consumers read must be identical or disjoint and cover
+  // every channel; in the backward pass (descending op index) the first consumer of a slice stores, later
+  // ones accumulate and the last one also emits the BN statistics partials of that slice
+  for (int pi = 0; pi + 1 < d.n_ops; ++pi) {
+    if (!ops[pi].adders.empty()) continue;   // residual ops: gradient gathered from their adders
+    std::vector<int> covered(ops[pi].cout, 0);
+    for (int i = d.n_ops - 1; i > pi; --i)
+      for (int j = 0; j < ops[i].n_src; ++j) {
+        if (ops[i].src[j] != pi) continue;
+        const int c0 = ops[i].sc0[j], cn = ops[i].scn[j];
+        bool first = true, last = true;
+        for (int i2 = pi + 1; i2 < d.n_ops; ++i2)
+          for (int j2 = 0; j2 < ops[i2].n_src; ++j2) {
+            if (ops[i2].src[j2] != pi || (i2 == i && j2 == j)) continue;
+            const int d0 = ops[i2].sc0[j2], dn = ops[i2].scn[j2];
+            if (d0 + dn <= c0 || c0 + cn <= d0) continue;   // disjoint
+            if (d0 != c0 || dn != cn) return fail(MWW_ERR_UNSUPPORTED, "op " + std::to_string(pi) + ": consumers read overlapping, unequal channel slices");
+            if (i2 > i) first = false;
+            if (i2 < i) last = false;
+          }
+        ops[i].src_first[j] = first;
+        ops[i].src_last[j] = last;
+        for (int cc = c0; cc < c0 + cn; ++cc) covered[cc] = 1;
+      }
+    for (int cc = 0; cc < ops[pi].cout; ++cc)
+      if (!covered[cc]) return fail(MWW_ERR_UNSUPPORTED, "op " + std::to_string(pi) + ": channel " + std::to_string(cc) + " has no consumer");
+  }
+  // planar tensors: a convolution + BatchNorm op whose consumers are all convolutions that read one of `planes` equal slices
+  // each (the fused 1x1 branch heads of an Inception block: 30 = 3 x 10, 48 = 3 x 16 channels).  Only for the widths whose
+  // own backward staging is the direct one (kernels_graph.hip.h GDpPipe is not planar-aware: 30 and 48 exceed its registers).
+  for (int pi = 0; pi + 1 < d.n_ops; ++pi) {
+    GOp& pr = ops[pi];
+    if (pr.kind != MWW_OP_CONV || pr.norm != MWW_NORM_BN || pr.res_src >= 0 || !pr.adders.empty() || (pr.cout != 30 && pr.cout != 48)) continue;
+    int cn = 0;
+    bool ok = true;
+    for (int i = pi + 1; i < d.n_ops && ok; ++i)
+      for (int j = 0; j < ops[i].n_src; ++j) {
+        if (ops[i].src[j] != pi) continue;
+        if (ops[i].kind != MWW_OP_CONV || ops[i].res_src >= 0 || ops[i].stride != 1) ok = false;
+        if (cn == 0) cn = ops[i].scn[j];
+        if (ops[i].scn[j] != cn || ops[i].scn[j] >= pr.cout || ops[i].sc0[j] % cn) ok = false;
+      }
+    if (ok && cn > 0 && pr.cout % cn == 0 && (cn % 2) == 0) {
+      pr.planes = pr.cout / cn;
+      pr.pc = cn;
+    }
+  }
+  if (n_consumers[d.n_ops - 1] != 0) return fail(MWW_ERR_INVALID, "the last op feeds the classifier head and cannot have other consumers");
+  {
+    const GOp& lo = ops[d.n_ops - 1];
+    if (lo.kind != MWW_OP_CONV || lo.norm != MWW_NORM_BN || lo.act != MWW_ACT_RELU)
+      return fail(MWW_ERR_UNSUPPORTED, "the classifier head expects a convolution + BatchNorm + ReLU as the last op");
+  }
+  // frame chunks ("graph_frame_chunks"): automatic for graphs with depthwise ops, i.e. MixedNet flag sets on this engine - their
+  // wide 1x1 ops hold 45-105 KB of LDS per whole-window workgroup; measured on the default MixedNet forced onto this engine
+  // 0.877 -> 0.815 ms/step (3: 0.818).  Off for pure convolution graphs: Inception 0.892 / 0.897 / 0.957 / 0.960 ms for 0 / 1 / 2 / 3
+  // (profiles/round3_frame_chunks.txt)
+  for (const GOp& o : ops)
+    if (o.kind == MWW_OP_DEPTHWISE) plan->chunks = 1;
+  {
+    // statistics hand-over: possible when every op is a convolution followed by a BatchNorm / SSN (or by nothing: a
+    // MixedNet's first convolution) or a depthwise op with a bias (or nothing), none has a residual branch and every folded
+    // tensor fits the kernels' fold table; first_consumer = the op whose launch folds
+    bool ok = true;
+    for (int i = 0; i < d.n_ops; ++i) {
+      GOp& o = ops[i];
+      const bool conv_ok = o.kind == MWW_OP_CONV && (o.norm == MWW_NORM_BN || o.norm == MWW_NORM_NONE);
+      const bool dw_ok = o.kind == MWW_OP_DEPTHWISE && (o.norm == MWW_NORM_BIAS || o.norm == MWW_NORM_NONE);
+      if (!(conv_ok || dw_ok) || o.res_src >= 0 || !o.adders.empty() || o.cout > kGFoldC) ok = false;
+      for (int j = 0; j < o.n_src; ++j)
+        if (o.src[j] >= 0 && ops[o.src[j]].first_consumer < 0) ops[o.src[j]].first_consumer = i;
+    }
+    plan->inline_ok = ok && !d.head_attention && !d.head_pool;
+  }
+  plan->P = off;
+  plan->S = soff;
+  return MWW_OK;
+}
+
+}  // namespace mww

@@ -27,6 +27,7 @@ struct AssembleArgs {
 
 constexpr int kMaxMasks = 16;
 
+#ifndef MWW_BLOCK_TU   // defined once, in mww_lib.hip (graph_engine.hip sees this header for AssembleArgs only)
 __global__ __launch_bounds__(kThreads) void assemble_kernel(AssembleArgs a) {
   __shared__ __attribute__((aligned(16))) int sMask[kMaxMasks * 2];
   const int j = blockIdx.x / a.split, part = blockIdx.x - j * a.split;
@@ -95,5 +96,6 @@ __global__ __launch_bounds__(kThreads) void assemble_kernel(AssembleArgs a) {
     }
   }
 }
+#endif
 
 }  // namespace mww

@@ -30,7 +30,7 @@
 // (one lane per output frame) - at 1024 windows per step a launch is 2-4 windows per CU and 12-30 us of latency chain
 // (weights -> slab -> tile -> epilogue) of which the contraction is 1-4 us.  What counts is how many workgroups a CU
 // holds: static LDS is kept to the fold tables, every launch takes the grid its own occupancy allows (g_role_grid in
-// mww_lib.hip: 1.030 -> 0.884 ms per Inception step), and the depthwise ops of MixedNet graphs are register-blocked.
+// graph_launch.hip.h: 1.030 -> 0.884 ms per Inception step), and the depthwise ops of MixedNet graphs are register-blocked.
 #pragma once
 #include <type_traits>
 #include "common.hip.h"
@@ -77,7 +77,7 @@ struct GSrc {
 // lengths.  Their launches turned out to be bound by instruction issue, not by memory latency (round-2 counters of the
 // default Inception step: 2 800 VALU + 2 400 SALU instructions per wave around 180 MFMAs - index arithmetic, loop control,
 // run-time divisions - with four waves per SIMD each active 20-30 % of its time: the SIMDs are saturated).  GShape names
-// what the instantiations for a known topology (mww_lib.hip MWW_G_SHAPES: the ops of the reference's default Inception
+// what the instantiations for a known topology (graph_launch.hip.h MWW_G_SHAPES: the ops of the reference's default Inception
 // flags, inception.py:146-209) know at compile time: kernel length K (dilation and stride 1), the number of sources and
 // each one's (width, row length of the tensor it is a channel slice of).  Everything derived from them - LDS pitches, the
 // thread <-> (channel group, frame group) maps, trip counts of the MFMA loops - folds to constants, LDS reads take
@@ -1898,6 +1898,9 @@ __global__ __launch_bounds__(kThreads) void gdw_kernel(GDwArgs a) {
 // summed in a fixed order through LDS at the end.  taps x channels <= kGDwTasks * kThreads keeps it at two (tap block,
 // part) pairs per thread.
 constexpr int kGDwTasks = 8;
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void gdw_wgrad_kernel(GDwArgs a);
+#else
 __global__ __launch_bounds__(kThreads) void gdw_wgrad_kernel(GDwArgs a) {
   HIP_DYNAMIC_SHARED(float4, g_smem4)
   float* g_smem = reinterpret_cast<float*>(g_smem4);
@@ -1970,6 +1973,7 @@ __global__ __launch_bounds__(kThreads) void gdw_wgrad_kernel(GDwArgs a) {
     a.grad_part[(size_t)blockIdx.x * tasks + task] = v;
   }
 }
+#endif
 
 // Gradient of a residual op R: the ops that add it (one per repeat of the block) already hold the gradient at
 // their own outputs, masked by their ReLU; R's gradient is their sum, frame t of adder X landing on frame
@@ -1985,6 +1989,9 @@ struct GResGatherArgs {
   float* gstat_part;              // [grid][2][C]
   int B, T, C;
 };
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void gres_gather_kernel(GResGatherArgs a);
+#else
 __global__ __launch_bounds__(kThreads) void gres_gather_kernel(GResGatherArgs a) {
   __shared__ float sRed[2 * kThreads];
   const int tid = threadIdx.x, C = a.C, nrg = kThreads / C, c = tid % C, rg = tid / C;
@@ -2006,6 +2013,7 @@ __global__ __launch_bounds__(kThreads) void gres_gather_kernel(GResGatherArgs a)
   }
   write_channel_partials(s1, s2, C, sRed, a.gstat_part + (size_t)blockIdx.x * 2 * C, tid, C);
 }
+#endif
 
 
 // ---------------------------------------------------------------------------------------------
@@ -2064,22 +2072,33 @@ __device__ __forceinline__ void gbn_fwd_finalize_body(const GBnFwdArgs& a, int s
   }
 }
 
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void gbn_fwd_finalize_kernel(GBnFwdArgs a);
+#else
 __global__ __launch_bounds__(kThreads) void gbn_fwd_finalize_kernel(GBnFwdArgs a) {
   __shared__ double sAcc[2 * kThreads];
   gbn_fwd_finalize_body(a, blockIdx.x, sAcc);
 }
+#endif
 // twin ops: slots of a0 first, then those of a1
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void gbn_fwd_finalize2_kernel(GBnFwdArgs a0, GBnFwdArgs a1, int n0);
+#else
 __global__ __launch_bounds__(kThreads) void gbn_fwd_finalize2_kernel(GBnFwdArgs a0, GBnFwdArgs a1, int n0) {
   __shared__ double sAcc[2 * kThreads];
   if ((int)blockIdx.x < n0) gbn_fwd_finalize_body(a0, blockIdx.x, sAcc);
   else gbn_fwd_finalize_body(a1, blockIdx.x - n0, sAcc);
 }
+#endif
 
 struct GBnEvalArgs {
   const float *gamma, *beta, *moving_mean, *moving_var;
   float *scale, *shift;
   int C, groups;
 };
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void gbn_eval_prepare_kernel(GBnEvalArgs a);
+#else
 __global__ __launch_bounds__(kThreads) void gbn_eval_prepare_kernel(GBnEvalArgs a) {
   for (int c = threadIdx.x; c < a.C; c += kThreads) {
     const int slot = a.groups > 1 ? c % a.groups : c;
@@ -2088,6 +2107,7 @@ __global__ __launch_bounds__(kThreads) void gbn_eval_prepare_kernel(GBnEvalArgs 
     a.shift[c] = a.beta[slot] - a.moving_mean[slot] * sc;
   }
 }
+#endif
 
 struct GBnBwdArgs {
   const float* gstat_part;   // [G][2][C]
@@ -2127,15 +2147,23 @@ __device__ __forceinline__ void gbn_bwd_finalize_body(const GBnBwdArgs& a, int s
   }
 }
 
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void gbn_bwd_finalize_kernel(GBnBwdArgs a);
+#else
 __global__ __launch_bounds__(kThreads) void gbn_bwd_finalize_kernel(GBnBwdArgs a) {
   __shared__ double sAcc[2 * kThreads];
   gbn_bwd_finalize_body(a, blockIdx.x, sAcc);
 }
+#endif
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void gbn_bwd_finalize2_kernel(GBnBwdArgs a0, GBnBwdArgs a1, int n0);
+#else
 __global__ __launch_bounds__(kThreads) void gbn_bwd_finalize2_kernel(GBnBwdArgs a0, GBnBwdArgs a1, int n0) {
   __shared__ double sAcc[2 * kThreads];
   if ((int)blockIdx.x < n0) gbn_bwd_finalize_body(a0, blockIdx.x, sAcc);
   else gbn_bwd_finalize_body(a1, blockIdx.x - n0, sAcc);
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // head: last op -> BN + ReLU -> Flatten -> Dropout -> Dense(1) -> sigmoid (inception.py:330-338)
@@ -2176,6 +2204,9 @@ __device__ __forceinline__ float dropout_keep(unsigned long long seed, unsigned 
   return u >= rate ? 1.0f / (1.0f - rate) : 0.f;
 }
 
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void ghead_kernel(GHeadArgs a);
+#else
 __global__ __launch_bounds__(kThreads) void ghead_kernel(GHeadArgs a) {
   __shared__ float sRed[8];
   __shared__ float sBcast[2];
@@ -2359,6 +2390,7 @@ __global__ __launch_bounds__(kThreads) void ghead_kernel(GHeadArgs a) {
   if (a.training & kHeadTraining)
     publish_channel_partials(g1, g2, C, sStat, a.gstat_part + (size_t)blockIdx.x * 2 * C, tid, C, a.gacc, 0, blockIdx.x, gridDim.x);
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // MixedNet's optional heads (mixednet.py:234-275 SpatialAttention, :362-384): on the last op's activations a
@@ -2376,6 +2408,9 @@ struct GHead2Args {
   float* watt_part;      // [grid][8]
 };
 
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void ghead_att_kernel(GHead2Args a);
+#else
 __global__ __launch_bounds__(kThreads) void ghead_att_kernel(GHead2Args a) {
   HIP_DYNAMIC_SHARED(float4, g_smem4)
   float* sm = reinterpret_cast<float*>(g_smem4);
@@ -2542,6 +2577,7 @@ __global__ __launch_bounds__(kThreads) void ghead_att_kernel(GHead2Args a) {
     if (att && tid < 8) a.watt_part[(size_t)blockIdx.x * 8 + tid] = wacc;
   }
 }
+#endif
 
 // Dropout keep-mask of one step as its own launch (the attention / pooled heads; ghead_kernel generates it inline)
 struct DropoutMaskArgs {
@@ -2551,11 +2587,15 @@ struct DropoutMaskArgs {
   const unsigned* counter;   // [2] low / high word of this step's counter (mapped mailbox)
   float rate;
 };
+#ifdef MWW_GRAPH_HOST_TU   // graph_engine.hip launches it; defined once, in tu_graph.hip
+__global__ void dropout_mask_kernel(DropoutMaskArgs a);
+#else
 __global__ __launch_bounds__(kThreads) void dropout_mask_kernel(DropoutMaskArgs a) {
   const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (e >= a.n) return;
   const unsigned long long step = ((unsigned long long)a.counter[1] << 32) | a.counter[0];
   a.keep[e] = dropout_keep(a.seed, step, (unsigned long long)e, a.rate);
 }
+#endif
 
 }  // namespace mww
