@@ -392,7 +392,8 @@ int mww_assemble_prefetched(mww_ctx* ctx, mww_prefetcher* p, float* out_labels, 
  * test.py:293-403 tflite_streaming_model_roc; inference.py:82-125 Model.predict_spectrogram) without TensorFlow / TFLite.
  * A stream object borrows an existing context's device, HIP stream and uploaded feature stores (the context must outlive
  * it).  Topology: MixedNet with a first convolution, any widths / kernels / repeat_in_block, no residual connections,
- * spatial attention or pooled head.  Weights arrive in Keras get_weights() order (BN moving statistics included), so the
+ * spatial attention or pooled head (mww_stream_create); Inception - any conv/BN graph of mww_convnet_desc's Inception
+ * vocabulary - through mww_stream_create_convnet below.  Weights arrive in Keras get_weights() order (BN moving statistics included), so the
  * same call serves the specialised-kernel and the generic-graph MixedNet contexts; BN is folded into the 1x1 weights.
  *   MWW_STREAM_MODE_STREAM: Modes.STREAM_INTERNAL_STATE_INFERENCE - every Stream layer keeps the last R frames of its
  *     input (zeros after create / reset; layers/stream.py:580-594), each `stride` frames fed yield one probability, the
@@ -417,6 +418,25 @@ typedef struct {
 typedef struct mww_stream mww_stream;
 /* MWW_ERR_UNSUPPORTED (+ message) for a malformed description or a topology outside the list above */
 int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* desc, mww_stream** out);
+/* The same handle for a conv -> BN/SSN -> ReLU graph: the streaming / non-streaming Inception model (inception.py:233-338 in
+ * Modes.STREAM_INTERNAL_STATE_INFERENCE, one frame per step; csrc/tu_stream_graph.hip).  `desc` is the mww_convnet_desc of the
+ * model with the ops in Keras layer-creation order (un-fused branch heads), `mode` a MWW_STREAM_MODE_*; `dropout` and
+ * `max_batch` are not read.  Every mww_stream_* call below works on it unchanged, except the int8 ones (mww_stream_num_tensors,
+ * _calibrate_host, _set_quantized, _q8_sizes, _read_q8, _get_state_q8), which return MWW_ERR_UNSUPPORTED with a message.
+ *   vocabulary: MWW_OP_CONV, stride 0 / 1, MWW_NORM_BN (BatchNormalization or SSN groups), MWW_ACT_RELU, 1..3 sources with
+ *     src_drop and channel slices, no residual, no head_attention / head_pool.  Anything else, sources that src_drop does not
+ *     align, or a graph that does not fit `frames` is refused with MWW_ERR_UNSUPPORTED and a message naming the field.
+ *   stream mode: every op with k > 1 keeps a ring of d(k - 1) rows of its own input (all sources concatenated), the head a
+ *     ring of T_f - 1 rows of the last op's output, all zeros after create / reset (layers/stream.py:580-594); src_drop
+ *     (StridedDrop) is the identity, the branches meet at the current frame (strided_drop.py:40-44).
+ *   non_stream mode: the non-streaming model on the windows of `frames` rows ending at frames T, T + 1, ... <= L of every
+ *     track; src_drop states the right alignment the kernel computes in.
+ *   weights: Keras get_weights() order - per op kernel [k,1,Cin,F], gamma, beta, moving_mean, moving_variance [slots]
+ *     (slots = bn_groups if > 1 else F); dense.kernel [T_f*C_last,1], dense.bias - folded once (eps 1e-3, channel c -> slot
+ *     c mod g).
+ *   mww_stream_get_state: the rows that can still influence an output, in op order - every op with k > 1: [d(k-1)][Cin] (an
+ *     op fed by the spectrogram holds raw input frames), then the head [T_f-1][C_last]. */
+int mww_stream_create_convnet(mww_ctx* ctx, const mww_convnet_desc* desc, int32_t mode, mww_stream** out);
 void mww_stream_destroy(mww_stream* s);
 int64_t mww_stream_num_weights(const mww_stream* s);   /* floats of the Keras-order weight vector */
 int64_t mww_stream_num_state(const mww_stream* s);     /* floats of the rings */

@@ -107,6 +107,8 @@ struct SQ8 {
 
 }  // namespace mww_stream_impl
 
+struct mww_stream_graph;   // conv/BN graph form (tu_stream_graph.hip)
+
 struct mww_stream {
   mww_ctx* ctx = nullptr;
   int device = 0;
@@ -120,6 +122,8 @@ struct mww_stream {
   int64_t n_dev_w = 0;     // folded device weights
   int64_t n_state = 0;
   int j0 = 0;              // non-stream: conv1 index of a track's first window
+  int tile_outputs = mww_stream_impl::kTileOutputs;   // outputs per tile of this stream's kernel
+  mww_stream_graph* graph = nullptr;   // set: a conv/BN graph stream (mww_stream_create_convnet), the float graph kernel runs it
   float* w = nullptr;
   float* st[2] = {nullptr, nullptr};
   int cur = 0;
@@ -313,11 +317,12 @@ inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk,
   // segments and tiles
   std::vector<int64_t> seg_v0, tile_m0, tile_out0;
   std::vector<int> seg_coff, tile_seg, tile_n;
+  const int tile_outputs = s->tile_outputs;
   auto add_tiles = [&](int sg, int64_t n, int64_t out0) {
-    for (int64_t m = 0; m < n; m += kTileOutputs) {
+    for (int64_t m = 0; m < n; m += tile_outputs) {
       tile_seg.push_back(sg);
       tile_m0.push_back(m);
-      tile_n.push_back((int)(n - m < kTileOutputs ? n - m : kTileOutputs));
+      tile_n.push_back((int)(n - m < tile_outputs ? n - m : tile_outputs));
       tile_out0.push_back(out0 + m);
     }
   };
@@ -375,7 +380,7 @@ inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk,
   a.w = s->w;
   a.st_in = s->st[s->cur];
   a.st_out = s->st[s->cur ^ 1];
-  a.buf_rows = kTileOutputs + net.reach1;
+  a.buf_rows = tile_outputs + net.reach1;
   a.prob = s->prob;
   a.logit = s->logit;
   return n_out;

@@ -28,6 +28,11 @@ namespace mww {
 int64_t stream_q8_launch(mww_stream* s, const mww_stream_impl::SStores& S, mww_stream_impl::SCall& a, int grid);
 int stream_q8_reset(mww_stream* s);
 void stream_q8_free(mww_stream* s);
+// conv/BN graph streams (tu_stream_graph.hip)
+int stream_graph_set_weights(mww_stream* s, const float* h, int64_t n);
+int64_t stream_graph_launch(mww_stream* s, const mww_stream_impl::SStores& S, mww_stream_impl::SCall& a, int grid);
+void stream_graph_free(mww_stream* s);
+int stream_graph_no_int8(const mww_stream* s);
 }  // namespace mww
 
 namespace {
@@ -313,6 +318,7 @@ void mww_stream_destroy(mww_stream* s) {
                   (void*)s->tables, (void*)s->host_frames, (void*)s->mtab, (void*)s->d_layers, (void*)s->rec})
     if (p) (void)hipFree(p);
   mww::stream_q8_free(s);
+  mww::stream_graph_free(s);
   delete s;
 }
 
@@ -322,6 +328,7 @@ int64_t mww_stream_num_state(const mww_stream* s) { return s ? s->n_state : 0; }
 int mww_stream_set_weights(mww_stream* s, const float* h, int64_t n) {
   if (!s || !h) return mww::set_error(MWW_ERR_INVALID, "null argument");
   if (n != s->n_weights) return mww::set_error(MWW_ERR_INVALID, ("expected " + std::to_string(s->n_weights) + " Keras-order floats").c_str());
+  if (s->graph) return mww::stream_graph_set_weights(s, h, n);
   // Keras get_weights() order (mixednet.py:307-386): conv1.kernel [k1,1,40,F]; per block and repeat: per MixConv group
   // kernel [k,1,gc,1] + bias [gc], pointwise kernel [1,1,C,F], BN gamma, beta, moving_mean, moving_variance; dense [T_f*C,1], bias.
   // BatchNormalization (inference: moving statistics, eps 1e-3) is folded into the 1x1 weights and a bias once, here.
@@ -400,6 +407,7 @@ static int64_t run_tracks(mww_stream* s, const mww_window* trk, int64_t n_trk, i
   int grid = 0;
   const int64_t n_out = prepare_call(s, trk, n_trk, out_off, n_host_frames, S, a, &grid);
   if (n_out <= 0) return n_out;
+  if (s->graph) return mww::stream_graph_launch(s, S, a, grid);
   if (s->q8 && !rec) return mww::stream_q8_launch(s, S, a, grid);
   const SNet& net = s->net;
   const int64_t rows = a.buf_rows;
@@ -444,10 +452,14 @@ int64_t mww_stream_run_host(mww_stream* s, const float* frames, int64_t n_frames
   return run_tracks(s, &w, 1, off, n_frames);
 }
 
-int mww_stream_num_tensors(const mww_stream* s) { return s ? s->net.n_layers + 3 : 0; }
+int mww_stream_num_tensors(const mww_stream* s) {
+  if (s && s->graph) return mww::stream_graph_no_int8(s);
+  return s ? s->net.n_layers + 3 : 0;
+}
 
 int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_frames, float* ranges) {
   if (!s || !ranges || (n_frames && !frames) || n_frames < 0 || n_frames > INT32_MAX) return mww::set_error(MWW_ERR_INVALID, "bad frames");
+  if (s->graph) return mww::stream_graph_no_int8(s);
   const int nt = s->net.n_layers + 3;
   for (int t = 0; t < nt; ++t) {
     ranges[2 * t] = INFINITY;

@@ -333,6 +333,8 @@ class InceptionLayout:
         self.native_segs.append(("dense.bias", [self._dense + 1], "param"))
         self.n_params = sum(int(np.prod(s)) for _, s, kind in self.keras_vars if kind == "param")
         self.n_state = sum(int(np.prod(s)) for _, s, kind in self.keras_vars if kind == "state")
+        # per native op: index in keras_vars of the kernel of its first Keras layer (its place in layer-creation order)
+        self.op_keras_index = [kidx[members[0][0]] for members in self.op_members]
 
     def keras_param_counts(self):
         total = sum(int(np.prod(s)) for _, s, _ in self.keras_vars)

@@ -113,7 +113,7 @@ EXPORTS = [
     "mww_stream_create", "mww_stream_destroy", "mww_stream_num_weights", "mww_stream_num_state", "mww_stream_set_weights",
     "mww_stream_reset", "mww_stream_get_state", "mww_stream_run", "mww_stream_run_host", "mww_stream_read", "mww_stream_set_probs",
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
-    "mww_stream_read_q8", "mww_stream_get_state_q8",
+    "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet",
 ]
 
 
@@ -203,6 +203,7 @@ class NativeLib:
         L.mww_allreduce_destroy.argtypes = [C.c_void_p]
         L.mww_evaluate_windows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int]
         L.mww_stream_create.argtypes = [C.c_void_p, C.POINTER(StreamDesc), C.POINTER(C.c_void_p)]
+        L.mww_stream_create_convnet.argtypes = [C.c_void_p, C.POINTER(ConvNetDesc), C.c_int32, C.POINTER(C.c_void_p)]
         L.mww_stream_destroy.argtypes = [C.c_void_p]
         L.mww_stream_destroy.restype = None
         for f in (L.mww_stream_num_weights, L.mww_stream_num_state):
@@ -337,6 +338,31 @@ class Prefetcher:
             pass
 
 
+def _fill_conv_ops(d: ConvNetDesc, conv_ops):
+    """the ``mww_conv_bn_op`` entries of ``d`` from a list of op dicts (``Engine``'s ``conv_ops``)"""
+    if len(conv_ops) > MWW_MAX_GRAPH_OPS:
+        raise ValueError("too many ops")
+    d.n_ops = len(conv_ops)
+    for i, op in enumerate(conv_ops):
+        o = d.ops[i]
+        src, drop = list(op["src"]), list(op.get("drop", [0] * len(op["src"])))
+        if len(src) > MWW_MAX_OP_SOURCES or len(src) != len(drop):
+            raise ValueError("bad source lists")
+        o.n_src = len(src)
+        sl = list(op.get("slice", [(0, 0)] * len(src)))   # (first channel, width); width 0 = whole tensor
+        for j, (sj, dj) in enumerate(zip(src, drop)):
+            o.src[j], o.src_drop[j] = int(sj), int(dj)
+            o.src_c0[j], o.src_cn[j] = int(sl[j][0]), int(sl[j][1])
+        o.kernel, o.dilation, o.filters = int(op["kernel"]), int(op.get("dilation", 1)), int(op["filters"])
+        o.bn_groups = int(op.get("bn_groups", 1))
+        o.kind = OP_KINDS[op.get("kind", "conv")]
+        o.stride = int(op.get("stride", 1))
+        o.norm = NORMS[op.get("norm", "bn")]
+        o.act = ACTS[op.get("act", "relu")]
+        o.residual = 0 if op.get("residual") is None else int(op["residual"]) + 1
+        o.residual_drop = int(op.get("residual_drop", 0))
+
+
 class Engine:
     """One device context (``mww_ctx``): model weights, HBM-resident feature stores, the train step."""
 
@@ -356,26 +382,7 @@ class Engine:
             d = ConvNetDesc()
             d.frames, d.n_ops, d.dropout, d.max_batch = int(frames), len(conv_ops), float(dropout), int(max_batch)
             d.head_attention, d.head_pool = int(bool(head_attention)), int(head_pool)
-            if len(conv_ops) > MWW_MAX_GRAPH_OPS:
-                raise ValueError("too many ops")
-            for i, op in enumerate(conv_ops):
-                o = d.ops[i]
-                src, drop = list(op["src"]), list(op.get("drop", [0] * len(op["src"])))
-                if len(src) > MWW_MAX_OP_SOURCES or len(src) != len(drop):
-                    raise ValueError("bad source lists")
-                o.n_src = len(src)
-                sl = list(op.get("slice", [(0, 0)] * len(src)))   # (first channel, width); width 0 = whole tensor
-                for j, (sj, dj) in enumerate(zip(src, drop)):
-                    o.src[j], o.src_drop[j] = int(sj), int(dj)
-                    o.src_c0[j], o.src_cn[j] = int(sl[j][0]), int(sl[j][1])
-                o.kernel, o.dilation, o.filters = int(op["kernel"]), int(op.get("dilation", 1)), int(op["filters"])
-                o.bn_groups = int(op.get("bn_groups", 1))
-                o.kind = OP_KINDS[op.get("kind", "conv")]
-                o.stride = int(op.get("stride", 1))
-                o.norm = NORMS[op.get("norm", "bn")]
-                o.act = ACTS[op.get("act", "relu")]
-                o.residual = 0 if op.get("residual") is None else int(op["residual"]) + 1
-                o.residual_drop = int(op.get("residual_drop", 0))
+            _fill_conv_ops(d, conv_ops)
             self.desc = d
             h = C.c_void_p()
             self.nl.check(self.nl.lib.mww_create_convnet(C.byref(d), int(device), C.c_void_p(stream or 0), C.byref(h)))
@@ -631,10 +638,13 @@ class Stream:
         d.t_final, d.frames, d.mode = int(desc["t_final"]), int(desc.get("frames", 0)), STREAM_MODES[desc.get("mode", "stream")]
         h = C.c_void_p()
         self.nl.check(self.nl.lib.mww_stream_create(engine.h, C.byref(d), C.byref(h)))
+        self._created(h, int(d.stride))
+
+    def _created(self, h, stride):
         self.h = h
         self.n_weights = int(self.nl.lib.mww_stream_num_weights(self.h))
         self.n_state = int(self.nl.lib.mww_stream_num_state(self.h))
-        self.stride = int(d.stride)
+        self.stride = stride
         self.n_out = 0
 
     def close(self):
@@ -738,6 +748,24 @@ class Stream:
         a = np.zeros(self.n_state, np.int8)
         self.nl.check(self.nl.lib.mww_stream_get_state_q8(self.h, a.ctypes.data_as(C.c_void_p), a.size))
         return a
+
+
+class GraphStream(Stream):
+    """``mww_stream_create_convnet``: the streaming / non-streaming form of a conv/BN graph (Inception) with the methods of
+    ``Stream``.  ``desc``: a dict with conv_ops (``Engine``'s op dicts in Keras layer-creation order:
+    ``InceptionLayout(flags, T, fuse_heads=False).ops``), frames, mode ("stream" / "non_stream") and, optionally,
+    head_attention / head_pool (both refused by the library).  The int8 methods raise ``NativeError``."""
+
+    def __init__(self, engine: "Engine", desc: dict):
+        self.engine = engine   # the context is borrowed: keep it alive
+        self.nl = engine.nl
+        d = ConvNetDesc()
+        d.frames, d.dropout, d.max_batch = int(desc["frames"]), 0.0, 1
+        d.head_attention, d.head_pool = int(bool(desc.get("head_attention", 0))), int(desc.get("head_pool", 0))
+        _fill_conv_ops(d, list(desc["conv_ops"]))
+        h = C.c_void_p()
+        self.nl.check(self.nl.lib.mww_stream_create_convnet(engine.h, C.byref(d), STREAM_MODES[desc.get("mode", "stream")], C.byref(h)))
+        self._created(h, 1)
 
 
 FEATURE_BINS_ = 40

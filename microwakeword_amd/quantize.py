@@ -328,11 +328,18 @@ def calibration_frames(data_processor, config) -> np.ndarray:
     return np.concatenate(parts + [np.zeros((0, FEATURE_BINS), np.float32)], 0)
 
 
+def _mixednet_only(model):
+    from .layout import InceptionLayout
+    if isinstance(getattr(model, "layout", None), InceptionLayout):
+        raise NotImplementedError("the int8 evaluation covers MixedNet only (int8 Inception is not implemented)")
+
+
 def calibrate(model, data_processor, config) -> np.ndarray:
     """The calibrated [min, max] of every tensor (``tensor_names``) of ``model`` (a trained MixedNet
     ``microwakeword_amd.model.Model``): one stream-mode run of the float streaming kernel from zero rings over
     ``calibration_frames``.  Returns float32 [n_tensors, 2]."""
     from .streaming import StreamingModel
+    _mixednet_only(model)
     frames = calibration_frames(data_processor, config)
     sm = StreamingModel(model, int(config["stride"]), "stream")
     return sm.native.calibrate_host(frames)
@@ -342,6 +349,7 @@ def quantize(model, ranges) -> QuantizedModel:
     """``quantize_weights`` of a trained MixedNet ``model`` at its own stride."""
     from .layout import _flag
     from .streaming import stream_description
+    _mixednet_only(model)
     lay = model.layout
     desc = stream_description(model.flags, lay.t_last, lay.frames, int(_flag(model.flags, "stride")), "stream")
     return quantize_weights(desc, model.get_weights(), ranges)

@@ -1,9 +1,9 @@
-"""Streaming inference and the FAPH / FRR evaluation of a trained MixedNet on the MI355X - the step after training that the
+"""Streaming inference and the FAPH / FRR evaluation of a trained MixedNet or Inception model on the MI355X - the step after training that the
 reference runs with its ``--test_*`` flags (microwakeword/model_train_eval.py:131-272 ``evaluate_model``):
 
   * ``StreamingModel``            the model the reference converts with ``utils.convert_model_saved`` and runs through
                                   ``inference.Model`` (inference.py:82-125 ``predict_spectrogram``), as a native
-                                  ``mww_stream`` (csrc/tu_stream.hip): ``mode="stream"`` is
+                                  ``mww_stream`` (csrc/tu_stream.hip; Inception: csrc/tu_stream_graph.hip): ``mode="stream"`` is
                                   Modes.STREAM_INTERNAL_STATE_INFERENCE (``--test_tflite_streaming``), ``mode="non_stream"``
                                   the non-streaming model on every ``stride``-th window (``--test_tflite_nonstreaming``)
   * ``false_accepts_per_hour``    test.py:94-137 ``compute_false_accepts_per_hour``
@@ -24,7 +24,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import native
-from .layout import FEATURE_BINS, _flag, parse
+from .layout import FEATURE_BINS, InceptionLayout, _flag, parse
 
 SCALE_U16 = np.float32(0.0390625)
 CUTOFFS = np.arange(0, 1.01, 0.01)   # test.py:331
@@ -59,9 +59,27 @@ def stream_description(flags, t_final: int, frames: int, stride: int, mode: str)
                 stride=int(stride), blocks=list(zip(rep, ksz, pf)), t_final=int(t_final), frames=int(frames), mode=mode)
 
 
+def graph_stream_description(flags, frames: int, stride: int, mode: str) -> dict:
+    """The description of a streaming Inception (inception.py:233-338) for ``native.GraphStream``: the un-fused op list in
+    Keras layer-creation order, so ``get_weights()`` feeds it as it is.  Inception has no ``--stride``: one frame per
+    step."""
+    if mode not in native.STREAM_MODES:
+        raise ValueError("mode must be 'stream' or 'non_stream'")
+    if int(stride) != 1:
+        raise ValueError("the streaming stride (%d) must be 1: an Inception model has no --stride" % int(stride))
+    lay = InceptionLayout(flags, int(frames), fuse_heads=False)
+    # the layout lists a block's three 1x1 branch heads first (b1, b2a, b3a, b2b, ...); Keras creates b1, b2a, b2b, b3a, ...
+    order = sorted(range(len(lay.ops)), key=lambda o: lay.op_keras_index[o])
+    at = {old: new for new, old in enumerate(order)}
+    ops = [dict(lay.ops[o], src=[at[s] if s >= 0 else -1 for s in lay.ops[o]["src"]]) for o in order]
+    assert all(s < i for i, op in enumerate(ops) for s in op["src"])
+    return dict(conv_ops=ops, frames=int(frames), stride=1, mode=mode)
+
+
 class StreamingModel:
-    """The streaming (``mode="stream"``) or non-streaming (``mode="non_stream"``) form of a trained MixedNet ``model``
-    (``microwakeword_amd.model.Model``, either kernel family), sharing the model's context: its device, HIP stream and the
+    """The streaming (``mode="stream"``) or non-streaming (``mode="non_stream"``) form of a trained MixedNet or Inception
+    ``model`` (``microwakeword_amd.model.Model``, any kernel family; MixedNet on csrc/tu_stream.hip, Inception on
+    csrc/tu_stream_graph.hip), sharing the model's context: its device, HIP stream and the
     feature stores a ``FeatureHandler`` uploaded there.  The weights are taken from ``model`` when this object is created
     (``set_weights`` takes new ones)."""
 
@@ -70,11 +88,15 @@ class StreamingModel:
         self.mode = mode
         self.stride = int(stride)
         lay = model.layout
-        if not hasattr(lay, "t_last") or lay.__class__.__name__ == "InceptionLayout":
-            raise NotImplementedError("streaming evaluation covers MixedNet only (streaming Inception is not implemented)")
+        if not hasattr(lay, "t_last"):
+            raise NotImplementedError("streaming evaluation covers MixedNet and Inception models")
         self.frames = int(lay.frames)   # input_feature_slices of the non-streaming model
-        self.desc = stream_description(model.flags, lay.t_last, lay.frames, stride, mode)
-        self.native = native.Stream(model.engine, self.desc)
+        if isinstance(lay, InceptionLayout):
+            self.desc = graph_stream_description(model.flags, lay.frames, stride, mode)
+            self.native = native.GraphStream(model.engine, self.desc)
+        else:
+            self.desc = stream_description(model.flags, lay.t_last, lay.frames, stride, mode)
+            self.native = native.Stream(model.engine, self.desc)
         self.set_weights(model.get_weights())
 
     def set_weights(self, weights: Sequence[np.ndarray]):

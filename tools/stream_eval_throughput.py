@@ -1,10 +1,11 @@
-"""Throughput of the streaming evaluation (csrc/tu_stream.hip) on synthetic u16 stores: N hours of ambient tracks plus
+"""Throughput of the streaming evaluation (csrc/tu_stream.hip; Inception: csrc/tu_stream_graph.hip) on synthetic u16 stores: N hours of ambient tracks plus
 positives through ``StreamingModel.predict_tracks`` + the metrics kernel, against the windowed alternative at the same stride
-(``Engine.evaluate_windows`` over every s-th 194-frame window of the ambient audio).  Prints one JSON line.
+(``Engine.evaluate_windows`` over every s-th T-frame window of the ambient audio).  Prints one JSON line.
 
     python tools/stream_eval_throughput.py --hours 20
     python tools/stream_eval_throughput.py --hours 20 --quantized   # the int8 model (csrc/tu_stream_q8.hip); also times
                                                                     # the calibration pass (500 spectrograms) + quantization
+    python tools/stream_eval_throughput.py --hours 20 --model inception   # the default Inception flags, T = 176
 """
 import argparse
 import json
@@ -15,11 +16,13 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from microwakeword_amd import mixednet, native, quantize, streaming  # noqa: E402
+from microwakeword_amd import inception, mixednet, native, quantize, streaming  # noqa: E402
 
 DEF = dict(pointwise_filters="48,48,48,48", residual_connection="0,0,0,0", repeat_in_block="1,1,1,1",
            mixconv_kernel_sizes="[5],[9],[13],[21]", max_pool=0, first_conv_filters=32, first_conv_kernel_size=3,
            spatial_attention=0, pooled=0, stride=1)
+INC = dict(cnn1_filters="24", cnn1_kernel_sizes="5", cnn1_subspectral_groups="4", cnn2_filters1="10,10,16", cnn2_filters2="10,10,16",
+           cnn2_kernel_sizes="5,5,5", cnn2_subspectral_groups="1,1,1", cnn2_dilation="1,1,1", dropout=0.2)   # inception.py:145-209
 
 
 def main():
@@ -27,13 +30,24 @@ def main():
     ap.add_argument("--hours", type=float, default=20.0)
     ap.add_argument("--track_minutes", type=float, default=60.0)
     ap.add_argument("--positives", type=int, default=2000)
-    ap.add_argument("--frames", type=int, default=194)
+    ap.add_argument("--model", choices=("mixednet", "inception"), default="mixednet")
+    ap.add_argument("--frames", type=int, default=None, help="window length T (default 194 for mixednet, 176 for inception)")
     ap.add_argument("--window_hours", type=float, default=1.0, help="ambient hours the windowed alternative is timed on")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--quantized", action="store_true", help="time the int8 streaming model instead of the float one")
     a = ap.parse_args()
-    T = a.frames
-    model = mixednet.model(DEF, (T, 40), 1024, max_batch=1024, seed=3)
+    if a.model == "inception":
+        if a.quantized:
+            ap.error("--quantized covers the MixedNet model only")
+        T = a.frames or 176
+        model = inception.model(INC, (T, 40), 1024, max_batch=1024, seed=3)
+        name = "inception cnn1 %s/%s/%s cnn2 %s/%s k %s d %s (T=%d)" % (
+            INC["cnn1_filters"], INC["cnn1_kernel_sizes"], INC["cnn1_subspectral_groups"], INC["cnn2_filters1"], INC["cnn2_filters2"],
+            INC["cnn2_kernel_sizes"], INC["cnn2_dilation"], T)
+    else:
+        T = a.frames or 194
+        model = mixednet.model(DEF, (T, 40), 1024, max_batch=1024, seed=3)
+        name = "mixednet default (T=%d)" % T
     rng = np.random.default_rng(0)
     per_track = int(a.track_minutes * 60 * 50)
     n_amb = max(1, int(round(a.hours * 60 / a.track_minutes)))
@@ -81,7 +95,7 @@ def main():
         ts.append(time.perf_counter() - t0)
     t = min(ts)
     hours = (amb_frames + int(pos_len.sum())) * 0.02 / 3600
-    # windowed alternative: every 1-frame-stride 194-frame window of `window_hours` of the ambient audio
+    # windowed alternative: every 1-frame-stride T-frame window of `window_hours` of the ambient audio
     nw = int(a.window_hours * 3600 * 50)
     nw = min(nw, amb_frames - T)
     win = np.zeros(nw, native.WINDOW_DTYPE)
@@ -93,7 +107,7 @@ def main():
     model.engine.evaluate_windows(win, labels, 1024)
     model.engine.synchronize()
     tw = time.perf_counter() - t0
-    rec = {"tool": "stream_eval_throughput", "model": "mixednet default (T=%d)" % T, **extra, "stride": 1, "ambient_hours": round(amb_frames * 0.02 / 3600, 3),
+    rec = {"tool": "stream_eval_throughput", "model": name, **extra, "stride": 1, "ambient_hours": round(amb_frames * 0.02 / 3600, 3),
            "ambient_tracks": n_amb, "positives": a.positives, "outputs": n_out, "seconds": round(t, 4),
            "outputs_per_s": round(n_out / t, 1), "audio_hours_per_s": round(hours / t, 3),
            "windowed_outputs": nw, "windowed_seconds": round(tw, 4), "windowed_outputs_per_s": round(nw / tw, 1),
