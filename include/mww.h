@@ -422,7 +422,9 @@ int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* desc, mww_stream** ou
  * Modes.STREAM_INTERNAL_STATE_INFERENCE, one frame per step; csrc/tu_stream_graph.hip).  `desc` is the mww_convnet_desc of the
  * model with the ops in Keras layer-creation order (un-fused branch heads), `mode` a MWW_STREAM_MODE_*; `dropout` and
  * `max_batch` are not read.  Every mww_stream_* call below works on it unchanged, except the int8 ones (mww_stream_num_tensors,
- * _calibrate_host, _set_quantized, _q8_sizes, _read_q8, _get_state_q8), which return MWW_ERR_UNSUPPORTED with a message.
+ * _calibrate_host, _set_quantized, _q8_sizes, _read_q8, _get_state_q8), which return MWW_ERR_UNSUPPORTED with a message
+ * ("... MixedNet streams only ...") on a stream of this creator; mww_stream_create_convnet_q8 below creates the graph stream
+ * that takes them.
  *   vocabulary: MWW_OP_CONV, stride 0 / 1, MWW_NORM_BN (BatchNormalization or SSN groups), MWW_ACT_RELU, 1..3 sources with
  *     src_drop and channel slices, no residual, no head_attention / head_pool.  Anything else, sources that src_drop does not
  *     align, or a graph that does not fit `frames` is refused with MWW_ERR_UNSUPPORTED and a message naming the field.
@@ -437,6 +439,26 @@ int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* desc, mww_stream** ou
  *   mww_stream_get_state: the rows that can still influence an output, in op order - every op with k > 1: [d(k-1)][Cin] (an
  *     op fed by the spectrogram holds raw input frames), then the head [T_f-1][C_last]. */
 int mww_stream_create_convnet(mww_ctx* ctx, const mww_convnet_desc* desc, int32_t mode, mww_stream** out);
+/* The same graph stream (same vocabulary, refusals, weights and state layout, same handle type) on which the six int8 entry
+ * points work: calibration on the float graph kernel, then the int8 graph kernel (csrc/tu_stream_graph_q8.hip) once
+ * mww_stream_set_quantized has loaded parameters.  It is a creator of its own, and not a behaviour of the one above,
+ * because the refusal of the int8 calls on a stream of mww_stream_create_convnet is pinned by the test-suite
+ * (tests/test_inception_streaming_emulated.py): the old name keeps its behaviour, the feature arrives under a new one.
+ *   tensors (mww_stream_num_tensors = n_ops + 2): 0 the input, 1 + i the output of op i (after folded BN/SSN + ReLU),
+ *     n_ops + 1 the Dense logit.  mww_stream_calibrate_host: as below; the input range is taken from the fed frames, every
+ *     other range over every position computed (a tile's halo only repeats real positions).
+ *   mww_stream_set_quantized on such a stream:
+ *     weights (int8): per op, output-major [Co][k][source 0: cn_0 rounded up to 4] ... [source n-1: cn rounded up to 4]
+ *                     (padding entries 0; every op starts on a 4-byte boundary); then the Dense [T_f][C_last rounded up to 4]
+ *     ints (int32):   per op: bias with the input zero point folded (b - zp_in * sum of the filter's weights over all taps
+ *                     and channels) [cout], multiplier [cout], shift [cout]; the Dense's bias, multiplier, shift; then the
+ *                     n_ops + 2 zero points.  All sources of an op share one scale and zero point (TFLite's CONCATENATION
+ *                     constraint; microwakeword_amd/quantize_graph.py), which is what makes one folded bias exact.
+ *     validation as for a MixedNet stream: sizes, zero points in [-128, 127], multipliers >= 0, shifts in [-31, 30].
+ *   mww_stream_reset fills every ring with the zero point of the tensor it holds; mww_stream_get_state_q8 has the layout of
+ *   mww_stream_get_state, one byte per value.  The uint8 output goes through the 256-entry table; probability
+ *   (float)u8 * (float)(1/255) and the int8 logit (as float) land in the buffers mww_stream_read / _metrics read. */
+int mww_stream_create_convnet_q8(mww_ctx* ctx, const mww_convnet_desc* desc, int32_t mode, mww_stream** out);
 void mww_stream_destroy(mww_stream* s);
 int64_t mww_stream_num_weights(const mww_stream* s);   /* floats of the Keras-order weight vector */
 int64_t mww_stream_num_state(const mww_stream* s);     /* floats of the rings */

@@ -1,4 +1,4 @@
-// Integer dot product of the int8 streaming kernel (tu_stream_q8.hip) and TFLite's fixed-point requantization.
+// Integer dot product of the int8 streaming kernels (tu_stream_q8.hip, tu_stream_graph_q8.hip), the input quantization and TFLite's fixed-point requantization.
 // On gfx950 mww_sdot4 is v_dot4_i32_i8 (__builtin_amdgcn_sdot4); under the host emulator (HIPEMU) it is a plain C++ twin,
 // exact because the arithmetic is integer.
 #pragma once
@@ -16,6 +16,15 @@ static inline int mww_sdot4(int a, int b, int c) {
 #else
 __device__ inline int mww_sdot4(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
 #endif
+
+__device__ inline int8_t quantize_input(float x, float scale, int zp) {
+  // inference.py:127-147 (data / scale + zp).astype(int8) with the float32 reading: IEEE division, float32 add, truncation;
+  // saturated to [-128, 127]
+  float t = x / scale + (float)zp;
+  t = truncf(t);
+  t = t < -128.f ? -128.f : (t > 127.f ? 127.f : t);
+  return (int8_t)(int)t;
+}
 
 // SaturatingRoundingDoublingHighMul: (a * b + nudge) / 2^31, C division (truncating)
 __device__ inline int32_t q8_srdhm(int32_t a, int32_t b) {

@@ -85,6 +85,25 @@ __device__ inline float frame_value(const SStores& S, const SCall& a, int64_t v,
   return static_cast<const float*>(S.p[w.store])[e];
 }
 
+// Calibration (REC): every thread keeps the min / max of the values it computes for the current tensor; the block folds
+// them in thread order into its running [n_tensors] min / max, written once per workgroup at the end.
+__device__ inline void rec_fold(float lmin, float lmax, int t, float* red, float* rmin, float* rmax) {
+  const int tid = threadIdx.x;
+  red[tid] = lmin;
+  red[kStreamThreads + tid] = lmax;
+  __syncthreads();
+  if (tid == 0) {
+    float lo = rmin[t], hi = rmax[t];
+    for (int i = 0; i < kStreamThreads; ++i) {
+      lo = fminf(lo, red[i]);
+      hi = fmaxf(hi, red[kStreamThreads + i]);
+    }
+    rmin[t] = lo;
+    rmax[t] = hi;
+  }
+  __syncthreads();
+}
+
 // int8 form (tu_stream_q8.hip): device copies of the quantized parameters; layout in include/mww.h
 struct SQ8 {
   const int8_t* w;       // int8 weights

@@ -33,28 +33,12 @@ int stream_graph_set_weights(mww_stream* s, const float* h, int64_t n);
 int64_t stream_graph_launch(mww_stream* s, const mww_stream_impl::SStores& S, mww_stream_impl::SCall& a, int grid);
 void stream_graph_free(mww_stream* s);
 int stream_graph_no_int8(const mww_stream* s);
+bool stream_graph_int8(const mww_stream* s);   // created by mww_stream_create_convnet_q8
+int stream_graph_num_tensors(const mww_stream* s);
+int64_t stream_graph_q8_launch(mww_stream* s, const mww_stream_impl::SStores& S, mww_stream_impl::SCall& a, int grid);   // tu_stream_graph_q8.hip
 }  // namespace mww
 
 namespace {
-
-// Calibration (REC): every thread keeps the min / max of the values it computes for the current tensor; the block folds
-// them in thread order into its running [n_tensors] min / max, written once per workgroup at the end.
-__device__ inline void rec_fold(float lmin, float lmax, int t, float* red, float* rmin, float* rmax) {
-  const int tid = threadIdx.x;
-  red[tid] = lmin;
-  red[kStreamThreads + tid] = lmax;
-  __syncthreads();
-  if (tid == 0) {
-    float lo = rmin[t], hi = rmax[t];
-    for (int i = 0; i < kStreamThreads; ++i) {
-      lo = fminf(lo, red[i]);
-      hi = fmaxf(hi, red[kStreamThreads + i]);
-    }
-    rmin[t] = lo;
-    rmax[t] = hi;
-  }
-  __syncthreads();
-}
 
 constexpr int kMaxTensors = 3 + 2 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT;
 
@@ -407,7 +391,12 @@ static int64_t run_tracks(mww_stream* s, const mww_window* trk, int64_t n_trk, i
   int grid = 0;
   const int64_t n_out = prepare_call(s, trk, n_trk, out_off, n_host_frames, S, a, &grid);
   if (n_out <= 0) return n_out;
-  if (s->graph) return mww::stream_graph_launch(s, S, a, grid);
+  if (s->graph) {
+    if (s->q8 && !rec) return mww::stream_graph_q8_launch(s, S, a, grid);
+    a.rec = rec;
+    a.n_tensors = rec ? mww::stream_graph_num_tensors(s) : 0;
+    return mww::stream_graph_launch(s, S, a, grid);
+  }
   if (s->q8 && !rec) return mww::stream_q8_launch(s, S, a, grid);
   const SNet& net = s->net;
   const int64_t rows = a.buf_rows;
@@ -453,14 +442,14 @@ int64_t mww_stream_run_host(mww_stream* s, const float* frames, int64_t n_frames
 }
 
 int mww_stream_num_tensors(const mww_stream* s) {
-  if (s && s->graph) return mww::stream_graph_no_int8(s);
+  if (s && s->graph) return mww::stream_graph_int8(s) ? mww::stream_graph_num_tensors(s) : mww::stream_graph_no_int8(s);
   return s ? s->net.n_layers + 3 : 0;
 }
 
 int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_frames, float* ranges) {
   if (!s || !ranges || (n_frames && !frames) || n_frames < 0 || n_frames > INT32_MAX) return mww::set_error(MWW_ERR_INVALID, "bad frames");
-  if (s->graph) return mww::stream_graph_no_int8(s);
-  const int nt = s->net.n_layers + 3;
+  if (s->graph && !mww::stream_graph_int8(s)) return mww::stream_graph_no_int8(s);
+  const int nt = s->graph ? mww::stream_graph_num_tensors(s) : s->net.n_layers + 3;
   for (int t = 0; t < nt; ++t) {
     ranges[2 * t] = INFINITY;
     ranges[2 * t + 1] = -INFINITY;
@@ -482,7 +471,7 @@ int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_fram
   int64_t off[2];
   const int64_t n_out = run_tracks(s, &w, 1, off, n_frames, s->rec);
   if (n_out <= 0) return (int)n_out;
-  const int64_t n_tiles = (n_out + kTileOutputs - 1) / kTileOutputs;
+  const int64_t n_tiles = (n_out + s->tile_outputs - 1) / s->tile_outputs;
   const int grid = (int)(n_tiles < 2 * s->n_cu ? n_tiles : 2 * s->n_cu);
   std::vector<float> part((size_t)grid * nt * 2);
   SCHK(hipMemcpy(part.data(), s->rec, part.size() * sizeof(float), hipMemcpyDeviceToHost));

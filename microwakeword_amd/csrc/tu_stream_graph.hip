@@ -35,45 +35,31 @@
 
 #include <algorithm>
 
-#include "stream_common.hip.h"
+#include "stream_graph.hip.h"
 
 using namespace mww_stream_impl;
 
 namespace {
 
-constexpr int kGraphTileOutputs = 256;   // outputs per tile
 constexpr double kBnEps = 1e-3;
+constexpr int kMaxGraphTensors = MWW_MAX_GRAPH_OPS + 2;
 
-struct GOp {
-  int n_src, k, d, cin, cout, R, reach, sync;
-  int src_C[MWW_MAX_OP_SOURCES];       // row pitch of the source tensor
-  int src_c0[MWW_MAX_OP_SOURCES];      // first channel of the slice read
-  int src_cn[MWW_MAX_OP_SOURCES];      // channels read
-  int src_reach[MWW_MAX_OP_SOURCES];   // reach of the source tensor (its first row in a tile: max(0, c0 - reach))
-  int64_t src_buf[MWW_MAX_OP_SOURCES]; // offset of the source tensor in the workgroup's scratch
-  int64_t out_buf, w, b, ring;         // scratch offset of the output; weight [k][cin][cout] / bias [cout] / ring [R][cin] offsets
-};
-
-struct GNet {
-  int n_ops, tf, c_last, in_reach;
-  int64_t in_buf, last_buf, wd, bd, ring_head;
-  const GOp* ops;   // [n_ops], device memory
-};
-
-}  // namespace
-
-struct mww_stream_graph {
-  GNet net{};
-  std::vector<GOp> ops;
-  std::vector<int> groups;   // bn_groups of each op
-  GOp* d_ops = nullptr;
-  int64_t scratch_per_wg = 0;
-};
-
-namespace {
-
+// REC (calibration, mww_stream_calibrate_host on a stream of mww_stream_create_convnet_q8): every thread keeps the min / max
+// of the values it computes for the current tensor (1 + o: the output of op o; n_ops + 1: the logit), the block folds them in
+// thread order after each op (rec_fold) and writes its [n_tensors] partial row once, at the end.  <false> is the kernel
+// as it was before recording existed.
+template <bool REC>
 __global__ void __launch_bounds__(kStreamThreads) stream_graph_kernel(GNet net, SStores S, SCall a) {
   const int tid = threadIdx.x;
+  __shared__ float red[REC ? 2 * kStreamThreads : 1], rmin[REC ? kMaxGraphTensors : 1], rmax[REC ? kMaxGraphTensors : 1];
+  float lmin = INFINITY, lmax = -INFINITY;
+  if (REC) {
+    for (int t = tid; t < a.n_tensors; t += kStreamThreads) {
+      rmin[t] = INFINITY;
+      rmax[t] = -INFINITY;
+    }
+    __syncthreads();
+  }
   float* B = a.scratch + (int64_t)blockIdx.x * a.scratch_per_wg;
   for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const int sg = a.tile_seg[tile];
@@ -125,6 +111,15 @@ __global__ void __launch_bounds__(kStreamThreads) stream_graph_kernel(GNet net, 
           }
         }
         out[idx] = acc > 0.f ? acc : 0.f;
+        if (REC) {
+          lmin = fminf(lmin, out[idx]);
+          lmax = fmaxf(lmax, out[idx]);
+        }
+      }
+      if (REC) {
+        rec_fold(lmin, lmax, 1 + o, red, rmin, rmax);
+        lmin = INFINITY;
+        lmax = -INFINITY;
       }
       if (last && R > 0) {   // this op's ring after the call: its input at positions [N - R, N)
         for (int idx = tid; idx < R * Ci; idx += kStreamThreads) {
@@ -161,6 +156,15 @@ __global__ void __launch_bounds__(kStreamThreads) stream_graph_kernel(GNet net, 
       const int64_t g = a.tile_out0[tile] + o;
       a.logit[g] = acc;
       a.prob[g] = 1.f / (1.f + expf(-acc));
+      if (REC) {
+        lmin = fminf(lmin, acc);
+        lmax = fmaxf(lmax, acc);
+      }
+    }
+    if (REC) {
+      rec_fold(lmin, lmax, net.n_ops + 1, red, rmin, rmax);
+      lmin = INFINITY;
+      lmax = -INFINITY;
     }
     if (last) {
       for (int idx = tid; idx < (TF - 1) * C; idx += kStreamThreads) {
@@ -171,6 +175,11 @@ __global__ void __launch_bounds__(kStreamThreads) stream_graph_kernel(GNet net, 
     }
     __syncthreads();   // the next tile reuses the scratch
   }
+  if (REC)
+    for (int t = tid; t < a.n_tensors; t += kStreamThreads) {
+      a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2] = rmin[t];
+      a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2 + 1] = rmax[t];
+    }
 }
 
 inline int bad(int op, const char* field, const std::string& why) {
@@ -218,6 +227,7 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
   std::vector<int> len((size_t)n), ch((size_t)n), reach((size_t)n, 0), last_use((size_t)n, -1);
   g->ops.assign((size_t)n, GOp{});
   g->groups.assign((size_t)n, 1);
+  g->src.assign((size_t)n * MWW_MAX_OP_SOURCES, -1);
   int64_t kw = 0, dw = 0, st = 0;
   for (int i = 0; i < n; ++i) {
     const mww_conv_bn_op& o = d.ops[i];
@@ -248,6 +258,7 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
       const int cn = o.src_cn[j] ? o.src_cn[j] : sc - o.src_c0[j];
       if (o.src_c0[j] < 0 || cn <= 0 || o.src_c0[j] + cn > sc) return bad(i, "src_c0 / src_cn", "is not a slice of the source");
       L.src_C[j] = sc;
+      g->src[(size_t)i * MWW_MAX_OP_SOURCES + j] = src;
       L.src_c0[j] = o.src_c0[j];
       L.src_cn[j] = cn;
       cin += cn;
@@ -285,53 +296,75 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
   }
   if (in_reach > d.frames - 1) return bad(-1, "frames", "is shorter than the graph's receptive field");   // cannot happen with aligned sources
   net.in_reach = in_reach;
-  // scratch plan by liveness + barrier flags
-  Arena ar;
-  std::vector<int64_t> buf((size_t)n), size((size_t)n);
-  const int64_t in_size = (int64_t)(tile + in_reach) * MWW_FEATURE_BINS;
-  net.in_buf = ar.take(in_size);
+  // scratch plan by liveness + barrier flags: once in floats (pitch C), once in bytes for the int8 kernel (pitch r4(C), so
+  // every offset stays 4-byte aligned); the two differ in which buffers the arena reuses, hence in the barrier flags too
   int in_last = -1;
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < d.ops[i].n_src; ++j)
       if (d.ops[i].src[j] < 0) in_last = i;
-  typedef std::pair<int64_t, int64_t> Iv;
-  std::vector<Iv> rd, wr;   // regions read / written since the last barrier
-  wr.emplace_back(net.in_buf, in_size);
-  auto hits = [](const std::vector<Iv>& v, int64_t off, int64_t sz) {
-    for (const Iv& r : v)
-      if (off < r.first + r.second && r.first < off + sz) return true;
-    return false;
+  auto place = [&](std::vector<GOp>& ops, GNet& pn, bool bytes) {
+    Arena ar;
+    std::vector<int64_t> buf((size_t)n), size((size_t)n);
+    const int64_t in_size = (int64_t)(tile + in_reach) * MWW_FEATURE_BINS;
+    pn.in_buf = ar.take(in_size);
+    typedef std::pair<int64_t, int64_t> Iv;
+    std::vector<Iv> rd, wr;   // regions read / written since the last barrier
+    wr.emplace_back(pn.in_buf, in_size);
+    auto hits = [](const std::vector<Iv>& v, int64_t off, int64_t sz) {
+      for (const Iv& r : v)
+        if (off < r.first + r.second && r.first < off + sz) return true;
+      return false;
+    };
+    for (int i = 0; i < n; ++i) {
+      GOp& L = ops[(size_t)i];
+      L.reach = reach[(size_t)i];
+      size[(size_t)i] = (int64_t)(tile + L.reach) * (bytes ? r4(L.cout) : L.cout);
+      buf[(size_t)i] = L.out_buf = ar.take(size[(size_t)i]);
+      bool need = hits(rd, L.out_buf, size[(size_t)i]) || hits(wr, L.out_buf, size[(size_t)i]);
+      for (int j = 0; j < L.n_src; ++j) {
+        const int src = d.ops[i].src[j];
+        L.src_buf[j] = src < 0 ? pn.in_buf : buf[(size_t)src];
+        L.src_reach[j] = src < 0 ? in_reach : reach[(size_t)src];
+        if (bytes) L.src_C[j] = (int)r4(L.src_C[j]);
+        need = need || hits(wr, L.src_buf[j], src < 0 ? in_size : size[(size_t)src]);
+      }
+      L.sync = need ? 1 : 0;
+      if (need) {
+        rd.clear();
+        wr.clear();
+      }
+      wr.emplace_back(L.out_buf, size[(size_t)i]);
+      for (int j = 0; j < L.n_src; ++j) {
+        const int src = d.ops[i].src[j];
+        rd.emplace_back(L.src_buf[j], src < 0 ? in_size : size[(size_t)src]);
+      }
+      // buffers whose last consumer this op is go back to the arena (an op nobody reads: at once; the last op: the head reads it)
+      if (in_last == i) ar.give(pn.in_buf, in_size);
+      for (int t = 0; t < i; ++t)
+        if (last_use[(size_t)t] == i) ar.give(buf[(size_t)t], size[(size_t)t]);
+      if (last_use[(size_t)i] < 0 && i != n - 1) ar.give(buf[(size_t)i], size[(size_t)i]);
+    }
+    pn.last_buf = buf[(size_t)n - 1];
+    return ar.top;
   };
+  g->qops = g->ops;   // before the float placement: src_C still counts channels
+  g->scratch_per_wg = (place(g->ops, net, false) + 255) & ~(int64_t)255;
+  // int8 form: weights [Co][k][sources, each r4(cn)], int32 values bias / multiplier / shift [Co] per op, then the Dense
+  g->qnet = net;
+  int64_t qw = 0, qi = 0;
   for (int i = 0; i < n; ++i) {
-    GOp& L = g->ops[(size_t)i];
-    L.reach = reach[(size_t)i];
-    size[(size_t)i] = (int64_t)(tile + L.reach) * L.cout;
-    buf[(size_t)i] = L.out_buf = ar.take(size[(size_t)i]);
-    bool need = hits(rd, L.out_buf, size[(size_t)i]) || hits(wr, L.out_buf, size[(size_t)i]);
-    for (int j = 0; j < L.n_src; ++j) {
-      const int src = d.ops[i].src[j];
-      L.src_buf[j] = src < 0 ? net.in_buf : buf[(size_t)src];
-      L.src_reach[j] = src < 0 ? in_reach : reach[(size_t)src];
-      need = need || hits(wr, L.src_buf[j], src < 0 ? in_size : size[(size_t)src]);
-    }
-    L.sync = need ? 1 : 0;
-    if (need) {
-      rd.clear();
-      wr.clear();
-    }
-    wr.emplace_back(L.out_buf, size[(size_t)i]);
-    for (int j = 0; j < L.n_src; ++j) {
-      const int src = d.ops[i].src[j];
-      rd.emplace_back(L.src_buf[j], src < 0 ? in_size : size[(size_t)src]);
-    }
-    // buffers whose last consumer this op is go back to the arena (an op nobody reads: at once; the last op: the head reads it)
-    if (in_last == i) ar.give(net.in_buf, in_size);
-    for (int t = 0; t < i; ++t)
-      if (last_use[(size_t)t] == i) ar.give(buf[(size_t)t], size[(size_t)t]);
-    if (last_use[(size_t)i] < 0 && i != n - 1) ar.give(buf[(size_t)i], size[(size_t)i]);
+    GOp& L = g->qops[(size_t)i];
+    int64_t kp = 0;
+    for (int j = 0; j < L.n_src; ++j) kp += r4(L.src_cn[j]);
+    L.w = qw; qw += (int64_t)L.cout * L.k * kp;
+    L.b = qi; qi += 3 * (int64_t)L.cout;
   }
-  net.last_buf = buf[(size_t)n - 1];
-  g->scratch_per_wg = (ar.top + 255) & ~(int64_t)255;
+  g->qnet.wd = qw; qw += (int64_t)net.tf * r4(net.c_last);
+  g->qnet.bd = qi; qi += 3;
+  g->q_izp = qi; qi += n + 2;
+  g->q_nw = qw;
+  g->q_ni = qi;
+  g->q_tile_bytes = place(g->qops, g->qnet, true);
   // what the shared call preparation reads (stream_common.hip.h): stride 1, halo of the input, first window's last frame
   s->net = SNet{};
   s->net.s = 1;
@@ -356,12 +389,18 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
 namespace mww {
 
 int stream_graph_no_int8(const mww_stream*) {
-  return set_error(MWW_ERR_UNSUPPORTED, "the int8 streaming model covers MixedNet streams only (this is a conv/BN graph stream)");
+  return set_error(MWW_ERR_UNSUPPORTED, "the int8 streaming model covers MixedNet streams only (this is a conv/BN graph stream; "
+                                          "mww_stream_create_convnet_q8 creates one that takes int8 parameters)");
 }
+
+bool stream_graph_int8(const mww_stream* s) { return s->graph && s->graph->int8; }
+
+int stream_graph_num_tensors(const mww_stream* s) { return s->graph->net.n_ops + 2; }
 
 void stream_graph_free(mww_stream* s) {
   if (!s->graph) return;
   if (s->graph->d_ops) (void)hipFree(s->graph->d_ops);
+  if (s->graph->d_qops) (void)hipFree(s->graph->d_qops);
   delete s->graph;
   s->graph = nullptr;
 }
@@ -407,7 +446,10 @@ int64_t stream_graph_launch(mww_stream* s, const SStores& S, SCall& a, int grid)
   a.st_out = s->st[s->cur ^ 1];
   a.scratch = s->scratch;
   a.scratch_per_wg = g->scratch_per_wg;
-  hipLaunchKernelGGL(stream_graph_kernel, dim3(grid), dim3(kStreamThreads), 0, s->stream, g->net, S, a);
+  if (a.rec)
+    hipLaunchKernelGGL(stream_graph_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, s->stream, g->net, S, a);
+  else
+    hipLaunchKernelGGL(stream_graph_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, s->stream, g->net, S, a);
   SCHK(hipGetLastError());
   SCHK(hipStreamSynchronize(s->stream));
   if (s->d.mode == MWW_STREAM_MODE_STREAM) s->cur ^= 1;   // the rings this call wrote are the state of the next one
@@ -416,7 +458,7 @@ int64_t stream_graph_launch(mww_stream* s, const SStores& S, SCall& a, int grid)
 
 }  // namespace mww
 
-extern "C" int mww_stream_create_convnet(mww_ctx* ctx, const mww_convnet_desc* d, int32_t mode, mww_stream** out) {
+static int create_graph_stream(mww_ctx* ctx, const mww_convnet_desc* d, int32_t mode, bool int8, mww_stream** out) {
   if (!ctx || !d || !out) return mww::set_error(MWW_ERR_INVALID, "null argument");
   *out = nullptr;
   mww_stream* s = new mww_stream();
@@ -424,6 +466,7 @@ extern "C" int mww_stream_create_convnet(mww_ctx* ctx, const mww_convnet_desc* d
   s->tile_outputs = kGraphTileOutputs;
   s->graph = new mww_stream_graph();
   mww_stream_graph* g = s->graph;
+  g->int8 = int8;
   int rc = plan_graph(*d, mode, s, g);
   void* stores[MWW_MAX_STORES];
   int dt[MWW_MAX_STORES];
@@ -435,6 +478,12 @@ extern "C" int mww_stream_create_convnet(mww_ctx* ctx, const mww_convnet_desc* d
   if (!rc && hipMemcpy(g->d_ops, g->ops.data(), g->ops.size() * sizeof(GOp), hipMemcpyHostToDevice) != hipSuccess)
     rc = mww::set_error(MWW_ERR_HIP, "hipMemcpy ops");
   g->net.ops = g->d_ops;
+  if (int8) {
+    if (!rc && hipMalloc((void**)&g->d_qops, g->qops.size() * sizeof(GOp) + 64) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc ops");
+    if (!rc && hipMemcpy(g->d_qops, g->qops.data(), g->qops.size() * sizeof(GOp), hipMemcpyHostToDevice) != hipSuccess)
+      rc = mww::set_error(MWW_ERR_HIP, "hipMemcpy ops");
+    g->qnet.ops = g->d_qops;
+  }
   for (int i = 0; i < 2 && !rc; ++i)
     if (hipMalloc((void**)&s->st[i], (size_t)(s->n_state + 1) * sizeof(float)) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc state");
   if (!rc) rc = mww_stream_reset(s);
@@ -444,4 +493,12 @@ extern "C" int mww_stream_create_convnet(mww_ctx* ctx, const mww_convnet_desc* d
   }
   *out = s;
   return MWW_OK;
+}
+
+extern "C" int mww_stream_create_convnet(mww_ctx* ctx, const mww_convnet_desc* d, int32_t mode, mww_stream** out) {
+  return create_graph_stream(ctx, d, mode, false, out);
+}
+
+extern "C" int mww_stream_create_convnet_q8(mww_ctx* ctx, const mww_convnet_desc* d, int32_t mode, mww_stream** out) {
+  return create_graph_stream(ctx, d, mode, true, out);
 }

@@ -18,22 +18,17 @@
 using namespace mww_stream_impl;
 
 namespace mww {
-int stream_graph_no_int8(const mww_stream* s);   // tu_stream_graph.hip: the refusal of a conv/BN graph stream
+int stream_graph_no_int8(const mww_stream* s);   // tu_stream_graph.hip: the refusal of a plain conv/BN graph stream
+bool stream_graph_int8(const mww_stream* s);     // created by mww_stream_create_convnet_q8: tu_stream_graph_q8.hip serves it
+int64_t stream_graph_q8_sizes(const mww_stream* s, int64_t* n_ints);
+int stream_graph_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_weights, const int32_t* ints, int64_t n_ints,
+                               float input_scale, const uint8_t* lut);
 }
 
 namespace {
 
 constexpr int64_t kMaxLds = 160 * 1024;   // LDS of a gfx950 CU
 constexpr float kInv255 = (float)(1.0 / 255.0);   // inference.py:170 1 / 255 as float32
-
-__device__ inline int8_t quantize_input(float x, float scale, int zp) {
-  // inference.py:127-147 (data / scale + zp).astype(int8) with the float32 reading: IEEE division, float32 add, truncation;
-  // saturated to [-128, 127]
-  float t = x / scale + (float)zp;
-  t = truncf(t);
-  t = t < -128.f ? -128.f : (t > 127.f ? 127.f : t);
-  return (int8_t)(int)t;
-}
 
 __global__ void __launch_bounds__(kStreamThreads) stream_q8_kernel(SNet net, SStores S, SCall a, SQ8 q) {
   HIP_DYNAMIC_SHARED(int, q8_lds)
@@ -283,7 +278,7 @@ extern "C" {
 
 int64_t mww_stream_q8_sizes(const mww_stream* s, int64_t* n_ints) {
   if (!s) return mww::set_error(MWW_ERR_INVALID, "null stream");
-  if (s->graph) return mww::stream_graph_no_int8(s);
+  if (s->graph) return mww::stream_graph_int8(s) ? mww::stream_graph_q8_sizes(s, n_ints) : mww::stream_graph_no_int8(s);
   int64_t w1, wd, i1, id, izp, nw, ni;
   q8_layout(s, nullptr, nullptr, &w1, &wd, &i1, &id, &izp, &nw, &ni);
   if (n_ints) *n_ints = ni;
@@ -293,7 +288,9 @@ int64_t mww_stream_q8_sizes(const mww_stream* s, int64_t* n_ints) {
 int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_weights, const int32_t* ints, int64_t n_ints,
                              float input_scale, const uint8_t* lut) {
   if (!s || !weights || !ints || !lut) return mww::set_error(MWW_ERR_INVALID, "null argument");
-  if (s->graph) return mww::stream_graph_no_int8(s);
+  if (s->graph)
+    return mww::stream_graph_int8(s) ? mww::stream_graph_set_quantized(s, weights, n_weights, ints, n_ints, input_scale, lut)
+                                     : mww::stream_graph_no_int8(s);
   std::vector<int64_t> lw, li;
   int64_t w1, wd, i1, id, izp, nw, ni;
   q8_layout(s, &lw, &li, &w1, &wd, &i1, &id, &izp, &nw, &ni);
@@ -350,7 +347,7 @@ int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_wei
 }
 
 int mww_stream_read_q8(mww_stream* s, uint8_t* out, int64_t n) {
-  if (s && s->graph) return mww::stream_graph_no_int8(s);
+  if (s && s->graph && !mww::stream_graph_int8(s)) return mww::stream_graph_no_int8(s);
   if (!s || !s->q8 || n < 0 || n > s->n_out || n > s->cap_q8_out || (n && !out)) return mww::set_error(MWW_ERR_INVALID, "more outputs requested than the last int8 run produced");
   if (!n) return MWW_OK;
   SCHK(hipSetDevice(s->device));
@@ -360,7 +357,7 @@ int mww_stream_read_q8(mww_stream* s, uint8_t* out, int64_t n) {
 }
 
 int mww_stream_get_state_q8(mww_stream* s, int8_t* h, int64_t n) {
-  if (s && s->graph) return mww::stream_graph_no_int8(s);
+  if (s && s->graph && !mww::stream_graph_int8(s)) return mww::stream_graph_no_int8(s);
   if (!s || !s->q8 || !h || n != s->n_state) return mww::set_error(MWW_ERR_INVALID, "state size mismatch (or no int8 parameters)");
   SCHK(hipSetDevice(s->device));
   SCHK(hipMemcpyAsync(h, s->q8_st[s->q8_cur], (size_t)n, hipMemcpyDeviceToHost, s->stream));

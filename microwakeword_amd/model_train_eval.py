@@ -172,7 +172,7 @@ def evaluate_model(flags, model_module, config, device=0):
     (its ``.npz`` twin) and is evaluated on the test sets - ``--test_tf_nonstreaming``: ``non_stream/testing_set_metrics.txt``;
     ``--test_tflite_nonstreaming``: ``tflite_non_stream/tflite_streaming_roc.txt``; ``--test_tflite_streaming``:
     ``tflite_stream_state_internal/tflite_streaming_roc.txt`` (streaming.py); ``--test_tflite_streaming_quantized`` with
-    ``--quantized_backend native``: calibration and int8 quantization (quantize.py), the parameters in
+    ``--quantized_backend native``: calibration and int8 quantization (quantize.py; Inception: quantize_graph.py), the parameters in
     ``tflite_stream_state_internal_quant/stream_state_internal_quant.npz`` and the ROC of the int8 streaming model in
     ``tflite_stream_state_internal_quant/tflite_streaming_roc.txt``.  No TFLite file is written: the streaming /
     non-streaming forms run natively from the same weights."""
@@ -193,10 +193,14 @@ def evaluate_model(flags, model_module, config, device=0):
             out[folder] = streaming.streaming_model_roc(config, folder, sm, data_processor, data_set="testing",
                                                         ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt")
     if getattr(flags, "test_tflite_streaming_quantized", 0):
-        from . import quantize
+        from .layout import InceptionLayout
+        if isinstance(model.layout, InceptionLayout):   # the conversion does not depend on the family; the graph here does
+            from . import quantize_graph as quantize
+        else:
+            from . import quantize
         folder = "tflite_stream_state_internal_quant"
         logging.info("Testing the quantized streaming model: calibrated and quantized by a restatement of TFLite's int8 "
-                     "arithmetic (quantize.py, INTEGRATION.md), not by TFLite")
+                     "arithmetic (quantize.py / quantize_graph.py, INTEGRATION.md), not by TFLite")
         ranges = quantize.calibrate(model, data_processor, config)
         qm = quantize.quantize(model, ranges)
         path = os.path.join(config["train_dir"], folder)

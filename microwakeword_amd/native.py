@@ -113,7 +113,7 @@ EXPORTS = [
     "mww_stream_create", "mww_stream_destroy", "mww_stream_num_weights", "mww_stream_num_state", "mww_stream_set_weights",
     "mww_stream_reset", "mww_stream_get_state", "mww_stream_run", "mww_stream_run_host", "mww_stream_read", "mww_stream_set_probs",
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
-    "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet",
+    "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
 ]
 
 
@@ -204,6 +204,7 @@ class NativeLib:
         L.mww_evaluate_windows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int]
         L.mww_stream_create.argtypes = [C.c_void_p, C.POINTER(StreamDesc), C.POINTER(C.c_void_p)]
         L.mww_stream_create_convnet.argtypes = [C.c_void_p, C.POINTER(ConvNetDesc), C.c_int32, C.POINTER(C.c_void_p)]
+        L.mww_stream_create_convnet_q8.argtypes = [C.c_void_p, C.POINTER(ConvNetDesc), C.c_int32, C.POINTER(C.c_void_p)]
         L.mww_stream_destroy.argtypes = [C.c_void_p]
         L.mww_stream_destroy.restype = None
         for f in (L.mww_stream_num_weights, L.mww_stream_num_state):
@@ -754,9 +755,11 @@ class GraphStream(Stream):
     """``mww_stream_create_convnet``: the streaming / non-streaming form of a conv/BN graph (Inception) with the methods of
     ``Stream``.  ``desc``: a dict with conv_ops (``Engine``'s op dicts in Keras layer-creation order:
     ``InceptionLayout(flags, T, fuse_heads=False).ops``), frames, mode ("stream" / "non_stream") and, optionally,
-    head_attention / head_pool (both refused by the library).  The int8 methods raise ``NativeError``."""
+    head_attention / head_pool (both refused by the library).  The int8 methods raise ``NativeError`` unless the stream
+    was created with ``int8=True`` (``mww_stream_create_convnet_q8``: the same stream, on which calibration and the int8
+    graph kernel of csrc/tu_stream_graph_q8.hip work)."""
 
-    def __init__(self, engine: "Engine", desc: dict):
+    def __init__(self, engine: "Engine", desc: dict, int8: bool = False):
         self.engine = engine   # the context is borrowed: keep it alive
         self.nl = engine.nl
         d = ConvNetDesc()
@@ -764,7 +767,8 @@ class GraphStream(Stream):
         d.head_attention, d.head_pool = int(bool(desc.get("head_attention", 0))), int(desc.get("head_pool", 0))
         _fill_conv_ops(d, list(desc["conv_ops"]))
         h = C.c_void_p()
-        self.nl.check(self.nl.lib.mww_stream_create_convnet(engine.h, C.byref(d), STREAM_MODES[desc.get("mode", "stream")], C.byref(h)))
+        create = self.nl.lib.mww_stream_create_convnet_q8 if int8 else self.nl.lib.mww_stream_create_convnet
+        self.nl.check(create(engine.h, C.byref(d), STREAM_MODES[desc.get("mode", "stream")], C.byref(h)))
         self._created(h, 1)
 
 

@@ -14,6 +14,7 @@
   * ``QuantizedModel``  those parameters, ``save`` / ``load`` as a data-only ``.npz`` and a readable ``summary``.
 
 Nothing here is pinned to TFLite (no TensorFlow on this path); the int8 kernel is pinned to tests/quant_oracle.py.
+The Inception twin (a graph with concatenations) is ``quantize_graph.py``, which imports the fixed-point helpers below.
 """
 from __future__ import annotations
 
@@ -331,7 +332,8 @@ def calibration_frames(data_processor, config) -> np.ndarray:
 def _mixednet_only(model):
     from .layout import InceptionLayout
     if isinstance(getattr(model, "layout", None), InceptionLayout):
-        raise NotImplementedError("the int8 evaluation covers MixedNet only (int8 Inception is not implemented)")
+        raise NotImplementedError("this module's int8 evaluation covers MixedNet only (an Inception model is calibrated and quantized by "
+                                  "quantize_graph.calibrate / quantize_graph.quantize)")
 
 
 def calibrate(model, data_processor, config) -> np.ndarray:

@@ -73,7 +73,7 @@ def graph_stream_description(flags, frames: int, stride: int, mode: str) -> dict
     at = {old: new for new, old in enumerate(order)}
     ops = [dict(lay.ops[o], src=[at[s] if s >= 0 else -1 for s in lay.ops[o]["src"]]) for o in order]
     assert all(s < i for i, op in enumerate(ops) for s in op["src"])
-    return dict(conv_ops=ops, frames=int(frames), stride=1, mode=mode)
+    return dict(conv_ops=ops, op_names=[lay.op_names[o] for o in order], frames=int(frames), stride=1, mode=mode)
 
 
 class StreamingModel:
@@ -137,16 +137,26 @@ class StreamingModel:
         return self.native.metrics(offsets, kind, cutoffs, sliding_window_length, ignore_slices_after_accept, ignore_slices_after_accept)
 
 
+def load_quantized(path):
+    """the ``QuantizedModel`` (MixedNet) or ``QuantizedGraphModel`` (Inception; its file carries ``family``) of an ``.npz``"""
+    from . import quantize, quantize_graph
+    with np.load(path, allow_pickle=False) as z:
+        family = str(z["family"]) if "family" in z.files else "mixednet"
+    return quantize_graph.QuantizedGraphModel.load(path) if family == quantize_graph.FAMILY else quantize.QuantizedModel.load(path)
+
+
 class QuantizedStreamingModel(StreamingModel):
-    """The int8 quantized streaming model (``--test_tflite_streaming_quantized``) on the int8 kernel
-    (csrc/tu_stream_q8.hip), with the methods of ``StreamingModel``: ``model_or_file`` is a ``quantize.QuantizedModel`` or
-    the path of its ``.npz``; ``context`` is the float MixedNet ``Model`` whose context (device, HIP stream, resident
-    feature stores) the stream borrows.  Probabilities are ``uint8 / 255`` in float32 (``read_q8`` gives the uint8
-    outputs), in the same device buffer the metrics kernel reads."""
+    """The int8 quantized streaming model (``--test_tflite_streaming_quantized``) with the methods of ``StreamingModel``:
+    ``model_or_file`` is a ``quantize.QuantizedModel`` (MixedNet: the int8 kernel of csrc/tu_stream_q8.hip), a
+    ``quantize_graph.QuantizedGraphModel`` (Inception: csrc/tu_stream_graph_q8.hip on a stream of
+    ``mww_stream_create_convnet_q8``) or the path of either's ``.npz``; ``context`` is the float ``Model`` whose context
+    (device, HIP stream, resident feature stores) the stream borrows.  Probabilities are ``uint8 / 255`` in float32
+    (``read_q8`` gives the uint8 outputs), in the same device buffer the metrics kernel reads."""
 
     def __init__(self, model_or_file, stride: int, mode: str = "stream", context=None):
         from .quantize import QuantizedModel
-        q = model_or_file if isinstance(model_or_file, QuantizedModel) else QuantizedModel.load(model_or_file)
+        from .quantize_graph import QuantizedGraphModel
+        q = model_or_file if isinstance(model_or_file, (QuantizedModel, QuantizedGraphModel)) else load_quantized(model_or_file)
         if context is None:
             raise ValueError("QuantizedStreamingModel needs the float model whose context it shares (context=...)")
         if mode not in native.STREAM_MODES:
@@ -159,7 +169,10 @@ class QuantizedStreamingModel(StreamingModel):
         self.stride = int(stride)
         self.frames = int(q.desc["frames"])
         self.desc = dict(q.desc, mode=mode)
-        self.native = native.Stream(context.engine, self.desc)
+        if isinstance(q, QuantizedGraphModel):
+            self.native = native.GraphStream(context.engine, self.desc, int8=True)
+        else:
+            self.native = native.Stream(context.engine, self.desc)
         self.native.set_quantized(*q.packed())
 
     def set_weights(self, weights):

@@ -6,6 +6,7 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
     python tools/stream_eval_throughput.py --hours 20 --quantized   # the int8 model (csrc/tu_stream_q8.hip); also times
                                                                     # the calibration pass (500 spectrograms) + quantization
     python tools/stream_eval_throughput.py --hours 20 --model inception   # the default Inception flags, T = 176
+    python tools/stream_eval_throughput.py --hours 20 --model inception --quantized   # its int8 model (csrc/tu_stream_graph_q8.hip)
 """
 import argparse
 import json
@@ -16,7 +17,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from microwakeword_amd import inception, mixednet, native, quantize, streaming  # noqa: E402
+from microwakeword_amd import inception, mixednet, native, quantize, quantize_graph, streaming  # noqa: E402
 
 DEF = dict(pointwise_filters="48,48,48,48", residual_connection="0,0,0,0", repeat_in_block="1,1,1,1",
            mixconv_kernel_sizes="[5],[9],[13],[21]", max_pool=0, first_conv_filters=32, first_conv_kernel_size=3,
@@ -37,8 +38,6 @@ def main():
     ap.add_argument("--quantized", action="store_true", help="time the int8 streaming model instead of the float one")
     a = ap.parse_args()
     if a.model == "inception":
-        if a.quantized:
-            ap.error("--quantized covers the MixedNet model only")
         T = a.frames or 176
         model = inception.model(INC, (T, 40), 1024, max_batch=1024, seed=3)
         name = "inception cnn1 %s/%s/%s cnn2 %s/%s k %s d %s (T=%d)" % (
@@ -68,13 +67,25 @@ def main():
     if a.quantized:
         # the calibration pass of --test_tflite_streaming_quantized: 500 spectrograms of T frames, chunks of s = 1
         cal = rng.integers(0, 1000, size=(quantize.CALIBRATION_SAMPLES * (T - 1), 40)).astype(np.float32) * streaming.SCALE_U16
-        sm.native.calibrate_host(cal[:1000])   # warm-up
+        if a.model == "inception":   # the graph stream that takes the int8 calls, and the graph contract
+            desc = streaming.graph_stream_description(INC, T, 1, "stream")
+            flat = np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in model.get_weights()])
+
+            def calibration_stream():
+                st = native.GraphStream(model.engine, desc, int8=True)
+                st.set_weights(flat)
+                return st
+            q = quantize_graph
+        else:
+            calibration_stream = lambda: streaming.StreamingModel(model, 1, "stream").native   # noqa: E731
+            q = quantize
+        calibration_stream().calibrate_host(cal[:1000])   # warm-up
         cs = []
         for _ in range(a.reps):
-            c = streaming.StreamingModel(model, 1, "stream")
+            c = calibration_stream()
             t0 = time.perf_counter()
-            ranges = c.native.calibrate_host(cal)
-            qm = quantize.quantize(model, ranges)
+            ranges = c.calibrate_host(cal)
+            qm = q.quantize(model, ranges)
             cs.append(time.perf_counter() - t0)
         sm = streaming.QuantizedStreamingModel(qm, 1, "stream", context=model)
         extra = {"quantized": "int8", "calibration_frames": int(cal.shape[0]), "calibration_seconds": round(min(cs), 4)}
