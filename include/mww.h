@@ -314,6 +314,9 @@ int64_t mww_debug_read(mww_ctx* ctx, const char* name, int B, float* host, int64
  * bf16 matrix pipe, fp32-grade; 0 = exact-fp32 MFMA), "conv1_x6_fwd" (default 0: the same form for the first convolution of the
  * forward kernel - measured slower), "bwd_first_wide" (default 0, with conv1_x6: the 512-thread form of the stride-1 first block's
  * backward kernel - measured equal),
+ * "dp_commit_late" (fp32 backward kernels: 1 = the dp rows of a tile are committed to LDS - and requested again for the next tile -
+ * behind the depthwise recompute, a phase after the input rows; 0 = both row groups in front of it; -1 = the default of each kernel
+ * family, the order that won its A/B: 1 for the first and the middle blocks, 0 for the last block.  A schedule only: results are bit-identical either way),
  * "grad_buckets" (data-parallel step: 1 = one exchange after the backward pass, the default; 2 =
  * overlapped two-bucket gradient exchange), "assemble_split" (workgroups per window of the
  * assembly kernel), "side_stream", "profile", "profile_split", "ablate" (profiling switches) */

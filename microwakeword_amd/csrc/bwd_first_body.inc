@@ -40,6 +40,8 @@
   const int c = tid % CIN, chunk = tid / CIN;
   const bool dw_active = chunk < NCH;
   const int Ta = (a.T - K1) / S + 1;
+  MWW_PC_DECL
+  MWW_PC_AT(0);   // kernel entry (profiling builds only: tools/phase_clocks.py)
 
   const bool tailmode = TAIL > 0 && Ta > TT && Ta <= TT + TAIL;   // the window is one tile: rows [TT, Ta) ride behind the TT tile rows
   const int ntiles = tailmode ? 1 : (Ta + TT - 1) / TT;
@@ -49,14 +51,23 @@
   DpStage<COUT, false, SB> dps;
   constexpr int NA = (RA * QI + kThreads - 1) / kThreads;
   float4 pre_a[NA];
-  auto issue = [&](int it) {
-    const int s = it / ntiles, b = blockIdx.x + s * gridDim.x, t0 = (it % ntiles) * TT;
-    const int nrx = ((tailmode ? Ta : min(TT, Ta - t0)) - 1) * S + K1;
+  // LATE: group A (x and a0, committed in P0) is requested again in front of barrier 1, group B (the dp rows) is committed and
+  // requested again behind P1: sDP is first read in the pointwise phase, and the g0 planes the x6 form keeps in its space are last
+  // read in front of the tile's last barrier.  (The x rows stay in group A: their LDS tile is read up to that last barrier, so
+  // they could only move towards the dW1 phase, where they would be requested - and waited for - behind both other groups.)
+  // `live` false: a request behind the last tile (the window slot of the last one, no rows, empty descriptors).  LATE requests
+  // its groups unconditionally: each wait then counts the loads known to follow its group instead of draining them.
+  auto issue_a = [&](int it, bool live) {
+    const int s = live ? it / ntiles : nsamp - 1, b = blockIdx.x + s * gridDim.x, t0 = (it % ntiles) * TT;
+    const int nrx = live ? ((tailmode ? Ta : min(TT, Ta - t0)) - 1) * S + K1 : 0;
     xs.issue(a.x, a.xg, sXg, s, b, a.T, t0 * S, nrx, tid);
-    const BufRsrc ra = tile_rsrc(a.a0 + ((size_t)b * Ta + t0) * CIN, min(RA, Ta - t0) * QI * 16);
+    const BufRsrc ra = tile_rsrc(a.a0 + ((size_t)b * Ta + t0) * CIN, live ? min(RA, Ta - t0) * QI * 16 : 0);
 #pragma unroll
     for (int j = 0; j < NA; ++j) pre_a[j] = tile_load4<MWW_AUX_LD_A0>(ra, (tid + j * kThreads) * 16);
-    const int nvk = max(0, min(TT, a.Tout - t0)) * (COUT / 4);
+  };
+  auto issue_b = [&](int it, bool live) {
+    const int b = blockIdx.x + (it / ntiles) * gridDim.x, t0 = (it % ntiles) * TT;
+    const int nvk = live ? max(0, min(TT, a.Tout - t0)) * (COUT / 4) : 0;
     const size_t koff = ((size_t)b * a.Tout + t0) * COUT;
     dps.issue(elem_ptr<SB>(a.pk, koff), elem_ptr<SB>(a.gk, koff), nvk, tid);
   };
@@ -86,7 +97,10 @@
   }
   if (a.xg.win) xgather_setup(a.xg, sXg, nsamp, tid);
   stagger_start<MWW_STAGGER_BWD>();
-  if (nitems > 0) issue(0);
+  if (nitems > 0) {
+    issue_a(0, true);
+    issue_b(0, true);
+  }
 
   // every global load of the prologue first (see WeightStage) ...
   WeightStage<CIN, COUT, 0, pitch_wt(CIN, BF)> wst;
@@ -141,6 +155,8 @@
     for (int nt = 0; nt < NT1; ++nt) w1acc[mi][nt] = zero4();
   __syncthreads();
 
+  MWW_PC_AT(1);   // prologue done
+  MWW_PC_START(MWW_ABLATE(a, 16) && tid == 0);
   for (int it = 0; it < nitems; ++it) {
     rotate_priority(it, 2);
     const int t0 = (it % ntiles) * TT;
@@ -157,10 +173,19 @@
         *reinterpret_cast<float4*>(sA + r * CPI + q * 4) = pre_a[j];
       }
     }
-    dps.commit(sDP, sKp, 0.f, nrows_new * (COUT / 4), tid);
+    MWW_PC_MARK(0);   // commit of group A (incl. the wait for the prefetched x / a0 rows)
+    if constexpr (!LATE) dps.commit(sDP, sKp, 0.f, nrows_new * (COUT / 4), tid);
     carry_du<K, CPI>(sDU, t0 == 0, tid);
+    if constexpr (LATE) issue_a(it + 1, it + 1 < nitems);
+    MWW_PC_MARK(LATE ? 0 : 8);   // !LATE: commit of group B (incl. the wait for the dp rows) + ring roll
     __syncthreads();
-    if (it + 1 < nitems) issue(it + 1);
+    MWW_PC_MARK(1);   // barrier 1
+    if constexpr (!LATE) {
+      if (it + 1 < nitems) {
+        issue_a(it + 1, true);
+        issue_b(it + 1, true);
+      }
+    }
     // ---- P1: u = depthwise(a0) + bias
     if (dw_active) {
       if (chunk * L < nrows_new) {
@@ -176,9 +201,18 @@
         for (int t = 0; t < L; ++t) sU[(chunk * L + t) * CPI + c] = 0.f;
       }
     }
+    MWW_PC_MARK(2);   // issue + P1 (u recompute)
+    if constexpr (LATE) {
+      dps.commit(sDP, sKp, 0.f, nrows_new * (COUT / 4), tid);
+      issue_b(it + 1, it + 1 < nitems);
+      MWW_PC_MARK(8);   // commit of group B (incl. the wait for the dp rows) + its next request
+    }
     __syncthreads();
+    MWW_PC_MARK(3);   // barrier 2
     pointwise_backward_tile<CIN, COUT, K, BF>(sU, sDP, sDU, wave, r16, g, sWt, dwacc, wave * 16 < nrows_new);
+    MWW_PC_MARK(4);   // MFMA (dW_pw, du)
     __syncthreads();
+    MWW_PC_MARK(5);   // barrier 3
     // ---- P4: depthwise backward -> g0 = da * relu'(a0) kept in LDS
     if (dw_active) {
       // one pass over LDS for the whole phase (see bwd_block_body.inc)
@@ -227,6 +261,7 @@
         }
       }
     }
+    MWW_PC_MARK(6);   // P4 (depthwise backward, g0)
     __syncthreads();
     // ---- dW1 += im2col(x)^T g0 : A[m][k=s] = x[s*S + m/40][m%40], B[k=s][n] = g0[s][n]
     // (operands one k-step ahead of their MFMAs, schedule pinned: see pointwise_backward_tile)
@@ -293,8 +328,11 @@
         }
       }
     }
+    MWW_PC_MARK(7);   // barrier 4 + the conv1 weight gradient
     __syncthreads();
+    MWW_PC_MARK(5);   // its barrier: counted with barrier 3
   }
+  MWW_PC_AT(2);   // tile loop done
   float* gdst = a.grad_part + (size_t)blockIdx.x * (M1 * C1 + (K + 1) * CIN + CIN * COUT);
 #pragma unroll
   for (int mi = 0; mi < MPW; ++mi)
@@ -306,3 +344,5 @@
         if (m < M1) gdst[m * C1 + nt * 16 + r16] = w1acc[mi][nt][r];
       }
   write_block_grad_partials<CIN, COUT, K>(smem, gdst + M1 * C1, dwacc, accw, accb, dw_active, c, chunk, tid, wave, r16, g);
+  MWW_PC_AT(3);   // epilogue done
+  MWW_PC_DUMP(a.phase_clk ? a.phase_clk + (size_t)blockIdx.x * kClkSlots : nullptr);

@@ -404,9 +404,10 @@ __device__ __forceinline__ void pin(int& v) { asm volatile("" : "+v"(v)); }
 #define MWW_PC_MARK(i) ((void)0)
 #define MWW_PC_DUMP(p) ((void)0)
 #endif
-constexpr int kClkSlots = 12;   // per workgroup: 8 phase accumulators + entry / loop start / loop end / exit timestamps
+constexpr int kClkPhases = 9;   // 8 phases of a block kernel's tile loop + the backward kernels' commit of the dp rows (slot 8)
+constexpr int kClkSlots = kClkPhases + 4;   // per workgroup: the phase accumulators + entry / loop start / loop end / exit timestamps
 struct PhaseClock {
-  unsigned long long last = 0, acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp[4] = {0, 0, 0, 0};
+  unsigned long long last = 0, acc[kClkPhases] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, stamp[4] = {0, 0, 0, 0};
   bool on = false;
   __device__ __forceinline__ void at(int i) { stamp[i] = __builtin_amdgcn_s_memtime(); }
   __device__ __forceinline__ void start(bool enable) {
@@ -422,8 +423,8 @@ struct PhaseClock {
   }
   __device__ __forceinline__ void dump(unsigned long long* dst) const {
     if (on) {
-      for (int i = 0; i < 8; ++i) dst[i] = acc[i];
-      for (int i = 0; i < 4; ++i) dst[8 + i] = stamp[i];
+      for (int i = 0; i < kClkPhases; ++i) dst[i] = acc[i];
+      for (int i = 0; i < 4; ++i) dst[kClkPhases + i] = stamp[i];
     }
   }
 };

@@ -29,6 +29,19 @@
 #ifndef MWW_BWD_WIDE_DEFAULT
 #define MWW_BWD_WIDE_DEFAULT 1
 #endif
+// option "dp_commit_late": the fp32 backward kernels commit the dp rows of a tile behind the depthwise recompute instead of with the
+// input rows in P0 (kernels_bwdw.hip.h bwd_blockw_kernel, bwd_first_body.inc).  Bit-identical results; the default of each kernel
+// family is the order that won its same-session A/B (profiles/dp_commit_late_ab.txt): the middle blocks and the first
+// block gain 0.5-1 us per launch, the last block's launch (its group B is p_k, the dense kernel's rows and dz) reads the same either way.
+#ifndef MWW_DP_COMMIT_LATE_BLOCK_DEFAULT   // bwd_blockw_kernel, middle blocks
+#define MWW_DP_COMMIT_LATE_BLOCK_DEFAULT 1
+#endif
+#ifndef MWW_DP_COMMIT_LATE_LAST_DEFAULT    // bwd_blockw_kernel, the last block (LAST)
+#define MWW_DP_COMMIT_LATE_LAST_DEFAULT 0
+#endif
+#ifndef MWW_DP_COMMIT_LATE_FIRST_DEFAULT   // bwd_first_kernel (x6 form), bwd_firstw_kernel
+#define MWW_DP_COMMIT_LATE_FIRST_DEFAULT 1
+#endif
 
 namespace mww {
 
@@ -122,6 +135,7 @@ struct mww_ctx {
   bool conv1_x6_fwd = MWW_CONV1_X6_FWD_DEFAULT != 0;
   bool bwd_first_wide = MWW_BWD_FIRST_WIDE_DEFAULT != 0;   // stride-1 first block (3-tap conv1) with conv1_x6: the 512-thread form of its backward kernel   // ... and the first convolution of the forward kernel
   bool bwd_wide = MWW_BWD_WIDE_DEFAULT != 0;   // fp32 block backward kernels: 512 threads per workgroup (bwd_blockw_kernel) or 256 (bwd_block_kernel)
+  int dp_commit_late = -1;   // -1: the per-family defaults above; 0 / 1: every kernel that has both orders
   int64_t P = 0, S = 0;
   int64_t o_conv1 = 0, o_dense_w = 0, o_dense_b = 0;
   int t_last = 0, c_last = 0, dwd_stride = 0;
@@ -225,7 +239,7 @@ struct mww_ctx {
   bool bce_clipped = false;   // "bce_from_logits" 0: probability-form BCE with the Keras clip instead of the logits form (common.hip.h)
   bool bn_eval_ready = false;   // inside mww_evaluate_windows: the moving statistics are folded once, not per batch
   int ablate = 0;
-  unsigned long long* phase_clk = nullptr;   // profiling: [2*layers][2048 workgroups][8 phases]
+  unsigned long long* phase_clk = nullptr;   // profiling: [2*layers][2048 workgroups][kClkSlots]
   std::vector<mww::ProfileEntry> prof;
   // cached graphs keyed by (B, flags)
   struct GraphEntry { int B, flags, mail, par; hipGraphExec_t exec; };

@@ -45,7 +45,7 @@ struct BwdBlockArgs {
   int B, Tin, Tout;
   int ablate;             // profiling only: bit0 skip P1, bit1 skip MFMA, bit2 skip P4 (results invalid); bit 16: phase clocks;
                           // parts of P4: 32 skip the g_{k-1} stores, 64 skip the depthwise weight gradient, 128 skip the input gradient
-  unsigned long long* phase_clk;   // [gridDim.x][8]
+  unsigned long long* phase_clk;   // [gridDim.x][kClkSlots]
   StatAcc gacc;           // (sum g, sum g*xhat) of g_{k-1} go to the accumulator rows instead of gstat_part when set
   BnGradFoldArgs gfold;   // gfold.acc set: k_c1 / k_mg / k_mgx are folded here from the producer's accumulator rows
 };
@@ -344,10 +344,13 @@ struct BwdFirstArgs {
   int B, T, Tout;         // a0 frames Ta = (T-K1)/S+1 ; Tout = Ta-(K-1)
   BnGradFoldArgs gfold;   // gfold.acc set: k_c1 / k_mg / k_mgx are folded here from the producer's accumulator rows
   XGather xg;             // xg.win set: x rows are gathered from the feature stores (see kernels_fwd.hip.h)
+  int ablate;             // profiling only: bit 16: phase clocks (bwd_first_kernel)
+  unsigned long long* phase_clk;   // [gridDim.x][kClkSlots]
 };
 
 // (stride-3 first convolutions stage 194 x rows per tile: 92-99 KB of LDS, one workgroup per CU)
-template <int K1, int C1, int COUT, int K, int S, bool BF, bool SB = false, bool X6 = false>
+// LATE (engine option "dp_commit_late"): the dp rows are committed behind P1 instead of in P0 (kernels_bwdw.hip.h bwd_blockw_kernel)
+template <int K1, int C1, int COUT, int K, int S, bool BF, bool SB = false, bool X6 = false, bool LATE = false>
 __global__ __launch_bounds__(kThreads, (S > 1 ? 1 : 2)) void bwd_first_kernel(BwdFirstArgs a) {
   typedef BwdFirstLds<K1, C1, COUT, K, S> Lds;
   __shared__ __attribute__((aligned(16))) float sX[X6 ? 3 * Lds::XR * 96 / 4 : Lds::XR * Lds::PX];   // X6: three bf16 planes, 96-byte rows

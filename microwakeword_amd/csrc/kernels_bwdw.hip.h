@@ -320,7 +320,13 @@ constexpr int wide_waves_per_simd() {
   return (BwdWideLds<C, K, NTH>::BYTES <= 80 * 1024 ? 2 : 1) * (NTH / 64) / 4;
 }
 
-template <int CIN, int COUT, int K, bool LAST, int NTH, bool BF = false, bool SB = false>
+// LATE (engine option "dp_commit_late"): the two row groups a tile loads are waited for where they are first read.  The
+// activated-input rows (group A, `pre_p`) are committed in P0 and requested again, for the next tile, in front of barrier 1;
+// the dp rows (group B, `dps` and `pre_dz`: ~64 % of the loaded bytes) are committed behind P1 - the depthwise recompute reads
+// only sP, and sDP was last read in the MFMA phase of the tile before - and requested again right there.  Each group keeps a
+// whole tile period of lead and the workgroups' lockstep burst becomes two smaller ones a phase apart.  Nothing else moves:
+// results are bit-identical to the other order (!LATE: both groups committed in P0, requested behind barrier 1).
+template <int CIN, int COUT, int K, bool LAST, int NTH, bool BF = false, bool SB = false, bool LATE = false>
 __global__ __launch_bounds__(NTH, (wide_waves_per_simd<CIN, K, NTH>())) void bwd_blockw_kernel(BwdBlockArgs a) {
   static_assert(CIN == COUT, "the wide form is instantiated for square blocks");
   constexpr int C = CIN;
@@ -357,19 +363,28 @@ __global__ __launch_bounds__(NTH, (wide_waves_per_simd<CIN, K, NTH>())) void bwd
   float4 pre_p[NP];
   DpStageW<C, LAST, SB, NTH, P> dps;
   float pre_dz = 0.f;
-  auto issue = [&](int it) {
+  // (`live` false: a request behind the last tile, through empty descriptors - LATE requests its groups unconditionally, so
+  // that each wait counts the loads and stores that are known to follow its group instead of draining them: a request under
+  // a branch of its own would have to be assumed absent)
+  auto issue_a = [&](int it, bool live) {   // group A: the input rows
     const int b = blockIdx.x + (it / ntiles) * gridDim.x, t0 = (it % ntiles) * TT;
-    const int nvp = min(RA, a.Tin - t0) * Q;
+    const int nvp = live ? min(RA, a.Tin - t0) * Q : 0;
     const BufRsrc src = tile_rsrc(elem_ptr<SB>(a.in, ((size_t)b * a.Tin + t0) * C), nvp * 4 * elem_bytes(SB));
 #pragma unroll
     for (int j = 0; j < NP; ++j) pre_p[j] = tile_load4s<SB, MWW_AUX_LD_BP>(src, tid + j * NTH);
-    const int nvk = max(0, min(TT, a.Tout - t0)) * Q;
+  };
+  auto issue_b = [&](int it, bool live) {   // group B: the dp rows (and dz of the tile's sample)
+    const int b = blockIdx.x + (it / ntiles) * gridDim.x, t0 = (it % ntiles) * TT;
+    const int nvk = live ? max(0, min(TT, a.Tout - t0)) * Q : 0;
     const size_t koff = ((size_t)b * a.Tout + t0) * C;
     dps.issue(elem_ptr<SB>(a.pk, koff), LAST ? a.wd + (size_t)t0 * C : elem_ptr<SB>(a.gk, koff), nvk, tid);
-    if (LAST) pre_dz = tile_load1(tile_rsrc(a.dz, a.B * 4), b * 4);
+    if (LAST) pre_dz = tile_load1(tile_rsrc(a.dz, live ? a.B * 4 : 0), b * 4);
   };
   stagger_start<MWW_STAGGER_BWD>();
-  if (nitems > 0) issue(0);
+  if (nitems > 0) {
+    issue_a(0, true);
+    issue_b(0, true);
+  }
 
   // ---- prologue: every global load first (one memory round trip), then the LDS copies
   constexpr int NWL = (C * C + NTH - 1) / NTH, NDL = (K * C + NTH - 1) / NTH;
@@ -443,7 +458,7 @@ __global__ __launch_bounds__(NTH, (wide_waves_per_simd<CIN, K, NTH>())) void bwd
     const int b = blockIdx.x + (it / ntiles) * gridDim.x, t0 = (it % ntiles) * TT;
     const int nrows_new = max(0, min(TT, a.Tout - t0));  // du rows produced by this tile
     const int rows_da = min(TT, a.Tin - t0);             // input-gradient rows finalised by this tile
-    // ---- P0: commit the activated input rows [t0, t0 + RA) (zero past the sample), the dp rows; roll the du ring
+    // ---- P0: commit the activated input rows [t0, t0 + RA) (zero past the sample), the dp rows (!LATE); roll the du ring
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
       const int i = tid + j * NTH;
@@ -458,12 +473,19 @@ __global__ __launch_bounds__(NTH, (wide_waves_per_simd<CIN, K, NTH>())) void bwd
         *reinterpret_cast<float4*>(sP + r * P + q * 4) = v;
       }
     }
-    dps.commit(sDP, sKp, pre_dz, nrows_new * Q, tid);
+    MWW_PC_MARK(0);   // commit of group A (incl. the wait for the prefetched input rows)
+    if constexpr (!LATE) dps.commit(sDP, sKp, pre_dz, nrows_new * Q, tid);
     for (int i = tid; i < (K - 1) * P; i += NTH) sDU[i] = (t0 == 0) ? 0.f : sDU[TT * P + i];
-    MWW_PC_MARK(0);   // commit (incl. the wait for the prefetched rows)
+    if constexpr (LATE) issue_a(it + 1, it + 1 < nitems);
+    MWW_PC_MARK(LATE ? 0 : 8);   // !LATE: commit of group B (incl. the wait for the dp rows) + ring roll
     __syncthreads();
     MWW_PC_MARK(1);   // barrier 1
-    if (it + 1 < nitems) issue(it + 1);
+    if constexpr (!LATE) {
+      if (it + 1 < nitems) {
+        issue_a(it + 1, true);
+        issue_b(it + 1, true);
+      }
+    }
     // ---- P1: recompute u = depthwise(a) + bias for the tile's output rows
     if (dw_active) {
       if (chunk * L < nrows_new) {
@@ -482,6 +504,12 @@ __global__ __launch_bounds__(NTH, (wide_waves_per_simd<CIN, K, NTH>())) void bwd
       }
     }
     MWW_PC_MARK(2);   // issue + P1 (u recompute)
+    if constexpr (LATE) {
+      // group B, a phase behind group A: sDP is free since barrier 3 of the tile before
+      dps.commit(sDP, sKp, pre_dz, nrows_new * Q, tid);
+      issue_b(it + 1, it + 1 < nitems);
+      MWW_PC_MARK(8);   // commit of group B (incl. the wait for the dp rows) + its next request
+    }
     __syncthreads();
     MWW_PC_MARK(3);   // barrier 2
     // ---- P2/P3: dW_pw += u^T dp ; du = dp W^T -> ring rows [K-1, K-1+TT)
@@ -644,7 +672,8 @@ constexpr int wide_first_waves_per_simd() {
   return (BwdFirstWideLds<K1, C1, COUT, K, S, NTH, X6>::BYTES <= 80 * 1024 ? 2 : 1) * (NTH / 64) / 4;
 }
 
-template <int K1, int C1, int COUT, int K, int S, int NTH, bool X6 = false>
+// LATE: see bwd_first_body.inc (x and a0 committed in P0 and requested again in front of barrier 1, the dp rows behind P1)
+template <int K1, int C1, int COUT, int K, int S, int NTH, bool X6 = false, bool LATE = false>
 __global__ __launch_bounds__(NTH, (wide_first_waves_per_simd<K1, C1, COUT, K, S, NTH, X6>())) void bwd_firstw_kernel(BwdFirstArgs a) {
   typedef BwdFirstWideLds<K1, C1, COUT, K, S, NTH, X6> Lds;
   constexpr bool SB = false;
@@ -683,14 +712,18 @@ __global__ __launch_bounds__(NTH, (wide_first_waves_per_simd<K1, C1, COUT, K, S,
   DpStageW<COUT, false, SB, NTH, PO> dps;
   constexpr int NA = (RA * QI + NTH - 1) / NTH;
   float4 pre_a[NA];
-  auto issue = [&](int it) {
-    const int s = it / ntiles, b = blockIdx.x + s * gridDim.x, t0 = (it % ntiles) * TT;
-    const int nrx = ((tailmode ? Ta : min(TT, Ta - t0)) - 1) * S + K1;
+  // (`live` false: a request behind the last tile - the window slot of the last one, no rows: see bwd_blockw_kernel)
+  auto issue_a = [&](int it, bool live) {
+    const int s = live ? it / ntiles : nsamp - 1, b = blockIdx.x + s * gridDim.x, t0 = (it % ntiles) * TT;
+    const int nrx = live ? ((tailmode ? Ta : min(TT, Ta - t0)) - 1) * S + K1 : 0;
     xs.issue(a.x, a.xg, sXg, s, b, a.T, t0 * S, nrx, tid);
-    const BufRsrc ra = tile_rsrc(a.a0 + ((size_t)b * Ta + t0) * CIN, min(RA, Ta - t0) * QI * 16);
+    const BufRsrc ra = tile_rsrc(a.a0 + ((size_t)b * Ta + t0) * CIN, live ? min(RA, Ta - t0) * QI * 16 : 0);
 #pragma unroll
     for (int j = 0; j < NA; ++j) pre_a[j] = tile_load4<MWW_AUX_LD_A0>(ra, (tid + j * NTH) * 16);
-    const int nvk = max(0, min(TT, a.Tout - t0)) * QO;
+  };
+  auto issue_b = [&](int it, bool live) {
+    const int b = blockIdx.x + (it / ntiles) * gridDim.x, t0 = (it % ntiles) * TT;
+    const int nvk = live ? max(0, min(TT, a.Tout - t0)) * QO : 0;
     const size_t koff = ((size_t)b * a.Tout + t0) * COUT;
     dps.issue(elem_ptr<SB>(a.pk, koff), elem_ptr<SB>(a.gk, koff), nvk, tid);
   };
@@ -717,7 +750,10 @@ __global__ __launch_bounds__(NTH, (wide_first_waves_per_simd<K1, C1, COUT, K, S,
   }
   if (a.xg.win) xgather_setup(a.xg, sXg, nsamp, tid);
   stagger_start<MWW_STAGGER_BWD>();
-  if (nitems > 0) issue(0);
+  if (nitems > 0) {
+    issue_a(0, true);
+    issue_b(0, true);
+  }
 
   // every global load of the prologue first, then the LDS copies
   constexpr int NWL = (CIN * COUT + NTH - 1) / NTH;
@@ -795,10 +831,16 @@ __global__ __launch_bounds__(NTH, (wide_first_waves_per_simd<K1, C1, COUT, K, S,
         *reinterpret_cast<float4*>(sA + r * PI + q * 4) = pre_a[j];
       }
     }
-    dps.commit(sDP, sKp, 0.f, nrows_new * QO, tid);
+    if constexpr (!LATE) dps.commit(sDP, sKp, 0.f, nrows_new * QO, tid);
     for (int i = tid; i < (K - 1) * PI; i += NTH) sDU[i] = (t0 == 0) ? 0.f : sDU[TT * PI + i];
+    if constexpr (LATE) issue_a(it + 1, it + 1 < nitems);
     __syncthreads();
-    if (it + 1 < nitems) issue(it + 1);
+    if constexpr (!LATE) {
+      if (it + 1 < nitems) {
+        issue_a(it + 1, true);
+        issue_b(it + 1, true);
+      }
+    }
     // ---- P1: u = depthwise(a0) + bias
     if (chunk * L < nrows_new) {
       float o[L];
@@ -811,6 +853,10 @@ __global__ __launch_bounds__(NTH, (wide_first_waves_per_simd<K1, C1, COUT, K, S,
     } else {
 #pragma unroll
       for (int t = 0; t < L; ++t) sU[(chunk * L + t) * PI + c] = 0.f;
+    }
+    if constexpr (LATE) {
+      dps.commit(sDP, sKp, 0.f, nrows_new * QO, tid);
+      issue_b(it + 1, it + 1 < nitems);
     }
     __syncthreads();
     // ---- P2/P3: waves 0-3: du tiles of row tile w; waves 4-7: dW_pw tiles (mt = v % 2, all nt) over the row half v / 2

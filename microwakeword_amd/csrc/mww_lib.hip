@@ -41,8 +41,9 @@ int launch_fwd_first(mww_ctx* c, int k1, int c1, int cout, int k, int st, const 
 }
 
 int launch_bwd_first(mww_ctx* c, int k1, int c1, int cout, int k, int st, const BwdFirstArgs& a, int grid) {
-  if (c->bwd_wide && !c->pw_bf16 && !c->st_bf16 && k_launch_bwd_firstw(c->stream, k1, c1, cout, k, st, a, grid, c->conv1_x6 && c->bwd_first_wide)) return MWW_OK;
-  if (k_launch_bwd_first(c->stream, c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0), k1, c1, cout, k, st, a, grid, c->conv1_x6)) return MWW_OK;
+  const bool late = c->dp_commit_late < 0 ? MWW_DP_COMMIT_LATE_FIRST_DEFAULT != 0 : c->dp_commit_late != 0;
+  if (c->bwd_wide && !c->pw_bf16 && !c->st_bf16 && k_launch_bwd_firstw(c->stream, k1, c1, cout, k, st, a, grid, c->conv1_x6 && c->bwd_first_wide, late)) return MWW_OK;
+  if (k_launch_bwd_first(c->stream, c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0), k1, c1, cout, k, st, a, grid, c->conv1_x6, late)) return MWW_OK;
   return fail(MWW_ERR_UNSUPPORTED, "no first-block backward kernel for this shape");
 }
 
@@ -53,7 +54,8 @@ int launch_fwd_block(mww_ctx* c, int cin, int cout, int k, const FwdBlockArgs& a
 
 int launch_bwd_block(mww_ctx* c, int cin, int cout, int k, bool last, const BwdBlockArgs& a, int grid) {
   const int mode = c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0);
-  if (c->bwd_wide && k_launch_bwd_blockw(c->stream, mode, cin, cout, k, last, a, grid)) return MWW_OK;
+  const bool late = c->dp_commit_late < 0 ? (last ? MWW_DP_COMMIT_LATE_LAST_DEFAULT : MWW_DP_COMMIT_LATE_BLOCK_DEFAULT) != 0 : c->dp_commit_late != 0;
+  if (c->bwd_wide && k_launch_bwd_blockw(c->stream, mode, cin, cout, k, last, a, grid, late)) return MWW_OK;
   if (k_launch_bwd_block(c->stream, c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0), cin, cout, k, last, a, grid)) return MWW_OK;
   return fail(MWW_ERR_UNSUPPORTED, "no block backward kernel for this shape");
 }
@@ -642,7 +644,8 @@ int enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       if (last) return fail(MWW_ERR_UNSUPPORTED, "single-block models are not supported");
       BwdFirstArgs a{c->x, c->a0, l.p, l.g, bn_slot(l, BN_MEAN), bn_slot(l, BN_RSTD), bn_slot(l, BN_C1),
                      bn_slot(l, BN_MG), bn_slot(l, BN_MGX), c->params + l.o_dw_w, c->params + l.o_dw_b,
-                     c->params + l.o_pw_w, l.grad_part, B, d.frames, l.tout, gf, x_gather(c)};
+                     c->params + l.o_pw_w, l.grad_part, B, d.frames, l.tout, gf, x_gather(c), c->ablate,
+                     c->phase_clk + (size_t)(2 * i + 1) * 2048 * kClkSlots};
       lp.begin("bwd_block", i);
       int rc = launch_bwd_first(c, d.conv1_kernel, d.conv1_filters, l.cout, l.k, d.conv1_stride, a, gbwd);
       lp.end();
@@ -1641,7 +1644,7 @@ int64_t mww_debug_read(mww_ctx* c, const char* name, int B, float* host, int64_t
   else if (!strcmp(name, "dz")) { src = c->dz; n = B; }
   else if (!strcmp(name, "a0")) { src = c->a0; n = (int64_t)B * c->L[0].tin * c->d.conv1_filters; }   // relu(conv1(x)) as the first block stored it
   else if (!strncmp(name, "clkf", 4) || !strncmp(name, "clkb", 4)) {
-    // phase clocks of layer k (1-based) as raw 64-bit counters viewed as floats: 2048 x 8 x 2 words
+    // phase clocks of layer k (1-based) as raw 64-bit counters viewed as floats: 2048 x kClkSlots x 2 words
     const int kk = atoi(name + 4);
     if (kk < 1 || kk > nb) return fail(MWW_ERR_INVALID, "bad layer");
     src = reinterpret_cast<const float*>(c->phase_clk + (size_t)(2 * (kk - 1) + (name[3] == 'b' ? 1 : 0)) * 2048 * kClkSlots);
@@ -1707,6 +1710,7 @@ int mww_set_option(mww_ctx* c, const char* name, int64_t v) {
   else if (!strcmp(name, "conv1_x6")) c->conv1_x6 = v != 0;
   else if (!strcmp(name, "conv1_x6_fwd")) c->conv1_x6_fwd = v != 0;
   else if (!strcmp(name, "bwd_first_wide")) c->bwd_first_wide = v != 0;
+  else if (!strcmp(name, "dp_commit_late")) { if (v < -1 || v > 1) return fail(MWW_ERR_INVALID, "dp_commit_late must be -1 (per-family defaults), 0 or 1"); c->dp_commit_late = (int)v; }
   else if (!strcmp(name, "grid_fwd")) { if (v < 1 || v > c->n_cu * 4) return fail(MWW_ERR_INVALID, "grid_fwd out of range"); c->grid_fwd = (int)v; }
   else if (!strcmp(name, "grid_bwd")) { if (v < 1 || v > c->n_cu * 2) return fail(MWW_ERR_INVALID, "grid_bwd out of range"); c->grid_bwd = (int)v; }
   else if (!strcmp(name, "grid_graph")) {   // 0: per-launch grids by occupancy (default); > 0: this many workgroups per launch

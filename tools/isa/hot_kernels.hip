@@ -14,5 +14,6 @@ template __global__ void bwd_block_kernel<48, 48, 13, false, false>(BwdBlockArgs
 template __global__ void bwd_block_kernel<48, 48, 21, true, false>(BwdBlockArgs);
 template __global__ void bwd_first_kernel<3, 32, 48, 5, 1, false>(BwdFirstArgs);
 template __global__ void bwd_first_kernel<3, 32, 48, 5, 1, false, false, true>(BwdFirstArgs);
+template __global__ void bwd_first_kernel<3, 32, 48, 5, 1, false, false, true, true>(BwdFirstArgs);   // option "dp_commit_late"
 template __global__ void head_kernel<48, 8>(HeadArgs);
 }

@@ -28,14 +28,20 @@ for _ in range(3):
     fh.next_training_batch_on_device(B, T, "default", synthetic.SPEC_AUGMENT_POLICY)
     eng.train_step(B, 1e-3)
 eng.synchronize()
-FWD = ["commit+wait", "barrier1", "issue", "depthwise", "barrier2", "mfma", "stores", "barrier3"]
-BWD = ["commit+wait", "barrier1", "issue+P1", "barrier2", "mfma", "barrier3", "P4", "barrier4"]
-S = 12   # kClkSlots
-for k in (2, 3, 4):
-    for tag, names, grid in (("f", FWD, 1024), ("b", BWD, 512)):
+FWD = ["commit+wait", "barrier1", "issue", "depthwise", "barrier2", "mfma", "stores", "barrier3", "-"]
+# backward: the wait for the input rows (group A) and the one for the dp rows (group B) are marked apart; with "dp_commit_late" the
+# second sits behind P1 and includes the next request of the dp rows
+BWD = ["commitA+wait", "barrier1", "issue+P1", "barrier2", "mfma", "barrier3", "P4", "barrier4", "commitB+wait"]
+BWD1 = ["commitA+wait", "barrier1", "issue+P1", "barrier2", "mfma", "barrier3+5", "P4", "barrier4+dW1", "commitB+wait"]   # first block
+NP = 9       # kClkPhases
+S = NP + 4   # kClkSlots
+for k in (1, 2, 3, 4):
+    for tag, names, grid in (("f", FWD, 1024), ("b", BWD if k > 1 else BWD1, 512)):
+        if k == 1 and tag == "f":
+            continue   # the first block's forward kernel carries no phase clocks
         raw = eng.debug_read("clk%s%d" % (tag, k), 1, 2048 * S * 2)
         rec = raw.view(np.uint64).reshape(2048, S)[:min(grid, B)].astype(np.float64)
-        clk, st = rec[:, :8], rec[:, 8:]
+        clk, st = rec[:, :NP], rec[:, NP:]
         tot = clk.sum(1)
         print("layer %d %s: total cycles/WG mean %.0f (min %.0f max %.0f)" % (k, "fwd" if tag == "f" else "bwd", tot.mean(), tot.min(), tot.max()))
         print("   " + "  ".join("%s=%.0f(%.0f%%)" % (n, v, 100 * v / tot.mean()) for n, v in zip(names, clk.mean(0))))
@@ -50,7 +56,7 @@ for k in (2, 3, 4):
 for k in (2, 4):
     raw = eng.debug_read("clkb%d" % k, 1, 2048 * S * 2)
     rec = raw.view(np.uint64).reshape(2048, S)[:min(512, B)].astype(np.float64)
-    tot = rec[:, :8].sum(1)
+    tot = rec[:, :NP].sum(1)
     print("layer %d bwd loop cycles by XCD:" % k, [int(tot[x::8].mean()) for x in range(8)], " spread within XCD0: min %d max %d" % (tot[0::8].min(), tot[0::8].max()))
     half = len(tot) // 2
     print("   first half of the grid (first WG on each CU?) mean %d, second half mean %d" % (tot[:half].mean(), tot[half:].mean()))
@@ -59,7 +65,7 @@ for k in (2, 4):
 for k in (2, 3, 4):
     raw = eng.debug_read("clkf%d" % k, 1, 2048 * S * 2)
     rec = raw.view(np.uint64).reshape(2048, S)[:min(1024, B)].astype(np.float64)
-    tot = rec[:, :8].sum(1)
+    tot = rec[:, :NP].sum(1)
     q = len(tot) // 4
     if q:
         print("layer %d fwd loop cycles by dispatch quartile (blockIdx >> 8):" % k, [int(tot[i * q:(i + 1) * q].mean()) for i in range(4)])
