@@ -1,6 +1,9 @@
-// Shared by the float (tu_stream.hip) and the int8 (tu_stream_q8.hip) streaming kernels: the plan of a streaming MixedNet
-// (layers, weight / ring offsets, reach of every layer), the stream object, and the per-call track / segment / tile
-// tables.  Both kernels walk the same tiles and the same ring layout; only the element type and the arithmetic differ.
+// Shared by the four streaming units.  A stream (mww_stream) has a front every stream has - context, per-call track /
+// segment / tile tables, outputs, float weights and state, int8 parameters and state; its host path is tu_stream.hip - and a
+// model part (SModel): MixedNet (tu_stream.hip float, tu_stream_q8.hip int8; its plan is here) or a conv/BN graph
+// (stream_graph.hip.h).  The model's virtual functions are the one place the two kinds are told apart.  The device code all
+// four kernels share is here too: the tile header, the Dense heads, the head-ring write-back and the calibration (REC) folds.
+// The kernels walk the same tiles and the same ring layout; only the element type and the arithmetic differ.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +14,7 @@
 #include <vector>
 
 #include "../../include/mww.h"
+#include "int8_ops.hip.h"
 
 namespace mww {
 int ctx_borrow(mww_ctx* c, int* device, hipStream_t* stream, void** stores, int* dtypes, int64_t* elems, int* n_cu);
@@ -23,6 +27,10 @@ constexpr int kStreamThreads = 256;
 constexpr int kHostStore = MWW_MAX_STORES;   // store slot of the frames mww_stream_run_host uploads
 constexpr int kTileOutputs = 256;            // outputs per tile (one head thread each)
 constexpr float kScaleU16 = 0.0390625f;      // data.py:268-269 / inference.py:93-94
+constexpr int64_t kMaxLds = 160 * 1024;      // LDS of a gfx950 CU: an int8 tile that fits sits there
+constexpr float kInv255 = (float)(1.0 / 255.0);   // inference.py:170 1 / 255 as float32
+
+inline int64_t r4(int64_t n) { return (n + 3) & ~(int64_t)3; }   // int8 rows and weight slices are padded to 32-bit words
 
 struct SLayer {
   int kind;          // 0: depthwise K taps + bias (fused MixConv groups, zero leading taps); 1: 1x1 + folded BN + ReLU
@@ -104,45 +112,160 @@ __device__ inline void rec_fold(float lmin, float lmax, int t, float* red, float
   __syncthreads();
 }
 
-// int8 form (tu_stream_q8.hip): device copies of the quantized parameters; layout in include/mww.h
+// Calibration prologue / epilogue of a workgroup: the running min / max start empty; its partial row [n_tensors][2] at the end
+__device__ inline void rec_init(const SCall& a, float* rmin, float* rmax) {
+  for (int t = threadIdx.x; t < a.n_tensors; t += kStreamThreads) {
+    rmin[t] = INFINITY;
+    rmax[t] = -INFINITY;
+  }
+  __syncthreads();
+}
+
+__device__ inline void rec_flush(const SCall& a, const float* rmin, const float* rmax) {
+  for (int t = threadIdx.x; t < a.n_tensors; t += kStreamThreads) {
+    a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2] = rmin[t];
+    a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2 + 1] = rmax[t];
+  }
+}
+
+// A tile: outputs [c0, c1) of its segment, counted in positions of the segment (stream mode: the segment is the call and
+// output n is position n, so the call ends at N = c1 in the tile that is `last`: that tile writes the rings)
+struct STile {
+  int64_t c0, c1, v_seg, out0;   // v_seg: the segment's first virtual frame; out0: global index of the tile's first output
+  int n;
+  bool last;
+};
+
+__device__ inline STile tile_of(const SCall& a, int tile) {
+  const int sg = a.tile_seg[tile];
+  STile t;
+  t.c0 = a.tile_m0[tile] + a.seg_coff[sg];
+  t.n = a.tile_n[tile];
+  t.c1 = t.c0 + t.n;
+  t.v_seg = a.seg_v0[sg];
+  t.out0 = a.tile_out0[tile];
+  t.last = a.use_state && t.out0 + t.n == a.n_out;
+  return t;
+}
+
+// Float head: Dense over the last TF rows of the final map at every output position, sigmoid.  fin: row 0 of the final map
+// as if it started at position 0 (pitch floats a row); positions before the stream start read the head ring.
+template <bool REC>
+__device__ inline void dense_head(const SCall& a, const STile& T, const float* fin, int pitch, const float* hring, int64_t wd_at,
+                                  int64_t bd_at, int C, int TF, float& lmin, float& lmax) {
+  for (int o = threadIdx.x; o < T.n; o += kStreamThreads) {
+    const int64_t c = T.c0 + o;
+    float acc = a.w[bd_at];
+    for (int t = 0; t < TF; ++t) {
+      const int64_t q = c - (TF - 1) + t;
+      const float* wd = a.w + wd_at + (int64_t)t * C;
+      const float* x = q >= 0 ? fin + q * pitch : hring + (TF - 1 + q) * C;
+      for (int ch = 0; ch < C; ++ch) acc = fmaf(x[ch], wd[ch], acc);
+    }
+    const int64_t g = T.out0 + o;
+    a.logit[g] = acc;
+    a.prob[g] = 1.f / (1.f + expf(-acc));
+    if (REC) {
+      lmin = fminf(lmin, acc);
+      lmax = fmaxf(lmax, acc);
+    }
+  }
+}
+
+// The head ring after the call: the final map at positions [N - (TF - 1), N), N = T.c1 of the last tile
+template <class E>
+__device__ inline void head_ring_store(E* ring_out, const STile& T, const E* fin, int pitch, const E* hring, int C, int TF) {
+  for (int idx = threadIdx.x; idx < (TF - 1) * C; idx += kStreamThreads) {
+    const int64_t q = T.c1 - (TF - 1) + idx / C;
+    const int ch = idx % C;
+    ring_out[idx] = q >= 0 ? fin[q * pitch + ch] : hring[(TF - 1 + q) * C + ch];
+  }
+}
+
+// int8 form: what both int8 kernels get of the quantized parameters (layout: include/mww.h) and the call
 struct SQ8 {
   const int8_t* w;       // int8 weights
-  const int32_t* iv;     // per op: bias (input zero point folded), multiplier, shift [cout] each; then the tensor zero points
+  const int32_t* iv;     // per op: bias (input zero point folded), multiplier, shift [cout] each; the Dense's three; the tensor zero points
   const uint8_t* lut;    // [256]: logit q + 128 -> output uint8
-  const int64_t* lw;     // [n_layers] offset of each layer's weights in w
-  const int64_t* li;     // [n_layers] offset of each layer's ints in iv
-  int64_t w1, wd, i1, id, izp;
+  int64_t izp;           // offset of the tensor zero points in iv
   float in_scale;
   int in_zp;
-  int kp1;               // conv1 reduction length k1 * 40
-  int cpd;               // dense row pitch: C_last rounded up to 4
-  int cp;                // activation row pitch: cmax rounded up to 4
   uint8_t* out;          // [n_out] uint8 outputs
   const int8_t* st_in;
   int8_t* st_out;
-  int8_t* scratch;       // global form: per-workgroup buffers
+  int8_t* scratch;       // global form: per-workgroup tiles of SCall::scratch_per_wg bytes
   int use_lds;
 };
 
-}  // namespace mww_stream_impl
+// int8 head: Dense (int8 logit; words of the final map's rows of `pitch` bytes, bytes of the unpadded head ring), Logistic
+// table, uint8 output, probability u8 / 255.  The Dense's weights are [TF][r4(C)] at wd_at, its three ints at id_at.
+__device__ inline void dense_head_q8(const SCall& a, const SQ8& q, const STile& T, const int8_t* fin, int pitch, const int8_t* hring,
+                                     int64_t wd_at, int64_t id_at, int zo, int C, int TF) {
+  const int32_t bias = q.iv[id_at], mul = q.iv[id_at + 1], shf = q.iv[id_at + 2];
+  const int pc = (C + 3) & ~3;
+  for (int o = threadIdx.x; o < T.n; o += kStreamThreads) {
+    const int64_t c = T.c0 + o;
+    int acc = bias;
+    for (int t = 0; t < TF; ++t) {
+      const int64_t p = c - (TF - 1) + t;
+      const int8_t* wd = q.w + wd_at + (int64_t)t * pc;
+      if (p >= 0) {
+        const int* x = reinterpret_cast<const int*>(fin + p * pitch);
+        const int* w = reinterpret_cast<const int*>(wd);
+        for (int r = 0; r < pc / 4; ++r) acc = mww_sdot4(x[r], w[r], acc);
+      } else {
+        const int8_t* x = hring + (TF - 1 + p) * C;
+        for (int ch = 0; ch < C; ++ch) acc += (int)x[ch] * (int)wd[ch];
+      }
+    }
+    const int lq = q8_requant(acc, mul, shf, zo, -128);
+    const uint8_t u = q.lut[lq + 128];
+    const int64_t g = T.out0 + o;
+    q.out[g] = u;
+    a.logit[g] = (float)lq;
+    a.prob[g] = (float)u * kInv255;
+  }
+}
 
-struct mww_stream_graph;   // conv/BN graph form (tu_stream_graph.hip)
+// What the shared call preparation needs of a model, filled by both planners
+struct SGeom {
+  int stride = 1;         // frames per output
+  int frames = 0;         // the non-stream window
+  int mode = 0;           // MWW_STREAM_MODE_*
+  int reach = 0;          // positions of input halo in front of a tile: a tile's buffers hold tile_outputs + reach rows
+  int j0 = 0;             // non-stream: position of a track's first window
+  int tile_outputs = kTileOutputs;
+};
+
+// The model part of a stream.  The planner fills the sizes; the virtual functions are all the front ever asks of it.
+struct SModel {
+  SGeom g;
+  int64_t n_weights = 0;        // Keras-order floats
+  int64_t n_dev_w = 0;          // folded device weights
+  int64_t n_state = 0;          // ring values (floats; the int8 state has one byte for each)
+  int64_t scratch_per_wg = 0;   // floats of one workgroup's tile (float kernel)
+  int n_tensors = 0;            // calibrated tensors: the input, every op's output, the logit
+  bool int8 = true;             // takes int8 parameters (a conv/BN graph: only from mww_stream_create_convnet_q8)
+  int64_t q8_nw = 0, q8_ni = 0, q8_izp = 0;   // int8 weights / int32 values expected; offset of the zero points
+  int64_t q8_tile_bytes = 0;                  // one workgroup's int8 tile
+  std::vector<std::pair<int64_t, int>> q8_requant;   // per op and the Dense: (offset of its bias / multiplier / shift, cout)
+  virtual ~SModel() {}                                // frees the device tables
+  virtual int upload() = 0;                           // device tables of the plan (the device is current)
+  virtual int64_t fold_weights(const float* h, float* w) const = 0;   // Keras order -> device layout; floats consumed
+  virtual void launch(const SStores& S, const SCall& a, int grid, hipStream_t hs) const = 0;   // a.rec: the <REC> form
+  virtual void q8_state0(const int32_t* zp, int8_t* st0) const = 0;   // rings at reset: each tensor's zero point
+  virtual const void* q8_kernel() const = 0;
+  virtual void launch_q8(const SStores& S, const SCall& a, const SQ8& q, int grid, size_t lds, hipStream_t hs) const = 0;
+};
+
+}  // namespace mww_stream_impl
 
 struct mww_stream {
   mww_ctx* ctx = nullptr;
   int device = 0;
   hipStream_t stream = nullptr;
   int n_cu = 256;
-  mww_stream_desc d{};
-  mww_stream_impl::SNet net{};
-  std::vector<mww_stream_impl::SLayer> layers;   // host copy of net.L
-  mww_stream_impl::SLayer* d_layers = nullptr;
-  int64_t n_weights = 0;   // Keras-order floats
-  int64_t n_dev_w = 0;     // folded device weights
-  int64_t n_state = 0;
-  int j0 = 0;              // non-stream: conv1 index of a track's first window
-  int tile_outputs = mww_stream_impl::kTileOutputs;   // outputs per tile of this stream's kernel
-  mww_stream_graph* graph = nullptr;   // set: a conv/BN graph stream (mww_stream_create_convnet), the float graph kernel runs it
+  mww_stream_impl::SModel* model = nullptr;
   float* w = nullptr;
   float* st[2] = {nullptr, nullptr};
   int cur = 0;
@@ -158,6 +281,7 @@ struct mww_stream {
   float* host_frames = nullptr;
   int64_t cap_host_frames = 0;
   int64_t n_out = 0;       // outputs held in prob (last run or set_probs)
+  int grid = 0;            // workgroups of the last launch
   // metrics
   char* mtab = nullptr;
   int64_t cap_mtab = 0;
@@ -166,17 +290,14 @@ struct mww_stream {
   int64_t cap_rec = 0;
   // int8 form (mww_stream_set_quantized): runs replace the float kernel with the int8 one
   bool q8 = false;
-  int64_t q8_nw = 0, q8_ni = 0;
   int8_t* q8_w = nullptr;
   int32_t* q8_i = nullptr;
   uint8_t* q8_lut = nullptr;
-  int64_t* q8_off = nullptr;           // [2 * n_layers]: weight offsets, then int offsets
   std::vector<int8_t> q8_state0;       // rings at reset: each ring filled with its tensor's zero point
   int8_t* q8_st[2] = {nullptr, nullptr};
   int q8_cur = 0;
   float q8_in_scale = 1.f;
   int q8_in_zp = 0;
-  int64_t q8_w1 = 0, q8_wd = 0, q8_i1 = 0, q8_id = 0, q8_izp = 0;
   uint8_t* q8_out = nullptr;
   int64_t cap_q8_out = 0;
   int8_t* q8_scratch = nullptr;
@@ -184,6 +305,9 @@ struct mww_stream {
 };
 
 namespace mww_stream_impl {
+
+// tu_stream.hip: a stream around a planned model (takes the model over, also on failure)
+int stream_create(mww_ctx* ctx, SModel* m, int rc_plan, mww_stream** out);
 
 #define SCHK(expr)                                                                                      \
   do {                                                                                                  \
@@ -204,9 +328,46 @@ inline int grow(T** p, int64_t* cap, int64_t n) {
   return MWW_OK;
 }
 
-// topology + weight / state layout from the description; Keras-order size in *keras
-inline int plan(const mww_stream_desc& d, SNet& net, std::vector<SLayer>& layers, int64_t* keras, int64_t* dev_w, int64_t* state, int* j0) {
-  std::memset(&net, 0, sizeof(net));
+// device copy of a plan table (+ 64 bytes, as every buffer here)
+template <class T>
+inline int upload_table(T** dev, const std::vector<T>& host) {
+  SCHK(hipMalloc((void**)dev, host.size() * sizeof(T) + 64));
+  if (!host.empty()) SCHK(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+  return MWW_OK;
+}
+
+// MixedNet: conv1, per block and repeat a fused MixConv depthwise layer (when max(ks) > 1) and a 1x1 layer, the Dense
+struct MixedNet : SModel {
+  mww_stream_desc d{};
+  SNet net{};
+  std::vector<SLayer> layers;   // host copy of net.L
+  SLayer* d_layers = nullptr;
+  // int8 layout (tu_stream_q8.hip): weight / int offsets of conv1, the layers and the Dense; pitches
+  struct Q8 {
+    const int64_t* lw;     // [n_layers] offset of each layer's weights
+    const int64_t* li;     // [n_layers] offset of each layer's ints
+    int64_t w1, wd, i1, id;
+    int kp1;               // conv1 reduction length k1 * 40
+    int cp;                // activation row pitch: cmax rounded up to 4
+  } q{};
+  std::vector<int64_t> q8_off;   // [2 * n_layers]: weight offsets, then int offsets
+  int64_t* d_q8_off = nullptr;
+  int plan();      // from d
+  void plan_q8();
+  ~MixedNet() override {
+    if (d_layers) (void)hipFree(d_layers);
+    if (d_q8_off) (void)hipFree(d_q8_off);
+  }
+  int upload() override;
+  int64_t fold_weights(const float* h, float* w) const override;
+  void launch(const SStores& S, const SCall& a, int grid, hipStream_t hs) const override;
+  void q8_state0(const int32_t* zp, int8_t* st0) const override;
+  const void* q8_kernel() const override;
+  void launch_q8(const SStores& S, const SCall& a, const SQ8& q, int grid, size_t lds, hipStream_t hs) const override;
+};
+
+// topology + weight / state layout, reach of every layer and the call geometry from the description
+inline int MixedNet::plan() {
   layers.assign((size_t)2 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT, SLayer{});
   if (d.mode != MWW_STREAM_MODE_STREAM && d.mode != MWW_STREAM_MODE_NON_STREAM) return unsupported("mode must be stream or non_stream");
   if (d.conv1_filters <= 0 || d.conv1_kernel <= 0 || d.stride <= 0)
@@ -270,18 +431,27 @@ inline int plan(const mww_stream_desc& d, SNet& net, std::vector<SLayer>& layers
   }
   layers.resize((size_t)nl);
   net.reach1 = reach;
-  *j0 = 0;
   if (d.mode == MWW_STREAM_MODE_NON_STREAM) {
     if (d.frames < net.k1) return unsupported("non_stream mode needs frames >= the first convolution's kernel");
     const int n1 = (d.frames - net.k1) / net.s + 1;
     if (n1 - sum_r != net.tf)
       return unsupported("t_final " + std::to_string(net.tf) + " does not match a " + std::to_string(d.frames) + "-frame window (" +
                          std::to_string(n1 - sum_r) + " final frames)");
-    *j0 = n1 - 1;
+    g.j0 = n1 - 1;
   }
-  *keras = kw;
-  *dev_w = dw;
-  *state = st;
+  g.stride = net.s;
+  g.frames = d.frames;
+  g.mode = d.mode;
+  g.reach = net.reach1;
+  n_weights = kw;
+  n_dev_w = dw;
+  n_state = st;
+  n_tensors = nl + 3;
+  // a tile: the gathered input rows and two activation buffers
+  const int64_t rows = g.tile_outputs + g.reach, g_rows = ((rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS;
+  scratch_per_wg = (g_rows + 2 * rows * net.cmax + 255) & ~(int64_t)255;
+  q8_tile_bytes = g_rows + 2 * rows * r4(net.cmax);
+  plan_q8();
   return MWW_OK;
 }
 
@@ -302,9 +472,9 @@ inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk,
   for (int i = 0; i < MWW_MAX_STORES; ++i) { S.p[i] = stores[i]; S.dtype[i] = dt[i]; }
   S.p[kHostStore] = s->host_frames;
   S.dtype[kHostStore] = MWW_DTYPE_F32;
-  const SNet& net = s->net;
-  const bool stream_mode = s->d.mode == MWW_STREAM_MODE_STREAM;
-  const int T = s->d.frames;
+  const SGeom& g = s->model->g;
+  const bool stream_mode = g.mode == MWW_STREAM_MODE_STREAM;
+  const int T = g.frames;
   // per track: frames fed and outputs (predict_spectrogram: chunks of s, trailing L mod s frames never fed; non-stream:
   // windows ending at T, T + s, ... <= L)
   std::vector<int64_t> v0((size_t)n_trk + 1, 0);
@@ -322,10 +492,10 @@ inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk,
     const int64_t L = (int64_t)w.pad_rows + w.copy_rows;
     int64_t n_o;
     if (stream_mode) {
-      n_o = L / net.s;
-      v0[t + 1] = v0[t] + n_o * net.s;
+      n_o = L / g.stride;
+      v0[t + 1] = v0[t] + n_o * g.stride;
     } else {
-      n_o = L >= T ? (L - T) / net.s + 1 : 0;
+      n_o = L >= T ? (L - T) / g.stride + 1 : 0;
       v0[t + 1] = v0[t] + L;
     }
     out_off[t + 1] = out_off[t] + n_o;
@@ -336,7 +506,7 @@ inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk,
   // segments and tiles
   std::vector<int64_t> seg_v0, tile_m0, tile_out0;
   std::vector<int> seg_coff, tile_seg, tile_n;
-  const int tile_outputs = s->tile_outputs;
+  const int tile_outputs = g.tile_outputs;
   auto add_tiles = [&](int sg, int64_t n, int64_t out0) {
     for (int64_t m = 0; m < n; m += tile_outputs) {
       tile_seg.push_back(sg);
@@ -354,7 +524,7 @@ inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk,
       const int64_t n = out_off[t + 1] - out_off[t];
       if (!n) continue;
       seg_v0.push_back(v0[t]);
-      seg_coff.push_back(s->j0);
+      seg_coff.push_back(g.j0);
       add_tiles((int)seg_v0.size() - 1, n, out_off[t]);
     }
   }
@@ -381,7 +551,7 @@ inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk,
   if ((rc = grow(&s->tables, &s->cap_tables, bytes))) return rc;
   if ((rc = grow(&s->prob, &s->cap_out, n_out))) return rc;
   if ((rc = grow(&s->logit, &s->cap_logit, n_out))) return rc;
-  *grid_out = n_tiles < 2 * s->n_cu ? n_tiles : 2 * s->n_cu;
+  *grid_out = s->grid = n_tiles < 2 * s->n_cu ? n_tiles : 2 * s->n_cu;
   SCHK(hipMemcpyAsync(s->tables, tab.data(), (size_t)bytes, hipMemcpyHostToDevice, s->stream));
   a = SCall{};
   a.trk = reinterpret_cast<const mww_window*>(s->tables + o_trk);
@@ -399,7 +569,7 @@ inline int64_t prepare_call(mww_stream* s, const mww_window* trk, int64_t n_trk,
   a.w = s->w;
   a.st_in = s->st[s->cur];
   a.st_out = s->st[s->cur ^ 1];
-  a.buf_rows = tile_outputs + net.reach1;
+  a.buf_rows = tile_outputs + g.reach;
   a.prob = s->prob;
   a.logit = s->logit;
   return n_out;

@@ -1,12 +1,11 @@
 // Shared by the float (tu_stream_graph.hip) and the int8 (tu_stream_graph_q8.hip) kernels of a conv/BN graph stream: the
-// planned ops (sources, reach, placement of every tensor in the workgroup's tile, barrier flags) and the graph part of the
-// stream object.  Both kernels walk the same ops, tiles and rings; the float plan counts floats, the int8 plan bytes.
+// planned ops (sources, reach, placement of every tensor in the workgroup's tile, barrier flags) and the graph model part
+// of a stream (stream_common.hip.h).  Both kernels walk the same ops, tiles and rings; the float plan counts floats, the
+// int8 plan bytes.
 #pragma once
 #include "stream_common.hip.h"
 
 namespace mww_stream_impl {
-
-constexpr int kGraphTileOutputs = 256;   // outputs per tile
 
 struct GOp {
   int n_src, k, d, cin, cout, R, reach, sync;
@@ -27,23 +26,28 @@ struct GNet {
 // The int8 plan is the same structure counted in bytes: rows have the pitch r4(C), src_C is that pitch, src_buf / out_buf /
 // in_buf / last_buf are 4-byte aligned byte offsets of the tile, w / wd offsets into the int8 weights, b / bd into the int32
 // values (bias, multiplier, shift [cout] each); ring offsets are unchanged (one byte per value).
-inline int64_t r4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
-}  // namespace mww_stream_impl
-
-struct mww_stream_graph {
-  mww_stream_impl::GNet net{};
-  std::vector<mww_stream_impl::GOp> ops;
+struct Graph : SModel {
+  GNet net{};
+  std::vector<GOp> ops;
   std::vector<int> groups;   // bn_groups of each op
   std::vector<int> src;      // [n_ops][MWW_MAX_OP_SOURCES] producing op of each source (-1: the spectrogram)
-  mww_stream_impl::GOp* d_ops = nullptr;
-  int64_t scratch_per_wg = 0;
-  // int8 form (mww_stream_create_convnet_q8)
-  bool int8 = false;
-  mww_stream_impl::GNet qnet{};
-  std::vector<mww_stream_impl::GOp> qops;
-  mww_stream_impl::GOp* d_qops = nullptr;
-  int64_t q_tile_bytes = 0;      // the byte plan of one tile
-  int64_t q_nw = 0, q_ni = 0;    // int8 weights / int32 values mww_stream_set_quantized expects
-  int64_t q_izp = 0;             // offset of the n_ops + 2 zero points in the int32 values
+  GOp* d_ops = nullptr;
+  // int8 form (mww_stream_create_convnet_q8): the byte plan
+  GNet qnet{};
+  std::vector<GOp> qops;
+  GOp* d_qops = nullptr;
+  int plan(const mww_convnet_desc& d, int mode);
+  ~Graph() override {
+    if (d_ops) (void)hipFree(d_ops);
+    if (d_qops) (void)hipFree(d_qops);
+  }
+  int upload() override;
+  int64_t fold_weights(const float* h, float* w) const override;
+  void launch(const SStores& S, const SCall& a, int grid, hipStream_t hs) const override;
+  void q8_state0(const int32_t* zp, int8_t* st0) const override;
+  const void* q8_kernel() const override;
+  void launch_q8(const SStores& S, const SCall& a, const SQ8& q, int grid, size_t lds, hipStream_t hs) const override;
 };
+
+}  // namespace mww_stream_impl

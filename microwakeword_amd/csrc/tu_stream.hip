@@ -18,25 +18,16 @@
 // each layer: T_f - 1 + sum(K - 1) conv1 frames) in a private global scratch region; positions before the start of the
 // stream read the layers' rings instead.  The tile that ends the call also writes the final rings (double-buffered
 // state, so no tile reads a ring another tile writes).  Every sum runs in a fixed order: no atomics, runs are bit-identical.
+//
+// Here: the float MixedNet kernel and the float half of the MixedNet model part (Keras-order weight folding, launch), the
+// detection-metrics kernels, and the host path of EVERY stream - creation, reset, the float and the int8 launch epilogue,
+// calibration, mww_stream_set_quantized - written once against SModel (stream_common.hip.h); the conv/BN graph model part
+// and its two creators are tu_stream_graph.hip / tu_stream_graph_q8.hip.
 #include <hip/hip_runtime.h>
 
 #include "stream_common.hip.h"
 
 using namespace mww_stream_impl;
-
-namespace mww {
-int64_t stream_q8_launch(mww_stream* s, const mww_stream_impl::SStores& S, mww_stream_impl::SCall& a, int grid);
-int stream_q8_reset(mww_stream* s);
-void stream_q8_free(mww_stream* s);
-// conv/BN graph streams (tu_stream_graph.hip)
-int stream_graph_set_weights(mww_stream* s, const float* h, int64_t n);
-int64_t stream_graph_launch(mww_stream* s, const mww_stream_impl::SStores& S, mww_stream_impl::SCall& a, int grid);
-void stream_graph_free(mww_stream* s);
-int stream_graph_no_int8(const mww_stream* s);
-bool stream_graph_int8(const mww_stream* s);   // created by mww_stream_create_convnet_q8
-int stream_graph_num_tensors(const mww_stream* s);
-int64_t stream_graph_q8_launch(mww_stream* s, const mww_stream_impl::SStores& S, mww_stream_impl::SCall& a, int grid);   // tu_stream_graph_q8.hip
-}  // namespace mww
 
 namespace {
 
@@ -47,24 +38,15 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
   const int tid = threadIdx.x;
   __shared__ float red[REC ? 2 * kStreamThreads : 1], rmin[REC ? kMaxTensors : 1], rmax[REC ? kMaxTensors : 1];
   float lmin = INFINITY, lmax = -INFINITY;
-  if (REC) {
-    for (int t = tid; t < a.n_tensors; t += kStreamThreads) {
-      rmin[t] = INFINITY;
-      rmax[t] = -INFINITY;
-    }
-    __syncthreads();
-  }
+  if (REC) rec_init(a, rmin, rmax);
   float* G = a.scratch + (int64_t)blockIdx.x * a.scratch_per_wg;            // gathered padded input rows [.][40]
   float* B0 = G + ((a.buf_rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS;   // two activation buffers [rows][cmax]
   float* B1 = B0 + a.buf_rows * net.cmax;
   const int r1 = a.use_state ? net.r1 : 0;
   for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-    const int sg = a.tile_seg[tile];
-    const int64_t c0 = a.tile_m0[tile] + a.seg_coff[sg];
-    const int64_t c1 = c0 + a.tile_n[tile];
-    const int64_t v_seg = a.seg_v0[sg];
-    const bool last = a.use_state && a.tile_out0[tile] + a.tile_n[tile] == a.n_out;
-    const int64_t N = c1;   // in stream mode the segment is the call and output n is conv1 index n
+    const STile T = tile_of(a, tile);
+    const int64_t c0 = T.c0, c1 = T.c1, v_seg = T.v_seg, N = T.c1;   // positions are conv1 indices
+    const bool last = T.last;
     // ---- gather the padded input rows the tile's conv1 outputs read: P index p = v + r1 (v virtual frame in the segment)
     int64_t lo = c0 - net.reach1;
     if (lo < 0) lo = 0;
@@ -161,49 +143,18 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
       in_lo = o_lo;
     }
     // ---- head: Dense over the last T_f frames of the final map at every output position
-    const int C = net.c_last, TF = net.tf;
+    const float* fin = in - in_lo * net.cmax;
     const float* hring = a.st_in + net.ring_head;
-    for (int o = tid; o < a.tile_n[tile]; o += kStreamThreads) {
-      const int64_t c = c0 + o;
-      float acc = a.w[net.bd];
-      for (int t = 0; t < TF; ++t) {
-        const int64_t q = c - (TF - 1) + t;
-        const float* wd = a.w + net.wd + (int64_t)t * C;
-        if (q >= 0) {
-          const float* x = in + (q - in_lo) * net.cmax;
-          for (int ch = 0; ch < C; ++ch) acc = fmaf(x[ch], wd[ch], acc);
-        } else {
-          const float* x = hring + (TF - 1 + q) * C;
-          for (int ch = 0; ch < C; ++ch) acc = fmaf(x[ch], wd[ch], acc);
-        }
-      }
-      const int64_t g = a.tile_out0[tile] + o;
-      a.logit[g] = acc;
-      a.prob[g] = 1.f / (1.f + expf(-acc));
-      if (REC) {
-        lmin = fminf(lmin, acc);
-        lmax = fmaxf(lmax, acc);
-      }
-    }
+    dense_head<REC>(a, T, fin, net.cmax, hring, net.wd, net.bd, net.c_last, net.tf, lmin, lmax);
     if (REC) {
       rec_fold(lmin, lmax, 2 + net.n_layers, red, rmin, rmax);
       lmin = INFINITY;
       lmax = -INFINITY;
     }
-    if (last) {
-      for (int idx = tid; idx < (TF - 1) * C; idx += kStreamThreads) {
-        const int64_t q = N - (TF - 1) + idx / C;
-        const int ch = idx % C;
-        a.st_out[net.ring_head + idx] = q >= 0 ? in[(q - in_lo) * net.cmax + ch] : hring[(TF - 1 + q) * C + ch];
-      }
-    }
+    if (last) head_ring_store(a.st_out + net.ring_head, T, fin, net.cmax, hring, net.c_last, net.tf);
     __syncthreads();   // the next tile reuses the scratch
   }
-  if (REC)
-    for (int t = tid; t < a.n_tensors; t += kStreamThreads) {
-      a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2] = rmin[t];
-      a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2 + 1] = rmax[t];
-    }
+  if (REC) rec_flush(a, rmin, rmax);
 }
 
 // Detection metrics (test.py:94-137 compute_false_accepts_per_hour, :329-376).  One workgroup per track: thread j < n_cut
@@ -264,74 +215,36 @@ __global__ void stream_counts_sum_kernel(const unsigned long long* counts, int n
 
 }  // namespace
 
-extern "C" {
+// ---- MixedNet, float half of the model part (tu_stream_q8.hip has the int8 half)
+namespace mww_stream_impl {
 
-int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* d, mww_stream** out) {
-  if (!ctx || !d || !out) return mww::set_error(MWW_ERR_INVALID, "null argument");
-  *out = nullptr;
-  mww_stream* s = new mww_stream();
-  s->ctx = ctx;
-  s->d = *d;
-  int rc = plan(*d, s->net, s->layers, &s->n_weights, &s->n_dev_w, &s->n_state, &s->j0);
-  void* stores[MWW_MAX_STORES];
-  int dt[MWW_MAX_STORES];
-  int64_t el[MWW_MAX_STORES];
-  if (!rc) rc = mww::ctx_borrow(ctx, &s->device, &s->stream, stores, dt, el, &s->n_cu);
-  if (!rc && hipSetDevice(s->device) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipSetDevice failed");
-  if (!rc && hipMalloc((void**)&s->w, (size_t)s->n_dev_w * sizeof(float)) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc weights");
-  if (!rc && hipMalloc((void**)&s->d_layers, s->layers.size() * sizeof(SLayer) + 64) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc layers");
-  if (!rc && hipMemcpy(s->d_layers, s->layers.data(), s->layers.size() * sizeof(SLayer), hipMemcpyHostToDevice) != hipSuccess)
-    rc = mww::set_error(MWW_ERR_HIP, "hipMemcpy layers");
-  s->net.L = s->d_layers;
-  for (int i = 0; i < 2 && !rc; ++i)
-    if (hipMalloc((void**)&s->st[i], (size_t)(s->n_state + 1) * sizeof(float)) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc state");
-  if (!rc) rc = mww_stream_reset(s);
-  if (rc) {
-    mww_stream_destroy(s);
-    return rc;
-  }
-  *out = s;
-  return MWW_OK;
+int MixedNet::upload() {
+  int rc = upload_table(&d_layers, layers);
+  if (!rc) rc = upload_table(&d_q8_off, q8_off);
+  net.L = d_layers;
+  q.lw = d_q8_off;
+  q.li = d_q8_off + net.n_layers;
+  return rc;
 }
 
-void mww_stream_destroy(mww_stream* s) {
-  if (!s) return;
-  (void)hipSetDevice(s->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  for (void* p : {(void*)s->w, (void*)s->st[0], (void*)s->st[1], (void*)s->prob, (void*)s->logit, (void*)s->scratch,
-                  (void*)s->tables, (void*)s->host_frames, (void*)s->mtab, (void*)s->d_layers, (void*)s->rec})
-    if (p) (void)hipFree(p);
-  mww::stream_q8_free(s);
-  mww::stream_graph_free(s);
-  delete s;
-}
-
-int64_t mww_stream_num_weights(const mww_stream* s) { return s ? s->n_weights : 0; }
-int64_t mww_stream_num_state(const mww_stream* s) { return s ? s->n_state : 0; }
-
-int mww_stream_set_weights(mww_stream* s, const float* h, int64_t n) {
-  if (!s || !h) return mww::set_error(MWW_ERR_INVALID, "null argument");
-  if (n != s->n_weights) return mww::set_error(MWW_ERR_INVALID, ("expected " + std::to_string(s->n_weights) + " Keras-order floats").c_str());
-  if (s->graph) return mww::stream_graph_set_weights(s, h, n);
+int64_t MixedNet::fold_weights(const float* h, float* w) const {
   // Keras get_weights() order (mixednet.py:307-386): conv1.kernel [k1,1,40,F]; per block and repeat: per MixConv group
   // kernel [k,1,gc,1] + bias [gc], pointwise kernel [1,1,C,F], BN gamma, beta, moving_mean, moving_variance; dense [T_f*C,1], bias.
   // BatchNormalization (inference: moving statistics, eps 1e-3) is folded into the 1x1 weights and a bias once, here.
-  const SNet& net = s->net;
-  std::vector<float> w((size_t)s->n_dev_w, 0.f);
   int64_t p = 0;
   const int64_t n1 = (int64_t)net.k1 * MWW_FEATURE_BINS * net.c1;
   std::memcpy(&w[net.w1], h, (size_t)n1 * sizeof(float));
   p += n1;
   int l = 0;
-  for (int b = 0; b < s->d.n_blocks; ++b) {
-    const int nk = s->d.n_kernels[b];
-    for (int r = 0; r < s->d.repeat[b]; ++r) {
-      if (s->layers[l].kind == 0) {
-        const SLayer& L = s->layers[l++];
+  for (int b = 0; b < d.n_blocks; ++b) {
+    const int nk = d.n_kernels[b];
+    for (int r = 0; r < d.repeat[b]; ++r) {
+      if (layers[l].kind == 0) {
+        const SLayer& L = layers[l++];
         const int C = L.cin, K = L.k;
         int c0 = 0;
         for (int g = 0; g < nk; ++g) {
-          const int gc = C / nk + (g == 0 ? C % nk : 0), k = s->d.kernels[b][g];
+          const int gc = C / nk + (g == 0 ? C % nk : 0), k = d.kernels[b][g];
           for (int j = 0; j < k; ++j)
             for (int q = 0; q < gc; ++q) w[L.w + (int64_t)(K - k + j) * C + c0 + q] = h[p + (int64_t)j * gc + q];   // right-aligned taps
           p += (int64_t)k * gc;
@@ -340,7 +253,7 @@ int mww_stream_set_weights(mww_stream* s, const float* h, int64_t n) {
           c0 += gc;
         }
       }
-      const SLayer& P = s->layers[l++];
+      const SLayer& P = layers[l++];
       const int Ci = P.cin, Co = P.cout;
       const float* kern = h + p;
       const float *gamma = kern + (int64_t)Ci * Co, *beta = gamma + Co, *mean = beta + Co, *var = mean + Co;
@@ -355,10 +268,172 @@ int mww_stream_set_weights(mww_stream* s, const float* h, int64_t n) {
   const int64_t nd = (int64_t)net.tf * net.c_last;
   std::memcpy(&w[net.wd], h + p, (size_t)nd * sizeof(float));
   w[net.bd] = h[p + nd];
-  p += nd + 1;
-  if (p != n) return mww::set_error(MWW_ERR_INVALID, "weight layout mismatch");
+  return p + nd + 1;
+}
+
+void MixedNet::launch(const SStores& S, const SCall& a, int grid, hipStream_t hs) const {
+  if (a.rec)
+    hipLaunchKernelGGL(stream_forward_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, hs, net, S, a);
+  else
+    hipLaunchKernelGGL(stream_forward_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, hs, net, S, a);
+}
+
+// ---- the host path of every stream: the front of mww_stream; whatever differs between the models is behind SModel
+int stream_create(mww_ctx* ctx, SModel* m, int rc, mww_stream** out) {
+  mww_stream* s = new mww_stream();
+  s->ctx = ctx;
+  s->model = m;
+  void* stores[MWW_MAX_STORES];
+  int dt[MWW_MAX_STORES];
+  int64_t el[MWW_MAX_STORES];
+  if (!rc) rc = mww::ctx_borrow(ctx, &s->device, &s->stream, stores, dt, el, &s->n_cu);
+  if (!rc && hipSetDevice(s->device) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipSetDevice failed");
+  if (!rc && hipMalloc((void**)&s->w, (size_t)m->n_dev_w * sizeof(float)) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc weights");
+  if (!rc) rc = m->upload();
+  for (int i = 0; i < 2 && !rc; ++i)
+    if (hipMalloc((void**)&s->st[i], (size_t)(m->n_state + 1) * sizeof(float)) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc state");
+  if (!rc) rc = mww_stream_reset(s);
+  if (rc) {
+    mww_stream_destroy(s);
+    return rc;
+  }
+  *out = s;
+  return MWW_OK;
+}
+
+}  // namespace mww_stream_impl
+
+namespace {
+
+int no_int8() {
+  return mww::set_error(MWW_ERR_UNSUPPORTED, "the int8 streaming model covers MixedNet streams only (this is a conv/BN graph stream; "
+                                               "mww_stream_create_convnet_q8 creates one that takes int8 parameters)");
+}
+
+void q8_free(mww_stream* s) {
+  for (void* p : {(void*)s->q8_w, (void*)s->q8_i, (void*)s->q8_lut, (void*)s->q8_st[0], (void*)s->q8_st[1], (void*)s->q8_out,
+                  (void*)s->q8_scratch})
+    if (p) (void)hipFree(p);
+  s->q8_w = nullptr;
+  s->q8_i = nullptr;
+  s->q8_lut = nullptr;
+  s->q8_st[0] = s->q8_st[1] = nullptr;
+  s->q8_out = nullptr;
+  s->q8_scratch = nullptr;
+  s->cap_q8_out = s->cap_q8_scratch = 0;
+  s->q8 = false;
+}
+
+// after a launch: in stream mode the rings this call wrote are the state of the next one
+int64_t finish_call(mww_stream* s, int* cur, int64_t n_out) {
+  SCHK(hipGetLastError());
+  SCHK(hipStreamSynchronize(s->stream));
+  if (s->model->g.mode == MWW_STREAM_MODE_STREAM) *cur ^= 1;
+  return n_out;
+}
+
+int64_t launch_float(mww_stream* s, const SStores& S, SCall& a, int grid, float* rec) {
+  const SModel& m = *s->model;
+  int rc = grow(&s->scratch, &s->cap_scratch, m.scratch_per_wg * grid);
+  if (rc) return rc;
+  a.scratch = s->scratch;
+  a.scratch_per_wg = m.scratch_per_wg;
+  a.rec = rec;
+  a.n_tensors = rec ? m.n_tensors : 0;
+  m.launch(S, a, grid, s->stream);
+  return finish_call(s, &s->cur, a.n_out);
+}
+
+// a tile's int8 buffers sit in LDS when they fit, else in a per-workgroup global scratch
+int64_t launch_q8(mww_stream* s, const SStores& S, SCall& a, int grid) {
+  const SModel& m = *s->model;
+  int rc = grow(&s->q8_out, &s->cap_q8_out, a.n_out);
+  if (rc) return rc;
+  SQ8 q{};
+  q.w = s->q8_w;
+  q.iv = s->q8_i;
+  q.lut = s->q8_lut;
+  q.izp = m.q8_izp;
+  q.in_scale = s->q8_in_scale;
+  q.in_zp = s->q8_in_zp;
+  q.out = s->q8_out;
+  q.st_in = s->q8_st[s->q8_cur];
+  q.st_out = s->q8_st[s->q8_cur ^ 1];
+  q.use_lds = m.q8_tile_bytes <= kMaxLds;
+  size_t lds = 0;
+  if (q.use_lds) {
+    lds = (size_t)m.q8_tile_bytes;
+    if (lds > 64 * 1024) SCHK(hipFuncSetAttribute(m.q8_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  } else {
+    a.scratch_per_wg = (m.q8_tile_bytes + 255) & ~(int64_t)255;
+    if ((rc = grow(&s->q8_scratch, &s->cap_q8_scratch, a.scratch_per_wg * grid))) return rc;
+    q.scratch = s->q8_scratch;
+  }
+  m.launch_q8(S, a, q, grid, lds, s->stream);
+  return finish_call(s, &s->q8_cur, a.n_out);
+}
+
+// one call over a track list: the int8 kernel once int8 parameters are loaded (except for calibration), else the float one
+int64_t run_tracks(mww_stream* s, const mww_window* trk, int64_t n_trk, int64_t* out_off, int64_t n_host_frames, float* rec = nullptr) {
+  if (!s->weights_set && !s->q8) return mww::set_error(MWW_ERR_STATE, "mww_stream_set_weights first");
+  if (rec && s->model->g.mode != MWW_STREAM_MODE_STREAM) return mww::set_error(MWW_ERR_STATE, "calibration runs a stream-mode object");
+  if (rec && !s->weights_set) return mww::set_error(MWW_ERR_STATE, "calibration runs the float weights: mww_stream_set_weights first");
+  SStores S;
+  SCall a;
+  int grid = 0;
+  const int64_t n_out = prepare_call(s, trk, n_trk, out_off, n_host_frames, S, a, &grid);
+  if (n_out <= 0) return n_out;
+  return s->q8 && !rec ? launch_q8(s, S, a, grid) : launch_float(s, S, a, grid, rec);
+}
+
+// the frames of a host call, uploaded as the one track of store kHostStore
+int64_t run_host(mww_stream* s, const float* frames, int64_t n_frames, float* rec = nullptr) {
   SCHK(hipSetDevice(s->device));
-  SCHK(hipMemcpyAsync(s->w, w.data(), (size_t)s->n_dev_w * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  int rc = grow(&s->host_frames, &s->cap_host_frames, (n_frames + 1) * MWW_FEATURE_BINS);
+  if (rc) return rc;
+  if (n_frames) SCHK(hipMemcpyAsync(s->host_frames, frames, (size_t)n_frames * MWW_FEATURE_BINS * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  mww_window w{};
+  w.store = -1;
+  w.copy_rows = (int32_t)n_frames;
+  int64_t off[2];
+  return run_tracks(s, &w, 1, off, n_frames, rec);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* d, mww_stream** out) {
+  if (!ctx || !d || !out) return mww::set_error(MWW_ERR_INVALID, "null argument");
+  *out = nullptr;
+  MixedNet* m = new MixedNet();
+  m->d = *d;
+  return stream_create(ctx, m, m->plan(), out);
+}
+
+void mww_stream_destroy(mww_stream* s) {
+  if (!s) return;
+  (void)hipSetDevice(s->device);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  for (void* p : {(void*)s->w, (void*)s->st[0], (void*)s->st[1], (void*)s->prob, (void*)s->logit, (void*)s->scratch,
+                  (void*)s->tables, (void*)s->host_frames, (void*)s->mtab, (void*)s->rec})
+    if (p) (void)hipFree(p);
+  q8_free(s);
+  delete s->model;
+  delete s;
+}
+
+int64_t mww_stream_num_weights(const mww_stream* s) { return s ? s->model->n_weights : 0; }
+int64_t mww_stream_num_state(const mww_stream* s) { return s ? s->model->n_state : 0; }
+
+int mww_stream_set_weights(mww_stream* s, const float* h, int64_t n) {
+  if (!s || !h) return mww::set_error(MWW_ERR_INVALID, "null argument");
+  const SModel& m = *s->model;
+  if (n != m.n_weights) return mww::set_error(MWW_ERR_INVALID, ("expected " + std::to_string(m.n_weights) + " Keras-order floats").c_str());
+  std::vector<float> w((size_t)m.n_dev_w, 0.f);
+  if (m.fold_weights(h, w.data()) != n) return mww::set_error(MWW_ERR_INVALID, "weight layout mismatch");
+  SCHK(hipSetDevice(s->device));
+  SCHK(hipMemcpyAsync(s->w, w.data(), (size_t)m.n_dev_w * sizeof(float), hipMemcpyHostToDevice, s->stream));
   SCHK(hipStreamSynchronize(s->stream));
   s->weights_set = true;
   return MWW_OK;
@@ -367,58 +442,18 @@ int mww_stream_set_weights(mww_stream* s, const float* h, int64_t n) {
 int mww_stream_reset(mww_stream* s) {
   if (!s) return mww::set_error(MWW_ERR_INVALID, "null argument");
   SCHK(hipSetDevice(s->device));
-  SCHK(hipMemsetAsync(s->st[s->cur], 0, (size_t)(s->n_state + 1) * sizeof(float), s->stream));
-  SCHK(hipStreamSynchronize(s->stream));
-  return s->q8 ? mww::stream_q8_reset(s) : MWW_OK;
-}
-
-int mww_stream_get_state(mww_stream* s, float* h, int64_t n) {
-  if (!s || !h || n != s->n_state) return mww::set_error(MWW_ERR_INVALID, "state size mismatch");
-  SCHK(hipSetDevice(s->device));
-  SCHK(hipMemcpyAsync(h, s->st[s->cur], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  SCHK(hipMemsetAsync(s->st[s->cur], 0, (size_t)(s->model->n_state + 1) * sizeof(float), s->stream));
+  if (s->q8) SCHK(hipMemcpyAsync(s->q8_st[s->q8_cur], s->q8_state0.data(), s->q8_state0.size(), hipMemcpyHostToDevice, s->stream));
   SCHK(hipStreamSynchronize(s->stream));
   return MWW_OK;
 }
 
-// one call over a track list: the int8 kernel once int8 parameters are loaded (except for calibration), else the float one
-static int64_t run_tracks(mww_stream* s, const mww_window* trk, int64_t n_trk, int64_t* out_off, int64_t n_host_frames,
-                          float* rec = nullptr) {
-  if (!s->weights_set && !s->q8) return mww::set_error(MWW_ERR_STATE, "mww_stream_set_weights first");
-  if (rec && s->d.mode != MWW_STREAM_MODE_STREAM) return mww::set_error(MWW_ERR_STATE, "calibration runs a stream-mode object");
-  if (rec && !s->weights_set) return mww::set_error(MWW_ERR_STATE, "calibration runs the float weights: mww_stream_set_weights first");
-  SStores S;
-  SCall a;
-  int grid = 0;
-  const int64_t n_out = prepare_call(s, trk, n_trk, out_off, n_host_frames, S, a, &grid);
-  if (n_out <= 0) return n_out;
-  if (s->graph) {
-    if (s->q8 && !rec) return mww::stream_graph_q8_launch(s, S, a, grid);
-    a.rec = rec;
-    a.n_tensors = rec ? mww::stream_graph_num_tensors(s) : 0;
-    return mww::stream_graph_launch(s, S, a, grid);
-  }
-  if (s->q8 && !rec) return mww::stream_q8_launch(s, S, a, grid);
-  const SNet& net = s->net;
-  const int64_t rows = a.buf_rows;
-  const int64_t per_wg = (((rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS + 2 * rows * net.cmax + 255) & ~(int64_t)255;
-  int rc = grow(&s->scratch, &s->cap_scratch, per_wg * grid);
-  if (rc) return rc;
-  a.w = s->w;
-  a.st_in = s->st[s->cur];
-  a.st_out = s->st[s->cur ^ 1];
-  a.scratch = s->scratch;
-  a.scratch_per_wg = per_wg;
-  if (rec) {
-    a.n_tensors = net.n_layers + 3;
-    a.rec = rec;
-    hipLaunchKernelGGL(stream_forward_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, s->stream, net, S, a);
-  } else {
-    hipLaunchKernelGGL(stream_forward_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, s->stream, net, S, a);
-  }
-  SCHK(hipGetLastError());
+int mww_stream_get_state(mww_stream* s, float* h, int64_t n) {
+  if (!s || !h || n != s->model->n_state) return mww::set_error(MWW_ERR_INVALID, "state size mismatch");
+  SCHK(hipSetDevice(s->device));
+  SCHK(hipMemcpyAsync(h, s->st[s->cur], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   SCHK(hipStreamSynchronize(s->stream));
-  if (s->d.mode == MWW_STREAM_MODE_STREAM) s->cur ^= 1;   // the rings this call wrote are the state of the next one
-  return n_out;
+  return MWW_OK;
 }
 
 int64_t mww_stream_run(mww_stream* s, const mww_window* tracks, int64_t n_tracks, int64_t* out_offsets) {
@@ -430,52 +465,36 @@ int64_t mww_stream_run(mww_stream* s, const mww_window* tracks, int64_t n_tracks
 
 int64_t mww_stream_run_host(mww_stream* s, const float* frames, int64_t n_frames) {
   if (!s || (n_frames && !frames) || n_frames < 0 || n_frames > INT32_MAX) return mww::set_error(MWW_ERR_INVALID, "bad frames");
-  SCHK(hipSetDevice(s->device));
-  int rc = grow(&s->host_frames, &s->cap_host_frames, (n_frames + 1) * MWW_FEATURE_BINS);
-  if (rc) return rc;
-  if (n_frames) SCHK(hipMemcpyAsync(s->host_frames, frames, (size_t)n_frames * MWW_FEATURE_BINS * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  mww_window w{};
-  w.store = -1;
-  w.copy_rows = (int32_t)n_frames;
-  int64_t off[2];
-  return run_tracks(s, &w, 1, off, n_frames);
+  return run_host(s, frames, n_frames);
 }
 
 int mww_stream_num_tensors(const mww_stream* s) {
-  if (s && s->graph) return mww::stream_graph_int8(s) ? mww::stream_graph_num_tensors(s) : mww::stream_graph_no_int8(s);
-  return s ? s->net.n_layers + 3 : 0;
+  if (s && !s->model->int8) return no_int8();
+  return s ? s->model->n_tensors : 0;
 }
 
 int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_frames, float* ranges) {
   if (!s || !ranges || (n_frames && !frames) || n_frames < 0 || n_frames > INT32_MAX) return mww::set_error(MWW_ERR_INVALID, "bad frames");
-  if (s->graph && !mww::stream_graph_int8(s)) return mww::stream_graph_no_int8(s);
-  const int nt = s->graph ? mww::stream_graph_num_tensors(s) : s->net.n_layers + 3;
+  if (!s->model->int8) return no_int8();
+  const int nt = s->model->n_tensors, stride = s->model->g.stride;
   for (int t = 0; t < nt; ++t) {
     ranges[2 * t] = INFINITY;
     ranges[2 * t + 1] = -INFINITY;
   }
   // the input tensor: every frame fed (chunks of s; the trailing L mod s frames are not), in order
-  const int64_t fed = n_frames / s->net.s * s->net.s;
+  const int64_t fed = n_frames / stride * stride;
   for (int64_t i = 0; i < fed * MWW_FEATURE_BINS; ++i) {
     ranges[0] = fminf(ranges[0], frames[i]);
     ranges[1] = fmaxf(ranges[1], frames[i]);
   }
   SCHK(hipSetDevice(s->device));
-  int rc = grow(&s->host_frames, &s->cap_host_frames, (n_frames + 1) * MWW_FEATURE_BINS);
-  if (!rc) rc = grow(&s->rec, &s->cap_rec, (int64_t)2 * s->n_cu * nt * 2);
+  int rc = grow(&s->rec, &s->cap_rec, (int64_t)2 * s->n_cu * nt * 2);   // a launch has at most 2 x CU workgroups
   if (rc) return rc;
-  if (n_frames) SCHK(hipMemcpyAsync(s->host_frames, frames, (size_t)n_frames * MWW_FEATURE_BINS * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  mww_window w{};
-  w.store = -1;
-  w.copy_rows = (int32_t)n_frames;
-  int64_t off[2];
-  const int64_t n_out = run_tracks(s, &w, 1, off, n_frames, s->rec);
+  const int64_t n_out = run_host(s, frames, n_frames, s->rec);
   if (n_out <= 0) return (int)n_out;
-  const int64_t n_tiles = (n_out + s->tile_outputs - 1) / s->tile_outputs;
-  const int grid = (int)(n_tiles < 2 * s->n_cu ? n_tiles : 2 * s->n_cu);
-  std::vector<float> part((size_t)grid * nt * 2);
+  std::vector<float> part((size_t)s->grid * nt * 2);   // one partial row per workgroup of the call just made
   SCHK(hipMemcpy(part.data(), s->rec, part.size() * sizeof(float), hipMemcpyDeviceToHost));
-  for (int g = 0; g < grid; ++g)   // fixed order
+  for (int g = 0; g < s->grid; ++g)   // fixed order
     for (int t = 1; t < nt; ++t) {
       ranges[2 * t] = fminf(ranges[2 * t], part[((size_t)g * nt + t) * 2]);
       ranges[2 * t + 1] = fmaxf(ranges[2 * t + 1], part[((size_t)g * nt + t) * 2 + 1]);
@@ -501,6 +520,75 @@ int mww_stream_set_probs(mww_stream* s, const float* probs, int64_t n) {
   if (n) SCHK(hipMemcpyAsync(s->prob, probs, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
   SCHK(hipStreamSynchronize(s->stream));
   s->n_out = n;
+  return MWW_OK;
+}
+
+// ---- int8 parameters (layout: include/mww.h); the model part says what it expects, validation and upload are here
+int64_t mww_stream_q8_sizes(const mww_stream* s, int64_t* n_ints) {
+  if (!s) return mww::set_error(MWW_ERR_INVALID, "null stream");
+  if (!s->model->int8) return no_int8();
+  if (n_ints) *n_ints = s->model->q8_ni;
+  return s->model->q8_nw;
+}
+
+int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_weights, const int32_t* ints, int64_t n_ints,
+                             float input_scale, const uint8_t* lut) {
+  if (!s || !weights || !ints || !lut) return mww::set_error(MWW_ERR_INVALID, "null argument");
+  const SModel& m = *s->model;
+  if (!m.int8) return no_int8();
+  const int64_t nw = m.q8_nw, ni = m.q8_ni, izp = m.q8_izp;
+  if (n_weights != nw || n_ints != ni)
+    return mww::set_error(MWW_ERR_INVALID, ("expected " + std::to_string(nw) + " int8 weights and " + std::to_string(ni) + " int32 values").c_str());
+  if (!(input_scale > 0.f) || !std::isfinite(input_scale)) return mww::set_error(MWW_ERR_INVALID, "input scale must be positive");
+  for (int t = 0; t < m.n_tensors; ++t)
+    if (ints[izp + t] < -128 || ints[izp + t] > 127) return mww::set_error(MWW_ERR_INVALID, "zero points must lie in [-128, 127]");
+  // q8_requant shifts by at most 31 bits either way: QuantizeMultiplier emits shifts in [-31, 30] and multipliers >= 0,
+  // anything else (from a hand-made .npz) would reach x >> e with e >= 32 on the device
+  auto bad_requant = [&](int64_t at, int64_t cout) {
+    for (int64_t c = 0; c < cout; ++c)
+      if (ints[at + cout + c] < 0 || ints[at + 2 * cout + c] < -31 || ints[at + 2 * cout + c] > 30) return true;
+    return false;
+  };
+  for (const auto& op : m.q8_requant)
+    if (bad_requant(op.first, op.second))
+      return mww::set_error(MWW_ERR_INVALID, "requantization multipliers must be >= 0 and shifts lie in [-31, 30]");
+  q8_free(s);
+  std::vector<int8_t> st0((size_t)m.n_state + 4, 0);
+  m.q8_state0(ints + izp, st0.data());
+  SCHK(hipSetDevice(s->device));
+  SCHK(hipMalloc((void**)&s->q8_w, (size_t)nw + 64));
+  SCHK(hipMalloc((void**)&s->q8_i, (size_t)ni * 4 + 64));
+  SCHK(hipMalloc((void**)&s->q8_lut, 256 + 64));
+  for (int i = 0; i < 2; ++i) SCHK(hipMalloc((void**)&s->q8_st[i], st0.size()));
+  SCHK(hipMemcpyAsync(s->q8_w, weights, (size_t)nw, hipMemcpyHostToDevice, s->stream));
+  SCHK(hipMemcpyAsync(s->q8_i, ints, (size_t)ni * 4, hipMemcpyHostToDevice, s->stream));
+  SCHK(hipMemcpyAsync(s->q8_lut, lut, 256, hipMemcpyHostToDevice, s->stream));
+  SCHK(hipMemcpyAsync(s->q8_st[0], st0.data(), st0.size(), hipMemcpyHostToDevice, s->stream));   // the float state stays as it is
+  SCHK(hipStreamSynchronize(s->stream));
+  s->q8_state0 = st0;
+  s->q8_in_scale = input_scale;
+  s->q8_in_zp = ints[izp];
+  s->q8_cur = 0;
+  s->q8 = true;
+  return MWW_OK;
+}
+
+int mww_stream_read_q8(mww_stream* s, uint8_t* out, int64_t n) {
+  if (s && !s->model->int8) return no_int8();
+  if (!s || !s->q8 || n < 0 || n > s->n_out || n > s->cap_q8_out || (n && !out)) return mww::set_error(MWW_ERR_INVALID, "more outputs requested than the last int8 run produced");
+  if (!n) return MWW_OK;
+  SCHK(hipSetDevice(s->device));
+  SCHK(hipMemcpyAsync(out, s->q8_out, (size_t)n, hipMemcpyDeviceToHost, s->stream));
+  SCHK(hipStreamSynchronize(s->stream));
+  return MWW_OK;
+}
+
+int mww_stream_get_state_q8(mww_stream* s, int8_t* h, int64_t n) {
+  if (s && !s->model->int8) return no_int8();
+  if (!s || !s->q8 || !h || n != s->model->n_state) return mww::set_error(MWW_ERR_INVALID, "state size mismatch (or no int8 parameters)");
+  SCHK(hipSetDevice(s->device));
+  SCHK(hipMemcpyAsync(h, s->q8_st[s->q8_cur], (size_t)n, hipMemcpyDeviceToHost, s->stream));
+  SCHK(hipStreamSynchronize(s->stream));
   return MWW_OK;
 }
 

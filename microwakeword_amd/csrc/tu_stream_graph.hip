@@ -31,6 +31,9 @@
 // writes the final rings into the other half of the double-buffered state.  Every sum runs in a fixed order that does not
 // depend on the partition (taps, then sources, then channels): no atomics, runs are bit-identical, and a position computes
 // the same bits whether its inputs come from a ring or from the tile.
+//
+// Here: the float kernel, the planner (float and byte placement) and the float half of the graph model part, and the two
+// creators.  The host path of the stream is tu_stream.hip; the head and the calibration folds are in stream_common.hip.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,21 +56,12 @@ __global__ void __launch_bounds__(kStreamThreads) stream_graph_kernel(GNet net, 
   const int tid = threadIdx.x;
   __shared__ float red[REC ? 2 * kStreamThreads : 1], rmin[REC ? kMaxGraphTensors : 1], rmax[REC ? kMaxGraphTensors : 1];
   float lmin = INFINITY, lmax = -INFINITY;
-  if (REC) {
-    for (int t = tid; t < a.n_tensors; t += kStreamThreads) {
-      rmin[t] = INFINITY;
-      rmax[t] = -INFINITY;
-    }
-    __syncthreads();
-  }
+  if (REC) rec_init(a, rmin, rmax);
   float* B = a.scratch + (int64_t)blockIdx.x * a.scratch_per_wg;
   for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-    const int sg = a.tile_seg[tile];
-    const int64_t c0 = a.tile_m0[tile] + a.seg_coff[sg];
-    const int64_t c1 = c0 + a.tile_n[tile];
-    const int64_t v_seg = a.seg_v0[sg];
-    const bool last = a.use_state && a.tile_out0[tile] + a.tile_n[tile] == a.n_out;
-    const int64_t N = c1;   // stream mode: the segment is the call, position n is frame n of the call
+    const STile T = tile_of(a, tile);
+    const int64_t c0 = T.c0, c1 = T.c1, v_seg = T.v_seg, N = T.c1;   // positions are frames of the segment
+    const bool last = T.last;
     // ---- gather the spectrogram rows [lo, c1) the tile reads
     int64_t lo = c0 - net.in_reach;
     if (lo < 0) lo = 0;
@@ -144,42 +138,16 @@ __global__ void __launch_bounds__(kStreamThreads) stream_graph_kernel(GNet net, 
     if (f_lo < 0) f_lo = 0;
     const float* fin = B + net.last_buf - f_lo * C;
     const float* hring = a.st_in + net.ring_head;
-    for (int o = tid; o < a.tile_n[tile]; o += kStreamThreads) {
-      const int64_t c = c0 + o;
-      float acc = a.w[net.bd];
-      for (int t = 0; t < TF; ++t) {
-        const int64_t q = c - (TF - 1) + t;
-        const float* wd = a.w + net.wd + (int64_t)t * C;
-        const float* x = q >= 0 ? fin + q * C : hring + (TF - 1 + q) * C;
-        for (int ch = 0; ch < C; ++ch) acc = fmaf(x[ch], wd[ch], acc);
-      }
-      const int64_t g = a.tile_out0[tile] + o;
-      a.logit[g] = acc;
-      a.prob[g] = 1.f / (1.f + expf(-acc));
-      if (REC) {
-        lmin = fminf(lmin, acc);
-        lmax = fmaxf(lmax, acc);
-      }
-    }
+    dense_head<REC>(a, T, fin, C, hring, net.wd, net.bd, C, TF, lmin, lmax);
     if (REC) {
       rec_fold(lmin, lmax, net.n_ops + 1, red, rmin, rmax);
       lmin = INFINITY;
       lmax = -INFINITY;
     }
-    if (last) {
-      for (int idx = tid; idx < (TF - 1) * C; idx += kStreamThreads) {
-        const int64_t q = N - (TF - 1) + idx / C;
-        const int ch = idx % C;
-        a.st_out[net.ring_head + idx] = q >= 0 ? fin[q * C + ch] : hring[(TF - 1 + q) * C + ch];
-      }
-    }
+    if (last) head_ring_store(a.st_out + net.ring_head, T, fin, C, hring, C, TF);
     __syncthreads();   // the next tile reuses the scratch
   }
-  if (REC)
-    for (int t = tid; t < a.n_tensors; t += kStreamThreads) {
-      a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2] = rmin[t];
-      a.rec[((int64_t)blockIdx.x * a.n_tensors + t) * 2 + 1] = rmax[t];
-    }
+  if (REC) rec_flush(a, rmin, rmax);
 }
 
 inline int bad(int op, const char* field, const std::string& why) {
@@ -216,18 +184,22 @@ struct Arena {
   }
 };
 
-// topology, weight / ring layout, reach of every tensor, scratch plan and barrier flags from the description
-int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_graph* g) {
+}  // namespace
+
+namespace mww_stream_impl {
+
+// topology, weight / ring layout, reach of every tensor, scratch plan, barrier flags and call geometry from the description
+int Graph::plan(const mww_convnet_desc& d, int mode) {
   if (mode != MWW_STREAM_MODE_STREAM && mode != MWW_STREAM_MODE_NON_STREAM) return bad(-1, "mode", "must be stream or non_stream");
   if (d.n_ops <= 0 || d.n_ops > MWW_MAX_GRAPH_OPS) return bad(-1, "n_ops", "must be 1.." + std::to_string(MWW_MAX_GRAPH_OPS));
   if (d.frames <= 0) return bad(-1, "frames", "must be positive");
   if (d.head_attention) return bad(-1, "head_attention", "is outside the streaming graph vocabulary");
   if (d.head_pool) return bad(-1, "head_pool", "is outside the streaming graph vocabulary");
-  const int n = d.n_ops, tile = s->tile_outputs;
+  const int n = d.n_ops, tile = g.tile_outputs;
   std::vector<int> len((size_t)n), ch((size_t)n), reach((size_t)n, 0), last_use((size_t)n, -1);
-  g->ops.assign((size_t)n, GOp{});
-  g->groups.assign((size_t)n, 1);
-  g->src.assign((size_t)n * MWW_MAX_OP_SOURCES, -1);
+  ops.assign((size_t)n, GOp{});
+  groups.assign((size_t)n, 1);
+  src.assign((size_t)n * MWW_MAX_OP_SOURCES, -1);
   int64_t kw = 0, dw = 0, st = 0;
   for (int i = 0; i < n; ++i) {
     const mww_conv_bn_op& o = d.ops[i];
@@ -241,7 +213,7 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
     if (o.filters <= 0 || o.filters > 1024) return bad(i, "filters", "must be 1..1024");
     if (o.bn_groups <= 0 || o.filters % o.bn_groups) return bad(i, "bn_groups", "must divide the filters");
     if (o.n_src <= 0 || o.n_src > MWW_MAX_OP_SOURCES) return bad(i, "n_src", "must be 1..3");
-    GOp& L = g->ops[(size_t)i];
+    GOp& L = ops[(size_t)i];
     L.n_src = o.n_src;
     L.k = o.kernel;
     L.d = o.dilation;
@@ -258,7 +230,7 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
       const int cn = o.src_cn[j] ? o.src_cn[j] : sc - o.src_c0[j];
       if (o.src_c0[j] < 0 || cn <= 0 || o.src_c0[j] + cn > sc) return bad(i, "src_c0 / src_cn", "is not a slice of the source");
       L.src_C[j] = sc;
-      g->src[(size_t)i * MWW_MAX_OP_SOURCES + j] = src;
+      this->src[(size_t)i * MWW_MAX_OP_SOURCES + j] = src;
       L.src_c0[j] = o.src_c0[j];
       L.src_cn[j] = cn;
       cin += cn;
@@ -268,14 +240,13 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
     len[(size_t)i] = tin - L.R;
     ch[(size_t)i] = o.filters;
     L.cin = cin;
-    g->groups[(size_t)i] = o.bn_groups;
+    groups[(size_t)i] = o.bn_groups;
     const int slots = o.bn_groups > 1 ? o.bn_groups : o.filters;
     kw += (int64_t)o.kernel * cin * o.filters + 4 * slots;   // kernel, gamma, beta, moving mean, moving variance
     L.w = dw; dw += (int64_t)o.kernel * cin * o.filters;
     L.b = dw; dw += o.filters;
     L.ring = st; st += (int64_t)L.R * cin;
   }
-  GNet& net = g->net;
   net.n_ops = n;
   net.tf = len[(size_t)n - 1];
   net.c_last = ch[(size_t)n - 1];
@@ -288,7 +259,7 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
   reach[(size_t)n - 1] = net.tf - 1;
   int in_reach = 0;
   for (int i = n - 1; i >= 0; --i) {
-    const GOp& L = g->ops[(size_t)i];
+    const GOp& L = ops[(size_t)i];
     for (int j = 0; j < L.n_src; ++j) {
       int& r = d.ops[i].src[j] < 0 ? in_reach : reach[(size_t)d.ops[i].src[j]];
       r = std::max(r, reach[(size_t)i] + L.R);
@@ -347,152 +318,84 @@ int plan_graph(const mww_convnet_desc& d, int mode, mww_stream* s, mww_stream_gr
     pn.last_buf = buf[(size_t)n - 1];
     return ar.top;
   };
-  g->qops = g->ops;   // before the float placement: src_C still counts channels
-  g->scratch_per_wg = (place(g->ops, net, false) + 255) & ~(int64_t)255;
+  qops = ops;   // before the float placement: src_C still counts channels
+  scratch_per_wg = (place(ops, net, false) + 255) & ~(int64_t)255;
   // int8 form: weights [Co][k][sources, each r4(cn)], int32 values bias / multiplier / shift [Co] per op, then the Dense
-  g->qnet = net;
+  qnet = net;
   int64_t qw = 0, qi = 0;
   for (int i = 0; i < n; ++i) {
-    GOp& L = g->qops[(size_t)i];
+    GOp& L = qops[(size_t)i];
     int64_t kp = 0;
     for (int j = 0; j < L.n_src; ++j) kp += r4(L.src_cn[j]);
     L.w = qw; qw += (int64_t)L.cout * L.k * kp;
     L.b = qi; qi += 3 * (int64_t)L.cout;
+    q8_requant.emplace_back(L.b, L.cout);
   }
-  g->qnet.wd = qw; qw += (int64_t)net.tf * r4(net.c_last);
-  g->qnet.bd = qi; qi += 3;
-  g->q_izp = qi; qi += n + 2;
-  g->q_nw = qw;
-  g->q_ni = qi;
-  g->q_tile_bytes = place(g->qops, g->qnet, true);
-  // what the shared call preparation reads (stream_common.hip.h): stride 1, halo of the input, first window's last frame
-  s->net = SNet{};
-  s->net.s = 1;
-  s->net.k1 = 1;
-  s->net.reach1 = in_reach;
-  s->net.tf = net.tf;
-  s->net.c_last = net.c_last;
-  s->d = mww_stream_desc{};
-  s->d.stride = 1;
-  s->d.t_final = net.tf;
-  s->d.frames = d.frames;
-  s->d.mode = mode;
-  s->j0 = mode == MWW_STREAM_MODE_NON_STREAM ? d.frames - 1 : 0;
-  s->n_weights = kw;
-  s->n_dev_w = dw;
-  s->n_state = st;
+  qnet.wd = qw; qw += (int64_t)net.tf * r4(net.c_last);
+  qnet.bd = qi; qi += 3;
+  q8_requant.emplace_back(qnet.bd, 1);
+  q8_izp = qi; qi += n + 2;
+  q8_nw = qw;
+  q8_ni = qi;
+  q8_tile_bytes = place(qops, qnet, true);
+  g.frames = d.frames;
+  g.mode = mode;
+  g.reach = in_reach;
+  g.j0 = mode == MWW_STREAM_MODE_NON_STREAM ? d.frames - 1 : 0;   // the first window's last frame
+  n_weights = kw;
+  n_dev_w = dw;
+  n_state = st;
+  n_tensors = n + 2;
   return MWW_OK;
 }
 
-}  // namespace
-
-namespace mww {
-
-int stream_graph_no_int8(const mww_stream*) {
-  return set_error(MWW_ERR_UNSUPPORTED, "the int8 streaming model covers MixedNet streams only (this is a conv/BN graph stream; "
-                                          "mww_stream_create_convnet_q8 creates one that takes int8 parameters)");
+int Graph::upload() {
+  int rc = upload_table(&d_ops, ops);
+  if (!rc && int8) rc = upload_table(&d_qops, qops);
+  net.ops = d_ops;
+  qnet.ops = d_qops;
+  return rc;
 }
 
-bool stream_graph_int8(const mww_stream* s) { return s->graph && s->graph->int8; }
-
-int stream_graph_num_tensors(const mww_stream* s) { return s->graph->net.n_ops + 2; }
-
-void stream_graph_free(mww_stream* s) {
-  if (!s->graph) return;
-  if (s->graph->d_ops) (void)hipFree(s->graph->d_ops);
-  if (s->graph->d_qops) (void)hipFree(s->graph->d_qops);
-  delete s->graph;
-  s->graph = nullptr;
-}
-
-int stream_graph_set_weights(mww_stream* s, const float* h, int64_t n) {
+int64_t Graph::fold_weights(const float* h, float* w) const {
   // Keras get_weights() order (inception.py:233-338): per convolution kernel [k,1,Cin,F], then gamma, beta, moving_mean,
   // moving_variance [slots] (slots = SSN groups, or F for BatchNormalization); dense [T_f*C,1], bias.  The normalisation
   // (moving statistics, eps 1e-3, channel c -> slot c mod g: sub_spectral_normalization.py:38-62) is folded here, once.
-  const mww_stream_graph* g = s->graph;
-  std::vector<float> w((size_t)s->n_dev_w, 0.f);
   int64_t p = 0;
-  for (size_t i = 0; i < g->ops.size(); ++i) {
-    const GOp& L = g->ops[i];
-    const int grp = g->groups[i], Co = L.cout, slots = grp > 1 ? grp : Co;
+  for (size_t i = 0; i < ops.size(); ++i) {
+    const GOp& L = ops[i];
+    const int grp = groups[i], Co = L.cout, slots = grp > 1 ? grp : Co;
     const int64_t rows = (int64_t)L.k * L.cin;
     const float *kern = h + p, *gamma = kern + rows * Co, *beta = gamma + slots, *mean = beta + slots, *var = mean + slots;
     for (int co = 0; co < Co; ++co) {
       const int sl = grp > 1 ? co % grp : co;
       const double sc = (double)gamma[sl] / std::sqrt((double)var[sl] + kBnEps);
-      for (int64_t r = 0; r < rows; ++r) w[(size_t)(L.w + r * Co + co)] = (float)((double)kern[r * Co + co] * sc);
-      w[(size_t)(L.b + co)] = (float)((double)beta[sl] - (double)mean[sl] * sc);
+      for (int64_t r = 0; r < rows; ++r) w[L.w + r * Co + co] = (float)((double)kern[r * Co + co] * sc);
+      w[L.b + co] = (float)((double)beta[sl] - (double)mean[sl] * sc);
     }
     p += rows * Co + 4 * slots;
   }
-  const int64_t nd = (int64_t)g->net.tf * g->net.c_last;
-  std::memcpy(&w[(size_t)g->net.wd], h + p, (size_t)nd * sizeof(float));
-  w[(size_t)g->net.bd] = h[p + nd];
-  p += nd + 1;
-  if (p != n) return set_error(MWW_ERR_INVALID, "weight layout mismatch");
-  SCHK(hipSetDevice(s->device));
-  SCHK(hipMemcpyAsync(s->w, w.data(), (size_t)s->n_dev_w * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  SCHK(hipStreamSynchronize(s->stream));
-  s->weights_set = true;
-  return MWW_OK;
+  const int64_t nd = (int64_t)net.tf * net.c_last;
+  std::memcpy(&w[net.wd], h + p, (size_t)nd * sizeof(float));
+  w[net.bd] = h[p + nd];
+  return p + nd + 1;
 }
 
-int64_t stream_graph_launch(mww_stream* s, const SStores& S, SCall& a, int grid) {
-  const mww_stream_graph* g = s->graph;
-  int rc = grow(&s->scratch, &s->cap_scratch, g->scratch_per_wg * grid);
-  if (rc) return rc;
-  a.w = s->w;
-  a.st_in = s->st[s->cur];
-  a.st_out = s->st[s->cur ^ 1];
-  a.scratch = s->scratch;
-  a.scratch_per_wg = g->scratch_per_wg;
+void Graph::launch(const SStores& S, const SCall& a, int grid, hipStream_t hs) const {
   if (a.rec)
-    hipLaunchKernelGGL(stream_graph_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, s->stream, g->net, S, a);
+    hipLaunchKernelGGL(stream_graph_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, hs, net, S, a);
   else
-    hipLaunchKernelGGL(stream_graph_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, s->stream, g->net, S, a);
-  SCHK(hipGetLastError());
-  SCHK(hipStreamSynchronize(s->stream));
-  if (s->d.mode == MWW_STREAM_MODE_STREAM) s->cur ^= 1;   // the rings this call wrote are the state of the next one
-  return a.n_out;
+    hipLaunchKernelGGL(stream_graph_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, hs, net, S, a);
 }
 
-}  // namespace mww
+}  // namespace mww_stream_impl
 
 static int create_graph_stream(mww_ctx* ctx, const mww_convnet_desc* d, int32_t mode, bool int8, mww_stream** out) {
   if (!ctx || !d || !out) return mww::set_error(MWW_ERR_INVALID, "null argument");
   *out = nullptr;
-  mww_stream* s = new mww_stream();
-  s->ctx = ctx;
-  s->tile_outputs = kGraphTileOutputs;
-  s->graph = new mww_stream_graph();
-  mww_stream_graph* g = s->graph;
-  g->int8 = int8;
-  int rc = plan_graph(*d, mode, s, g);
-  void* stores[MWW_MAX_STORES];
-  int dt[MWW_MAX_STORES];
-  int64_t el[MWW_MAX_STORES];
-  if (!rc) rc = mww::ctx_borrow(ctx, &s->device, &s->stream, stores, dt, el, &s->n_cu);
-  if (!rc && hipSetDevice(s->device) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipSetDevice failed");
-  if (!rc && hipMalloc((void**)&s->w, (size_t)s->n_dev_w * sizeof(float)) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc weights");
-  if (!rc && hipMalloc((void**)&g->d_ops, g->ops.size() * sizeof(GOp) + 64) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc ops");
-  if (!rc && hipMemcpy(g->d_ops, g->ops.data(), g->ops.size() * sizeof(GOp), hipMemcpyHostToDevice) != hipSuccess)
-    rc = mww::set_error(MWW_ERR_HIP, "hipMemcpy ops");
-  g->net.ops = g->d_ops;
-  if (int8) {
-    if (!rc && hipMalloc((void**)&g->d_qops, g->qops.size() * sizeof(GOp) + 64) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc ops");
-    if (!rc && hipMemcpy(g->d_qops, g->qops.data(), g->qops.size() * sizeof(GOp), hipMemcpyHostToDevice) != hipSuccess)
-      rc = mww::set_error(MWW_ERR_HIP, "hipMemcpy ops");
-    g->qnet.ops = g->d_qops;
-  }
-  for (int i = 0; i < 2 && !rc; ++i)
-    if (hipMalloc((void**)&s->st[i], (size_t)(s->n_state + 1) * sizeof(float)) != hipSuccess) rc = mww::set_error(MWW_ERR_HIP, "hipMalloc state");
-  if (!rc) rc = mww_stream_reset(s);
-  if (rc) {
-    mww_stream_destroy(s);
-    return rc;
-  }
-  *out = s;
-  return MWW_OK;
+  Graph* m = new Graph();
+  m->int8 = int8;
+  return stream_create(ctx, m, m->plan(*d, mode), out);
 }
 
 extern "C" int mww_stream_create_convnet(mww_ctx* ctx, const mww_convnet_desc* d, int32_t mode, mww_stream** out) {

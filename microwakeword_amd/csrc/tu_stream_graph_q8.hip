@@ -15,50 +15,26 @@
 // reset holds zero points, so it contributes what the fold assumes.  Every sum runs in a fixed order and every op is an
 // exact integer function of its inputs: no atomics, outputs and rings are bit-identical from run to run and equal to the
 // NumPy restatement (tests/quant_graph_oracle.py).
+//
+// Here: the kernel (int8 weights per op [Co][k][source 0: r4(cn_0)] ... [source n-1], then the Dense [T_f][r4(C_last)]) and
+// the int8 half of the graph model part.  The head is the shared one of stream_common.hip.h, the host path tu_stream.hip.
 #include <hip/hip_runtime.h>
 
-#include "int8_ops.hip.h"
 #include "stream_graph.hip.h"
 
 using namespace mww_stream_impl;
 
-namespace mww {
-int stream_q8_reset(mww_stream* s);
-void stream_q8_free(mww_stream* s);
-}  // namespace mww
-
 namespace {
 
-constexpr int64_t kMaxLds = 160 * 1024;   // LDS of a gfx950 CU
-constexpr float kInv255 = (float)(1.0 / 255.0);   // inference.py:170 1 / 255 as float32
-
-struct GQ8 {
-  const int8_t* w;       // int8 weights: per op [Co][k][source 0: r4(cn_0)] ... [source n-1], then the Dense [T_f][r4(C_last)]
-  const int32_t* iv;     // per op bias (input zero point folded), multiplier, shift [Co] each; the Dense's three; the zero points
-  const uint8_t* lut;    // [256]: logit q + 128 -> output uint8
-  int64_t izp;           // offset of the n_ops + 2 tensor zero points in iv
-  float in_scale;
-  int in_zp;
-  uint8_t* out;          // [n_out] uint8 outputs
-  const int8_t* st_in;
-  int8_t* st_out;
-  int8_t* scratch;       // global form: per-workgroup tiles
-  int64_t scratch_per_wg;
-  int use_lds;
-};
-
-__global__ void __launch_bounds__(kStreamThreads) stream_graph_q8_kernel(GNet net, SStores S, SCall a, GQ8 q) {
+__global__ void __launch_bounds__(kStreamThreads) stream_graph_q8_kernel(GNet net, SStores S, SCall a, SQ8 q) {
   HIP_DYNAMIC_SHARED(int, gq8_lds)
   const int tid = threadIdx.x;
-  int8_t* B = q.use_lds ? reinterpret_cast<int8_t*>(gq8_lds) : q.scratch + (int64_t)blockIdx.x * q.scratch_per_wg;
+  int8_t* B = q.use_lds ? reinterpret_cast<int8_t*>(gq8_lds) : q.scratch + (int64_t)blockIdx.x * a.scratch_per_wg;
   const int32_t* zps = q.iv + q.izp;
   for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-    const int sg = a.tile_seg[tile];
-    const int64_t c0 = a.tile_m0[tile] + a.seg_coff[sg];
-    const int64_t c1 = c0 + a.tile_n[tile];
-    const int64_t v_seg = a.seg_v0[sg];
-    const bool last = a.use_state && a.tile_out0[tile] + a.tile_n[tile] == a.n_out;
-    const int64_t N = c1;   // stream mode: the segment is the call, position n is frame n of the call
+    const STile T = tile_of(a, tile);
+    const int64_t c0 = T.c0, c1 = T.c1, v_seg = T.v_seg, N = T.c1;   // positions are frames of the segment
+    const bool last = T.last;
     // ---- gather + quantize the spectrogram rows [lo, c1) the tile reads, four bins to a word
     int64_t lo = c0 - net.in_reach;
     if (lo < 0) lo = 0;
@@ -150,136 +126,36 @@ __global__ void __launch_bounds__(kStreamThreads) stream_graph_q8_kernel(GNet ne
     if (f_lo < 0) f_lo = 0;
     const int8_t* fin = B + net.last_buf - f_lo * pc;
     const int8_t* hring = q.st_in + net.ring_head;
-    {
-      const int32_t bias = q.iv[net.bd], mul = q.iv[net.bd + 1], shf = q.iv[net.bd + 2];
-      const int zo = zps[net.n_ops + 1];
-      for (int o = tid; o < a.tile_n[tile]; o += kStreamThreads) {
-        const int64_t c = c0 + o;
-        int acc = bias;
-        for (int t = 0; t < TF; ++t) {
-          const int64_t p = c - (TF - 1) + t;
-          const int8_t* wd = q.w + net.wd + (int64_t)t * pc;
-          if (p >= 0) {
-            const int* x = reinterpret_cast<const int*>(fin + p * pc);
-            const int* w = reinterpret_cast<const int*>(wd);
-            for (int r = 0; r < pc / 4; ++r) acc = mww_sdot4(x[r], w[r], acc);
-          } else {
-            const int8_t* x = hring + (TF - 1 + p) * C;
-            for (int ch = 0; ch < C; ++ch) acc += (int)x[ch] * (int)wd[ch];
-          }
-        }
-        const int lq = q8_requant(acc, mul, shf, zo, -128);
-        const uint8_t u = q.lut[lq + 128];
-        const int64_t g = a.tile_out0[tile] + o;
-        q.out[g] = u;
-        a.logit[g] = (float)lq;
-        a.prob[g] = (float)u * kInv255;
-      }
-    }
-    if (last) {
-      for (int idx = tid; idx < (TF - 1) * C; idx += kStreamThreads) {
-        const int64_t p = N - (TF - 1) + idx / C;
-        const int ch = idx % C;
-        q.st_out[net.ring_head + idx] = p >= 0 ? fin[p * pc + ch] : hring[(TF - 1 + p) * C + ch];
-      }
-    }
+    dense_head_q8(a, q, T, fin, pc, hring, net.wd, net.bd, zps[net.n_ops + 1], C, TF);
+    if (last) head_ring_store(q.st_out + net.ring_head, T, fin, pc, hring, C, TF);
     __syncthreads();   // the next tile reuses the buffers
   }
 }
 
 }  // namespace
 
-namespace mww {
+namespace mww_stream_impl {
 
-int64_t stream_graph_q8_sizes(const mww_stream* s, int64_t* n_ints) {
-  if (n_ints) *n_ints = s->graph->q_ni;
-  return s->graph->q_nw;
-}
-
-int stream_graph_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_weights, const int32_t* ints, int64_t n_ints,
-                               float input_scale, const uint8_t* lut) {
-  const mww_stream_graph* g = s->graph;
-  const int n = g->net.n_ops;
-  const int64_t nw = g->q_nw, ni = g->q_ni, izp = g->q_izp;
-  if (n_weights != nw || n_ints != ni)
-    return set_error(MWW_ERR_INVALID, ("expected " + std::to_string(nw) + " int8 weights and " + std::to_string(ni) + " int32 values").c_str());
-  if (!(input_scale > 0.f) || !std::isfinite(input_scale)) return set_error(MWW_ERR_INVALID, "input scale must be positive");
-  for (int t = 0; t < n + 2; ++t)
-    if (ints[izp + t] < -128 || ints[izp + t] > 127) return set_error(MWW_ERR_INVALID, "zero points must lie in [-128, 127]");
-  // q8_requant shifts by at most 31 bits either way (see mww_stream_set_quantized of a MixedNet stream)
-  auto bad_requant = [&](int64_t at, int64_t cout) {
-    for (int64_t c = 0; c < cout; ++c)
-      if (ints[at + cout + c] < 0 || ints[at + 2 * cout + c] < -31 || ints[at + 2 * cout + c] > 30) return true;
-    return false;
-  };
-  bool bad = bad_requant(g->qnet.bd, 1);
-  for (int i = 0; i < n && !bad; ++i) bad = bad_requant(g->qops[(size_t)i].b, g->qops[(size_t)i].cout);
-  if (bad) return set_error(MWW_ERR_INVALID, "requantization multipliers must be >= 0 and shifts lie in [-31, 30]");
-  stream_q8_free(s);
-  // rings at reset: real zero, i.e. the zero point of the tensor each ring column holds
-  std::vector<int8_t> st0((size_t)s->n_state + 4, 0);
+// rings at reset: real zero, i.e. the zero point of the tensor each ring column holds
+void Graph::q8_state0(const int32_t* zp, int8_t* st0) const {
+  const int n = net.n_ops;
   for (int i = 0; i < n; ++i) {
-    const GOp& L = g->qops[(size_t)i];
+    const GOp& L = qops[(size_t)i];
     for (int r = 0; r < L.R; ++r) {
       int64_t at = L.ring + (int64_t)r * L.cin;
       for (int j = 0; j < L.n_src; ++j) {
-        const int8_t zp = (int8_t)ints[izp + 1 + g->src[(size_t)i * MWW_MAX_OP_SOURCES + j]];   // source -1: tensor 0, the input
-        for (int c = 0; c < L.src_cn[j]; ++c) st0[(size_t)at++] = zp;
+        const int8_t z = (int8_t)zp[1 + src[(size_t)i * MWW_MAX_OP_SOURCES + j]];   // source -1: tensor 0, the input
+        for (int c = 0; c < L.src_cn[j]; ++c) st0[at++] = z;
       }
     }
   }
-  for (int64_t k = 0; k < (int64_t)(g->net.tf - 1) * g->net.c_last; ++k) st0[(size_t)(g->net.ring_head + k)] = (int8_t)ints[izp + n];
-  SCHK(hipSetDevice(s->device));
-  SCHK(hipMalloc((void**)&s->q8_w, (size_t)nw + 64));
-  SCHK(hipMalloc((void**)&s->q8_i, (size_t)ni * 4 + 64));
-  SCHK(hipMalloc((void**)&s->q8_lut, 256 + 64));
-  for (int i = 0; i < 2; ++i) SCHK(hipMalloc((void**)&s->q8_st[i], st0.size()));
-  SCHK(hipMemcpyAsync(s->q8_w, weights, (size_t)nw, hipMemcpyHostToDevice, s->stream));
-  SCHK(hipMemcpyAsync(s->q8_i, ints, (size_t)ni * 4, hipMemcpyHostToDevice, s->stream));
-  SCHK(hipMemcpyAsync(s->q8_lut, lut, 256, hipMemcpyHostToDevice, s->stream));
-  SCHK(hipStreamSynchronize(s->stream));
-  s->q8_state0 = st0;
-  s->q8_in_scale = input_scale;
-  s->q8_in_zp = ints[izp];
-  s->q8_izp = izp;
-  s->q8_cur = 0;
-  s->q8 = true;
-  return stream_q8_reset(s);
+  for (int64_t k = 0; k < (int64_t)(net.tf - 1) * net.c_last; ++k) st0[net.ring_head + k] = (int8_t)zp[n];
 }
 
-int64_t stream_graph_q8_launch(mww_stream* s, const SStores& S, SCall& a, int grid) {
-  const mww_stream_graph* g = s->graph;
-  GQ8 q{};
-  q.w = s->q8_w;
-  q.iv = s->q8_i;
-  q.lut = s->q8_lut;
-  q.izp = s->q8_izp;
-  q.in_scale = s->q8_in_scale;
-  q.in_zp = s->q8_in_zp;
-  const int64_t n_out = a.n_out;
-  int rc = grow(&s->q8_out, &s->cap_q8_out, n_out);
-  if (rc) return rc;
-  q.out = s->q8_out;
-  q.st_in = s->q8_st[s->q8_cur];
-  q.st_out = s->q8_st[s->q8_cur ^ 1];
-  const int64_t bytes = g->q_tile_bytes;
-  q.use_lds = bytes <= kMaxLds;
-  size_t lds = 0;
-  if (q.use_lds) {
-    lds = (size_t)bytes;
-    if (lds > 64 * 1024)
-      SCHK(hipFuncSetAttribute((const void*)stream_graph_q8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  } else {
-    const int64_t per_wg = (bytes + 255) & ~(int64_t)255;
-    if ((rc = grow(&s->q8_scratch, &s->cap_q8_scratch, per_wg * grid))) return rc;
-    q.scratch = s->q8_scratch;
-    q.scratch_per_wg = per_wg;
-  }
-  hipLaunchKernelGGL(stream_graph_q8_kernel, dim3(grid), dim3(kStreamThreads), lds, s->stream, g->qnet, S, a, q);
-  SCHK(hipGetLastError());
-  SCHK(hipStreamSynchronize(s->stream));
-  if (s->d.mode == MWW_STREAM_MODE_STREAM) s->q8_cur ^= 1;
-  return n_out;
+const void* Graph::q8_kernel() const { return (const void*)stream_graph_q8_kernel; }
+
+void Graph::launch_q8(const SStores& S, const SCall& a, const SQ8& q, int grid, size_t lds, hipStream_t hs) const {
+  hipLaunchKernelGGL(stream_graph_q8_kernel, dim3(grid), dim3(kStreamThreads), lds, hs, qnet, S, a, q);
 }
 
-}  // namespace mww
+}  // namespace mww_stream_impl

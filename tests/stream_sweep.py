@@ -30,7 +30,7 @@ import streaming_checks as sc
 import streaming_oracle as so
 
 SEED = 2026
-KMAX_LDS = 160 * 1024   # kMaxLds of csrc/tu_stream_q8.hip
+KMAX_LDS = 160 * 1024   # kMaxLds of csrc/stream_common.hip.h
 TILE = 256              # kTileOutputs of csrc/stream_common.hip.h
 CHAIN_MAX_RING = 40     # one-output chains run where the longest ring is at most this (they cost one call per output)
 
@@ -68,7 +68,7 @@ def r4(n):
 
 
 def tile_bytes(desc):
-    """bytes of one int8 tile (stream_q8_launch restated): the gathered input rows and two activation buffers"""
+    """bytes of one int8 tile (MixedNet::plan restated): the gathered input rows and two activation buffers"""
     rows = TILE + reach1_of(desc)
     return ((rows - 1) * desc["stride"] + desc["conv1_kernel"]) * 40 + 2 * rows * r4(cmax_of(desc))
 
