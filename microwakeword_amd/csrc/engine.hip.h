@@ -1,5 +1,6 @@
-// What the two engines of libmww_hip.so share: the context, its per-layer / per-op records, error reporting, profiling brackets and
-// the helpers of mww_lib.hip that the conv/BN graph engine (graph_engine.hip) calls.  Internal: the ABI is include/mww.h.
+// What the units of libmww_hip.so's training side share: the core of a context (mww_ctx), the interface of its model part (Model:
+// block_engine.hip, graph_engine.hip), the tensor record of both, error reporting, profiling brackets and the helpers of mww_lib.hip
+// that the engines call.  Internal: the ABI is include/mww.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,37 +12,6 @@
 #include "../../include/mww.h"
 #include "kernels_bwd.hip.h"    // GradReduceArgs, XGather
 #include "kernels_data.hip.h"   // AssembleArgs
-
-// the fp32 block backward runs as the wide-workgroup form (option "bwd_wide"; kernels_bwdw.hip.h) unless told otherwise
-// options "conv1_x6" (the conv1 weight gradient in the first block's backward kernel) and "conv1_x6_fwd" (the first convolution
-// itself): see common.hip.h "fp32-grade products on the bf16 matrix pipe".  Same-session A/B at B = 1024 (profiles/round6_conv1_x6_ab.txt):
-// backward 49.7 -> 44.0 us; forward 33.5 -> 36-37 us (the matrix pipe's 6.5 us are paid back by the slicing of x and W1 in a
-// launch whose workgroups see three tiles each) - so the default is backward only.
-#ifndef MWW_CONV1_X6_DEFAULT
-#define MWW_CONV1_X6_DEFAULT 1
-#endif
-#ifndef MWW_CONV1_X6_FWD_DEFAULT
-#define MWW_CONV1_X6_FWD_DEFAULT 0
-#endif
-#ifndef MWW_BWD_FIRST_WIDE_DEFAULT   // option "bwd_first_wide"
-#define MWW_BWD_FIRST_WIDE_DEFAULT 0
-#endif
-#ifndef MWW_BWD_WIDE_DEFAULT
-#define MWW_BWD_WIDE_DEFAULT 1
-#endif
-// option "dp_commit_late": the fp32 backward kernels commit the dp rows of a tile behind the depthwise recompute instead of with the
-// input rows in P0 (kernels_bwdw.hip.h bwd_blockw_kernel, bwd_first_body.inc).  Bit-identical results; the default of each kernel
-// family is the order that won its same-session A/B (profiles/dp_commit_late_ab.txt): the middle blocks and the first
-// block gain 0.5-1 us per launch, the last block's launch (its group B is p_k, the dense kernel's rows and dz) reads the same either way.
-#ifndef MWW_DP_COMMIT_LATE_BLOCK_DEFAULT   // bwd_blockw_kernel, middle blocks
-#define MWW_DP_COMMIT_LATE_BLOCK_DEFAULT 1
-#endif
-#ifndef MWW_DP_COMMIT_LATE_LAST_DEFAULT    // bwd_blockw_kernel, the last block (LAST)
-#define MWW_DP_COMMIT_LATE_LAST_DEFAULT 0
-#endif
-#ifndef MWW_DP_COMMIT_LATE_FIRST_DEFAULT   // bwd_first_kernel (x6 form), bwd_firstw_kernel
-#define MWW_DP_COMMIT_LATE_FIRST_DEFAULT 1
-#endif
 
 namespace mww {
 
@@ -55,18 +25,19 @@ int fail(int code, const std::string& msg);   // sets mww_last_error(), returns 
     if (e_ != hipSuccess)                                                                         \
       return fail(MWW_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                \
   } while (0)
+#define MWW_TRY(call)                                                                             \
+  do {                                                                                            \
+    int rc_ = (call);                                                                             \
+    if (rc_) return rc_;                                                                          \
+  } while (0)
 
-struct Layer {
-  int cin, cout, k, tin, tout;
-  // offsets into the flat parameter / state vectors
-  int64_t o_dw_w, o_dw_b, o_pw_w, o_gamma, o_beta, o_mm, o_mv;
-  // device buffers
+// the device buffers every BN'd tensor of either engine owns: block k of a MixedNet (Layer) or op i of a graph (GOp)
+struct Tensor {
   float* p = nullptr;          // pre-BN output [maxB][tout][cout]
   float* g = nullptr;          // gradient at the BN output (masked by ReLU) [maxB][tout][cout]
-  float* stat_part = nullptr;  // [grid_fwd][2][cout]
-  float* gstat_part = nullptr; // [grid_bwd or grid_head][2][cout]
-  float* grad_part = nullptr;  // [grid_bwd][params of the block (+ conv1 for block 0)]
-  int grad_part_stride = 0;
+  float* stat_part = nullptr;  // [rows_fwd][2][cout]
+  float* gstat_part = nullptr; // [rows_bwd][2][cout]
+  float* grad_part = nullptr;  // [rows][the weights this tensor's backward launch produces]
   float* bn = nullptr;         // 9 x cout: scale, shift, mean, rstd, c1, mg, mgx, (spare x2)
   // statistics hand-over without finalize launches (common.hip.h): [parity][kStatRows][2][cout] for the forward
   // sums (x, x^2) and the backward sums (g, g*xhat); *_cur = rows the latest producer launch added to
@@ -75,9 +46,19 @@ struct Layer {
   double* facc_cur = nullptr;
   double* gacc_cur = nullptr;
 };
+// everything but p and g (whose sizes and owners are the engine's business) / every buffer that is set
+int tensor_alloc(Tensor* t, int cout, size_t rows_fwd, size_t rows_bwd, size_t grad_part);
+void tensor_free(Tensor* t);
+
+struct Layer : Tensor {
+  int cin, cout, k, tin, tout;
+  // offsets into the flat parameter / state vectors
+  int64_t o_dw_w, o_dw_b, o_pw_w, o_gamma, o_beta, o_mm, o_mv;
+  int grad_part_stride = 0;    // grad_part: [grid_bwd][params of the block (+ conv1 for block 0)]
+};
 
 // one conv -> BN/SSN -> ReLU op of a mww_convnet_desc graph (kernels_graph.hip.h)
-struct GOp {
+struct GOp : Tensor {
   int n_src = 0, src[MWW_MAX_OP_SOURCES] = {0, 0, 0}, toff[MWW_MAX_OP_SOURCES] = {0, 0, 0};
   int sc0[MWW_MAX_OP_SOURCES] = {0, 0, 0}, scn[MWW_MAX_OP_SOURCES] = {0, 0, 0};   // channel slice of each source
   bool src_first[MWW_MAX_OP_SOURCES] = {false, false, false}, src_last[MWW_MAX_OP_SOURCES] = {false, false, false};   // this op's place among the consumers of that slice (backward order)
@@ -86,19 +67,12 @@ struct GOp {
   int res_src = -1, res_drop = 0;     // residual branch added before this op's activation
   std::vector<int> adders;           // (residual ops) the ops that add this one
   int64_t o_w = 0, o_gamma = 0, o_beta = 0, o_mm = 0, o_mv = 0;
-  float *p = nullptr, *g = nullptr, *stat_part = nullptr, *gstat_part = nullptr, *grad_part = nullptr, *bn = nullptr;
   bool needs_dx = false;
   bool twin_next = false;     // op i+1 is an independent op of the same shape: the pair shares its launches
   int planes = 1, pc = 0;     // > 1: every consumer reads one of `planes` equal channel slices of pc channels: the tensors p / g may be
                               // stored one plane per slice (kernels_graph.hip.h GSrc; "graph_planar")
   size_t lds_fwd = 0, lds_dx = 0, lds_wg = 0;
-  // statistics hand-over (kernels_graph.hip.h): [parity][kStatRows][2][cout] accumulator rows of the forward / backward sums,
-  // *_cur = the rows the latest producer launch added to; first_consumer = the lowest op index that reads this op
-  double* facc[2] = {nullptr, nullptr};
-  double* gacc[2] = {nullptr, nullptr};
-  double* facc_cur = nullptr;
-  double* gacc_cur = nullptr;
-  int first_consumer = -1;
+  int first_consumer = -1;    // the lowest op index that reads this op: its launch folds the forward statistics
 };
 
 struct ProfileEntry {
@@ -122,47 +96,60 @@ struct RcclApi {
 constexpr int kRing = 8;
 constexpr int kDenseChunks = 32;  // batch chunks of the dense-weight gradient reduction
 
+// the last tensor as the dense-weight gradient reads it (kernels_head.hip.h DenseGradArgs): BN'd p_L (bf16: stored so), the
+// dropout keep-scale and the residual branch added before the last ReLU, where the model has them
+struct DenseSource {
+  const float *p = nullptr, *scale = nullptr, *shift = nullptr, *keep = nullptr, *rp = nullptr, *rscale = nullptr, *rshift = nullptr;
+  int rT = 0, rdrop = 0, bf16 = 0;
+};
+
+enum OptionOwner { OPT_CORE, OPT_BLOCK, OPT_GRAPH };
+// one option of mww_set_option: lo <= hi: accepted range (hi_cu > 0: up to hi_cu workgroups per CU) and what a value outside it reports
+struct OptionRow { const char* name; OptionOwner owner; int64_t lo, hi; int hi_cu; const char* range_error; };
+
+// what mww_debug_read copies out: n floats at src; stored as bf16 / as `planes` planes of pc channels, pstride floats apart
+struct DebugTensor { const float* src = nullptr; int64_t n = 0; bool bf16 = false; int planes = 1, pc = 0, cout = 0; long long pstride = 0; };
+
+struct BnSlots { int64_t o_gamma, o_beta, o_mv; int n; };   // a BN's (or a bias's) places in the flat vectors
+
+// The model part of a context: the topology, its tensors and options, and the launch sequences of one engine
+// (block_engine.hip: the specialised MixedNet kernels; graph_engine.hip: conv/BN graphs).  The destructor frees its buffers.
+struct Model {
+  Model() = default;
+  Model(const Model&) = delete;   // (it owns device buffers)
+  virtual ~Model() {}
+  // after the device is open: the offsets into the flat vectors (sets P, S, o_dense_*, t_last, c_last, dwd_stride) and the
+  // default grids; then, behind alloc_common, the model's own buffers (bn: the slots init_defaults marks)
+  virtual int layout(mww_ctx* c) = 0;
+  virtual int alloc(mww_ctx* c, std::vector<BnSlots>* bn) = 0;
+  virtual int enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) = 0;
+  virtual int enqueue_backward(mww_ctx* c, int B, bool fuse_adam) = 0;
+  virtual std::vector<int> stat_widths() const = 0;   // channels of every BN'd tensor, in sync-BN order
+  virtual bool lazy_ok(const mww_ctx* c, int B) const = 0;   // may this batch stay descriptor-only ("fused_input")?
+  virtual bool step_counter(unsigned long long* n) { return false; }   // the counter this step's dropout mask is drawn from, if one is
+  // the model's word of the hipGraph cache key; *handover: the statistics hand-over is possible (its parities are baked into a capture)
+  virtual unsigned replay_key(bool* handover) const = 0;
+  virtual bool eval_fold_cached() const { return false; }   // the eval BN fold survives from batch to batch of one evaluation
+  virtual int debug_tensor(mww_ctx* c, const char* name, int B, DebugTensor* t) = 0;   // 1: found, 0: not one of mine, < 0: error
+  virtual int set_option(mww_ctx* c, const OptionRow& o, int64_t v) = 0;   // (rows of the other engine: no-op)
+  virtual int set_dropout_mask(mww_ctx* c, const uint8_t* keep, int B);
+};
+
 }  // namespace mww
 
+// The core of a context: one device + one HIP stream + the flat vectors, mailboxes, step state and options no engine owns.
 struct mww_ctx {
-  mww_mixednet_desc d;
+  mww::Model* model = nullptr;
+  int frames = 0, max_batch = 0;
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   int n_cu = 256;
-  int grid_fwd = 0, grid_bwd = 0, grid_head = 0;
-  bool conv1_x6 = MWW_CONV1_X6_DEFAULT != 0;   // conv1 weight gradient as six bf16 slice products per fp32 product (stride-1 shapes, fp32 mode)
-  bool conv1_x6_fwd = MWW_CONV1_X6_FWD_DEFAULT != 0;
-  bool bwd_first_wide = MWW_BWD_FIRST_WIDE_DEFAULT != 0;   // stride-1 first block (3-tap conv1) with conv1_x6: the 512-thread form of its backward kernel   // ... and the first convolution of the forward kernel
-  bool bwd_wide = MWW_BWD_WIDE_DEFAULT != 0;   // fp32 block backward kernels: 512 threads per workgroup (bwd_blockw_kernel) or 256 (bwd_block_kernel)
-  int dp_commit_late = -1;   // -1: the per-family defaults above; 0 / 1: every kernel that has both orders
+  int grid_head = 0;
   int64_t P = 0, S = 0;
-  int64_t o_conv1 = 0, o_dense_w = 0, o_dense_b = 0;
+  int64_t o_dense_w = 0, o_dense_b = 0;
   int t_last = 0, c_last = 0, dwd_stride = 0;
-  std::vector<mww::Layer> L;
-  // conv/BN graph models (mww_create_convnet)
-  bool generic = false;
-  std::vector<mww::GOp> G;
-  float dropout = 0.f;
-  float* keep = nullptr;            // [max_batch][t_last*c_last] dropout keep-scale
-  bool keep_explicit = false;       // set by mww_set_dropout_mask: do not regenerate
-  unsigned long long dropout_seed = 0x5EEDull, dropout_counter = 0;
-  bool head2 = false;               // attention / pooled head (ghead_att_kernel)
-  bool head_att = false;
-  int head_pool = 0;
-  int64_t o_att = 0;
-  float *hact = nullptr, *watt_part = nullptr;
-  size_t lds_head2 = 0;
-  float *ones = nullptr, *zeros = nullptr;   // [256] constants standing in for the BN arrays of ops without a BN
-  int grid_g = 0;
-  int g_cap_fwd = 4, g_cap_bwd = 4;   // "graph_fwd_wg_per_cu" / "graph_bwd_wg_per_cu" (g_role_grid)
   int metric_launches = 0;   // launches of the step being enqueued that carry the metric role (kernels_head.hip.h MetricState: one writer)
-  bool g_planar = true;   // "graph_planar": tensors read only as equal channel slices are stored one plane per slice
-  bool g_static = true;   // "graph_static_shapes": ops whose shape has a compile-time instantiation (MWW_G_SHAPES) use it
-  int g_chunks = 0;   // "graph_frame_chunks" (g_chunks())
-  int g_dgrad_share = 50;   // "graph_dgrad_share"
-  bool grid_g_auto = true;   // per-launch grids from the kernel's occupancy (g_role_grid); "grid_graph" > 0 fixes one grid
-  std::map<std::pair<const void*, size_t>, int> g_occ;   // workgroups per CU of (kernel, dynamic LDS)
   // data-parallel exchange hook (mww_set_allreduce_hook)
   mww_allreduce_fn hook = nullptr;
   void* hook_user = nullptr;
@@ -179,8 +166,6 @@ struct mww_ctx {
                                             // bucket overlapped with the backward tail - slower at W = 1, unmeasured at W > 1, so not the default)
   float* bn_state = nullptr;
   float *x = nullptr, *y = nullptr, *sw = nullptr, *z = nullptr, *prob = nullptr, *dz = nullptr, *loss_part = nullptr;
-  float* a0 = nullptr;     // relu(conv1(x)) [max_batch][Ta][conv1_filters]: written by the training forward, read by bwd_first_kernel
-  float* gbuf[2] = {nullptr, nullptr};   // the two buffers the blocks' g_k take in turn (block k uses gbuf[k & 1])
   float* dwd_part = nullptr;
   mww::MetricState* metrics = nullptr;
   // "mailboxes": pinned host memory mapped into the device address space.  The host writes one
@@ -205,9 +190,9 @@ struct mww_ctx {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool side_pending = false;
   int asm_split = 2;        // workgroups per window of the assembly kernel ("assemble_split" option)
-  // "fused_input" option (default on, specialised MixedNet kernels only): mww_assemble_batch only uploads the window
-  // descriptors; the first block's forward / backward kernels gather their rows from the stores themselves
-  // (kernels_fwd.hip.h XGather).  x is materialised (assemble_kernel) only for a reader that needs it.
+  // "fused_input" option (default on): mww_assemble_batch only uploads the window descriptors where the model's first
+  // kernels gather their rows from the stores themselves (kernels_fwd.hip.h XGather; Model::lazy_ok).  x is materialised
+  // (assemble_kernel) only for a reader that needs it.
   bool fused_input = true;
   bool x_lazy = false;
   int lazy_slot = -1;
@@ -217,13 +202,10 @@ struct mww_ctx {
   // "bn_inline" option (default on): BN statistics travel through replicated fp64 accumulator rows and are folded by
   // their first consumer instead of by a finalize launch (off with sync-BN: the sums must be exchanged in between)
   bool bn_inline = true;
-  bool g_role_split = true;   // launches that hold several roles (twin ops, weight + data gradient) divide the workgroups between the
-                              // roles instead of multiplying them ("graph_role_split"; needs the statistics hand-over: the partial-row
-                              // readers assume one row count per tensor)
-  bool g_inline_ok = false;   // conv/BN graph: every op is a convolution with a BatchNorm and no residual branch => hand-over possible
   int fpar = 0, gpar = 0;   // accumulator parity of the next training forward / backward
   bool tail_pending = false, tail_metrics = false;   // dense gradient (+ metrics) ride in the first backward launch
   bool tail_in_reduce = false;   // ... or, with the statistics hand-over, in the gradient-reduction launch ("tail_roles" option)
+  mww::DenseSource tail_src;     // what that dense gradient reads
   bool tail_roles = true;
   void* store[MWW_MAX_STORES] = {};
   int store_dtype[MWW_MAX_STORES] = {};
@@ -231,18 +213,13 @@ struct mww_ctx {
   int64_t step = 0;
   int have_batch = 0, have_targets = 0;
   bool use_graphs = false, profile = false;
-  bool profile_split = false;   // "profile_split" option: keep weight- and data-gradient of a graph op in separate launches
   bool use_side = false;  // "side_stream" option: metric update + dense-weight gradient on a second stream (measured: co-running
                           // kernels displace workgroups of the occupancy-tuned block kernels; serial is 8 us/step faster)
-  bool pw_bf16 = false;   // 1x1 contractions with bf16 operands (mww_set_option "pointwise_bf16")
-  bool st_bf16 = false;   // p_k / g_k stored as bf16 ("storage_bf16", implies pointwise_bf16: BASELINE configs[4])
   bool bce_clipped = false;   // "bce_from_logits" 0: probability-form BCE with the Keras clip instead of the logits form (common.hip.h)
   bool bn_eval_ready = false;   // inside mww_evaluate_windows: the moving statistics are folded once, not per batch
-  int ablate = 0;
-  unsigned long long* phase_clk = nullptr;   // profiling: [2*layers][2048 workgroups][kClkSlots]
   std::vector<mww::ProfileEntry> prof;
-  // cached graphs keyed by (B, flags)
-  struct GraphEntry { int B, flags, mail, par; hipGraphExec_t exec; };
+  // cached graphs keyed by (B, flags, mailbox, the core's and the model's option / parity words)
+  struct GraphEntry { int B, flags, mail; unsigned core, model; hipGraphExec_t exec; };
   std::vector<GraphEntry> graphs;
 };
 
@@ -274,36 +251,34 @@ struct Launcher {
 enum { BN_SCALE = 0, BN_SHIFT, BN_MEAN, BN_RSTD, BN_C1, BN_MG, BN_MGX };
 
 // ---- mww_lib.hip
+template <typename T>
+int dev_alloc(T** p, size_t n) {
+  HIPCHK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
+  HIPCHK(hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(T)));
+  return MWW_OK;
+}
+int create_context(Model* m, int frames, int max_batch, int device, void* stream, mww_ctx** out);   // takes the model over, also when it fails
 const float* mail_hyper(mww_ctx* c);
 int materialise_x(mww_ctx* c);   // descriptor-only batch -> x, for readers outside the first block's kernels
 XGather x_gather(mww_ctx* c);
-int enqueue_side_work(mww_ctx* c, int B, bool metrics, bool loss, const float* p_last, const float* scale, const float* shift, const float* keep);
+int enqueue_side_work(mww_ctx* c, int B, bool metrics, bool loss, const DenseSource& last);
 // sync-BN: the partial rows (or their sum over the ranks) the finalize kernel should read
 struct StatSource { const float* part; int G; float inv_n; float dscale; };
 int exchange_stats(mww_ctx* c, Launcher& lp, const char* what, int layer, const float* part, int G, int C, int bwd, float local_inv_n, StatSource* out);
 int enqueue_grad_assembly(mww_ctx* c, int B, GradReduceArgs& ga, bool fuse_adam, int64_t lo = 0, int64_t hi = -1, bool last_range = true);
+// the block engine's classifier head and the launch that opens its backward pass (BN_L's backward finalize + dense gradient +
+// metrics): their kernels share kernels_head.hip.h / kernels_tail.hip.h with the core's own, which one unit alone can include
+int head_frame_limit(int ch);   // final frames one head workgroup covers at `ch` channels
+int enqueue_block_head(mww_ctx* c, int B, const Tensor& last, int T, int C, bool bf16, const BnFoldArgs& fold, const StatAcc& gacc, bool loss, bool metrics);
+int enqueue_head_tail(mww_ctx* c, int B, const BnBwdFinalizeArgs& fin);
+
+// ---- block_engine.hip: MixedNets on the specialised block kernels (mww_create)
+bool shape_supported(const mww_mixednet_desc& d, std::string* why, bool bf16 = false);
+int plan_mixednet(const mww_mixednet_desc& d, Model** out);
 
 // ---- graph_engine.hip: conv/BN graph models (mww_create_convnet)
-// gfx950 has 160 KB of LDS per CU; tiles above the 64 KB default need the function attribute
-constexpr size_t kMaxDynLds = 144 * 1024;
-// planar tensors (GOp::planes) lie kPlanePad floats further apart than their size: without it two planes lie a multiple of 4-8 KB
-// apart - max_batch x T x pc x 4 bytes - and twin ops that walk their planes in step hit the same HBM channels: the 16-channel
-// twin backward launch went 45 -> 55 us
-constexpr long long kPlanePad = 1088;   // 17 x 256 bytes
-// planes of op `o`'s tensors in effect (1 = interleaved) and the distance between two planes in floats
-int g_planes(const mww_ctx* c, const GOp& o);
-long long g_pstride(const mww_ctx* c, const GOp& o);
-bool g_stem_gathers(const mww_ctx* c);
 // validates a graph description and plans it: ops with their LDS sizes, gradient routing, twins and planar tensors, the offsets
-// into the flat parameter / state vectors (P, S: the sizes so far - the head's parameters follow)
-struct GPlan {
-  std::vector<GOp> ops;
-  int64_t P = 0, S = 0;
-  bool inline_ok = false;   // statistics hand-over possible (mww_ctx::g_inline_ok)
-  int chunks = 0;           // default of "graph_frame_chunks"
-};
-int g_plan_convnet(const mww_convnet_desc& d, GPlan* plan);
-int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics);
-int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam);
+// into the flat parameter / state vectors
+int plan_convnet(const mww_convnet_desc& d, Model** out);
 
 }  // namespace mww

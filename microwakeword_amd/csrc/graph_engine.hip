@@ -5,6 +5,7 @@
 #define MWW_BLOCK_TU 1        // the non-template kernels of the block-kernel headers belong to mww_lib.hip,
 #define MWW_GRAPH_HOST_TU 1   // those of the graph kernel headers to tu_graph.hip
 #include <cstring>
+#include <map>
 
 #include "engine.hip.h"
 #include "graph_launch.hip.h"
@@ -14,6 +15,73 @@ namespace mww {
 static_assert(kGMaxSrc == MWW_MAX_OP_SOURCES, "GOp holds MWW_MAX_OP_SOURCES sources");
 
 namespace {
+
+// gfx950 has 160 KB of LDS per CU; tiles above the 64 KB default need the function attribute
+constexpr size_t kMaxDynLds = 144 * 1024;
+// planar tensors (GOp::planes) lie kPlanePad floats further apart than their size: without it two planes lie a multiple of 4-8 KB
+// apart - max_batch x T x pc x 4 bytes - and twin ops that walk their planes in step hit the same HBM channels: the 16-channel
+// twin backward launch went 45 -> 55 us
+constexpr long long kPlanePad = 1088;   // 17 x 256 bytes
+
+struct GraphModel : Model {
+  std::vector<GOp> G;
+  int64_t plan_P = 0, plan_S = 0;   // sizes of the flat vectors behind the ops (the head's parameters follow)
+  float dropout = 0.f;
+  float* keep = nullptr;            // [max_batch][t_last*c_last] dropout keep-scale
+  bool keep_explicit = false;       // set by mww_set_dropout_mask: do not regenerate
+  unsigned long long dropout_seed = 0x5EEDull, dropout_counter = 0;
+  bool head2 = false;               // attention / pooled head (ghead_att_kernel)
+  bool head_att = false;
+  int head_pool = 0;
+  int64_t o_att = 0;
+  float *hact = nullptr, *watt_part = nullptr;
+  size_t lds_head2 = 0;
+  float *ones = nullptr, *zeros = nullptr;   // [256] constants standing in for the BN arrays of ops without a BN
+  int grid_g = 0;
+  int g_cap_fwd = 4, g_cap_bwd = 4;   // "graph_fwd_wg_per_cu" / "graph_bwd_wg_per_cu" (g_role_grid)
+  bool g_planar = true;   // "graph_planar": tensors read only as equal channel slices are stored one plane per slice
+  bool g_static = true;   // "graph_static_shapes": ops whose shape has a compile-time instantiation (MWW_G_SHAPES) use it
+  int frame_chunks = 0;   // "graph_frame_chunks" (g_chunks())
+  int g_dgrad_share = 50;   // "graph_dgrad_share"
+  bool grid_g_auto = true;   // per-launch grids from the kernel's occupancy (g_role_grid); "grid_graph" > 0 fixes one grid
+  std::map<std::pair<const void*, size_t>, int> g_occ;   // workgroups per CU of (kernel, dynamic LDS)
+  bool g_role_split = true;   // launches that hold several roles (twin ops, weight + data gradient) divide the workgroups between the
+                              // roles instead of multiplying them ("graph_role_split"; needs the statistics hand-over: the partial-row
+                              // readers assume one row count per tensor)
+  bool g_inline_ok = false;   // every op is a convolution with a BatchNorm and no residual branch => hand-over possible
+  bool profile_split = false;   // "profile_split" option: keep weight- and data-gradient of an op in separate launches
+
+  ~GraphModel() override {
+    for (GOp& o : G) tensor_free(&o);
+    void* own[] = {keep, hact, watt_part, ones, zeros};
+    for (void* p : own) if (p) (void)hipFree(p);
+  }
+  int layout(mww_ctx* c) override;
+  int alloc(mww_ctx* c, std::vector<BnSlots>* bn) override;
+  int enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) override;
+  int enqueue_backward(mww_ctx* c, int B, bool fuse_adam) override;
+  std::vector<int> stat_widths() const override {
+    std::vector<int> w;
+    for (const GOp& o : G) w.push_back(o.cout);
+    return w;
+  }
+  // (the stem's launches check their own grids and write x out themselves if a workgroup would own too many windows)
+  bool lazy_ok(const mww_ctx* c, int) const override;
+  bool step_counter(unsigned long long* n) override {
+    if (!(dropout > 0.f) || keep_explicit) return false;
+    *n = dropout_counter++;
+    return true;
+  }
+  unsigned replay_key(bool* handover) const override {
+    *handover = g_inline_ok && !profile_split;
+    return (g_role_split ? 1 : 0) | (grid_g_auto ? 2 : 0) | (frame_chunks << 2) | (g_cap_fwd << 5) | (g_cap_bwd << 9) | (g_dgrad_share << 13);
+  }
+  int debug_tensor(mww_ctx* c, const char* name, int B, DebugTensor* t) override;
+  int set_option(mww_ctx* c, const OptionRow& o, int64_t v) override;
+  int set_dropout_mask(mww_ctx* c, const uint8_t* keep, int B) override;
+};
+
+GraphModel& gm(const mww_ctx* c) { return *static_cast<GraphModel*>(c->model); }
 
 bool g_width_supported(int n) {
 #define X(N) if (n == N) return true;
@@ -52,8 +120,8 @@ int g_chunk_in(const GOp& o, int t) { return (t - 1) * o.stride + (o.k - 1) * o.
 int g_chunks(const mww_ctx* c, const GOp& o, bool inl, bool backward, int* Tc) {
   *Tc = o.tout;
   // the data gradient is only chunked without a halo (k = 1); forward convolution and a weight gradient on its own take any k
-  if (!inl || c->g_chunks == 0 || o.kind != MWW_OP_CONV || o.tout < 32 || (backward && o.needs_dx && o.k != 1)) return 1;
-  int S = c->g_chunks;
+  if (!inl || gm(c).frame_chunks == 0 || o.kind != MWW_OP_CONV || o.tout < 32 || (backward && o.needs_dx && o.k != 1)) return 1;
+  int S = gm(c).frame_chunks;
   if (S == 1) {
     for (S = 1; S < 4; ++S) {
       const int t = (o.tout + S - 1) / S, ti = g_chunk_in(o, t);
@@ -66,23 +134,19 @@ int g_chunks(const mww_ctx* c, const GOp& o, bool inl, bool backward, int* Tc) {
   return (S - 1) * *Tc < o.tout ? S : 1;   // (every chunk non-empty)
 }
 
-}  // namespace
-
-int g_planes(const mww_ctx* c, const GOp& o) { return (c->g_planar && o.planes > 1) ? o.planes : 1; }
-long long g_pstride(const mww_ctx* c, const GOp& o) { return (long long)c->d.max_batch * o.tout * o.pc + kPlanePad; }
-
-namespace {
+int g_planes(const mww_ctx* c, const GOp& o) { return (gm(c).g_planar && o.planes > 1) ? o.planes : 1; }
+long long g_pstride(const mww_ctx* c, const GOp& o) { return (long long)c->max_batch * o.tout * o.pc + kPlanePad; }
 
 // the static shape of op `o`, or 0
 int g_shape_id(const mww_ctx* c, const GOp& o) {
-  if (!c->g_static || o.kind != MWW_OP_CONV || o.dil != 1 || o.stride != 1 || o.res_src >= 0 || o.n_src < 1) return 0;
+  if (!gm(c).g_static || o.kind != MWW_OP_CONV || o.dil != 1 || o.stride != 1 || o.res_src >= 0 || o.n_src < 1) return 0;
   if (o.tin > kGTmax || o.tout > kGTmax) return 0;   // a window's rows travel in a fixed set of registers (GSliceRegs)
   int C[kGMaxSrc] = {0, 0, 0}, L[kGMaxSrc] = {0, 0, 0};
   for (int i = 0; i < o.n_src; ++i) {
     if (o.src[i] < 0) {
       C[i] = L[i] = MWW_FEATURE_BINS;
     } else {
-      const GOp& pr = c->G[o.src[i]];
+      const GOp& pr = gm(c).G[o.src[i]];
       if (pr.res_src >= 0) return 0;
       C[i] = o.scn[i];
       L[i] = g_planes(c, pr) > 1 ? o.scn[i] : pr.cout;   // (a plane of a planar producer is a whole tensor of its own)
@@ -97,30 +161,27 @@ int g_shape_id(const mww_ctx* c, const GOp& o) {
   return 0;
 }
 
-}  // namespace
-
 // The stem of a conv/BN graph can read a descriptor-only batch in place ("fused_input", kernels_graph.hip.h XG): exactly one
 // op reads the spectrogram, as its only source, and its shape has a gathering instantiation.
 bool g_stem_gathers(const mww_ctx* c) {
-  if (!c->generic || !c->fused_input || c->d.frames > kGXRows) return false;
+  if (!c->fused_input || c->frames > kGXRows) return false;
   int readers = 0, stem = -1;
-  for (size_t i = 0; i < c->G.size(); ++i)
-    for (int s = 0; s < c->G[i].n_src; ++s)
-      if (c->G[i].src[s] < 0) {
+  for (size_t i = 0; i < gm(c).G.size(); ++i)
+    for (int s = 0; s < gm(c).G[i].n_src; ++s)
+      if (gm(c).G[i].src[s] < 0) {
         ++readers;
         stem = (int)i;
       }
   if (readers != 1) return false;
-  const GOp& o = c->G[stem];
-  if (o.n_src != 1 || o.toff[0] != 0 || o.tin != c->d.frames) return false;
+  const GOp& o = gm(c).G[stem];
+  if (o.n_src != 1 || o.toff[0] != 0 || o.tin != c->frames) return false;
   const int shape = g_shape_id(c, o);
 #define XS(ID, N) if (shape == ID && o.cout == N) return true;
   MWW_G_SHAPE_XG(XS)
 #undef XS
   return false;
 }
-
-namespace {
+bool GraphModel::lazy_ok(const mww_ctx* c, int) const { return g_stem_gathers(c); }
 
 bool g_reads_lazy_x(const mww_ctx* c, const GSrc* src, int n) {
   if (!c->x_lazy) return false;
@@ -129,7 +190,7 @@ bool g_reads_lazy_x(const mww_ctx* c, const GSrc* src, int n) {
   return false;
 }
 
-GLaunch g_launch_ctx(mww_ctx* c) { return GLaunch{c->stream, c->n_cu, c->g_dgrad_share, &c->g_occ}; }
+GLaunch g_launch_ctx(mww_ctx* c) { return GLaunch{c->stream, c->n_cu, gm(c).g_dgrad_share, &gm(c).g_occ}; }
 
 // result of a launcher of graph_launch.hip.h -> MWW_* code
 int g_rc(int r, const char* no_kernel = "conv width not instantiated") {
@@ -165,18 +226,18 @@ float* gbn_slot(GOp& o, int i) { return o.bn + (size_t)i * o.cout; }
 
 // source i of op `oi` as the kernels see it; `backward` adds the gradient routing flags
 GSrc g_make_src(mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
-  GOp& o = c->G[oi];
+  GOp& o = gm(c).G[oi];
   GSrc s;
   memset(&s, 0, sizeof(s));
   s.toff = o.toff[i];
   if (o.src[i] < 0) {
     s.p = c->x;
-    s.T = c->d.frames;
+    s.T = c->frames;
     s.C = s.ld = s.sld = MWW_FEATURE_BINS;
     s.flags = GSRC_IDENTITY;
     return s;
   }
-  GOp& pr = c->G[o.src[i]];
+  GOp& pr = gm(c).G[o.src[i]];
   s.p = pr.p;
   if (pr.norm == MWW_NORM_BN) {
     s.scale = gbn_slot(pr, BN_SCALE);
@@ -184,10 +245,10 @@ GSrc g_make_src(mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
     s.mean = gbn_slot(pr, BN_MEAN);
     s.rstd = gbn_slot(pr, BN_RSTD);
   } else {   // a bias (or nothing) instead of a BN: y = p * 1 + bias
-    s.scale = c->ones;
-    s.shift = pr.norm == MWW_NORM_BIAS ? c->params + pr.o_beta : c->zeros;
-    s.mean = c->zeros;
-    s.rstd = c->ones;
+    s.scale = gm(c).ones;
+    s.shift = pr.norm == MWW_NORM_BIAS ? c->params + pr.o_beta : gm(c).zeros;
+    s.mean = gm(c).zeros;
+    s.rstd = gm(c).ones;
   }
   s.g = pr.g;
   s.gstat_part = pr.gstat_part;
@@ -209,7 +270,7 @@ GSrc g_make_src(mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
   }
   if (pr.act == MWW_ACT_LINEAR) s.flags |= GSRC_LINEAR;
   if (pr.res_src >= 0) {
-    GOp& rr = c->G[pr.res_src];
+    GOp& rr = gm(c).G[pr.res_src];
     s.rp = rr.p;
     s.rscale = gbn_slot(rr, BN_SCALE);
     s.rshift = gbn_slot(rr, BN_SHIFT);
@@ -231,7 +292,7 @@ GBnBwd g_make_bnbwd(mww_ctx* c, GOp& o) {
   y.g = o.g;
   y.p = o.p;
   if (o.norm != MWW_NORM_BN) {   // dp = g
-    y.mean = c->zeros; y.rstd = c->ones; y.c1 = c->ones; y.mg = c->zeros; y.mgx = c->zeros;
+    y.mean = gm(c).zeros; y.rstd = gm(c).ones; y.c1 = gm(c).ones; y.mg = gm(c).zeros; y.mgx = gm(c).zeros;
   } else {
     y.mean = gbn_slot(o, BN_MEAN); y.rstd = gbn_slot(o, BN_RSTD); y.c1 = gbn_slot(o, BN_C1); y.mg = gbn_slot(o, BN_MG); y.mgx = gbn_slot(o, BN_MGX);
   }
@@ -242,7 +303,7 @@ GBnBwd g_make_bnbwd(mww_ctx* c, GOp& o) {
 }
 
 GDwArgs g_make_dw(mww_ctx* c, int oi, int B, bool backward, bool inl = false) {
-  GOp& o = c->G[oi];
+  GOp& o = gm(c).G[oi];
   GDwArgs a;
   memset(&a, 0, sizeof(a));
   a.src = g_make_src(c, oi, 0, backward, inl);
@@ -260,20 +321,21 @@ GDwArgs g_make_dw(mww_ctx* c, int oi, int B, bool backward, bool inl = false) {
 
 }  // namespace
 
-int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) {
+int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) {
+  GraphModel& m = *this;
   if (c->x_lazy && !g_stem_gathers(c)) {   // (an option changed since the batch was assembled)
     int rcx = materialise_x(c);
     if (rcx) return rcx;
   }
   Launcher lp{c};
-  const int n = (int)c->G.size();
-  const int gg = std::min(B, c->grid_g);
+  const int n = (int)m.G.size();
+  const int gg = std::min(B, m.grid_g);
   // statistics hand-over instead of finalize launches (kernels_graph.hip.h)
-  const bool inl = training && c->bn_inline && c->g_inline_ok && !(c->hook && c->sync_bn) && !c->profile_split;
-  const bool pick = inl && c->grid_g_auto;   // per-launch grids (g_role_grid)
-  auto leader = [&](int oi) { return (oi > 0 && c->G[oi - 1].twin_next) ? oi - 1 : oi; };   // first op of the launch op oi rides in
+  const bool inl = training && c->bn_inline && m.g_inline_ok && !(c->hook && c->sync_bn) && !m.profile_split;
+  const bool pick = inl && m.grid_g_auto;   // per-launch grids (g_role_grid)
+  auto leader = [&](int oi) { return (oi > 0 && m.G[oi - 1].twin_next) ? oi - 1 : oi; };   // first op of the launch op oi rides in
   auto fold_of = [&](int pi, bool publish) {
-    GOp& pr = c->G[pi];
+    GOp& pr = m.G[pi];
     GFoldFwd f;
     memset(&f, 0, sizeof(f));
     f.acc = pr.facc_cur;
@@ -293,7 +355,7 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
     return f;
   };
   for (int i = 0; i < n; ++i) {
-    GOp& o = c->G[i];
+    GOp& o = m.G[i];
     if (!training && o.norm == MWW_NORM_BN) {
       GBnEvalArgs e{c->params + o.o_gamma, c->params + o.o_beta, c->bn_state + o.o_mm, c->bn_state + o.o_mv,
                     gbn_slot(o, BN_SCALE), gbn_slot(o, BN_SHIFT), o.cout, o.groups};
@@ -303,17 +365,17 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
     }
     if (o.kind == MWW_OP_DEPTHWISE) {
       GDwArgs dw = g_make_dw(c, i, B, false);
-      if (inl && o.src[0] >= 0 && c->G[o.src[0]].norm == MWW_NORM_BN && c->G[o.src[0]].first_consumer == i)
+      if (inl && o.src[0] >= 0 && m.G[o.src[0]].norm == MWW_NORM_BN && m.G[o.src[0]].first_consumer == i)
         dw.fold = fold_of(o.src[0], true);
       lp.begin("dw_fwd", i);
       // (no statistics leave this launch: its grid is free to follow its occupancy even without the hand-over)
-      const int rc = g_rc(k_launch_gdw(g_launch_ctx(c), 0, dw, GridPick{c->grid_g_auto ? 0 : gg, B, 1, c->g_cap_fwd, nullptr}, o.lds_fwd));
+      const int rc = g_rc(k_launch_gdw(g_launch_ctx(c), 0, dw, GridPick{m.grid_g_auto ? 0 : gg, B, 1, m.g_cap_fwd, nullptr}, o.lds_fwd));
       lp.end();
       if (rc) return rc;
       continue;
     }
     auto fwd_args = [&](int oi) {
-      GOp& q = c->G[oi];
+      GOp& q = m.G[oi];
       GConvArgs a;
       memset(&a, 0, sizeof(a));
       a.n_src = q.n_src;
@@ -337,8 +399,8 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
         q.facc_cur = a.sacc.acc;
         for (int s = 0; s < q.n_src; ++s) {
           const int pi = q.src[s];
-          if (pi < 0 || c->G[pi].norm != MWW_NORM_BN) continue;   // (no statistics to fold)
-          const int fc = c->G[pi].first_consumer;
+          if (pi < 0 || m.G[pi].norm != MWW_NORM_BN) continue;   // (no statistics to fold)
+          const int fc = m.G[pi].first_consumer;
           if (leader(oi) != leader(fc)) continue;   // a later launch: the arrays were published by the first one
           bool first_ref = true;
           for (int s2 = 0; s2 < s; ++s2) first_ref = first_ref && q.src[s2] != pi;
@@ -348,15 +410,15 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
       return a;
     };
     auto fin_args = [&](int oi, const StatSource& ss) {
-      GOp& q = c->G[oi];
+      GOp& q = m.G[oi];
       return GBnFwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
                         c->params + q.o_gamma, c->params + q.o_beta, c->bn_state + q.o_mm, c->bn_state + q.o_mv,
                         gbn_slot(q, BN_SCALE), gbn_slot(q, BN_SHIFT), gbn_slot(q, BN_MEAN), gbn_slot(q, BN_RSTD), update_moving ? 1 : 0};
     };
     const bool sync = c->hook && c->sync_bn;
-    if (o.twin_next && !sync && !c->profile_split) {
+    if (o.twin_next && !sync && !m.profile_split) {
       // twins: one convolution launch and one finalize launch for the pair
-      GOp& o2 = c->G[i + 1];
+      GOp& o2 = m.G[i + 1];
       if (!training) {
         GBnEvalArgs e{c->params + o2.o_gamma, c->params + o2.o_beta, c->bn_state + o2.o_mm, c->bn_state + o2.o_mv,
                       gbn_slot(o2, BN_SCALE), gbn_slot(o2, BN_SHIFT), o2.cout, o2.groups};
@@ -364,8 +426,8 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
       }
       const GConvArgs fa0 = fwd_args(i), fa1 = fwd_args(i + 1);
       lp.begin("conv_fwd2_", i);
-      const bool split2 = inl && c->g_role_split;
-      const int r2 = k_launch_gfwd2(g_launch_ctx(c), o.cout, fa0, fa1, GridPick{pick ? 0 : (split2 ? std::max(1, gg / 2) : gg), B, split2 ? 2 : 1, c->g_cap_fwd, nullptr},
+      const bool split2 = inl && m.g_role_split;
+      const int r2 = k_launch_gfwd2(g_launch_ctx(c), o.cout, fa0, fa1, GridPick{pick ? 0 : (split2 ? std::max(1, gg / 2) : gg), B, split2 ? 2 : 1, m.g_cap_fwd, nullptr},
                                     std::max(o.lds_fwd, o2.lds_fwd), g_shape_id(c, o) == g_shape_id(c, o2) ? g_shape_id(c, o) : 0);
       lp.end();
       if (r2 != kGNoKernel) {
@@ -396,9 +458,9 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
     if (S > 1) {
       fa.S = S;
       fa.Tc = Tc;
-      rc = launch_gconv(c, true, o.cout, fa, GridPick{pick ? 0 : gg, B * S, 1, c->g_cap_fwd, nullptr}, g_lds_fwd(o, g_chunk_in(o, Tc), Tc));
+      rc = launch_gconv(c, true, o.cout, fa, GridPick{pick ? 0 : gg, B * S, 1, m.g_cap_fwd, nullptr}, g_lds_fwd(o, g_chunk_in(o, Tc), Tc));
     } else {
-      rc = launch_gconv(c, false, o.cout, fa, GridPick{pick ? 0 : gg, B, 1, c->g_cap_fwd, nullptr}, o.lds_fwd, g_shape_id(c, o));
+      rc = launch_gconv(c, false, o.cout, fa, GridPick{pick ? 0 : gg, B, 1, m.g_cap_fwd, nullptr}, o.lds_fwd, g_shape_id(c, o));
     }
     lp.end();
     if (rc) return rc;
@@ -414,12 +476,12 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
       lp.end();
     }
   }
-  GOp& lo = c->G[n - 1];
-  const bool drop = loss && c->dropout > 0.f;   // Dropout is active in the train step only (Keras training=True)
-  const bool gen_inline = drop && !c->keep_explicit && !c->head2;   // ghead_kernel draws the mask itself
-  if (drop && !c->keep_explicit && !gen_inline) {
+  GOp& lo = m.G[n - 1];
+  const bool drop = loss && m.dropout > 0.f;   // Dropout is active in the train step only (Keras training=True)
+  const bool gen_inline = drop && !m.keep_explicit && !m.head2;   // ghead_kernel draws the mask itself
+  if (drop && !m.keep_explicit && !gen_inline) {
     const long long ne = (long long)B * c->t_last * c->c_last;
-    DropoutMaskArgs dm{c->keep, ne, c->dropout_seed, reinterpret_cast<const unsigned*>(mail_hyper(c)) + 2, c->dropout};
+    DropoutMaskArgs dm{m.keep, ne, m.dropout_seed, reinterpret_cast<const unsigned*>(mail_hyper(c)) + 2, m.dropout};
     lp.begin("dropout_mask");
     hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, dm);
     lp.end();
@@ -436,12 +498,12 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
   h.bd = c->params + c->o_dense_b;
   h.y = (loss || metrics) ? c->y_cur : nullptr;
   h.sw = c->sw_cur;
-  h.keep = (drop && !gen_inline) ? c->keep : nullptr;
+  h.keep = (drop && !gen_inline) ? m.keep : nullptr;
   if (gen_inline) {
-    h.keep_gen = c->keep;
-    h.seed = c->dropout_seed;
+    h.keep_gen = m.keep;
+    h.seed = m.dropout_seed;
     h.counter = reinterpret_cast<const unsigned*>(mail_hyper(c)) + 2;
-    h.rate = c->dropout;
+    h.rate = m.dropout;
   }
   h.z = c->z;
   h.prob = c->prob;
@@ -464,44 +526,51 @@ int g_enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool
     }
   }
   if (lo.res_src >= 0) {
-    GOp& rr = c->G[lo.res_src];
+    GOp& rr = m.G[lo.res_src];
     h.rp = rr.p;
     h.rscale = gbn_slot(rr, BN_SCALE);
     h.rshift = gbn_slot(rr, BN_SHIFT);
     h.rT = rr.tout;
     h.rdrop = lo.res_drop;
   }
-  if (c->head2) {
+  if (m.head2) {
     GHead2Args h2;
     h2.h = h;
-    h2.watt = c->head_att ? c->params + c->o_att : nullptr;
-    h2.pool = c->head_pool;
-    h2.hact = c->hact;
-    h2.watt_part = c->watt_part;
-    if (c->lds_head2 > 64 * 1024)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ghead_att_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_head2));
+    h2.watt = m.head_att ? c->params + m.o_att : nullptr;
+    h2.pool = m.head_pool;
+    h2.hact = m.hact;
+    h2.watt_part = m.watt_part;
+    const size_t lds = m.lds_head2;
+    if (lds > 64 * 1024)
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ghead_att_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     lp.begin("head");
-    hipLaunchKernelGGL(ghead_att_kernel, dim3(ghead), dim3(kThreads), c->lds_head2, c->stream, h2);
+    hipLaunchKernelGGL(ghead_att_kernel, dim3(ghead), dim3(kThreads), lds, c->stream, h2);
     lp.end();
     // the dense layer sees hact (already activated): identity "BN" for the dense-weight gradient
-    return enqueue_side_work(c, B, metrics, loss, c->hact, c->ones, c->zeros, nullptr);
+    DenseSource ds;
+    ds.p = m.hact;
+    ds.scale = m.ones;
+    ds.shift = m.zeros;
+    return enqueue_side_work(c, B, metrics, loss, ds);
   }
   lp.begin("head");
   hipLaunchKernelGGL(ghead_kernel, dim3(ghead), dim3(kThreads), 0, c->stream, h);
   lp.end();
-  return enqueue_side_work(c, B, metrics, loss, lo.p, gbn_slot(lo, BN_SCALE), gbn_slot(lo, BN_SHIFT), drop ? c->keep : nullptr);
+  const DenseSource ds{lo.p, h.scale, h.shift, drop ? m.keep : nullptr, h.rp, h.rscale, h.rshift, h.rT, h.rdrop, 0};
+  return enqueue_side_work(c, B, metrics, loss, ds);
 }
 
-int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
+int GraphModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
+  GraphModel& m = *this;
   Launcher lp{c};
-  const int n = (int)c->G.size();
-  const int gg = std::min(B, c->grid_g);
+  const int n = (int)m.G.size();
+  const int gg = std::min(B, m.grid_g);
   const int ghead = std::min(B, c->grid_head);
   GradReduceArgs ga;
   memset(&ga, 0, sizeof(ga));
   // statistics hand-over: the op's own backward launch folds (sum g, sum g*xhat) from the accumulator rows its consumers
   // (or the head) added to; the weight-gradient role publishes c1 / mg / mgx / dgamma / dbeta
-  const bool inl = c->bn_inline && c->g_inline_ok && !(c->hook && c->sync_bn) && !c->profile_split;
+  const bool inl = c->bn_inline && m.g_inline_ok && !(c->hook && c->sync_bn) && !m.profile_split;
   auto bfold = [&](GOp& q, bool publish) {
     GFoldBwd f;
     memset(&f, 0, sizeof(f));
@@ -520,13 +589,13 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     return f;
   };
   auto bwd_fin_args = [&](int oi, const StatSource& ss) {
-    GOp& q = c->G[oi];
+    GOp& q = m.G[oi];
     return GBnBwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
                       c->params + q.o_gamma, gbn_slot(q, BN_RSTD), gbn_slot(q, BN_C1), gbn_slot(q, BN_MG), gbn_slot(q, BN_MGX),
                       c->grads + q.o_gamma, c->grads + q.o_beta, ss.dscale, 0};
   };
   auto wgrad_args = [&](int oi) {
-    GOp& q = c->G[oi];
+    GOp& q = m.G[oi];
     GWgradArgs w;
     memset(&w, 0, sizeof(w));
     w.n_src = q.n_src;
@@ -544,7 +613,7 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     return w;
   };
   auto dgrad_args = [&](int oi) {
-    GOp& q = c->G[oi];
+    GOp& q = m.G[oi];
     GConvArgs a;
     memset(&a, 0, sizeof(a));
     a.n_src = q.n_src;
@@ -561,11 +630,11 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     a.y.fold = bfold(q, false);
     return a;
   };
-  const bool split = inl && c->g_role_split;
-  const bool pick = inl && c->grid_g_auto;   // per-launch grids (g_role_grid)
+  const bool split = inl && m.g_role_split;
+  const bool pick = inl && m.grid_g_auto;   // per-launch grids (g_role_grid)
   const int gg2 = split ? std::max(1, gg / 2) : gg, gg4 = split ? std::max(1, gg / 4) : gg;
   auto add_segment = [&](int oi, int rows) {
-    GOp& q = c->G[oi];
+    GOp& q = m.G[oi];
     GradSegment s;
     s.part = q.grad_part;
     s.G = rows;
@@ -576,11 +645,11 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
   };
   const bool sync = c->hook && c->sync_bn;
   for (int i = n - 1; i >= 0; --i) {
-    GOp& o = c->G[i];
+    GOp& o = m.G[i];
     const int members = o.groups > 1 ? o.cout / o.groups : 1;
-    if (i > 0 && c->G[i - 1].twin_next && !sync && !c->profile_split) {
+    if (i > 0 && m.G[i - 1].twin_next && !sync && !m.profile_split) {
       // twins (i-1, i): one finalize launch and one four-role backward launch for the pair
-      GOp& o1 = c->G[i - 1];
+      GOp& o1 = m.G[i - 1];
       const float inv_n = 1.0f / ((float)B * (float)o.tout * (float)members);
       StatSource s0{o.gstat_part, gg, inv_n, 1.0f}, s1{o1.gstat_part, gg, inv_n, 1.0f};
       const GBnBwdArgs bf0 = bwd_fin_args(i, s0), bf1 = bwd_fin_args(i - 1, s1);
@@ -590,7 +659,7 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       lp.begin("conv_bwd2_", i);
       if (!inl) hipLaunchKernelGGL(gbn_bwd_finalize2_kernel, dim3(o.slots + o1.slots), dim3(kThreads), 0, c->stream, bf0, bf1, n0);
       int rows = gg4;
-      const int r2 = k_launch_gbwd2(g_launch_ctx(c), o.cout, w0, d0, w1, d1, GridPick{pick ? 0 : gg4, B, split ? 4 : 1, c->g_cap_bwd, &rows},
+      const int r2 = k_launch_gbwd2(g_launch_ctx(c), o.cout, w0, d0, w1, d1, GridPick{pick ? 0 : gg4, B, split ? 4 : 1, m.g_cap_bwd, &rows},
                                    std::max(std::max(o.lds_wg, o.lds_dx), std::max(o1.lds_wg, o1.lds_dx)),
                                    g_shape_id(c, o) == g_shape_id(c, o1) ? g_shape_id(c, o) : 0);
       lp.end();
@@ -605,7 +674,7 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       memset(&ra, 0, sizeof(ra));
       ra.n = (int)o.adders.size();
       for (int q = 0; q < ra.n; ++q) {
-        GOp& x = c->G[o.adders[q]];
+        GOp& x = m.G[o.adders[q]];
         ra.gx[q] = x.g;
         ra.Tx[q] = x.tout;
         ra.drop[q] = x.res_drop;
@@ -648,13 +717,13 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       }
       lp.begin("dw_wgrad", i);
       int gwg = 0;   // (its partial rows are its own)
-      int rc = g_rc(k_launch_gdw_wgrad(g_launch_ctx(c), dw, GridPick{c->grid_g_auto ? 0 : gg, B, 1, c->g_cap_bwd, &gwg}, o.lds_wg));
+      int rc = g_rc(k_launch_gdw_wgrad(g_launch_ctx(c), dw, GridPick{m.grid_g_auto ? 0 : gg, B, 1, m.g_cap_bwd, &gwg}, o.lds_wg));
       lp.end();
       if (rc) return rc;
       if (o.needs_dx) {
         lp.begin("dw_dgrad", i);
         // (partial statistics rows are shared without the hand-over)
-        rc = g_rc(k_launch_gdw(g_launch_ctx(c), 1, dw, GridPick{pick ? 0 : gg, B, 1, c->g_cap_bwd, nullptr}, o.lds_dx));
+        rc = g_rc(k_launch_gdw(g_launch_ctx(c), 1, dw, GridPick{pick ? 0 : gg, B, 1, m.g_cap_bwd, nullptr}, o.lds_dx));
         lp.end();
         if (rc) return rc;
       }
@@ -709,9 +778,9 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       lds_dx = o.needs_dx ? g_lds_dx(o, Tc, Tc) : 0;
     }
     const int items = B * S;
-    if (o.needs_dx && !c->profile_split) {
+    if (o.needs_dx && !m.profile_split) {
       lp.begin("conv_bwd", i);
-      const GridPick pkf{pick ? 0 : gg2, items, split ? 2 : 1, c->g_cap_bwd, &rows};
+      const GridPick pkf{pick ? 0 : gg2, items, split ? 2 : 1, m.g_cap_bwd, &rows};
       const int rf = k_launch_gbwd(g_launch_ctx(c), S > 1, o.cout, o.cin, w, a, pkf, std::max(lds_wg, lds_dx), g_shape_id(c, o));
       lp.end();
       if (rf > 0) return g_rc(rf);
@@ -724,13 +793,13 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     }
     if (!fused) {
       lp.begin("conv_wgrad", i);
-      const GridPick pkw{pick ? 0 : gg, items, 1, c->g_cap_bwd, &rows};
+      const GridPick pkw{pick ? 0 : gg, items, 1, m.g_cap_bwd, &rows};
       int rc = launch_gwgrad(c, S > 1, o.cout, w, pkw, lds_wg, g_shape_id(c, o));
       lp.end();
       if (rc) return rc;
       if (o.needs_dx) {
         lp.begin("conv_dgrad", i);
-        const GridPick pkd{pick ? 0 : gg, items, 1, c->g_cap_bwd, nullptr};
+        const GridPick pkd{pick ? 0 : gg, items, 1, m.g_cap_bwd, nullptr};
         rc = g_rc(k_launch_gdgrad(g_launch_ctx(c), S > 1, o.cin, a, pkd, lds_dx));
         lp.end();
         if (rc) return rc;
@@ -744,24 +813,25 @@ int g_enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     s.dst = (int)o.o_w;
     ga.seg[ga.nseg++] = s;
   }
-  if (c->head2 && c->head_att) {
+  if (m.head2 && m.head_att) {
     GradSegment s;
-    s.part = c->watt_part;
+    s.part = m.watt_part;
     s.G = ghead;
     s.stride = 8;
     s.n = 8;
-    s.dst = (int)c->o_att;
+    s.dst = (int)m.o_att;
     ga.seg[ga.nseg++] = s;
   }
   if (inl) c->gpar ^= 1;
   return enqueue_grad_assembly(c, B, ga, fuse_adam);
 }
 
-int g_plan_convnet(const mww_convnet_desc& d, GPlan* plan) {
+namespace {
+int plan_ops(const mww_convnet_desc& d, GraphModel* plan) {
   if (d.n_ops < 1 || d.n_ops > MWW_MAX_GRAPH_OPS) return fail(MWW_ERR_INVALID, "n_ops out of range");
   if (d.max_batch <= 0 || d.frames <= 0) return fail(MWW_ERR_INVALID, "frames and max_batch must be positive");
   if (!(d.dropout >= 0.f && d.dropout < 1.f)) return fail(MWW_ERR_INVALID, "dropout rate must be in [0, 1)");
-  std::vector<GOp>& ops = plan->ops;
+  std::vector<GOp>& ops = plan->G;
   ops.assign(d.n_ops, GOp());
   std::vector<int> n_consumers(d.n_ops, 0);
   int64_t off = 0, soff = 0;
@@ -939,7 +1009,7 @@ int g_plan_convnet(const mww_convnet_desc& d, GPlan* plan) {
   // 0.877 -> 0.815 ms/step (3: 0.818).  Off for pure convolution graphs: Inception 0.892 / 0.897 / 0.957 / 0.960 ms for 0 / 1 / 2 / 3
   // (profiles/round3_frame_chunks.txt)
   for (const GOp& o : ops)
-    if (o.kind == MWW_OP_DEPTHWISE) plan->chunks = 1;
+    if (o.kind == MWW_OP_DEPTHWISE) plan->frame_chunks = 1;
   {
     // statistics hand-over: possible when every op is a convolution followed by a BatchNorm / SSN (or by nothing: a
     // MixedNet's first convolution) or a depthwise op with a bias (or nothing), none has a residual branch and every folded
@@ -953,11 +1023,134 @@ int g_plan_convnet(const mww_convnet_desc& d, GPlan* plan) {
       for (int j = 0; j < o.n_src; ++j)
         if (o.src[j] >= 0 && ops[o.src[j]].first_consumer < 0) ops[o.src[j]].first_consumer = i;
     }
-    plan->inline_ok = ok && !d.head_attention && !d.head_pool;
+    plan->g_inline_ok = ok && !d.head_attention && !d.head_pool;
   }
-  plan->P = off;
-  plan->S = soff;
+  plan->plan_P = off;
+  plan->plan_S = soff;
+  plan->dropout = d.dropout;
+  plan->head_att = d.head_attention != 0;   // (whether the model gets that head: layout)
+  plan->head_pool = d.head_pool;
   return MWW_OK;
+}
+}  // namespace
+
+int plan_convnet(const mww_convnet_desc& d, Model** out) {
+  GraphModel* m = new GraphModel();
+  const int rc = plan_ops(d, m);
+  if (rc) delete m;
+  else *out = m;
+  return rc;
+}
+
+// the head and the dense layer behind the ops
+int GraphModel::layout(mww_ctx* c) {
+  int64_t off = plan_P;
+  GOp& lo = G.back();
+  c->t_last = lo.tout;
+  c->c_last = lo.cout;
+  const bool want_att = head_att;
+  const int want_pool = head_pool;
+  head_att = false;
+  head_pool = 0;
+  if (lo.tout > 1 && (want_att || want_pool)) {   // mixednet.py:362: only if more than one frame remains
+    if (want_pool < 0 || want_pool > 2) return fail(MWW_ERR_INVALID, "head_pool must be 0, 1 or 2");
+    if (want_att && lo.tout < 4) return fail(MWW_ERR_INVALID, "spatial attention needs at least 4 frames");
+    if (dropout > 0.f) return fail(MWW_ERR_UNSUPPORTED, "dropout with the attention / pooled head");
+    head2 = true;
+    head_att = want_att;
+    head_pool = want_pool;
+    const int to = lo.tout - (head_att ? 3 : 0);
+    c->t_last = head_pool ? 1 : to;
+    if (head_att) { o_att = off; off += 8; }
+    lds_head2 = ((size_t)lo.tout * (lo.cout | 1) + 7 * (size_t)lo.tout + 3 * (size_t)lo.cout) * sizeof(float);
+    if (lds_head2 > kMaxDynLds) return fail(MWW_ERR_UNSUPPORTED, "window does not fit the head's LDS tile");
+  }
+  c->o_dense_w = off; off += (int64_t)c->t_last * lo.cout;
+  c->o_dense_b = off; off += 1;
+  c->P = off;
+  c->S = plan_S;
+  c->dwd_stride = c->t_last * lo.cout + 4;
+  grid_g = c->n_cu * 3;   // measured on the Inception step: 3 workgroups per CU and launch (roles share them) beats 2 and 4
+  return MWW_OK;
+}
+
+int GraphModel::alloc(mww_ctx* c, std::vector<BnSlots>* bn) {
+  const size_t mb = (size_t)c->max_batch;
+  const size_t gmax = (size_t)c->n_cu * 4;   // ("grid_graph" may be raised to it)
+  GOp& lo = G.back();
+  MWW_TRY(dev_alloc(&keep, mb * lo.tout * lo.cout));
+  if (head2) {
+    MWW_TRY(dev_alloc(&hact, mb * c->t_last * lo.cout));
+    MWW_TRY(dev_alloc(&watt_part, gmax * 8));
+  }
+  for (GOp& o : G) {
+    MWW_TRY(dev_alloc(&o.p, mb * o.tout * o.cout + (size_t)o.planes * kPlanePad));
+    MWW_TRY(dev_alloc(&o.g, mb * o.tout * o.cout + (size_t)o.planes * kPlanePad));
+    MWW_TRY(tensor_alloc(&o, o.cout, gmax, gmax, gmax * o.k * (o.kind == MWW_OP_DEPTHWISE ? 1 : o.cin) * o.cout));
+    if (o.norm == MWW_NORM_BN) bn->push_back(BnSlots{o.o_gamma, o.o_beta, o.o_mv, o.slots});
+    else if (o.norm == MWW_NORM_BIAS) bn->push_back(BnSlots{o.o_beta, o.o_beta, -1, o.cout});   // bias gradient is written directly too
+  }
+  MWW_TRY(dev_alloc(&ones, (size_t)kThreads));
+  MWW_TRY(dev_alloc(&zeros, (size_t)kThreads));
+  const std::vector<float> one((size_t)kThreads, 1.0f);
+  HIPCHK(hipMemcpy(ones, one.data(), one.size() * sizeof(float), hipMemcpyHostToDevice));
+  return MWW_OK;
+}
+
+int GraphModel::set_option(mww_ctx* c, const OptionRow& o, int64_t v) {
+  const std::string name = o.name;
+  if (o.owner != OPT_GRAPH) return (v && (name == "pointwise_bf16" || name == "storage_bf16")) ? fail(MWW_ERR_UNSUPPORTED, "the conv/BN graph kernels have no bf16 mode") : MWW_OK;
+  const std::pair<const char*, bool GraphModel::*> flags[] = {{"graph_role_split", &GraphModel::g_role_split}, {"graph_static_shapes", &GraphModel::g_static},
+                                                              {"graph_planar", &GraphModel::g_planar}, {"profile_split", &GraphModel::profile_split}};
+  const std::pair<const char*, int GraphModel::*> ints[] = {{"graph_fwd_wg_per_cu", &GraphModel::g_cap_fwd}, {"graph_bwd_wg_per_cu", &GraphModel::g_cap_bwd},
+                                                            {"graph_frame_chunks", &GraphModel::frame_chunks}, {"graph_dgrad_share", &GraphModel::g_dgrad_share}};
+  for (auto& f : flags) if (name == f.first) this->*f.second = v != 0;
+  for (auto& f : ints) if (name == f.first) this->*f.second = (int)v;
+  if (name == "grid_graph") {
+    grid_g_auto = v == 0;
+    if (v > 0) grid_g = (int)v;
+  }
+  if (name == "dropout_seed") { dropout_seed = (unsigned long long)v; dropout_counter = 0; }
+  return MWW_OK;
+}
+
+int GraphModel::set_dropout_mask(mww_ctx* c, const uint8_t* mask, int B) {
+  if (!mask) { keep_explicit = false; return MWW_OK; }
+  if (B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (!(dropout > 0.f)) return fail(MWW_ERR_STATE, "model was created with dropout = 0");
+  const size_t n = (size_t)B * c->t_last * c->c_last;
+  std::vector<float> h(n);
+  const float sc = 1.0f / (1.0f - dropout);
+  for (size_t i = 0; i < n; ++i) h[i] = mask[i] ? sc : 0.f;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(keep, h.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  keep_explicit = true;
+  return MWW_OK;
+}
+
+// p<i> / g<i> / bn<i> of op i (1-based), keep, and x (written out first where the batch is descriptor-only)
+int GraphModel::debug_tensor(mww_ctx* c, const char* name, int B, DebugTensor* t) {
+  auto gidx = [&](const char* prefix) -> int {
+    const size_t pl = strlen(prefix);
+    if (strncmp(name, prefix, pl) != 0 || name[pl] < '0' || name[pl] > '9') return -1;
+    const int kk = atoi(name + pl);
+    return (kk >= 1 && kk <= (int)G.size()) ? kk - 1 : -1;
+  };
+  int k;
+  if ((k = gidx("p")) >= 0 || (k = gidx("g")) >= 0) {
+    const GOp& o = G[k];
+    *t = DebugTensor{name[0] == 'p' ? o.p : o.g, (int64_t)B * o.tout * o.cout, false, g_planes(c, o), o.pc, o.cout, g_pstride(c, o)};
+  }
+  else if ((k = gidx("bn")) >= 0) { t->src = G[k].bn; t->n = (int64_t)9 * G[k].cout; }
+  else if (!strcmp(name, "keep")) { t->src = keep; t->n = (int64_t)B * c->t_last * c->c_last; }
+  else if (!strcmp(name, "x")) {
+    if (materialise_x(c)) return -1;
+    t->src = c->x;
+    t->n = (int64_t)B * c->frames * MWW_FEATURE_BINS;
+  }
+  else return 0;
+  return 1;
 }
 
 }  // namespace mww

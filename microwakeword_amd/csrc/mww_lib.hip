@@ -1,5 +1,6 @@
-// libmww_hip.so — context, device memory, the MixedNet block engine's launch sequences, gradient assembly, RCCL and the C ABI of
-// include/mww.h.  The conv/BN graph engine is graph_engine.hip; engine.hip.h holds what the two share.
+// libmww_hip.so — the C ABI of include/mww.h and the core of a context: device memory, mailboxes, batch assembly, gradient
+// assembly / exchange / Adam, side work, RCCL and the step driver.  The model part of a context is one of the two engines
+// (block_engine.hip, graph_engine.hip); engine.hip.h holds what the three share.
 // One context = one device + one HIP stream + one model; every call enqueues on that stream.
 #include <hip/hip_runtime.h>
 
@@ -14,7 +15,6 @@
 #include <vector>
 
 #include "engine.hip.h"
-#include "block_launch.hip.h"
 #include "kernels_data.hip.h"
 #include "kernels_head.hip.h"
 #include "kernels_tail.hip.h"
@@ -32,42 +32,13 @@ int mww::fail(int code, const std::string& msg) {
 
 namespace {
 
-// ---------------------------------------------------------------------------------- dispatch
-// The block kernels are instantiated and launched in their own translation units (tu_fwd.hip, tu_bwd.hip, tu_bwdw.hip:
-// compiled in parallel by build()); block_launch.hip.h declares their launchers and the table of specialised shapes.
-int launch_fwd_first(mww_ctx* c, int k1, int c1, int cout, int k, int st, const FwdFirstArgs& a, int grid) {
-  if (k_launch_fwd_first(c->stream, c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0), k1, c1, cout, k, st, a, grid, c->conv1_x6_fwd)) return MWW_OK;
-  return fail(MWW_ERR_UNSUPPORTED, "no first-block kernel for this (conv1 kernel, filters, pointwise, depthwise) shape");
-}
-
-int launch_bwd_first(mww_ctx* c, int k1, int c1, int cout, int k, int st, const BwdFirstArgs& a, int grid) {
-  const bool late = c->dp_commit_late < 0 ? MWW_DP_COMMIT_LATE_FIRST_DEFAULT != 0 : c->dp_commit_late != 0;
-  if (c->bwd_wide && !c->pw_bf16 && !c->st_bf16 && k_launch_bwd_firstw(c->stream, k1, c1, cout, k, st, a, grid, c->conv1_x6 && c->bwd_first_wide, late)) return MWW_OK;
-  if (k_launch_bwd_first(c->stream, c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0), k1, c1, cout, k, st, a, grid, c->conv1_x6, late)) return MWW_OK;
-  return fail(MWW_ERR_UNSUPPORTED, "no first-block backward kernel for this shape");
-}
-
-int launch_fwd_block(mww_ctx* c, int cin, int cout, int k, const FwdBlockArgs& a, int grid) {
-  if (k_launch_fwd_block(c->stream, c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0), cin, cout, k, a, grid)) return MWW_OK;
-  return fail(MWW_ERR_UNSUPPORTED, "no block kernel for this (cin, cout, depthwise) shape");
-}
-
-int launch_bwd_block(mww_ctx* c, int cin, int cout, int k, bool last, const BwdBlockArgs& a, int grid) {
-  const int mode = c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0);
-  const bool late = c->dp_commit_late < 0 ? (last ? MWW_DP_COMMIT_LATE_LAST_DEFAULT : MWW_DP_COMMIT_LATE_BLOCK_DEFAULT) != 0 : c->dp_commit_late != 0;
-  if (c->bwd_wide && k_launch_bwd_blockw(c->stream, mode, cin, cout, k, last, a, grid, late)) return MWW_OK;
-  if (k_launch_bwd_block(c->stream, c->st_bf16 ? 2 : (c->pw_bf16 ? 1 : 0), cin, cout, k, last, a, grid)) return MWW_OK;
-  return fail(MWW_ERR_UNSUPPORTED, "no block backward kernel for this shape");
-}
-
+// ---------------------------------------------------------------------------------- the block engine's head
 constexpr int kHeadMaxRows = 24;   // frames per frame group of the widest head_kernel instantiation below
-// final frames one head workgroup covers at `ch` channels (a thread keeps one float4 of every frame of its group)
-int head_frame_limit(int ch) { return (kThreads / (ch / 4)) * kHeadMaxRows; }
 
-int launch_head(mww_ctx* c, int ch, int jmax, const HeadArgs& a, int grid) {
+int launch_head(mww_ctx* c, int ch, int jmax, bool bf16, const HeadArgs& a, int grid) {
 #define X(C, J)                                                                                                \
   if (ch == C && jmax <= J) {                                                                                  \
-    if (c->st_bf16)                                                                                            \
+    if (bf16)                                                                                                  \
       hipLaunchKernelGGL((head_kernel<C, J, true>), dim3(grid), dim3(kThreads), 0, c->stream, a);              \
     else                                                                                                       \
       hipLaunchKernelGGL((head_kernel<C, J>), dim3(grid), dim3(kThreads), 0, c->stream, a);                    \
@@ -79,39 +50,25 @@ int launch_head(mww_ctx* c, int ch, int jmax, const HeadArgs& a, int grid) {
   return fail(MWW_ERR_UNSUPPORTED, "no head kernel for this (channels, frames) shape");
 }
 
-// does every block of the model have a specialised kernel (bf16: in the bf16 modes too)?
-bool shape_supported(const mww_mixednet_desc& d, std::string* why, bool bf16 = false) {
-  if (d.n_blocks < 2 || d.n_blocks > MWW_MAX_BLOCKS) { *why = "the block kernels serve 2.." + std::to_string(MWW_MAX_BLOCKS) + " blocks"; return false; }
-  bool ok = false;
-#define X(K1, C1, CO, K, S) ok = ok || (d.conv1_kernel == K1 && d.conv1_filters == C1 && d.block_filters[0] == CO && d.block_kernel[0] == K && d.conv1_stride == S);
-  if (bf16) { MWW_FIRST_SHAPES_BF16(X) } else { MWW_FIRST_SHAPES(X) }
-#undef X
-  if (!ok) { *why = "first block (conv1 kernel/filters/stride, pointwise filters, depthwise kernel) not instantiated"; return false; }
-  for (int i = 1; i < d.n_blocks; ++i) {
-    ok = false;
-#define X(CI, CO, K) ok = ok || (d.block_filters[i - 1] == CI && d.block_filters[i] == CO && d.block_kernel[i] == K);
-    if (bf16) { MWW_BLOCK_SHAPES_BF16(X) } else { MWW_BLOCK_SHAPES(X) }
-#undef X
-    if (!ok) { *why = "block " + std::to_string(i) + " (cin, cout, depthwise kernel) not instantiated"; return false; }
-  }
-  const int cl = d.block_filters[d.n_blocks - 1];
-  if (cl != 32 && cl != 48 && cl != 64) { *why = "head kernel needs 32, 48 or 64 channels"; return false; }
-  // the classifier head keeps a window's final frames in registers: more of them than its widest instantiation holds would only
-  // surface as MWW_ERR_UNSUPPORTED at the first forward (found by tools/gpu_x6_fuzz.py case 460: 64 channels x 390 frames)
-  int t = d.frames >= d.conv1_kernel && d.conv1_stride > 0 ? (d.frames - d.conv1_kernel) / d.conv1_stride + 1 : 0;
-  for (int i = 0; i < d.n_blocks; ++i) t -= d.block_kernel[i] - 1;
-  if (t > head_frame_limit(cl)) {
-    *why = "head kernel holds at most " + std::to_string(head_frame_limit(cl)) + " final frames at " + std::to_string(cl) + " channels (" + std::to_string(t) + " here)";
-    return false;
-  }
-  return true;
-}
-
-float* bn_slot(Layer& l, int i) { return l.bn + (size_t)i * l.cout; }
-
 }  // namespace
 
 namespace mww {
+
+// final frames one head workgroup covers at `ch` channels (a thread keeps one float4 of every frame of its group)
+int head_frame_limit(int ch) { return (kThreads / (ch / 4)) * kHeadMaxRows; }
+
+int enqueue_block_head(mww_ctx* c, int B, const Tensor& last, int T, int C, bool bf16, const BnFoldArgs& fold, const StatAcc& gacc, bool loss, bool metrics) {
+  float* const bn = last.bn;
+  const HeadArgs h{last.p, bn + (size_t)BN_SCALE * C, bn + (size_t)BN_SHIFT * C, bn + (size_t)BN_MEAN * C, bn + (size_t)BN_RSTD * C,
+                   c->params + c->o_dense_w, c->params + c->o_dense_b, (loss || metrics) ? c->y_cur : nullptr, c->sw_cur, c->z, c->prob, c->dz,
+                   c->loss_part, last.gstat_part, B, T, 1.0f / (float)B, (loss ? kHeadTraining : 0) | (c->bce_clipped ? kHeadClippedLoss : 0), fold, gacc};
+  const int q = C / 4, nrg = kThreads / q;
+  Launcher lp{c};
+  lp.begin("head");
+  int rc = launch_head(c, C, (T + nrg - 1) / nrg, bf16, h, std::min(B, c->grid_head));
+  lp.end();
+  return rc;
+}
 
 // ---------------------------------------------------------------------------------- sequences
 const float* mail_hyper(mww_ctx* c) { return reinterpret_cast<const float*>(c->mail_dev[c->mail_cur] + c->mail_off_hyper); }
@@ -165,10 +122,14 @@ static int join_side(mww_ctx* c) {
   return MWW_OK;
 }
 
+static DenseGradArgs dense_args(mww_ctx* c, int B, const DenseSource& s, float* part, int stride) {
+  return DenseGradArgs{s.p, s.scale, s.shift, c->dz, part, B, c->t_last * c->c_last, c->c_last, stride, (B + kDenseChunks - 1) / kDenseChunks,
+                       s.keep, s.rp, s.rscale, s.rshift, s.rT, s.rdrop, s.bf16};
+}
+
 // off the critical path: metric update and (training) the dense-weight gradient run on the side
 // stream while the backward chain proceeds; joined before the gradient assembly
-int enqueue_side_work(mww_ctx* c, int B, bool metrics, bool loss, const float* p_last, const float* scale,
-                      const float* shift, const float* keep) {
+int enqueue_side_work(mww_ctx* c, int B, bool metrics, bool loss, const DenseSource& last) {
   Launcher lp{c};
   if (metrics || loss) {
     const bool inline_side = c->profile || !c->use_side;
@@ -186,18 +147,8 @@ int enqueue_side_work(mww_ctx* c, int B, bool metrics, bool loss, const float* p
       lp.end();
     }
     if (loss) {
-      const int dchunk = (B + kDenseChunks - 1) / kDenseChunks;
-      const int ndchunks = (B + dchunk - 1) / dchunk;
-      DenseGradArgs dg{p_last, scale, shift, c->dz, c->dwd_part, B, c->t_last * c->c_last, c->c_last, c->dwd_stride, dchunk, keep,
-                       nullptr, nullptr, nullptr, 0, 0, c->st_bf16 ? 1 : 0};
-      if (c->generic && !c->head2 && c->G.back().res_src >= 0) {
-        GOp& rr = c->G[c->G.back().res_src];
-        dg.rp = rr.p;
-        dg.rscale = rr.bn + (size_t)BN_SCALE * rr.cout;
-        dg.rshift = rr.bn + (size_t)BN_SHIFT * rr.cout;
-        dg.rT = rr.tout;
-        dg.rdrop = c->G.back().res_drop;
-      }
+      const DenseGradArgs dg = dense_args(c, B, last, c->dwd_part, c->dwd_stride);
+      const int ndchunks = (B + dg.chunk - 1) / dg.chunk;
       if (one_launch) {
         HeadTailArgs ht;
         memset(&ht, 0, sizeof(ht));
@@ -250,140 +201,7 @@ int exchange_stats(mww_ctx* c, Launcher& lp, const char* what, int layer, const 
 }
 
 }  // namespace mww
-
 namespace {
-
-// Workgroups of one forward block launch: its (window, time tile) items over at most the workgroups the instantiation
-// keeps resident (the __launch_bounds__ of fwd_block_kernel), so that no launch runs a partial second dispatch round.
-int fwd_block_grid(const mww_ctx* c, const Layer& l, int B) {
-  const int per_cu = l.cin > 48 ? 2 : (l.k > 13 ? 3 : 4);
-  const long long items = (long long)B * ((l.tout + TT - 1) / TT);
-  return (int)std::min<long long>(items, std::min(c->grid_fwd, c->n_cu * per_cu));
-}
-
-int enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) {
-  if (c->generic) return g_enqueue_forward(c, B, training, update_moving, loss, metrics);
-  Launcher lp{c};
-  const mww_mixednet_desc& d = c->d;
-  const int nb = d.n_blocks;
-  if (!training && !c->bn_eval_ready) {
-    for (int i = 0; i < nb; ++i) {
-      Layer& l = c->L[i];
-      BnEvalPrepareArgs a{c->params + l.o_gamma, c->params + l.o_beta, c->bn_state + l.o_mm, c->bn_state + l.o_mv,
-                          bn_slot(l, BN_SCALE), bn_slot(l, BN_SHIFT), l.cout};
-      lp.begin("bn_eval_prepare", i);
-      hipLaunchKernelGGL(bn_eval_prepare_kernel, dim3(1), dim3(64), 0, c->stream, a);
-      lp.end();
-    }
-  }
-  // statistics of BN_i: accumulator rows folded by the next kernel, or partial rows + a finalize launch
-  const bool inl = training && c->bn_inline && !(c->hook && c->sync_bn);
-  auto fold_of = [&](Layer& pl) {
-    BnFoldArgs f;
-    memset(&f, 0, sizeof(f));
-    if (!inl) return f;
-    f.acc = pl.facc_cur;
-    f.inv_n = 1.0f / ((float)B * (float)pl.tout);
-    f.update_moving = update_moving ? 1 : 0;
-    f.gamma = c->params + pl.o_gamma;
-    f.beta = c->params + pl.o_beta;
-    f.moving_mean = c->bn_state + pl.o_mm;
-    f.moving_var = c->bn_state + pl.o_mv;
-    f.scale = bn_slot(pl, BN_SCALE);
-    f.shift = bn_slot(pl, BN_SHIFT);
-    f.mean = bn_slot(pl, BN_MEAN);
-    f.rstd = bn_slot(pl, BN_RSTD);
-    return f;
-  };
-  for (int i = 0; i < nb; ++i) {
-    Layer& l = c->L[i];
-    const int grid = i == 0 ? std::min(B, c->grid_fwd) : fwd_block_grid(c, l, B);
-    StatAcc sacc{nullptr, nullptr};
-    if (inl) {
-      sacc.acc = l.facc[c->fpar];
-      sacc.clear = l.facc[c->fpar ^ 1];
-      l.facc_cur = sacc.acc;
-    }
-    if (i == 0) {
-      FwdFirstArgs a{c->x, c->params + c->o_conv1, c->params + l.o_dw_w, c->params + l.o_dw_b, c->params + l.o_pw_w,
-                     l.p, l.stat_part, B, d.frames, l.tout, 0, sacc, x_gather(c), training ? c->a0 : nullptr};
-      lp.begin("fwd_block", i);
-      int rc = launch_fwd_first(c, d.conv1_kernel, d.conv1_filters, l.cout, l.k, d.conv1_stride, a, grid);
-      lp.end();
-      if (rc) return rc;
-    } else {
-      Layer& pl = c->L[i - 1];
-      FwdBlockArgs a{pl.p, bn_slot(pl, BN_SCALE), bn_slot(pl, BN_SHIFT), c->params + l.o_dw_w, c->params + l.o_dw_b,
-                     c->params + l.o_pw_w, l.p, l.stat_part, B, l.tin, l.tout, c->ablate, c->phase_clk + (size_t)(2 * i) * 2048 * kClkSlots,
-                     sacc, fold_of(pl)};
-      lp.begin("fwd_block", i);
-      int rc = launch_fwd_block(c, l.cin, l.cout, l.k, a, grid);
-      lp.end();
-      if (rc) return rc;
-    }
-    if (training && !inl) {
-      StatSource ss;
-      int rcs = exchange_stats(c, lp, "bn_stat_exchange", i, l.stat_part, grid, l.cout, 0, 1.0f / ((float)B * (float)l.tout), &ss);
-      if (rcs) return rcs;
-      BnFwdFinalizeArgs f{ss.part, ss.G, l.cout, ss.inv_n, c->params + l.o_gamma,
-                          c->params + l.o_beta, c->bn_state + l.o_mm, c->bn_state + l.o_mv, bn_slot(l, BN_SCALE),
-                          bn_slot(l, BN_SHIFT), bn_slot(l, BN_MEAN), bn_slot(l, BN_RSTD), update_moving ? 1 : 0};
-      lp.begin("bn_fwd_finalize", i);
-      hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(l.cout), dim3(kThreads), 0, c->stream, f);
-      lp.end();
-    }
-  }
-  Layer& ll = c->L[nb - 1];
-  const int ghead = std::min(B, c->grid_head);
-  HeadArgs h;
-  h.p = ll.p;
-  h.scale = bn_slot(ll, BN_SCALE);
-  h.shift = bn_slot(ll, BN_SHIFT);
-  h.mean = bn_slot(ll, BN_MEAN);
-  h.rstd = bn_slot(ll, BN_RSTD);
-  h.wd = c->params + c->o_dense_w;
-  h.bd = c->params + c->o_dense_b;
-  h.y = (loss || metrics) ? c->y_cur : nullptr;
-  h.sw = c->sw_cur;
-  h.z = c->z;
-  h.prob = c->prob;
-  h.dz = c->dz;
-  h.loss_part = c->loss_part;
-  h.gstat_part = ll.gstat_part;
-  h.B = B;
-  h.T = ll.tout;
-  h.inv_b = 1.0f / (float)B;
-  h.training = (loss ? kHeadTraining : 0) | (c->bce_clipped ? kHeadClippedLoss : 0);
-  h.fold = fold_of(ll);
-  if (inl) c->fpar ^= 1;
-  // train step with the statistics hand-over: BN_L's backward sums go to accumulator rows (folded by the last block's
-  // backward kernel) and the dense-weight gradient / metric update ride in the gradient-reduction launch
-  const bool tail_late = loss && inl && c->tail_roles;
-  h.gacc = StatAcc{nullptr, nullptr};
-  if (tail_late) {
-    h.gacc.acc = ll.gacc[c->gpar];
-    h.gacc.clear = ll.gacc[c->gpar ^ 1];
-    ll.gacc_cur = h.gacc.acc;
-  }
-  const int q = ll.cout / 4, nrg = kThreads / q;
-  lp.begin("head");
-  int rc = launch_head(c, ll.cout, (ll.tout + nrg - 1) / nrg, h, ghead);
-  lp.end();
-  if (rc) return rc;
-  if (tail_late) {
-    c->tail_in_reduce = true;
-    c->tail_metrics = metrics;
-    return MWW_OK;
-  }
-  if (loss && !(c->hook && c->sync_bn)) {
-    // train step: the dense-weight gradient and the metric update share the launch of the last block's
-    // BN-backward finalize (head_tail_kernel, first thing in enqueue_backward)
-    c->tail_pending = true;
-    c->tail_metrics = metrics;
-    return MWW_OK;
-  }
-  return enqueue_side_work(c, B, metrics, loss, ll.p, bn_slot(ll, BN_SCALE), bn_slot(ll, BN_SHIFT), nullptr);
-}
 
 // gradient assembly: fixed-order sum of the per-workgroup partials (+ the dense layer's, which come
 // from the side stream), structural mask, optionally fused with the Adam update
@@ -405,9 +223,7 @@ int assemble_range(mww_ctx* c, int B, const GradReduceArgs& ga, int64_t lo, int6
   GradFinalArgs a;
   memset(&a, 0, sizeof(a));
   if (tail_dense && c->o_dense_w >= lo && c->o_dense_w < hi) {
-    Layer& ll = c->L[c->d.n_blocks - 1];
-    a.dense = DenseGradArgs{ll.p, bn_slot(ll, BN_SCALE), bn_slot(ll, BN_SHIFT), c->dz, nullptr, B, c->t_last * c->c_last,
-                            c->c_last, 0, (B + kDenseChunks - 1) / kDenseChunks, nullptr, nullptr, nullptr, nullptr, 0, 0, c->st_bf16 ? 1 : 0};
+    a.dense = dense_args(c, B, c->tail_src, nullptr, 0);
     segs.push_back(FinalSegment{nullptr, B, 0, c->t_last * c->c_last + 1, (int)c->o_dense_w, kSegDense, 0});
   }
   std::sort(segs.begin(), segs.end(), [](const FinalSegment& x, const FinalSegment& y) { return x.dst < y.dst; });
@@ -511,152 +327,31 @@ int enqueue_grad_assembly(mww_ctx* c, int B, GradReduceArgs& ga, bool fuse_adam,
 
 }  // namespace mww
 
-namespace {
+namespace mww {
 
-// the weight-gradient partial rows of blocks [b0, b1)
-void block_segments(mww_ctx* c, int gbwd, int b0, int b1, GradReduceArgs* ga) {
-  memset(ga, 0, sizeof(*ga));
-  for (int i = b0; i < b1; ++i) {
-    Layer& l = c->L[i];
-    GradSegment s;
-    s.part = l.grad_part;
-    s.G = gbwd;
-    s.stride = l.grad_part_stride;
-    s.n = l.grad_part_stride;
-    s.dst = (int)(i == 0 ? c->o_conv1 : l.o_dw_w);
-    ga->seg[ga->nseg++] = s;
-  }
-}
-
-int enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
-  if (c->generic) return g_enqueue_backward(c, B, fuse_adam);
+// first launch of the block engine's backward pass after a train step's head: BN_L's backward finalize, the dense-weight
+// gradient of c->tail_src and (tail_metrics) the metric update as roles of one launch
+int enqueue_head_tail(mww_ctx* c, int B, const BnBwdFinalizeArgs& fin) {
+  const int dchunk = (B + kDenseChunks - 1) / kDenseChunks;
+  HeadTailArgs ht;
+  ht.fin = fin;
+  ht.dense = dense_args(c, B, c->tail_src, c->dwd_part, c->dwd_stride);
+  ht.met = MetricsArgs{c->prob, c->y_cur, c->metrics, B, c->bce_clipped ? nullptr : c->z};
+  ht.n_fin = fin.C;
+  ht.ndx = (ht.dense.n + 1 + kThreads - 1) / kThreads;
+  ht.ndy = (B + dchunk - 1) / dchunk;
+  ht.do_metrics = c->tail_metrics ? 1 : 0;
+  c->metric_launches += ht.do_metrics;
   Launcher lp{c};
-  const mww_mixednet_desc& d = c->d;
-  const int nb = d.n_blocks;
-  const int gbwd = std::min(B, c->grid_bwd);
-  const int ghead = std::min(B, c->grid_head);
-  const bool inl = c->bn_inline && !(c->hook && c->sync_bn);
-  // data-parallel step: the gradient of [blocks >= split, dense] (a contiguous tail of the flat vector) is final once
-  // block `split`'s backward kernel is enqueued; it is assembled and handed to the exchange hook there, so that the
-  // all-reduce runs next to the remaining backward kernels.  Needs the statistics hand-over (the BN
-  // gamma / beta gradients of a block are then written by that block's own backward kernel).
-  const int split = nb >= 3 ? nb - 2 : 0;
-  const bool bucketed = fuse_adam && c->hook && c->reduce_grads && !c->sync_bn && inl && c->tail_in_reduce && c->grad_buckets == 2 && split > 0;
-  for (int i = nb - 1; i >= 0; --i) {
-    Layer& l = c->L[i];
-    const bool last = (i == nb - 1);
-    // BN_i's backward sums: the last block's come from the head kernel's partial rows (folded by head_tail);
-    // the others arrive in accumulator rows and are folded by this block's backward kernel
-    const bool fold_here = inl && (!last || c->tail_in_reduce);
-    StatSource ss{nullptr, 0, 0.f, 1.0f};
-    if (!fold_here) {
-      int rcs = exchange_stats(c, lp, "bn_gstat_exchange", i, l.gstat_part, last ? ghead : gbwd, l.cout, 1,
-                               1.0f / ((float)B * (float)l.tout), &ss);
-      if (rcs) return rcs;
-    }
-    BnBwdFinalizeArgs f{ss.part, ss.G, l.cout, ss.inv_n,
-                        c->params + l.o_gamma, bn_slot(l, BN_RSTD), bn_slot(l, BN_C1), bn_slot(l, BN_MG),
-                        bn_slot(l, BN_MGX), c->grads + l.o_gamma, c->grads + l.o_beta, ss.dscale};
-    BnGradFoldArgs gf;
-    memset(&gf, 0, sizeof(gf));
-    if (fold_here) {
-      gf.acc = l.gacc_cur;
-      gf.inv_n = 1.0f / ((float)B * (float)l.tout);
-      gf.dscale = 1.0f;
-      gf.gamma = c->params + l.o_gamma;
-      gf.c1 = bn_slot(l, BN_C1);
-      gf.mg = bn_slot(l, BN_MG);
-      gf.mgx = bn_slot(l, BN_MGX);
-      gf.dgamma = c->grads + l.o_gamma;
-      gf.dbeta = c->grads + l.o_beta;
-    }
-    if (fold_here) {
-      // no launch
-    } else if (last && c->tail_pending) {
-      c->tail_pending = false;
-      const int dchunk = (B + kDenseChunks - 1) / kDenseChunks;
-      HeadTailArgs ht;
-      ht.fin = f;
-      ht.dense = DenseGradArgs{l.p, bn_slot(l, BN_SCALE), bn_slot(l, BN_SHIFT), c->dz, c->dwd_part, B, c->t_last * c->c_last,
-                               c->c_last, c->dwd_stride, dchunk, nullptr, nullptr, nullptr, nullptr, 0, 0, c->st_bf16 ? 1 : 0};
-      ht.met = MetricsArgs{c->prob, c->y_cur, c->metrics, B, c->bce_clipped ? nullptr : c->z};
-      ht.n_fin = l.cout;
-      ht.ndx = (ht.dense.n + 1 + kThreads - 1) / kThreads;
-      ht.ndy = (B + dchunk - 1) / dchunk;
-      ht.do_metrics = c->tail_metrics ? 1 : 0;
-      c->metric_launches += ht.do_metrics;
-      lp.begin("head_tail");
-      hipLaunchKernelGGL(head_tail_kernel, dim3(ht.n_fin + ht.ndx * ht.ndy + ht.do_metrics), dim3(kThreads), 0, c->stream, ht);
-      lp.end();
-    } else {
-      lp.begin("bn_bwd_finalize", i);
-      hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(l.cout), dim3(kThreads), 0, c->stream, f);
-      lp.end();
-    }
-    if (i > 0) {
-      Layer& pl = c->L[i - 1];
-      BwdBlockArgs a;
-      a.in = pl.p;
-      a.in_scale = bn_slot(pl, BN_SCALE);
-      a.in_shift = bn_slot(pl, BN_SHIFT);
-      a.in_mean = bn_slot(pl, BN_MEAN);
-      a.in_rstd = bn_slot(pl, BN_RSTD);
-      a.pk = l.p;
-      a.gk = l.g;
-      a.k_mean = bn_slot(l, BN_MEAN);
-      a.k_rstd = bn_slot(l, BN_RSTD);
-      a.k_c1 = bn_slot(l, BN_C1);
-      a.k_mg = bn_slot(l, BN_MG);
-      a.k_mgx = bn_slot(l, BN_MGX);
-      a.k_scale = bn_slot(l, BN_SCALE);
-      a.k_shift = bn_slot(l, BN_SHIFT);
-      a.wd = c->params + c->o_dense_w;
-      a.dz = c->dz;
-      a.dw_w = c->params + l.o_dw_w;
-      a.dw_b = c->params + l.o_dw_b;
-      a.pw_w = c->params + l.o_pw_w;
-      a.g_out = pl.g;
-      a.gstat_part = pl.gstat_part;
-      a.grad_part = l.grad_part;
-      a.B = B;
-      a.Tin = l.tin;
-      a.Tout = l.tout;
-      a.ablate = c->ablate;
-      a.phase_clk = c->phase_clk + (size_t)(2 * i + 1) * 2048 * kClkSlots;
-      a.gacc = StatAcc{nullptr, nullptr};
-      if (inl) {
-        a.gacc.acc = pl.gacc[c->gpar];
-        a.gacc.clear = pl.gacc[c->gpar ^ 1];
-        pl.gacc_cur = a.gacc.acc;
-      }
-      a.gfold = gf;
-      lp.begin("bwd_block", i);
-      int rc = launch_bwd_block(c, l.cin, l.cout, l.k, last, a, gbwd);
-      lp.end();
-      if (rc) return rc;
-      if (bucketed && i == split) {
-        GradReduceArgs gb;
-        block_segments(c, gbwd, split, nb, &gb);
-        rc = enqueue_grad_assembly(c, B, gb, fuse_adam, l.o_dw_w, c->P, false);
-        if (rc) return rc;
-      }
-    } else {
-      if (last) return fail(MWW_ERR_UNSUPPORTED, "single-block models are not supported");
-      BwdFirstArgs a{c->x, c->a0, l.p, l.g, bn_slot(l, BN_MEAN), bn_slot(l, BN_RSTD), bn_slot(l, BN_C1),
-                     bn_slot(l, BN_MG), bn_slot(l, BN_MGX), c->params + l.o_dw_w, c->params + l.o_dw_b,
-                     c->params + l.o_pw_w, l.grad_part, B, d.frames, l.tout, gf, x_gather(c), c->ablate,
-                     c->phase_clk + (size_t)(2 * i + 1) * 2048 * kClkSlots};
-      lp.begin("bwd_block", i);
-      int rc = launch_bwd_first(c, d.conv1_kernel, d.conv1_filters, l.cout, l.k, d.conv1_stride, a, gbwd);
-      lp.end();
-      if (rc) return rc;
-    }
-  }
-  if (inl) c->gpar ^= 1;
-  GradReduceArgs ga;
-  block_segments(c, gbwd, 0, bucketed ? split : nb, &ga);
-  return enqueue_grad_assembly(c, B, ga, fuse_adam, 0, bucketed ? c->L[split].o_dw_w : c->P, true);
+  lp.begin("head_tail");
+  hipLaunchKernelGGL(head_tail_kernel, dim3(ht.n_fin + ht.ndx * ht.ndy + ht.do_metrics), dim3(kThreads), 0, c->stream, ht);
+  lp.end();
+  return MWW_OK;
 }
+
+}  // namespace mww
+
+namespace {
 
 int enqueue_adam(mww_ctx* c) {
   Launcher lp{c};
@@ -713,23 +408,14 @@ float adam_alpha(float lr, int64_t t) {
 
 int step_sequence(mww_ctx* c, int B, int flags) {
   c->metric_launches = 0;
-  int rc = enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS));
+  int rc = c->model->enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS));
   if (rc) return rc;
-  rc = enqueue_backward(c, B, !(flags & MWW_STEP_NO_APPLY));
+  rc = c->model->enqueue_backward(c, B, !(flags & MWW_STEP_NO_APPLY));
   if (rc) return rc;
   // the metric state has one writer per step (kernels_head.hip.h MetricState): a second launch with the role would lose counts
   if (c->metric_launches > 1) return fail(MWW_ERR_STATE, "internal: more than one launch of this step carries the metric update");
   return MWW_OK;
 }
-
-template <typename T>
-int dev_alloc(T** p, size_t n) {
-  HIPCHK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
-  HIPCHK(hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(T)));
-  return MWW_OK;
-}
-
-struct BnSlots { int64_t o_gamma, o_beta, o_mv; int n; };
 
 // mask = 1 everywhere, direct flags on the BN gamma/beta slots; moving variance starts at 1
 int init_defaults(mww_ctx* c, const std::vector<BnSlots>& bn) {
@@ -751,51 +437,44 @@ int init_defaults(mww_ctx* c, const std::vector<BnSlots>& bn) {
 
 // buffers, mailboxes and streams that do not depend on the topology (needs P, S, t_last, c_last)
 int alloc_common(mww_ctx* c) {
-  const mww_mixednet_desc& d = c->d;
-  const size_t mb = (size_t)d.max_batch;
-  int rc = 0;
-#define A(call) if ((rc = (call)) != 0) return rc;
-#define H(call) if ((call) != hipSuccess) return fail(MWW_ERR_HIP, #call);
-  A(dev_alloc(&c->params, c->P));
-  A(dev_alloc(&c->grads, c->P));
-  A(dev_alloc(&c->adam_m, c->P));
-  A(dev_alloc(&c->adam_v, c->P));
-  A(dev_alloc(&c->mask, c->P));
-  A(dev_alloc(&c->direct, c->P));
-  A(dev_alloc(&c->bn_state, c->S));
-  A(dev_alloc(&c->x, mb * d.frames * MWW_FEATURE_BINS));
-  A(dev_alloc(&c->y, mb));
-  A(dev_alloc(&c->sw, mb));
+  const size_t mb = (size_t)c->max_batch;
+  MWW_TRY(dev_alloc(&c->params, c->P));
+  MWW_TRY(dev_alloc(&c->grads, c->P));
+  MWW_TRY(dev_alloc(&c->adam_m, c->P));
+  MWW_TRY(dev_alloc(&c->adam_v, c->P));
+  MWW_TRY(dev_alloc(&c->mask, c->P));
+  MWW_TRY(dev_alloc(&c->direct, c->P));
+  MWW_TRY(dev_alloc(&c->bn_state, c->S));
+  MWW_TRY(dev_alloc(&c->x, mb * c->frames * MWW_FEATURE_BINS));
+  MWW_TRY(dev_alloc(&c->y, mb));
+  MWW_TRY(dev_alloc(&c->sw, mb));
   c->y_cur = c->y;
   c->sw_cur = c->sw;
-  A(dev_alloc(&c->z, mb));
-  A(dev_alloc(&c->prob, mb));
-  A(dev_alloc(&c->dz, mb));
-  A(dev_alloc(&c->loss_part, mb));
-  A(dev_alloc(&c->dwd_part, (size_t)kDenseChunks * c->dwd_stride));
-  A(dev_alloc(&c->metrics, 1));
-  A(dev_alloc(&c->phase_clk, (size_t)2 * MWW_MAX_BLOCKS * 2048 * kClkSlots));
+  MWW_TRY(dev_alloc(&c->z, mb));
+  MWW_TRY(dev_alloc(&c->prob, mb));
+  MWW_TRY(dev_alloc(&c->dz, mb));
+  MWW_TRY(dev_alloc(&c->loss_part, mb));
+  MWW_TRY(dev_alloc(&c->dwd_part, (size_t)kDenseChunks * c->dwd_stride));
+  MWW_TRY(dev_alloc(&c->metrics, 1));
   c->mail_off_masks = mb * sizeof(mww_window);
   c->mail_off_y = c->mail_off_masks + mb * kMaxMasks * 2 * sizeof(int);
   c->mail_off_sw = c->mail_off_y + mb * sizeof(float);
   c->mail_off_hyper = c->mail_off_sw + mb * sizeof(float);
   c->mail_bytes = c->mail_off_hyper + 16;
   for (int i = 0; i < kRing; ++i) {
-    H(hipHostMalloc((void**)&c->mail_host[i], c->mail_bytes, hipHostMallocMapped));
+    HIPCHK(hipHostMalloc((void**)&c->mail_host[i], c->mail_bytes, hipHostMallocMapped));
     memset(c->mail_host[i], 0, c->mail_bytes);
-    H(hipHostGetDevicePointer((void**)&c->mail_dev[i], c->mail_host[i], 0));
-    H(hipEventCreateWithFlags(&c->mail_ev[i], hipEventDisableTiming));
+    HIPCHK(hipHostGetDevicePointer((void**)&c->mail_dev[i], c->mail_host[i], 0));
+    HIPCHK(hipEventCreateWithFlags(&c->mail_ev[i], hipEventDisableTiming));
   }
-  H(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
   for (int i = 0; i < kRing; ++i) {
-    A(dev_alloc(&c->mail_hbm[i], c->mail_bytes));
-    H(hipEventCreateWithFlags(&c->ev_copy[i], hipEventDisableTiming));
+    MWW_TRY(dev_alloc(&c->mail_hbm[i], c->mail_bytes));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_copy[i], hipEventDisableTiming));
   }
-  H(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-  H(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-  H(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-#undef A
-#undef H
+  HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+  HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   return MWW_OK;
 }
 
@@ -816,22 +495,52 @@ int open_device(mww_ctx* c, int device, void* stream) {
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->own_stream = true;
   }
-  c->grid_fwd = c->n_cu * 4;
-  c->grid_bwd = c->n_cu * 2;
-  bool wide64 = false;
-  for (int i = 0; i < c->d.n_blocks; ++i) wide64 = wide64 || c->d.block_filters[i] > 48;
-  if (!c->generic && wide64) {
-    // 64-wide blocks: the backward kernels fit once per CU (LDS), the forward kernels twice - grids of resident workgroups
-    // only, no second dispatch round (tools/gpu_r3g.sh: notebook topology grid sweep)
-    c->grid_fwd = c->n_cu * 2;
-    c->grid_bwd = c->n_cu;
-  }
   c->grid_head = c->n_cu * 2;   // one window per workgroup at a time, two resident per CU (177 VGPRs): measured 13.5 us vs 15.4 (x4) / 17.4 (x1)
-  c->grid_g = c->n_cu * 3;   // measured on the Inception step: 3 workgroups per CU and launch (roles share them) beats 2 and 4
   return MWW_OK;
 }
 
 }  // namespace
+
+namespace mww {
+
+int tensor_alloc(Tensor* t, int cout, size_t rows_fwd, size_t rows_bwd, size_t grad_part) {
+  MWW_TRY(dev_alloc(&t->stat_part, rows_fwd * 2 * cout));
+  MWW_TRY(dev_alloc(&t->gstat_part, rows_bwd * 2 * cout));
+  MWW_TRY(dev_alloc(&t->grad_part, grad_part));
+  MWW_TRY(dev_alloc(&t->bn, (size_t)9 * cout));
+  for (int par = 0; par < 2; ++par) {
+    MWW_TRY(dev_alloc(&t->facc[par], (size_t)kStatRows * 2 * cout));
+    MWW_TRY(dev_alloc(&t->gacc[par], (size_t)kStatRows * 2 * cout));
+  }
+  return MWW_OK;
+}
+
+void tensor_free(Tensor* t) {
+  void* all[] = {t->p, t->g, t->stat_part, t->gstat_part, t->grad_part, t->bn, t->facc[0], t->facc[1], t->gacc[0], t->gacc[1]};
+  for (void* p : all) if (p) (void)hipFree(p);
+}
+
+int Model::set_dropout_mask(mww_ctx*, const uint8_t*, int) { return fail(MWW_ERR_INVALID, "context has no dropout layer"); }
+
+// plan (the caller's) -> device -> layout -> the core's buffers -> the model's -> defaults
+int create_context(Model* m, int frames, int max_batch, int device, void* stream, mww_ctx** out) {
+  mww_ctx* c = new mww_ctx();
+  c->model = m;
+  c->frames = frames;
+  c->max_batch = max_batch;
+  std::vector<BnSlots> bn;
+  int rc = open_device(c, device, stream);
+  if (!rc) rc = m->layout(c);
+  if (!rc) rc = alloc_common(c);
+  if (!rc) rc = m->alloc(c, &bn);
+  if (!rc) rc = init_defaults(c, bn);
+  if (rc) { mww_destroy(c); return rc; }
+  HIPCHK(hipDeviceSynchronize());
+  *out = c;
+  return MWW_OK;
+}
+
+}  // namespace mww
 
 // ====================================================================================== C ABI
 extern "C" {
@@ -855,179 +564,16 @@ int mww_block_kernels_cover(const mww_mixednet_desc* desc, int bf16) {
 
 int mww_create(const mww_mixednet_desc* desc, int device, void* stream, mww_ctx** out) {
   if (!desc || !out) return fail(MWW_ERR_INVALID, "null argument");
-  const mww_mixednet_desc& d = *desc;
-  if (d.n_blocks < 2 || d.n_blocks > MWW_MAX_BLOCKS) return fail(MWW_ERR_INVALID, "n_blocks must be in [2, 8]");
-  if (d.conv1_stride < 1 || d.frames < d.conv1_kernel) return fail(MWW_ERR_INVALID, "bad first-conv stride / kernel");
-  if (d.conv1_filters <= 0) return fail(MWW_ERR_UNSUPPORTED, "first_conv_filters == 0 is not implemented");
-  if (d.max_batch <= 0 || d.frames <= 0) return fail(MWW_ERR_INVALID, "frames and max_batch must be positive");
-  std::string why;
-  if (!shape_supported(d, &why)) return fail(MWW_ERR_UNSUPPORTED, why);
-  mww_ctx* c = new mww_ctx();
-  c->d = d;
-  {
-    int rco = open_device(c, device, stream);
-    if (rco) { delete c; return rco; }
-  }
-  // ---- parameter layout
-  int64_t off = 0, soff = 0;
-  c->o_conv1 = off;
-  off += (int64_t)d.conv1_kernel * MWW_FEATURE_BINS * d.conv1_filters;
-  int t = (d.frames - d.conv1_kernel) / d.conv1_stride + 1, ch = d.conv1_filters;
-  c->L.resize(d.n_blocks);
-  for (int i = 0; i < d.n_blocks; ++i) {
-    Layer& l = c->L[i];
-    l.cin = ch;
-    l.cout = d.block_filters[i];
-    l.k = d.block_kernel[i];
-    l.tin = t;
-    l.tout = t - (l.k - 1);
-    if (l.tout <= 0) { mww_destroy(c); return fail(MWW_ERR_INVALID, "spectrogram too short for the kernel sizes"); }
-    l.o_dw_w = off; off += (int64_t)l.k * l.cin;
-    l.o_dw_b = off; off += l.cin;
-    l.o_pw_w = off; off += (int64_t)l.cin * l.cout;
-    l.o_gamma = off; off += l.cout;
-    l.o_beta = off; off += l.cout;
-    l.o_mm = soff; soff += l.cout;
-    l.o_mv = soff; soff += l.cout;
-    t = l.tout;
-    ch = l.cout;
-  }
-  c->t_last = t;
-  c->c_last = ch;
-  c->o_dense_w = off; off += (int64_t)t * ch;
-  c->o_dense_b = off; off += 1;
-  c->P = off;
-  c->S = soff;
-  c->dwd_stride = t * ch + 4;
-  const size_t mb = (size_t)d.max_batch;
-  // partial rows are sized for the largest grids the "grid_fwd" / "grid_bwd" / "grid_head" options accept, not for this
-  // topology's defaults (until round 3 a 64-wide context - defaults 2 / 1 workgroups per CU - overran them when the options
-  // asked for more: found by the shape fuzz on the emulator)
-  const int gmax_f = c->n_cu * 4, gmax_b = c->n_cu * 2;
-  int rc = 0;
-#define A(call) if ((rc = (call)) != 0) { mww_destroy(c); return rc; }
-  A(alloc_common(c));
-  A(dev_alloc(&c->a0, mb * c->L[0].tin * d.conv1_filters));
-#ifndef MWW_G_PINGPONG
-#define MWW_G_PINGPONG 1
-#endif
-  // g_k (the gradient at block k's BN output) is written by the backward launch of block k+1 and read by block k's, once: two
-  // buffers taken in turn hold them all (35 MB each at the headline batch instead of one per block - address space the
-  // memory-side cache does not have to give up activations for)
-  if (MWW_G_PINGPONG) {
-    size_t need[2] = {0, 0};
-    for (int i = 0; i < d.n_blocks; ++i) need[i & 1] = std::max(need[i & 1], mb * c->L[i].tout * c->L[i].cout);
-    for (int par = 0; par < 2; ++par)
-      if (need[par]) A(dev_alloc(&c->gbuf[par], need[par]));
-  }
-  for (int i = 0; i < d.n_blocks; ++i) {
-    Layer& l = c->L[i];
-    A(dev_alloc(&l.p, mb * l.tout * l.cout));
-    if (MWW_G_PINGPONG) l.g = c->gbuf[i & 1];
-    else A(dev_alloc(&l.g, mb * l.tout * l.cout));
-    A(dev_alloc(&l.stat_part, (size_t)gmax_f * 2 * l.cout));
-    A(dev_alloc(&l.gstat_part, (size_t)std::max(gmax_b, c->n_cu * 4) * 2 * l.cout));
-    for (int par = 0; par < 2; ++par) {
-      A(dev_alloc(&l.facc[par], (size_t)kStatRows * 2 * l.cout));
-      A(dev_alloc(&l.gacc[par], (size_t)kStatRows * 2 * l.cout));
-    }
-    l.grad_part_stride = (l.k + 1) * l.cin + l.cin * l.cout;
-    if (i == 0) l.grad_part_stride += d.conv1_kernel * MWW_FEATURE_BINS * d.conv1_filters;
-    A(dev_alloc(&l.grad_part, (size_t)gmax_b * l.grad_part_stride));
-    A(dev_alloc(&l.bn, (size_t)9 * l.cout));
-  }
-  {
-    std::vector<BnSlots> bn;
-    for (int i = 0; i < d.n_blocks; ++i) bn.push_back(BnSlots{c->L[i].o_gamma, c->L[i].o_beta, c->L[i].o_mv, c->L[i].cout});
-    A(init_defaults(c, bn));
-  }
-#undef A
-  HIPCHK(hipDeviceSynchronize());
-  *out = c;
-  return MWW_OK;
+  Model* m = nullptr;
+  MWW_TRY(plan_mixednet(*desc, &m));
+  return create_context(m, desc->frames, desc->max_batch, device, stream, out);
 }
 
 int mww_create_convnet(const mww_convnet_desc* desc, int device, void* stream, mww_ctx** out) {
   if (!desc || !out) return fail(MWW_ERR_INVALID, "null argument");
-  const mww_convnet_desc& d = *desc;
-  GPlan plan;
-  {
-    int rcp = g_plan_convnet(d, &plan);
-    if (rcp) return rcp;
-  }
-  int64_t off = plan.P;
-  const int64_t soff = plan.S;
-
-  mww_ctx* c = new mww_ctx();
-  memset(&c->d, 0, sizeof(c->d));
-  c->d.frames = d.frames;
-  c->d.max_batch = d.max_batch;
-  c->generic = true;
-  c->dropout = d.dropout;
-  c->G = std::move(plan.ops);
-  c->g_chunks = plan.chunks;
-  c->g_inline_ok = plan.inline_ok;
-  {
-    int rco = open_device(c, device, stream);
-    if (rco) { mww_destroy(c); return rco; }
-  }
-  GOp& lo = c->G.back();
-  c->t_last = lo.tout;
-  c->c_last = lo.cout;
-  if (lo.tout > 1 && (d.head_attention || d.head_pool)) {   // mixednet.py:362: only if more than one frame remains
-    if (d.head_pool < 0 || d.head_pool > 2) { mww_destroy(c); return fail(MWW_ERR_INVALID, "head_pool must be 0, 1 or 2"); }
-    if (d.head_attention && lo.tout < 4) { mww_destroy(c); return fail(MWW_ERR_INVALID, "spatial attention needs at least 4 frames"); }
-    if (d.dropout > 0.f) { mww_destroy(c); return fail(MWW_ERR_UNSUPPORTED, "dropout with the attention / pooled head"); }
-    c->head2 = true;
-    c->head_att = d.head_attention != 0;
-    c->head_pool = d.head_pool;
-    const int to = lo.tout - (c->head_att ? 3 : 0);
-    c->t_last = c->head_pool ? 1 : to;
-    if (c->head_att) { c->o_att = off; off += 8; }
-    c->lds_head2 = ((size_t)lo.tout * (lo.cout | 1) + 7 * (size_t)lo.tout + 3 * (size_t)lo.cout) * sizeof(float);
-    if (c->lds_head2 > kMaxDynLds) { mww_destroy(c); return fail(MWW_ERR_UNSUPPORTED, "window does not fit the head's LDS tile"); }
-  }
-  c->o_dense_w = off; off += (int64_t)c->t_last * lo.cout;
-  c->o_dense_b = off; off += 1;
-  c->P = off;
-  c->S = soff;
-  c->dwd_stride = c->t_last * lo.cout + 4;
-  const size_t mb = (size_t)d.max_batch;
-  const int gmax = c->n_cu * 4;
-  int rc = 0;
-#define A(call) if ((rc = (call)) != 0) { mww_destroy(c); return rc; }
-  A(alloc_common(c));
-  A(dev_alloc(&c->keep, mb * lo.tout * lo.cout));
-  if (c->head2) {
-    A(dev_alloc(&c->hact, mb * c->t_last * lo.cout));
-    A(dev_alloc(&c->watt_part, (size_t)gmax * 8));
-  }
-  std::vector<BnSlots> bn;
-  for (GOp& o : c->G) {
-    A(dev_alloc(&o.p, mb * o.tout * o.cout + (size_t)o.planes * kPlanePad));
-    A(dev_alloc(&o.g, mb * o.tout * o.cout + (size_t)o.planes * kPlanePad));
-    A(dev_alloc(&o.stat_part, (size_t)gmax * 2 * o.cout));
-    A(dev_alloc(&o.gstat_part, (size_t)gmax * 2 * o.cout));
-    A(dev_alloc(&o.grad_part, (size_t)gmax * o.k * (o.kind == MWW_OP_DEPTHWISE ? 1 : o.cin) * o.cout));   // ("grid_graph" may be raised to gmax)
-    A(dev_alloc(&o.bn, (size_t)9 * o.cout));
-    for (int par = 0; par < 2; ++par) {
-      A(dev_alloc(&o.facc[par], (size_t)kStatRows * 2 * o.cout));
-      A(dev_alloc(&o.gacc[par], (size_t)kStatRows * 2 * o.cout));
-    }
-    if (o.norm == MWW_NORM_BN) bn.push_back(BnSlots{o.o_gamma, o.o_beta, o.o_mv, o.slots});
-    else if (o.norm == MWW_NORM_BIAS) bn.push_back(BnSlots{o.o_beta, o.o_beta, -1, o.cout});   // bias gradient is written directly too
-  }
-  {
-    A(dev_alloc(&c->ones, (size_t)kThreads));
-    A(dev_alloc(&c->zeros, (size_t)kThreads));
-    std::vector<float> one((size_t)kThreads, 1.0f);
-    if (hipMemcpy(c->ones, one.data(), one.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { mww_destroy(c); return fail(MWW_ERR_HIP, "hipMemcpy"); }
-  }
-  A(init_defaults(c, bn));
-#undef A
-  HIPCHK(hipDeviceSynchronize());
-  *out = c;
-  return MWW_OK;
+  Model* m = nullptr;
+  MWW_TRY(plan_convnet(*desc, &m));
+  return create_context(m, desc->frames, desc->max_batch, device, stream, out);
 }
 
 int mww_set_allreduce_hook(mww_ctx* c, mww_allreduce_fn fn, void* user, int world_size, int sync_bn, int reduce_grads) {
@@ -1043,8 +589,7 @@ int mww_set_allreduce_hook(mww_ctx* c, mww_allreduce_fn fn, void* user, int worl
   if (c->sync_bn && !c->sync_buf) {
     int64_t off = 0;
     c->sync_off.clear();
-    if (c->generic) for (auto& o : c->G) { c->sync_off.push_back(off); off += 4 * (int64_t)o.cout; }
-    else for (auto& l : c->L) { c->sync_off.push_back(off); off += 4 * (int64_t)l.cout; }
+    for (int w : c->model->stat_widths()) { c->sync_off.push_back(off); off += 4 * (int64_t)w; }
     int rc = dev_alloc(&c->sync_buf, (size_t)off);
     if (rc) return rc;
   }
@@ -1185,19 +730,8 @@ int mww_allreduce_init(mww_ctx* c, int rank, int world, const void* unique_id, i
 }
 
 int mww_set_dropout_mask(mww_ctx* c, const uint8_t* keep, int B) {
-  if (!c || !c->generic) return fail(MWW_ERR_INVALID, "context has no dropout layer");
-  if (!keep) { c->keep_explicit = false; return MWW_OK; }
-  if (B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
-  if (!(c->dropout > 0.f)) return fail(MWW_ERR_STATE, "model was created with dropout = 0");
-  const size_t n = (size_t)B * c->t_last * c->c_last;
-  std::vector<float> h(n);
-  const float sc = 1.0f / (1.0f - c->dropout);
-  for (size_t i = 0; i < n; ++i) h[i] = keep[i] ? sc : 0.f;
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(c->keep, h.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->keep_explicit = true;
-  return MWW_OK;
+  if (!c) return fail(MWW_ERR_INVALID, "context has no dropout layer");
+  return c->model->set_dropout_mask(c, keep, B);
 }
 
 void mww_destroy(mww_ctx* c) {
@@ -1208,23 +742,8 @@ void mww_destroy(mww_ctx* c) {
   for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
   for (auto& e : c->prof) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   void* flat[] = {c->params, c->grads, c->adam_m, c->adam_v, c->mask, c->direct, c->bn_state, c->x, c->y, c->sw,
-                  c->z, c->prob, c->dz, c->loss_part, c->dwd_part, c->metrics, c->phase_clk, c->a0};
+                  c->z, c->prob, c->dz, c->loss_part, c->dwd_part, c->metrics, c->sync_buf};
   for (void* p : flat) if (p) (void)hipFree(p);
-  for (auto& l : c->L) {
-    void* lp[] = {l.p, (c->gbuf[0] || c->gbuf[1]) ? nullptr : l.g, l.stat_part, l.gstat_part, l.grad_part, l.bn, l.facc[0], l.facc[1], l.gacc[0], l.gacc[1]};
-    for (void* p : lp) if (p) (void)hipFree(p);
-  }
-  for (float* p : c->gbuf) if (p) (void)hipFree(p);
-  for (auto& o : c->G) {
-    void* op[] = {o.p, o.g, o.stat_part, o.gstat_part, o.grad_part, o.bn, o.facc[0], o.facc[1], o.gacc[0], o.gacc[1]};
-    for (void* p : op) if (p) (void)hipFree(p);
-  }
-  if (c->sync_buf) (void)hipFree(c->sync_buf);
-  if (c->hact) (void)hipFree(c->hact);
-  if (c->watt_part) (void)hipFree(c->watt_part);
-  if (c->ones) (void)hipFree(c->ones);
-  if (c->zeros) (void)hipFree(c->zeros);
-  if (c->keep) (void)hipFree(c->keep);
   for (int i = 0; i < MWW_MAX_STORES; ++i) if (c->store[i]) (void)hipFree(c->store[i]);
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
   for (int i = 0; i < kRing; ++i) {
@@ -1236,6 +755,7 @@ void mww_destroy(mww_ctx* c) {
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+  delete c->model;   // (its own buffers)
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1316,10 +836,10 @@ int mww_upload_store(mww_ctx* c, int id, const void* data, int64_t n, int dtype)
 }
 
 int mww_assemble_batch(mww_ctx* c, const mww_window* win, const int32_t* masks, int B, int ntm, int nfm) {
-  if (!c || !win || B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (!c || !win || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
   const int nm = ntm + nfm;
   if (ntm < 0 || nfm < 0 || nm > kMaxMasks || (nm > 0 && !masks)) return fail(MWW_ERR_INVALID, "too many masks");
-  const int T = c->d.frames;
+  const int T = c->frames;
   for (int j = 0; j < B; ++j) {
     const mww_window& w = win[j];
     if (w.store < 0 || w.store >= MWW_MAX_STORES || !c->store[w.store]) return fail(MWW_ERR_INVALID, "window refers to a store that was not uploaded");
@@ -1354,11 +874,7 @@ int mww_assemble_batch(mww_ctx* c, const mww_window* win, const int32_t* masks, 
   a.nfm = nfm;
   a.split = c->asm_split;
   {
-    const int per_fwd = (B + std::min(B, c->grid_fwd) - 1) / std::min(B, c->grid_fwd);
-    const int per_bwd = (B + std::min(B, c->grid_bwd) - 1) / std::min(B, c->grid_bwd);
-    // (conv/BN graphs: the stem's launches check their own grids and write x out themselves if a workgroup would own too many windows)
-    const bool lazy_ok = c->generic ? g_stem_gathers(c) : (per_fwd <= kXMaxSamples && per_bwd <= kXMaxSamples);
-    if (c->fused_input && lazy_ok && T <= 32 * kXRowWords && nm <= kXMaxMasks) {
+    if (c->fused_input && c->model->lazy_ok(c, B) && T <= 32 * kXRowWords && nm <= kXMaxMasks) {
       // descriptor-only batch: the first block's kernels gather from the stores (the labels / weights that
       // arrived in this mailbox are read in place)
       if (a.n_targets) {
@@ -1395,25 +911,25 @@ int mww_assemble_batch(mww_ctx* c, const mww_window* win, const int32_t* masks, 
 }
 
 int mww_set_batch(mww_ctx* c, const float* hx, int B) {
-  if (!c || !hx || B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (!c || !hx || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
   HIPCHK(hipSetDevice(c->device));
   int rc = bring_targets(c);
   if (rc) return rc;
   c->x_lazy = false;
-  rc = copy_in(c, c->x, hx, (size_t)B * c->d.frames * MWW_FEATURE_BINS * sizeof(float));
+  rc = copy_in(c, c->x, hx, (size_t)B * c->frames * MWW_FEATURE_BINS * sizeof(float));
   if (!rc) c->have_batch = B;
   return rc;
 }
 int mww_get_batch(mww_ctx* c, float* hx, int B) {
-  if (!c || !hx || B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (!c || !hx || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
   HIPCHK(hipSetDevice(c->device));
   int rc = materialise_x(c);
   if (rc) return rc;
-  return copy_out(c, hx, c->x, (size_t)B * c->d.frames * MWW_FEATURE_BINS * sizeof(float));
+  return copy_out(c, hx, c->x, (size_t)B * c->frames * MWW_FEATURE_BINS * sizeof(float));
 }
 
 int mww_set_targets(mww_ctx* c, const float* hy, const float* hw, int B) {
-  if (!c || !hy || !hw || B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (!c || !hy || !hw || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
   HIPCHK(hipSetDevice(c->device));
   int rc = mail_begin(c);
   if (rc) return rc;
@@ -1443,7 +959,7 @@ int mww_assemble_prefetched(mww_ctx* c, mww_prefetcher* p, float* out_labels, fl
 }
 
 int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
-  if (!c || B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (!c || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
   if (c->have_batch < B || c->have_targets < B) return fail(MWW_ERR_STATE, "train step needs a batch and targets of at least B rows");
   HIPCHK(hipSetDevice(c->device));
   int rc = flush_targets(c);
@@ -1458,25 +974,27 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
     rc = push_hyper(c, adam_alpha(lr, c->step), (c->hook && c->reduce_grads) ? 1.0f / (float)c->world : 1.0f);
     if (rc) return rc;
   }
-  const bool gen_dropout = c->generic && c->dropout > 0.f && !c->keep_explicit;
+  unsigned long long counter = 0;
+  const bool gen_dropout = c->model->step_counter(&counter);
   if (gen_dropout) {
     // the mask generator reads this step's counter from the mailbox (a graph node cannot carry it)
     rc = mail_begin(c);
     if (rc) return rc;
     unsigned* h = reinterpret_cast<unsigned*>(c->mail_host[c->mail_cur] + c->mail_off_hyper);
-    h[2] = (unsigned)(c->dropout_counter & 0xFFFFFFFFull);
-    h[3] = (unsigned)(c->dropout_counter >> 32);
-    c->dropout_counter += 1;
+    h[2] = (unsigned)(counter & 0xFFFFFFFFull);
+    h[3] = (unsigned)(counter >> 32);
   }
   if (c->use_graphs && !c->profile && !c->hook) {   // the exchange hook enqueues foreign work: no capture
     // only the Adam / dropout nodes and the gather of a descriptor-only batch read the mailbox
     const int mail = (apply || gen_dropout || c->x_lazy) ? c->mail_cur : -1;
     // the accumulator parities of the statistics hand-over are baked into the captured kernel arguments
-    const bool flips = c->bn_inline && (!c->generic || (c->g_inline_ok && !c->profile_split));
-    const int par = (flips ? (4 | c->fpar | (c->gpar << 1)) : 0) | (c->x_lazy ? 8 : 0) | (c->y_cur != c->y ? 16 : 0) | (c->tail_roles ? 32 : 0) | (c->g_role_split ? 64 : 0) | (c->grid_g_auto ? 128 : 0) | (c->g_dgrad_share << 8) | (c->g_cap_fwd << 16) | (c->g_cap_bwd << 20) | (c->g_chunks << 24);
+    bool handover = false;
+    const unsigned mkey = c->model->replay_key(&handover);
+    const bool flips = c->bn_inline && handover;
+    const unsigned ckey = (flips ? (4 | c->fpar | (c->gpar << 1)) : 0) | (c->x_lazy ? 8 : 0) | (c->y_cur != c->y ? 16 : 0) | (c->tail_roles ? 32 : 0);
     hipGraphExec_t exec = nullptr;
     for (auto& g : c->graphs)
-      if (g.B == B && g.flags == flags && g.mail == mail && g.par == par) exec = g.exec;
+      if (g.B == B && g.flags == flags && g.mail == mail && g.core == ckey && g.model == mkey) exec = g.exec;
     if (exec && flips) {
       c->fpar ^= 1;
       c->gpar ^= 1;
@@ -1490,7 +1008,7 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
       if (e != hipSuccess) return fail(MWW_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
       HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
       HIPCHK(hipGraphDestroy(graph));
-      c->graphs.push_back({B, flags, mail, par, exec});
+      c->graphs.push_back({B, flags, mail, ckey, mkey, exec});
     }
     HIPCHK(hipGraphLaunch(exec, c->stream));
     return mail_commit(c);
@@ -1514,7 +1032,7 @@ int mww_apply_gradients(mww_ctx* c, float lr, float gscale) {
 }
 
 int mww_forward(mww_ctx* c, int B, int training, int update_metrics) {
-  if (!c || B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (!c || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
   if (c->have_batch < B) return fail(MWW_ERR_STATE, "forward needs a batch of at least B rows");
   if (update_metrics && c->have_targets < B) return fail(MWW_ERR_STATE, "metric update needs targets");
   HIPCHK(hipSetDevice(c->device));
@@ -1524,7 +1042,7 @@ int mww_forward(mww_ctx* c, int B, int training, int update_metrics) {
     rc = materialise_x(c);
     if (rc) return rc;
   }
-  rc = enqueue_forward(c, B, training != 0, false, false, update_metrics != 0);
+  rc = c->model->enqueue_forward(c, B, training != 0, false, false, update_metrics != 0);
   if (rc) return rc;
   rc = join_side(c);
   if (rc) return rc;
@@ -1533,7 +1051,7 @@ int mww_forward(mww_ctx* c, int B, int training, int update_metrics) {
 }
 
 int mww_evaluate_windows(mww_ctx* c, const mww_window* windows, const float* labels, int64_t n, int batch) {
-  if (!c || !windows || !labels || n < 0 || batch <= 0 || batch > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad evaluation arguments");
+  if (!c || !windows || !labels || n < 0 || batch <= 0 || batch > c->max_batch) return fail(MWW_ERR_INVALID, "bad evaluation arguments");
   std::vector<float> ones((size_t)batch, 1.0f);
   int rc = MWW_OK;
   for (int64_t s = 0; s < n && !rc; s += batch) {
@@ -1541,14 +1059,14 @@ int mww_evaluate_windows(mww_ctx* c, const mww_window* windows, const float* lab
     rc = mww_set_targets(c, labels + s, ones.data(), b);
     if (!rc) rc = mww_assemble_batch(c, windows + s, nullptr, b, 0, 0);
     if (!rc) rc = mww_forward(c, b, 0, 1);
-    c->bn_eval_ready = !c->generic;   // the weights cannot change between the batches of this call
+    c->bn_eval_ready = c->model->eval_fold_cached();   // the weights cannot change between the batches of this call
   }
   c->bn_eval_ready = false;
   return rc;
 }
 
 int mww_read_outputs(mww_ctx* c, int B, float* probs, float* logits, float* loss) {
-  if (!c || B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (!c || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
   if (probs) HIPCHK(hipMemcpyAsync(probs, c->prob, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (logits) HIPCHK(hipMemcpyAsync(logits, c->z, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   std::vector<float> lp;
@@ -1589,73 +1107,32 @@ void* mww_device_ptr(mww_ctx* c, int which) {
 }
 
 int64_t mww_debug_read(mww_ctx* c, const char* name, int B, float* host, int64_t cap) {
-  if (!c || !name || !host || B <= 0 || B > c->d.max_batch) return fail(MWW_ERR_INVALID, "bad debug_read arguments");
-  const float* src = nullptr;
-  int64_t n = 0;
-  const int nb = c->d.n_blocks;
-  auto idx = [&](const char* prefix) -> int {
-    const size_t pl = strlen(prefix);
-    if (strncmp(name, prefix, pl) != 0) return -1;
-    const int k = atoi(name + pl);
-    return (k >= 1 && k <= nb && name[pl] >= '0' && name[pl] <= '9') ? k - 1 : -1;
-  };
-  int k;
-  if (c->generic) {
-    const int no = (int)c->G.size();
-    auto gidx = [&](const char* prefix) -> int {
-      const size_t pl = strlen(prefix);
-      if (strncmp(name, prefix, pl) != 0 || name[pl] < '0' || name[pl] > '9') return -1;
-      const int kk = atoi(name + pl);
-      return (kk >= 1 && kk <= no) ? kk - 1 : -1;
-    };
-    if ((k = gidx("p")) >= 0) { src = c->G[k].p; n = (int64_t)B * c->G[k].tout * c->G[k].cout; }
-    else if ((k = gidx("g")) >= 0) { src = c->G[k].g; n = (int64_t)B * c->G[k].tout * c->G[k].cout; }
-    else if ((k = gidx("bn")) >= 0) { src = c->G[k].bn; n = (int64_t)9 * c->G[k].cout; }
-    else if (!strcmp(name, "dz")) { src = c->dz; n = B; }
-    else if (!strcmp(name, "keep")) { src = c->keep; n = (int64_t)B * c->t_last * c->c_last; }
-    else if (!strcmp(name, "x")) {
-      if (materialise_x(c)) return -1;
-      src = c->x;
-      n = (int64_t)B * c->d.frames * MWW_FEATURE_BINS;
-    }
+  if (!c || !name || !host || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad debug_read arguments");
+  DebugTensor t;
+  const int found = c->model->debug_tensor(c, name, B, &t);   // the model's tensors first: p<k>, g<k>, bn<k> and its own
+  if (found < 0) return found;
+  if (!found) {
+    if (!strcmp(name, "dz")) { t.src = c->dz; t.n = B; }
+    else if (!strcmp(name, "x")) { t.src = c->x; t.n = (int64_t)B * c->frames * MWW_FEATURE_BINS; }
     else return fail(MWW_ERR_INVALID, std::string("unknown tensor name: ") + name);
-    if (n > cap) return fail(MWW_ERR_INVALID, "host buffer too small");
-    const int kpl = gidx("p") >= 0 ? gidx("p") : gidx("g");
-    if (kpl >= 0 && g_planes(c, c->G[kpl]) > 1) {
-      // a planar tensor is handed out interleaved [B][T][C], as the caller expects it
-      const GOp& o = c->G[kpl];
-      const int planes = g_planes(c, o);
-      std::vector<float> tmp((size_t)B * o.tout * o.pc);
-      for (int pl = 0; pl < planes; ++pl) {
-        int rcp = copy_out(c, tmp.data(), src + (size_t)pl * g_pstride(c, o), tmp.size() * sizeof(float));
-        if (rcp) return rcp;
-        for (int64_t r = 0; r < (int64_t)B * o.tout; ++r)
-          for (int cc = 0; cc < o.pc; ++cc) host[r * o.cout + pl * o.pc + cc] = tmp[(size_t)r * o.pc + cc];
-      }
-      return n;
-    }
-    int rcg = copy_out(c, host, src, (size_t)n * sizeof(float));
-    return rcg ? rcg : n;
   }
-  bool stored = false;   // p_k / g_k: bf16 in HBM under "storage_bf16", widened for the caller
-  if ((k = idx("p")) >= 0) { src = c->L[k].p; n = (int64_t)B * c->L[k].tout * c->L[k].cout; stored = true; }
-  else if ((k = idx("g")) >= 0) { src = c->L[k].g; n = (int64_t)B * c->L[k].tout * c->L[k].cout; stored = true; }
-  else if ((k = idx("bn")) >= 0) { src = c->L[k].bn; n = (int64_t)9 * c->L[k].cout; }
-  else if (!strcmp(name, "dz")) { src = c->dz; n = B; }
-  else if (!strcmp(name, "a0")) { src = c->a0; n = (int64_t)B * c->L[0].tin * c->d.conv1_filters; }   // relu(conv1(x)) as the first block stored it
-  else if (!strncmp(name, "clkf", 4) || !strncmp(name, "clkb", 4)) {
-    // phase clocks of layer k (1-based) as raw 64-bit counters viewed as floats: 2048 x kClkSlots x 2 words
-    const int kk = atoi(name + 4);
-    if (kk < 1 || kk > nb) return fail(MWW_ERR_INVALID, "bad layer");
-    src = reinterpret_cast<const float*>(c->phase_clk + (size_t)(2 * (kk - 1) + (name[3] == 'b' ? 1 : 0)) * 2048 * kClkSlots);
-    n = 2048 * kClkSlots * 2;
-  }
-  else if (!strcmp(name, "x")) { src = c->x; n = (int64_t)B * c->d.frames * MWW_FEATURE_BINS; }
-  else return fail(MWW_ERR_INVALID, std::string("unknown tensor name: ") + name);
+  const int64_t n = t.n;
   if (n > cap) return fail(MWW_ERR_INVALID, "host buffer too small");
-  if (stored && c->st_bf16) {
+  if (t.planes > 1) {
+    // a planar tensor is handed out interleaved [B][T][C], as the caller expects it
+    const int64_t rows = n / t.cout;
+    std::vector<float> tmp((size_t)rows * t.pc);
+    for (int pl = 0; pl < t.planes; ++pl) {
+      int rcp = copy_out(c, tmp.data(), t.src + (size_t)pl * t.pstride, tmp.size() * sizeof(float));
+      if (rcp) return rcp;
+      for (int64_t r = 0; r < rows; ++r)
+        for (int cc = 0; cc < t.pc; ++cc) host[r * t.cout + pl * t.pc + cc] = tmp[(size_t)r * t.pc + cc];
+    }
+    return n;
+  }
+  if (t.bf16) {
     std::vector<unsigned short> half((size_t)n);
-    int rch = copy_out(c, half.data(), src, (size_t)n * sizeof(unsigned short));
+    int rch = copy_out(c, half.data(), t.src, (size_t)n * sizeof(unsigned short));
     if (rch) return rch;
     for (int64_t i = 0; i < n; ++i) {
       const unsigned bits = (unsigned)half[(size_t)i] << 16;
@@ -1663,64 +1140,68 @@ int64_t mww_debug_read(mww_ctx* c, const char* name, int B, float* host, int64_t
     }
     return n;
   }
-  int rc = copy_out(c, host, src, (size_t)n * sizeof(float));
+  int rc = copy_out(c, host, t.src, (size_t)n * sizeof(float));
   return rc ? rc : n;
 }
 
-int mww_set_option(mww_ctx* c, const char* name, int64_t v) {
-  if (!c || !name) return fail(MWW_ERR_INVALID, "null argument");
-  if (!strcmp(name, "graphs")) c->use_graphs = v != 0;
-  else if (!strcmp(name, "profile")) {
-    c->profile = v != 0;
+namespace {
+// every option of mww_set_option (include/mww.h): its owner sets it; a value outside [lo, hi] (hi_cu: hi workgroups per CU) is refused
+const OptionRow kOptions[] = {
+    {"graphs", OPT_CORE, 1, 0, 0, nullptr},
+    {"profile", OPT_CORE, 1, 0, 0, nullptr},
+    {"side_stream", OPT_CORE, 1, 0, 0, nullptr},
+    {"bn_inline", OPT_CORE, 1, 0, 0, nullptr},
+    {"tail_roles", OPT_CORE, 1, 0, 0, nullptr},
+    {"bce_from_logits", OPT_CORE, 1, 0, 0, nullptr},
+    {"grad_buckets", OPT_CORE, 1, 2, 0, "grad_buckets must be 1 or 2"},
+    {"fused_input", OPT_CORE, 1, 0, 0, nullptr},
+    {"assemble_split", OPT_CORE, 1, 8, 0, "assemble_split out of range"},
+    {"grid_head", OPT_CORE, 1, 4, 1, "grid_head out of range"},
+    {"ablate", OPT_BLOCK, 1, 0, 0, nullptr},
+    {"pointwise_bf16", OPT_BLOCK, 1, 0, 0, nullptr},
+    {"storage_bf16", OPT_BLOCK, 1, 0, 0, nullptr},
+    {"bwd_wide", OPT_BLOCK, 1, 0, 0, nullptr},
+    {"conv1_x6", OPT_BLOCK, 1, 0, 0, nullptr},
+    {"conv1_x6_fwd", OPT_BLOCK, 1, 0, 0, nullptr},
+    {"bwd_first_wide", OPT_BLOCK, 1, 0, 0, nullptr},
+    {"dp_commit_late", OPT_BLOCK, -1, 1, 0, "dp_commit_late must be -1 (per-family defaults), 0 or 1"},
+    {"grid_fwd", OPT_BLOCK, 1, 4, 1, "grid_fwd out of range"},
+    {"grid_bwd", OPT_BLOCK, 1, 2, 1, "grid_bwd out of range"},
+    {"graph_role_split", OPT_GRAPH, 1, 0, 0, nullptr},
+    {"graph_static_shapes", OPT_GRAPH, 1, 0, 0, nullptr},
+    {"graph_planar", OPT_GRAPH, 1, 0, 0, nullptr},
+    {"graph_fwd_wg_per_cu", OPT_GRAPH, 1, 8, 0, "graph_fwd_wg_per_cu must be 1..8"},
+    {"graph_bwd_wg_per_cu", OPT_GRAPH, 1, 8, 0, "graph_bwd_wg_per_cu must be 1..8"},
+    {"graph_frame_chunks", OPT_GRAPH, 0, 4, 0, "graph_frame_chunks must be 0..4"},
+    {"graph_dgrad_share", OPT_GRAPH, 10, 90, 0, "graph_dgrad_share must be 10..90"},
+    {"profile_split", OPT_GRAPH, 1, 0, 0, nullptr},
+    {"grid_graph", OPT_GRAPH, 0, 4, 1, "grid_graph out of range"},   // 0: per-launch grids by occupancy (default); > 0: this many workgroups per launch
+    {"dropout_seed", OPT_GRAPH, 1, 0, 0, nullptr},
+};
+
+int set_core_option(mww_ctx* c, const std::string& name, int64_t v) {
+  const std::pair<const char*, bool*> flags[] = {{"graphs", &c->use_graphs}, {"profile", &c->profile}, {"side_stream", &c->use_side}, {"bn_inline", &c->bn_inline},
+                                                 {"tail_roles", &c->tail_roles}, {"fused_input", &c->fused_input}};
+  const std::pair<const char*, int*> ints[] = {{"grad_buckets", &c->grad_buckets}, {"assemble_split", &c->asm_split}, {"grid_head", &c->grid_head}};
+  for (auto& f : flags) if (name == f.first) *f.second = v != 0;
+  for (auto& f : ints) if (name == f.first) *f.second = (int)v;
+  if (name == "bce_from_logits") c->bce_clipped = v == 0;
+  if (name == "profile") {   // (the events recorded so far)
     for (auto& e : c->prof) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->prof.clear();
   }
-  else if (!strcmp(name, "ablate")) c->ablate = (int)v;
-  else if (!strcmp(name, "side_stream")) c->use_side = v != 0;
-  else if (!strcmp(name, "bn_inline")) c->bn_inline = v != 0;
-  else if (!strcmp(name, "graph_role_split")) c->g_role_split = v != 0;
-  else if (!strcmp(name, "graph_static_shapes")) c->g_static = v != 0;
-  else if (!strcmp(name, "graph_planar")) c->g_planar = v != 0;
-  else if (!strcmp(name, "graph_fwd_wg_per_cu")) { if (v < 1 || v > 8) return fail(MWW_ERR_INVALID, "graph_fwd_wg_per_cu must be 1..8"); c->g_cap_fwd = (int)v; }
-  else if (!strcmp(name, "graph_bwd_wg_per_cu")) { if (v < 1 || v > 8) return fail(MWW_ERR_INVALID, "graph_bwd_wg_per_cu must be 1..8"); c->g_cap_bwd = (int)v; }
-  else if (!strcmp(name, "graph_frame_chunks")) { if (v < 0 || v > 4) return fail(MWW_ERR_INVALID, "graph_frame_chunks must be 0..4"); c->g_chunks = (int)v; }
-  else if (!strcmp(name, "graph_dgrad_share")) { if (v < 10 || v > 90) return fail(MWW_ERR_INVALID, "graph_dgrad_share must be 10..90"); c->g_dgrad_share = (int)v; }
-  else if (!strcmp(name, "tail_roles")) c->tail_roles = v != 0;
-  else if (!strcmp(name, "bce_from_logits")) c->bce_clipped = v == 0;
-  else if (!strcmp(name, "grad_buckets")) { if (v < 1 || v > 2) return fail(MWW_ERR_INVALID, "grad_buckets must be 1 or 2"); c->grad_buckets = (int)v; }
-  else if (!strcmp(name, "fused_input")) {
-    c->fused_input = v != 0;
-    if (!v) { int rc = materialise_x(c); if (rc) return rc; }
-  }
-  else if (!strcmp(name, "assemble_split")) { if (v < 1 || v > 8) return fail(MWW_ERR_INVALID, "assemble_split out of range"); c->asm_split = (int)v; }
-  else if (!strcmp(name, "profile_split")) c->profile_split = v != 0;
-  else if (!strcmp(name, "pointwise_bf16")) {
-    if (c->generic && v) return fail(MWW_ERR_UNSUPPORTED, "the conv/BN graph kernels have no bf16 mode");
-    { std::string why; if (v && !shape_supported(c->d, &why, true)) return fail(MWW_ERR_UNSUPPORTED, "no bf16 mode for this topology: " + why); }
-    c->pw_bf16 = v != 0;
-    if (!v) c->st_bf16 = false;
-  }
-  else if (!strcmp(name, "storage_bf16")) {
-    if (c->generic && v) return fail(MWW_ERR_UNSUPPORTED, "the conv/BN graph kernels have no bf16 mode");
-    { std::string why; if (v && !shape_supported(c->d, &why, true)) return fail(MWW_ERR_UNSUPPORTED, "no bf16 mode for this topology: " + why); }
-    c->st_bf16 = v != 0;
-    if (v) c->pw_bf16 = true;
-  }
-  else if (!strcmp(name, "bwd_wide")) c->bwd_wide = v != 0;
-  else if (!strcmp(name, "conv1_x6")) c->conv1_x6 = v != 0;
-  else if (!strcmp(name, "conv1_x6_fwd")) c->conv1_x6_fwd = v != 0;
-  else if (!strcmp(name, "bwd_first_wide")) c->bwd_first_wide = v != 0;
-  else if (!strcmp(name, "dp_commit_late")) { if (v < -1 || v > 1) return fail(MWW_ERR_INVALID, "dp_commit_late must be -1 (per-family defaults), 0 or 1"); c->dp_commit_late = (int)v; }
-  else if (!strcmp(name, "grid_fwd")) { if (v < 1 || v > c->n_cu * 4) return fail(MWW_ERR_INVALID, "grid_fwd out of range"); c->grid_fwd = (int)v; }
-  else if (!strcmp(name, "grid_bwd")) { if (v < 1 || v > c->n_cu * 2) return fail(MWW_ERR_INVALID, "grid_bwd out of range"); c->grid_bwd = (int)v; }
-  else if (!strcmp(name, "grid_graph")) {   // 0: per-launch grids by occupancy (default); > 0: this many workgroups per launch
-    if (v < 0 || v > c->n_cu * 4) return fail(MWW_ERR_INVALID, "grid_graph out of range");
-    c->grid_g_auto = v == 0;
-    if (v > 0) c->grid_g = (int)v;
-  }
-  else if (!strcmp(name, "dropout_seed")) { c->dropout_seed = (unsigned long long)v; c->dropout_counter = 0; }
-  else if (!strcmp(name, "grid_head")) { if (v < 1 || v > c->n_cu * 4) return fail(MWW_ERR_INVALID, "grid_head out of range"); c->grid_head = (int)v; }
-  else return fail(MWW_ERR_INVALID, std::string("unknown option: ") + name);
+  return (name == "fused_input" && !v) ? materialise_x(c) : MWW_OK;
+}
+}  // namespace
+
+int mww_set_option(mww_ctx* c, const char* name, int64_t v) {
+  if (!c || !name) return fail(MWW_ERR_INVALID, "null argument");
+  const OptionRow* o = nullptr;
+  for (const OptionRow& r : kOptions)
+    if (!strcmp(name, r.name)) o = &r;
+  if (!o) return fail(MWW_ERR_INVALID, std::string("unknown option: ") + name);
+  if (o->lo <= o->hi && (v < o->lo || v > (o->hi_cu ? (int64_t)c->n_cu * o->hi : o->hi))) return fail(MWW_ERR_INVALID, o->range_error);
+  MWW_TRY(o->owner == OPT_CORE ? set_core_option(c, name, v) : c->model->set_option(c, *o, v));
   for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
   c->graphs.clear();
   return MWW_OK;
