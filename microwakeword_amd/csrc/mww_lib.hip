@@ -73,6 +73,14 @@ int enqueue_block_head(mww_ctx* c, int B, const Tensor& last, int T, int C, bool
 // ---------------------------------------------------------------------------------- sequences
 const float* mail_hyper(mww_ctx* c) { return reinterpret_cast<const float*>(c->mail_dev[c->mail_cur] + c->mail_off_hyper); }
 
+// A read of the HBM copy of a descriptor-only batch's mailbox, enqueued after that slot was committed: the slot's stamp
+// (mail_commit) lies in front of the read, so it is moved behind it - mail_begin waits for the stamp before the slot is
+// rewritten, eight commits later.  (While the slot is still the current one, its commit comes after the read anyway.)
+static int restamp_lazy_slot(mww_ctx* c) {
+  if (c->lazy_slot >= 0 && c->lazy_slot != c->mail_cur) HIPCHK(hipEventRecord(c->mail_ev[c->lazy_slot], c->stream));
+  return MWW_OK;
+}
+
 // labels / weights read in place from the mailbox of a descriptor-only batch -> the y / sw buffers (before that
 // mailbox slot can be rewritten)
 static int bring_targets(mww_ctx* c) {
@@ -82,7 +90,7 @@ static int bring_targets(mww_ctx* c) {
   HIPCHK(hipMemcpyAsync(c->sw, c->sw_cur, n, hipMemcpyDeviceToDevice, c->stream));
   c->y_cur = c->y;
   c->sw_cur = c->sw;
-  return MWW_OK;
+  return restamp_lazy_slot(c);
 }
 
 // descriptor-only batch -> x, for readers outside the first block's kernels
@@ -97,7 +105,7 @@ int materialise_x(mww_ctx* c) {
   lp.end();
   HIPCHK(hipGetLastError());
   c->x_lazy = false;
-  return MWW_OK;
+  return restamp_lazy_slot(c);
 }
 
 XGather x_gather(mww_ctx* c) {
