@@ -394,8 +394,9 @@ int mww_assemble_prefetched(mww_ctx* ctx, mww_prefetcher* p, float* out_labels, 
  * (model_train_eval.py:131-272 evaluate_model with --test_tflite_streaming / --test_tflite_nonstreaming;
  * test.py:293-403 tflite_streaming_model_roc; inference.py:82-125 Model.predict_spectrogram) without TensorFlow / TFLite.
  * A stream object borrows an existing context's device, HIP stream and uploaded feature stores (the context must outlive
- * it).  Topology: MixedNet with a first convolution, any widths / kernels / repeat_in_block, no residual connections,
- * spatial attention or pooled head (mww_stream_create); Inception - any conv/BN graph of mww_convnet_desc's Inception
+ * it).  Topology: MixedNet with a first convolution, any widths / kernels / repeat_in_block - without residual connections,
+ * spatial attention or pooled head through mww_stream_create, with them through mww_stream_create_mixednet below (spatial
+ * attention in non_stream mode only); Inception - any conv/BN graph of mww_convnet_desc's Inception
  * vocabulary - through mww_stream_create_convnet below.  Weights arrive in Keras get_weights() order (BN moving statistics included), so the
  * same call serves the specialised-kernel and the generic-graph MixedNet contexts; BN is folded into the 1x1 weights.
  *   MWW_STREAM_MODE_STREAM: Modes.STREAM_INTERNAL_STATE_INFERENCE - every Stream layer keeps the last R frames of its
@@ -421,6 +422,41 @@ typedef struct {
 typedef struct mww_stream mww_stream;
 /* MWW_ERR_UNSUPPORTED (+ message) for a malformed description or a topology outside the list above */
 int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* desc, mww_stream** out);
+/* The same handle for a MixedNet with residual connections, a pooled head or spatial attention (csrc/tu_stream_mixednet.hip).
+ * The description is the superset of mww_stream_desc; with no option set the stream is the one of mww_stream_create.  It is a
+ * creator of its own because the test-suite pins what mww_stream_create takes and refuses: the old name keeps its behaviour.
+ *   residual[b] (--residual_connection; mixednet.py:340-358): r = BN(Conv1x1(block input)), no bias, no ring and no state, is
+ *     added to the BN output of EVERY repeat of block b before that repeat's ReLU, at the same position (the non-streaming
+ *     graph's StridedDrop drops the residual's leading frames: right alignment; in stream mode both branches hold the current
+ *     frame).  Keras order: b.res.kernel [1,1,Cin,F], gamma, beta, moving_mean, moving_variance in front of the block's repeats.
+ *   pool (--pooled / --max_pool; mixednet.py:362-381): 0 none, 1 average, 2 max over the frames the head holds - in stream mode
+ *     the head ring [T_f - 1][C] plus the current frame, cold-ring zeros included (the average divides by T_f from the first
+ *     output on, the maximum includes 0) - then the Dense over the C pooled values.
+ *   spatial_attention (--spatial_attention; mixednet.py:234-275), non_stream mode only: per final-map position the mean and
+ *     the max over the channels, a[q] = sigmoid(sum_{i<4} w[i,0] avg[q-3+i] + w[i,1] max[q-3+i]), g[q] = h[q] a[q]; the Dense
+ *     (or the pooling, then the Dense) reads the last T_f - 3 positions of g.  Keras order: attention.kernel [4,1,2,1] in front
+ *     of the Dense.  Stream mode is refused: the reference's streaming clone gates the last T_f - 3 ring frames with the
+ *     CURRENT attention value (by our reading), which is not this computation, and nothing available pins that reading.
+ *   t_final: frames of the final map BEFORE attention and pooling; with t_final = 1 the head options do nothing (mixednet.py:362).
+ *   The state layout is that of mww_stream_create (residuals add nothing).  The six int8 entry points return
+ *   MWW_ERR_UNSUPPORTED on a stream whose description uses any of the three options.
+ * MWW_ERR_UNSUPPORTED (+ message) at creation: attention with t_final < 4 or in stream mode, a t_final that does not match the
+ * non_stream window, option values outside their range, everything mww_stream_create refuses. */
+typedef struct {
+  int32_t conv1_filters, conv1_kernel, stride;
+  int32_t n_blocks;
+  int32_t repeat[MWW_MAX_BLOCKS];
+  int32_t n_kernels[MWW_MAX_BLOCKS];
+  int32_t kernels[MWW_MAX_BLOCKS][MWW_STREAM_MAX_KERNELS];
+  int32_t pointwise_filters[MWW_MAX_BLOCKS];
+  int32_t t_final;                                        /* frames of the final map before attention and pooling */
+  int32_t frames;
+  int32_t mode;
+  int32_t residual[MWW_MAX_BLOCKS];                       /* 0 / 1 per block */
+  int32_t spatial_attention;                              /* 0 / 1 */
+  int32_t pool;                                           /* 0 none, 1 average, 2 max */
+} mww_mixednet_stream_desc;
+int mww_stream_create_mixednet(mww_ctx* ctx, const mww_mixednet_stream_desc* desc, mww_stream** out);
 /* The same handle for a conv -> BN/SSN -> ReLU graph: the streaming / non-streaming Inception model (inception.py:233-338 in
  * Modes.STREAM_INTERNAL_STATE_INFERENCE, one frame per step; csrc/tu_stream_graph.hip).  `desc` is the mww_convnet_desc of the
  * model with the ops in Keras layer-creation order (un-fused branch heads), `mode` a MWW_STREAM_MODE_*; `dropout` and

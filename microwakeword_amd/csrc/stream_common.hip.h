@@ -1,6 +1,7 @@
-// Shared by the four streaming units.  A stream (mww_stream) has a front every stream has - context, per-call track /
+// Shared by the streaming units.  A stream (mww_stream) has a front every stream has - context, per-call track /
 // segment / tile tables, outputs, float weights and state, int8 parameters and state; its host path is tu_stream.hip - and a
-// model part (SModel): MixedNet (tu_stream.hip float, tu_stream_q8.hip int8; its plan is here) or a conv/BN graph
+// model part (SModel): MixedNet (tu_stream.hip float, tu_stream_mixednet.hip float with residuals / pooling / attention,
+// tu_stream_q8.hip int8; its plan is here) or a conv/BN graph
 // (stream_graph.hip.h).  The model's virtual functions are the one place the two kinds are told apart.  The device code all
 // four kernels share is here too: the tile header, the Dense heads, the head-ring write-back and the calibration (REC) folds.
 // The kernels walk the same tiles and the same ring layout; only the element type and the arithmetic differ.
@@ -33,7 +34,9 @@ constexpr float kInv255 = (float)(1.0 / 255.0);   // inference.py:170 1 / 255 as
 inline int64_t r4(int64_t n) { return (n + 3) & ~(int64_t)3; }   // int8 rows and weight slices are padded to 32-bit words
 
 struct SLayer {
-  int kind;          // 0: depthwise K taps + bias (fused MixConv groups, zero leading taps); 1: 1x1 + folded BN + ReLU
+  int kind;          // 0: depthwise K taps + bias (fused MixConv groups, zero leading taps); 1: 1x1 + folded BN + ReLU;
+                     // (tu_stream_mixednet.hip only) 2: a block's residual 1x1 + folded BN, linear, of the block input, kept
+                     // aside; 3: kind 1 with that residual added at equal positions before the ReLU
   int cin, cout, k;
   int64_t w, b;      // offsets into the weight buffer
   int64_t ring;      // depthwise: offset of its ring ((k - 1) x cin) in the state buffer
@@ -46,6 +49,14 @@ struct SNet {
   int64_t ring1, ring_head;  // conv1 ring [r1][40] (spectrogram rows), head ring [tf - 1][c_last]
   int reach1;                // conv1 positions of halo in front of a tile
   const SLayer* L;           // [n_layers], device memory (the kernel argument stays small)
+};
+
+// What a MixedNet with residual connections, a pooled head or spatial attention adds to SNet (tu_stream_mixednet.hip)
+struct SVar {
+  int has_res;               // a third activation buffer holds the current block's residual
+  int att, pool;             // spatial attention (non_stream mode only); 0 none, 1 average, 2 max pooling
+  int tp;                    // frames the Dense or the pooling reads: tf - 3 with attention, else tf
+  int64_t wa;                // attention kernel [4][2] (avg, max)
 };
 
 struct SStores {
@@ -246,6 +257,7 @@ struct SModel {
   int64_t scratch_per_wg = 0;   // floats of one workgroup's tile (float kernel)
   int n_tensors = 0;            // calibrated tensors: the input, every op's output, the logit
   bool int8 = true;             // takes int8 parameters (a conv/BN graph: only from mww_stream_create_convnet_q8)
+  std::string int8_refusal;     // int8 = false: what the int8 entry points answer (empty: the conv/BN graph's message)
   int64_t q8_nw = 0, q8_ni = 0, q8_izp = 0;   // int8 weights / int32 values expected; offset of the zero points
   int64_t q8_tile_bytes = 0;                  // one workgroup's int8 tile
   std::vector<std::pair<int64_t, int>> q8_requant;   // per op and the Dense: (offset of its bias / multiplier / shift, cout)
@@ -339,6 +351,10 @@ inline int upload_table(T** dev, const std::vector<T>& host) {
 // MixedNet: conv1, per block and repeat a fused MixConv depthwise layer (when max(ks) > 1) and a 1x1 layer, the Dense
 struct MixedNet : SModel {
   mww_stream_desc d{};
+  int residual[MWW_MAX_BLOCKS] = {};   // mww_stream_create_mixednet: per block; spatial attention; pooling (0 / 1 / 2)
+  int att = 0, pool = 0;
+  SVar var{};
+  bool variant() const { return var.has_res || var.att || var.pool; }   // runs the kernel of tu_stream_mixednet.hip
   SNet net{};
   std::vector<SLayer> layers;   // host copy of net.L
   SLayer* d_layers = nullptr;
@@ -366,14 +382,23 @@ struct MixedNet : SModel {
   void launch_q8(const SStores& S, const SCall& a, const SQ8& q, int grid, size_t lds, hipStream_t hs) const override;
 };
 
+// tu_stream_mixednet.hip: the float kernel of a MixedNet with residuals, a pooled head or attention
+void launch_mixednet_variant(const SNet& net, const SVar& var, const SStores& S, const SCall& a, int grid, hipStream_t hs);
+
 // topology + weight / state layout, reach of every layer and the call geometry from the description
 inline int MixedNet::plan() {
-  layers.assign((size_t)2 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT, SLayer{});
+  layers.assign((size_t)2 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT + MWW_MAX_BLOCKS, SLayer{});
   if (d.mode != MWW_STREAM_MODE_STREAM && d.mode != MWW_STREAM_MODE_NON_STREAM) return unsupported("mode must be stream or non_stream");
   if (d.conv1_filters <= 0 || d.conv1_kernel <= 0 || d.stride <= 0)
     return unsupported("streaming needs a first convolution (first_conv_filters > 0, kernel and stride > 0)");
   if (d.n_blocks <= 0 || d.n_blocks > MWW_MAX_BLOCKS) return unsupported("n_blocks must be 1..8");
   if (d.t_final <= 0) return unsupported("t_final must be positive");
+  if (pool < 0 || pool > 2 || att < 0 || att > 1) return unsupported("pool must be 0 (none), 1 (average) or 2 (max), spatial_attention 0 or 1");
+  if (att && d.t_final < 4) return unsupported("spatial attention (kernel 4) needs t_final >= 4, not " + std::to_string(d.t_final));
+  if (att && d.mode != MWW_STREAM_MODE_NON_STREAM)
+    return unsupported("spatial attention runs in non_stream mode only: the reference's streaming clone gates the ring frames with the "
+                       "current attention value, which is not the non-streaming computation, and nothing pins that reading");
+  if (d.t_final == 1) pool = 0;   // mixednet.py:362: the head options need more than one frame
   net.k1 = d.conv1_kernel;
   net.s = d.stride;
   net.c1 = d.conv1_filters;
@@ -395,6 +420,15 @@ inline int MixedNet::plan() {
       if (g && d.kernels[b][g] < d.kernels[b][g - 1]) return unsupported("mixconv kernel sizes must be ascending (alignment uses the last one)");
       K = d.kernels[b][g] > K ? d.kernels[b][g] : K;
     }
+    if (residual[b] != 0 && residual[b] != 1) return unsupported("block " + std::to_string(b) + ": residual must be 0 or 1");
+    if (residual[b]) {   // 1x1 + BN of the block input, no ring: every repeat's 1x1 layer adds it
+      SLayer& Rl = layers[nl++];
+      Rl.kind = 2; Rl.cin = c; Rl.cout = f; Rl.k = 1;
+      Rl.w = dw; dw += (int64_t)c * f;
+      Rl.b = dw; dw += f;
+      kw += (int64_t)c * f + 4 * f;
+      var.has_res = 1;
+    }
     for (int r = 0; r < d.repeat[b]; ++r) {
       if (K > 1) {   // MixConv: depthwise groups (+ bias) fused to one [K][C] table, own ring of K - 1 frames
         if (nk > c) return unsupported("more MixConv groups than channels");
@@ -407,7 +441,7 @@ inline int MixedNet::plan() {
         sum_r += K - 1;
       }
       SLayer& P = layers[nl++];
-      P.kind = 1; P.cin = c; P.cout = f; P.k = 1;
+      P.kind = residual[b] ? 3 : 1; P.cin = c; P.cout = f; P.k = 1;
       P.w = dw; dw += (int64_t)c * f;
       P.b = dw; dw += f;
       kw += (int64_t)c * f + 4 * f;   // kernel, gamma, beta, moving mean, moving variance
@@ -418,9 +452,17 @@ inline int MixedNet::plan() {
   net.n_layers = nl;
   net.c_last = c;
   net.cmax = cmax;
-  net.wd = dw; dw += (int64_t)net.tf * c;
+  var.att = att;
+  var.pool = pool;
+  var.tp = net.tf - 3 * att;
+  const int td = pool ? 1 : var.tp;   // frames the Dense reads
+  if (att) {
+    var.wa = dw; dw += 8;
+    kw += 8;
+  }
+  net.wd = dw; dw += (int64_t)td * c;
   net.bd = dw; dw += 1;
-  kw += (int64_t)net.tf * c + 1;
+  kw += (int64_t)td * c + 1;
   net.ring_head = st;
   st += (int64_t)(net.tf - 1) * c;
   // reach: conv1 positions between a layer's output and the first head input of a tile
@@ -449,6 +491,13 @@ inline int MixedNet::plan() {
   n_tensors = nl + 3;
   // a tile: the gathered input rows and two activation buffers
   const int64_t rows = g.tile_outputs + g.reach, g_rows = ((rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS;
+  if (variant()) {   // + the residual buffer, + per position the channel mean, the channel max and the gate
+    scratch_per_wg = (g_rows + (2 + var.has_res) * rows * net.cmax + (att ? 3 * rows : 0) + 255) & ~(int64_t)255;
+    int8 = false;
+    int8_refusal = "the int8 streaming model does not cover MixedNet with residual_connection, pooled or spatial_attention "
+                   "(TFLite's int8 ADD, pooling and MUL are not restated): this stream runs the float model only";
+    return MWW_OK;
+  }
   scratch_per_wg = (g_rows + 2 * rows * net.cmax + 255) & ~(int64_t)255;
   q8_tile_bytes = g_rows + 2 * rows * r4(net.cmax);
   plan_q8();

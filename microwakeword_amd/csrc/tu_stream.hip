@@ -22,7 +22,9 @@
 // Here: the float MixedNet kernel and the float half of the MixedNet model part (Keras-order weight folding, launch), the
 // detection-metrics kernels, and the host path of EVERY stream - creation, reset, the float and the int8 launch epilogue,
 // calibration, mww_stream_set_quantized - written once against SModel (stream_common.hip.h); the conv/BN graph model part
-// and its two creators are tu_stream_graph.hip / tu_stream_graph_q8.hip.
+// and its two creators are tu_stream_graph.hip / tu_stream_graph_q8.hip.  A MixedNet with residual connections, a pooled head or
+// spatial attention (mww_stream_create_mixednet) is the same model part with three more plan inputs; its float kernel is
+// tu_stream_mixednet.hip, a plain plan never leaves the kernel below.
 #include <hip/hip_runtime.h>
 
 #include "stream_common.hip.h"
@@ -235,9 +237,22 @@ int64_t MixedNet::fold_weights(const float* h, float* w) const {
   const int64_t n1 = (int64_t)net.k1 * MWW_FEATURE_BINS * net.c1;
   std::memcpy(&w[net.w1], h, (size_t)n1 * sizeof(float));
   p += n1;
+  // a 1x1 layer (a block's residual included): kernel [1,1,Ci,Co], gamma, beta, moving_mean, moving_variance
+  auto fold_pw = [&](const SLayer& P) {
+    const int Ci = P.cin, Co = P.cout;
+    const float* kern = h + p;
+    const float *gamma = kern + (int64_t)Ci * Co, *beta = gamma + Co, *mean = beta + Co, *variance = mean + Co;
+    for (int co = 0; co < Co; ++co) {
+      const double sc = (double)gamma[co] / std::sqrt((double)variance[co] + 1e-3);
+      for (int ci = 0; ci < Ci; ++ci) w[P.w + (int64_t)ci * Co + co] = (float)((double)kern[(int64_t)ci * Co + co] * sc);
+      w[P.b + co] = (float)((double)beta[co] - (double)mean[co] * sc);
+    }
+    p += (int64_t)Ci * Co + 4 * Co;
+  };
   int l = 0;
   for (int b = 0; b < d.n_blocks; ++b) {
     const int nk = d.n_kernels[b];
+    if (residual[b]) fold_pw(layers[l++]);   // b.res.kernel + BN, in front of the block's repeats
     for (int r = 0; r < d.repeat[b]; ++r) {
       if (layers[l].kind == 0) {
         const SLayer& L = layers[l++];
@@ -253,26 +268,23 @@ int64_t MixedNet::fold_weights(const float* h, float* w) const {
           c0 += gc;
         }
       }
-      const SLayer& P = layers[l++];
-      const int Ci = P.cin, Co = P.cout;
-      const float* kern = h + p;
-      const float *gamma = kern + (int64_t)Ci * Co, *beta = gamma + Co, *mean = beta + Co, *var = mean + Co;
-      for (int co = 0; co < Co; ++co) {
-        const double sc = (double)gamma[co] / std::sqrt((double)var[co] + 1e-3);
-        for (int ci = 0; ci < Ci; ++ci) w[P.w + (int64_t)ci * Co + co] = (float)((double)kern[(int64_t)ci * Co + co] * sc);
-        w[P.b + co] = (float)((double)beta[co] - (double)mean[co] * sc);
-      }
-      p += (int64_t)Ci * Co + 4 * Co;
+      fold_pw(layers[l++]);
     }
   }
-  const int64_t nd = (int64_t)net.tf * net.c_last;
+  if (var.att) {   // attention.kernel [4,1,2,1]: tap i, (avg, max)
+    std::memcpy(&w[var.wa], h + p, 8 * sizeof(float));
+    p += 8;
+  }
+  const int64_t nd = (int64_t)(var.pool ? 1 : var.tp) * net.c_last;
   std::memcpy(&w[net.wd], h + p, (size_t)nd * sizeof(float));
   w[net.bd] = h[p + nd];
   return p + nd + 1;
 }
 
 void MixedNet::launch(const SStores& S, const SCall& a, int grid, hipStream_t hs) const {
-  if (a.rec)
+  if (variant())
+    launch_mixednet_variant(net, var, S, a, grid, hs);
+  else if (a.rec)
     hipLaunchKernelGGL(stream_forward_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, hs, net, S, a);
   else
     hipLaunchKernelGGL(stream_forward_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, hs, net, S, a);
@@ -305,7 +317,8 @@ int stream_create(mww_ctx* ctx, SModel* m, int rc, mww_stream** out) {
 
 namespace {
 
-int no_int8() {
+int no_int8(const mww_stream* s) {
+  if (!s->model->int8_refusal.empty()) return mww::set_error(MWW_ERR_UNSUPPORTED, s->model->int8_refusal.c_str());
   return mww::set_error(MWW_ERR_UNSUPPORTED, "the int8 streaming model covers MixedNet streams only (this is a conv/BN graph stream; "
                                                "mww_stream_create_convnet_q8 creates one that takes int8 parameters)");
 }
@@ -411,6 +424,28 @@ int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* d, mww_stream** out) 
   return stream_create(ctx, m, m->plan(), out);
 }
 
+int mww_stream_create_mixednet(mww_ctx* ctx, const mww_mixednet_stream_desc* d, mww_stream** out) {
+  if (!ctx || !d || !out) return mww::set_error(MWW_ERR_INVALID, "null argument");
+  *out = nullptr;
+  MixedNet* m = new MixedNet();
+  mww_stream_desc& b = m->d;   // the common part, field by field
+  b.conv1_filters = d->conv1_filters;
+  b.conv1_kernel = d->conv1_kernel;
+  b.stride = d->stride;
+  b.n_blocks = d->n_blocks;
+  std::memcpy(b.repeat, d->repeat, sizeof(b.repeat));
+  std::memcpy(b.n_kernels, d->n_kernels, sizeof(b.n_kernels));
+  std::memcpy(b.kernels, d->kernels, sizeof(b.kernels));
+  std::memcpy(b.pointwise_filters, d->pointwise_filters, sizeof(b.pointwise_filters));
+  b.t_final = d->t_final;
+  b.frames = d->frames;
+  b.mode = d->mode;
+  std::memcpy(m->residual, d->residual, sizeof(m->residual));
+  m->att = d->spatial_attention;
+  m->pool = d->pool;
+  return stream_create(ctx, m, m->plan(), out);
+}
+
 void mww_stream_destroy(mww_stream* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
@@ -469,13 +504,13 @@ int64_t mww_stream_run_host(mww_stream* s, const float* frames, int64_t n_frames
 }
 
 int mww_stream_num_tensors(const mww_stream* s) {
-  if (s && !s->model->int8) return no_int8();
+  if (s && !s->model->int8) return no_int8(s);
   return s ? s->model->n_tensors : 0;
 }
 
 int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_frames, float* ranges) {
   if (!s || !ranges || (n_frames && !frames) || n_frames < 0 || n_frames > INT32_MAX) return mww::set_error(MWW_ERR_INVALID, "bad frames");
-  if (!s->model->int8) return no_int8();
+  if (!s->model->int8) return no_int8(s);
   const int nt = s->model->n_tensors, stride = s->model->g.stride;
   for (int t = 0; t < nt; ++t) {
     ranges[2 * t] = INFINITY;
@@ -526,7 +561,7 @@ int mww_stream_set_probs(mww_stream* s, const float* probs, int64_t n) {
 // ---- int8 parameters (layout: include/mww.h); the model part says what it expects, validation and upload are here
 int64_t mww_stream_q8_sizes(const mww_stream* s, int64_t* n_ints) {
   if (!s) return mww::set_error(MWW_ERR_INVALID, "null stream");
-  if (!s->model->int8) return no_int8();
+  if (!s->model->int8) return no_int8(s);
   if (n_ints) *n_ints = s->model->q8_ni;
   return s->model->q8_nw;
 }
@@ -535,7 +570,7 @@ int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_wei
                              float input_scale, const uint8_t* lut) {
   if (!s || !weights || !ints || !lut) return mww::set_error(MWW_ERR_INVALID, "null argument");
   const SModel& m = *s->model;
-  if (!m.int8) return no_int8();
+  if (!m.int8) return no_int8(s);
   const int64_t nw = m.q8_nw, ni = m.q8_ni, izp = m.q8_izp;
   if (n_weights != nw || n_ints != ni)
     return mww::set_error(MWW_ERR_INVALID, ("expected " + std::to_string(nw) + " int8 weights and " + std::to_string(ni) + " int32 values").c_str());
@@ -574,7 +609,7 @@ int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_wei
 }
 
 int mww_stream_read_q8(mww_stream* s, uint8_t* out, int64_t n) {
-  if (s && !s->model->int8) return no_int8();
+  if (s && !s->model->int8) return no_int8(s);
   if (!s || !s->q8 || n < 0 || n > s->n_out || n > s->cap_q8_out || (n && !out)) return mww::set_error(MWW_ERR_INVALID, "more outputs requested than the last int8 run produced");
   if (!n) return MWW_OK;
   SCHK(hipSetDevice(s->device));
@@ -584,7 +619,7 @@ int mww_stream_read_q8(mww_stream* s, uint8_t* out, int64_t n) {
 }
 
 int mww_stream_get_state_q8(mww_stream* s, int8_t* h, int64_t n) {
-  if (s && !s->model->int8) return no_int8();
+  if (s && !s->model->int8) return no_int8(s);
   if (!s || !s->q8 || !h || n != s->model->n_state) return mww::set_error(MWW_ERR_INVALID, "state size mismatch (or no int8 parameters)");
   SCHK(hipSetDevice(s->device));
   SCHK(hipMemcpyAsync(h, s->q8_st[s->q8_cur], (size_t)n, hipMemcpyDeviceToHost, s->stream));

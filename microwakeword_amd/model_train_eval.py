@@ -6,8 +6,9 @@ Mirrors microwakeword/model_train_eval.py:
     spectrogram_length_final_layer, spectrogram_length, flags, training_input_shape``)
   * ``train_model(config, model, data_processor, restore_checkpoint)``   :99-128
   * ``evaluate_model``                         :131-272 (``--test_tf_nonstreaming``, ``--test_tflite_nonstreaming``,
-    ``--test_tflite_streaming`` run natively through streaming.py, after ``--train 1`` or on an existing ``train_dir``; the
-    int8 ``*_quantized`` flags raise)
+    ``--test_tflite_streaming`` run natively through streaming.py, after ``--train 1`` or on an existing ``train_dir``; what
+    a requested evaluation does not cover - stream-mode spatial attention, int8 with residual / pooled / attention models -
+    raises before training starts)
   * argparse surface                          :277-389
 
 Data-parallel over the GPUs of one node (no reference equivalent): launched as
@@ -213,6 +214,18 @@ def evaluate_model(flags, model_module, config, device=0):
     return out
 
 
+def check_evaluation_flags(flags, model_module, config):
+    """The topology check of the requested ``--test_*`` evaluations, from the flags alone: a MixedNet flag set one of them
+    does not cover raises NotImplementedError here, not after the training run it would follow."""
+    if model_module is not mixednet:
+        return
+    from . import streaming
+    modes = [mode for flag, mode in ((flags.test_tflite_nonstreaming, "non_stream"), (flags.test_tflite_streaming, "stream")) if flag]
+    int8 = bool(getattr(flags, "test_tflite_streaming_quantized", 0))
+    if modes or int8:
+        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], modes, int8=int8)
+
+
 def _evaluate(flags, model_module, config, device, world):
     """rank 0 evaluates, the other ranks of a data-parallel job wait at a barrier"""
     if not any((flags.test_tf_nonstreaming, flags.test_tflite_nonstreaming, flags.test_tflite_streaming,
@@ -239,6 +252,7 @@ def _run(flags, model_module, rank, local_rank, world):
                     "well-defined calibration to restate")
         raise NotImplementedError(msg)
     config = load_config(flags, model_module)
+    check_evaluation_flags(flags, model_module, config)   # before training and before train_dir is claimed
     device = flags.device if local_rank is None else local_rank
     if flags.train:
         device = flags.device if local_rank is None else local_rank

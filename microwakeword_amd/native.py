@@ -90,6 +90,14 @@ class StreamDesc(C.Structure):
                 ("t_final", C.c_int32), ("frames", C.c_int32), ("mode", C.c_int32)]
 
 
+class MixedNetStreamDesc(C.Structure):
+    """mww_mixednet_stream_desc: StreamDesc + residual, spatial_attention, pool"""
+    _fields_ = StreamDesc._fields_ + [("residual", C.c_int32 * MWW_MAX_BLOCKS), ("spatial_attention", C.c_int32), ("pool", C.c_int32)]
+
+
+STREAM_POOLS = {None: 0, "none": 0, "average": 1, "max": 2}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)   # mww_allreduce_fn
 EXCHANGE_IN_ORDER, EXCHANGE_DEFERRED, EXCHANGE_FLUSH = 0, 1, 2
 
@@ -114,6 +122,7 @@ EXPORTS = [
     "mww_stream_reset", "mww_stream_get_state", "mww_stream_run", "mww_stream_run_host", "mww_stream_read", "mww_stream_set_probs",
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
+    "mww_stream_create_mixednet",
 ]
 
 
@@ -203,6 +212,7 @@ class NativeLib:
         L.mww_allreduce_destroy.argtypes = [C.c_void_p]
         L.mww_evaluate_windows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int]
         L.mww_stream_create.argtypes = [C.c_void_p, C.POINTER(StreamDesc), C.POINTER(C.c_void_p)]
+        L.mww_stream_create_mixednet.argtypes = [C.c_void_p, C.POINTER(MixedNetStreamDesc), C.POINTER(C.c_void_p)]
         L.mww_stream_create_convnet.argtypes = [C.c_void_p, C.POINTER(ConvNetDesc), C.c_int32, C.POINTER(C.c_void_p)]
         L.mww_stream_create_convnet_q8.argtypes = [C.c_void_p, C.POINTER(ConvNetDesc), C.c_int32, C.POINTER(C.c_void_p)]
         L.mww_stream_destroy.argtypes = [C.c_void_p]
@@ -618,12 +628,21 @@ _METRIC_SCALARS = ("n", "correct", "tp5", "fp5", "fn5", "pos", "neg", "bce_sum")
 class Stream:
     """``mww_stream``: streaming / non-streaming inference of a MixedNet over tracks of the resident feature stores of
     ``engine``'s context, plus the detection metrics (include/mww.h).  ``desc``: a dict with conv1_filters, conv1_kernel,
-    stride, blocks = [(repeat, kernel sizes, pointwise filters), ...], t_final, frames, mode ("stream" / "non_stream")."""
+    stride, blocks = [(repeat, kernel sizes, pointwise filters), ...], t_final, frames, mode ("stream" / "non_stream").
+    With any of the optional keys set - residual (0 / 1 per block), attention (0 / 1), pool (0 / "average" / "max") - the
+    stream comes from ``mww_stream_create_mixednet`` and ``t_final`` counts the final map's frames before attention and
+    pooling (``streaming.mixednet_stream_description``); the int8 methods raise ``NativeError`` on it."""
 
     def __init__(self, engine: "Engine", desc: dict):
         self.engine = engine   # the context is borrowed: keep it alive
         self.nl = engine.nl
-        d = StreamDesc()
+        residual = [int(bool(r)) for r in desc.get("residual") or []]
+        attention, pool = int(bool(desc.get("attention", 0))), desc.get("pool", 0)
+        if isinstance(pool, str) and pool not in STREAM_POOLS:
+            raise ValueError("pool must be 0, 'average' or 'max', not %r" % (pool,))
+        pool = STREAM_POOLS[pool] if pool in STREAM_POOLS else int(pool)   # (a number outside 0..2: the library refuses it)
+        extended = any(residual) or attention or pool
+        d = MixedNetStreamDesc() if extended else StreamDesc()
         d.conv1_filters, d.conv1_kernel, d.stride = int(desc["conv1_filters"]), int(desc["conv1_kernel"]), int(desc["stride"])
         blocks = list(desc["blocks"])
         if len(blocks) > MWW_MAX_BLOCKS:
@@ -638,7 +657,15 @@ class Stream:
                 d.kernels[i][j] = int(k)
         d.t_final, d.frames, d.mode = int(desc["t_final"]), int(desc.get("frames", 0)), STREAM_MODES[desc.get("mode", "stream")]
         h = C.c_void_p()
-        self.nl.check(self.nl.lib.mww_stream_create(engine.h, C.byref(d), C.byref(h)))
+        if extended:
+            if residual and len(residual) != len(blocks):
+                raise ValueError("residual needs one entry per block")
+            for i, r in enumerate(residual):
+                d.residual[i] = r
+            d.spatial_attention, d.pool = attention, pool
+            self.nl.check(self.nl.lib.mww_stream_create_mixednet(engine.h, C.byref(d), C.byref(h)))
+        else:
+            self.nl.check(self.nl.lib.mww_stream_create(engine.h, C.byref(d), C.byref(h)))
         self._created(h, int(d.stride))
 
     def _created(self, h, stride):

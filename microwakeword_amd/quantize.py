@@ -334,6 +334,11 @@ def _mixednet_only(model):
     if isinstance(getattr(model, "layout", None), InceptionLayout):
         raise NotImplementedError("this module's int8 evaluation covers MixedNet only (an Inception model is calibrated and quantized by "
                                   "quantize_graph.calibrate / quantize_graph.quantize)")
+    from .streaming import mixednet_variant_flags
+    if mixednet_variant_flags(model.flags):   # before any device work: the float stream of such a model takes no int8 parameters
+        raise NotImplementedError("the int8 quantized streaming evaluation does not cover MixedNet with "
+                                  + ", ".join(mixednet_variant_flags(model.flags))
+                                  + " (TFLite's int8 ADD, pooling and MUL are not restated)")
 
 
 def calibrate(model, data_processor, config) -> np.ndarray:

@@ -59,6 +59,62 @@ def stream_description(flags, t_final: int, frames: int, stride: int, mode: str)
                 stride=int(stride), blocks=list(zip(rep, ksz, pf)), t_final=int(t_final), frames=int(frames), mode=mode)
 
 
+STREAM_ATTENTION_REASON = (
+    "spatial_attention in stream mode: the reference's streaming clone replays the slice net[:, -T_a:] with its build-time bound "
+    "next to a 4-tap Stream(Conv2D) that yields one frame, which by our reading gates the last T_f - 3 ring frames with the "
+    "CURRENT attention value - not the non-streaming computation even when warm, and nothing available pins that reading")
+
+
+def mixednet_variant_flags(flags) -> List[str]:
+    """the flags of a MixedNet flag set that ask for a residual connection, a pooled head or spatial attention"""
+    out = ["residual_connection"] if any(parse(_flag(flags, "residual_connection"))) else []
+    return out + [name for name in ("pooled", "spatial_attention") if _flag(flags, name)]
+
+
+def mixednet_stream_description(flags, frames: int, stride: int, mode: str) -> dict:
+    """The ``mww_mixednet_stream_desc`` of any MixedNet flag set with a first convolution (mixednet.py:307-386): the keys of
+    ``stream_description`` plus ``residual`` (0 / 1 per block), ``attention`` and ``pool`` (0 / "average" / "max").  ``t_final``
+    is T_f, the frames of the final map BEFORE attention and pooling, derived from the flags and ``frames`` (a pooled
+    layout's ``t_last`` is 1 whatever T_f is); with T_f = 1 the head flags do nothing and are dropped.  Raises
+    NotImplementedError for ``first_conv_filters = 0`` and for spatial attention in stream mode, ValueError where the model
+    itself cannot be built."""
+    if mode not in native.STREAM_MODES:
+        raise ValueError("mode must be 'stream' or 'non_stream'")
+    pf = [int(f) for f in parse(_flag(flags, "pointwise_filters"))]
+    rep = [int(r) for r in parse(_flag(flags, "repeat_in_block"))]
+    ksz = [tuple(int(k) for k in (ks if isinstance(ks, (list, tuple)) else (ks,))) for ks in parse(_flag(flags, "mixconv_kernel_sizes"))]
+    res = [int(bool(r)) for r in parse(_flag(flags, "residual_connection"))]
+    for lst in (rep, ksz, res):
+        if len(pf) != len(lst):
+            raise ValueError("all input lists have to be the same length")   # mixednet.py:298-305
+    f0, k1 = int(_flag(flags, "first_conv_filters")), int(_flag(flags, "first_conv_kernel_size"))
+    if f0 <= 0:
+        raise NotImplementedError("streaming evaluation does not cover MixedNet with first_conv_filters = 0")
+    if int(stride) != int(_flag(flags, "stride")):
+        raise ValueError("the streaming stride (%d) must be the model's --stride (%d)" % (stride, _flag(flags, "stride")))
+    t_final = (int(frames) - k1) // int(stride) + 1 - sum(r * (max(ks) - 1) for r, ks in zip(rep, ksz))
+    if int(frames) < k1 or t_final < 1:
+        raise ValueError("spectrogram of %d frames is too short for this network" % int(frames))
+    attention = int(bool(_flag(flags, "spatial_attention"))) if t_final > 1 else 0   # mixednet.py:362
+    pool = (("max" if _flag(flags, "max_pool") else "average") if _flag(flags, "pooled") else 0) if t_final > 1 else 0
+    if attention and t_final < 4:
+        raise ValueError("spatial attention needs at least 4 frames after the last block")
+    if attention and mode == "stream":
+        raise NotImplementedError("streaming evaluation does not cover MixedNet with " + STREAM_ATTENTION_REASON)
+    return dict(conv1_filters=f0, conv1_kernel=k1, stride=int(stride), blocks=list(zip(rep, ksz, pf)), t_final=int(t_final),
+                frames=int(frames), mode=mode, residual=res, attention=attention, pool=pool)
+
+
+def check_evaluation_topology(flags, frames: int, stride: int, modes: Sequence[str], int8: bool = False):
+    """What ``model_train_eval`` asks BEFORE it trains: raises NotImplementedError naming the flag when a requested
+    streaming / non-streaming evaluation (``modes``) or the int8 one does not cover the MixedNet flag set."""
+    if int8 and mixednet_variant_flags(flags):
+        raise NotImplementedError("the int8 quantized streaming evaluation does not cover MixedNet with "
+                                  + ", ".join(mixednet_variant_flags(flags)) + " (TFLite's int8 ADD, pooling and MUL are not restated)")
+    for mode in list(modes) + (["stream"] if int8 and "stream" not in modes else []):   # the int8 model is a stream-mode model
+        mixednet_stream_description(flags, frames, stride, mode)
+
+
 def graph_stream_description(flags, frames: int, stride: int, mode: str) -> dict:
     """The description of a streaming Inception (inception.py:233-338) for ``native.GraphStream``: the un-fused op list in
     Keras layer-creation order, so ``get_weights()`` feeds it as it is.  Inception has no ``--stride``: one frame per
@@ -78,7 +134,8 @@ def graph_stream_description(flags, frames: int, stride: int, mode: str) -> dict
 
 class StreamingModel:
     """The streaming (``mode="stream"``) or non-streaming (``mode="non_stream"``) form of a trained MixedNet or Inception
-    ``model`` (``microwakeword_amd.model.Model``, any kernel family; MixedNet on csrc/tu_stream.hip, Inception on
+    ``model`` (``microwakeword_amd.model.Model``, any kernel family; MixedNet on csrc/tu_stream.hip - with residual
+    connections, a pooled head or, in non_stream mode, spatial attention on csrc/tu_stream_mixednet.hip -, Inception on
     csrc/tu_stream_graph.hip), sharing the model's context: its device, HIP stream and the
     feature stores a ``FeatureHandler`` uploaded there.  The weights are taken from ``model`` when this object is created
     (``set_weights`` takes new ones)."""
@@ -94,6 +151,9 @@ class StreamingModel:
         if isinstance(lay, InceptionLayout):
             self.desc = graph_stream_description(model.flags, lay.frames, stride, mode)
             self.native = native.GraphStream(model.engine, self.desc)
+        elif mixednet_variant_flags(model.flags):   # residual / pooled / attention: T_f from the flags, not from lay.t_last
+            self.desc = mixednet_stream_description(model.flags, lay.frames, stride, mode)
+            self.native = native.Stream(model.engine, self.desc)
         else:
             self.desc = stream_description(model.flags, lay.t_last, lay.frames, stride, mode)
             self.native = native.Stream(model.engine, self.desc)

@@ -7,6 +7,9 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
                                                                     # the calibration pass (500 spectrograms) + quantization
     python tools/stream_eval_throughput.py --hours 20 --model inception   # the default Inception flags, T = 176
     python tools/stream_eval_throughput.py --hours 20 --model inception --quantized   # its int8 model (csrc/tu_stream_graph_q8.hip)
+    python tools/stream_eval_throughput.py --hours 20 --residual_connection 1,0,1,0 --pooled 1   # csrc/tu_stream_mixednet.hip
+    python tools/stream_eval_throughput.py --hours 20 --mode non_stream --residual_connection 1,0,1,0 --repeat_in_block 1,2,1,1 \
+        --spatial_attention 1 --pooled 1 --max_pool 1     # every window of the non-streaming model (attention: this mode only)
 """
 import argparse
 import json
@@ -36,6 +39,11 @@ def main():
     ap.add_argument("--window_hours", type=float, default=1.0, help="ambient hours the windowed alternative is timed on")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--quantized", action="store_true", help="time the int8 streaming model instead of the float one")
+    ap.add_argument("--mode", choices=("stream", "non_stream"), default="stream")
+    for flag in ("residual_connection", "repeat_in_block"):
+        ap.add_argument("--" + flag, default=DEF[flag], help="mixednet flag (default %s)" % DEF[flag])
+    for flag in ("spatial_attention", "pooled", "max_pool"):
+        ap.add_argument("--" + flag, type=int, default=0, help="mixednet flag")
     a = ap.parse_args()
     if a.model == "inception":
         T = a.frames or 176
@@ -45,8 +53,11 @@ def main():
             INC["cnn2_kernel_sizes"], INC["cnn2_dilation"], T)
     else:
         T = a.frames or 194
-        model = mixednet.model(DEF, (T, 40), 1024, max_batch=1024, seed=3)
-        name = "mixednet default (T=%d)" % T
+        flags = dict(DEF, residual_connection=a.residual_connection, repeat_in_block=a.repeat_in_block,
+                     spatial_attention=a.spatial_attention, pooled=a.pooled, max_pool=a.max_pool)
+        model = mixednet.model(flags, (T, 40), 1024, max_batch=1024, seed=3)
+        changed = ["%s=%s" % (k, v) for k, v in flags.items() if v != DEF[k]]
+        name = "mixednet default%s (T=%d)" % ("".join(" " + c for c in changed), T)
     rng = np.random.default_rng(0)
     per_track = int(a.track_minutes * 60 * 50)
     n_amb = max(1, int(round(a.hours * 60 / a.track_minutes)))
@@ -62,8 +73,8 @@ def main():
     pos_off = np.concatenate([[0], np.cumsum(pos_len)[:-1]]).astype(np.int64)
     pos_win["store"], pos_win["pad_rows"] = 1, np.maximum(0, T - pos_len)
     pos_win["copy_rows"], pos_win["src_elem"] = pos_len, pos_off * 40
-    sm = streaming.StreamingModel(model, 1, "stream")
-    extra = {}
+    sm = streaming.StreamingModel(model, 1, a.mode)
+    extra = {} if a.mode == "stream" else {"mode": a.mode}
     if a.quantized:
         # the calibration pass of --test_tflite_streaming_quantized: 500 spectrograms of T frames, chunks of s = 1
         cal = rng.integers(0, 1000, size=(quantize.CALIBRATION_SAMPLES * (T - 1), 40)).astype(np.float32) * streaming.SCALE_U16
