@@ -457,6 +457,15 @@ typedef struct {
   int32_t pool;                                           /* 0 none, 1 average, 2 max */
 } mww_mixednet_stream_desc;
 int mww_stream_create_mixednet(mww_ctx* ctx, const mww_mixednet_stream_desc* desc, mww_stream** out);
+/* The same MixedNet stream (same description, plan, float weights, state layout, same handle type) on which the six int8 entry
+ * points work when the description uses residual or pool: calibration on the float kernel of csrc/tu_stream_mixednet.hip, then
+ * the int8 kernel of csrc/tu_stream_mixednet_q8.hip once mww_stream_set_quantized has loaded parameters (layout: next to
+ * mww_stream_set_quantized below; contract: INTEGRATION.md 6, "residual and pooled MixedNets").  A creator of its own for the
+ * reason mww_stream_create_convnet_q8 gives: the refusal of the int8 calls on a stream of mww_stream_create_mixednet is pinned
+ * by the test-suite (tests/mixednet_variant_checks.py).  spatial_attention is refused here in BOTH modes
+ * (MWW_ERR_UNSUPPORTED naming it): the int8 model is a stream-mode model and int8 MUL / Logistic gating is not restated.  A
+ * description with no option set, or with t_final = 1, is the plain plan on the plain kernels, as mww_stream_create. */
+int mww_stream_create_mixednet_q8(mww_ctx* ctx, const mww_mixednet_stream_desc* desc, mww_stream** out);
 /* The same handle for a conv -> BN/SSN -> ReLU graph: the streaming / non-streaming Inception model (inception.py:233-338 in
  * Modes.STREAM_INTERNAL_STATE_INFERENCE, one frame per step; csrc/tu_stream_graph.hip).  `desc` is the mww_convnet_desc of the
  * model with the ops in Keras layer-creation order (un-fused branch heads), `mode` a MWW_STREAM_MODE_*; `dropout` and
@@ -537,7 +546,23 @@ int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_fram
  *   ints (int32):   per op: bias with the input zero point folded (b - zp_in * sum of the channel's weights) [cout],
  *                   multiplier [cout], shift [cout] (TFLite QuantizeMultiplier); then the n_tensors zero points
  *   input_scale:    the input tensor's scale (its zero point is the first of the zero points)
- *   lut (uint8):    [256] logit q + 128 -> the uint8 output; probability = (float)u8 * (float)(1/255) */
+ *   lut (uint8):    [256] logit q + 128 -> the uint8 output; probability = (float)u8 * (float)(1/255)
+ * On a stream of mww_stream_create_mixednet_q8 whose plan has a residual block or a pooled head (a plain plan keeps every
+ * offset above):
+ *   tensors:  input, conv1; per block: its residual r (1x1 + folded BN of the block input, linear) when it has one, in front
+ *             of its repeats; per repeat: the MixConv output (when max(ks) > 1), the 1x1 output (with a residual: linear,
+ *             BEFORE the add), the ADD output (after the fused ReLU; only with a residual); the Dense logit.
+ *   ops:      conv1; per block the residual 1x1 (when it has one), per repeat MixConv and 1x1; the Dense.
+ *   weights:  the residual 1x1 and a residual block's 1x1 are [Co][Ci rounded up to 4] like any 1x1; a pooled Dense is
+ *             [1][C_last rounded up to 4] (it reads the C pooled values).
+ *   ints:     per op bias / multiplier / shift [cout] as above; a residual block's 1x1 is followed by the six integers of
+ *             its ADD: M1, sh1 (the 1x1 output), M2, sh2 (r), Mo, sho (TFLite int8 Add, left_shift 20: QuantizeMultiplier
+ *             of s1 / (2 max(s1, s2)), s2 / (2 max(s1, s2)), 2 max(s1, s2) / (2^20 s_out); multipliers >= 0, shifts in
+ *             [-31, 0]); then the n_tensors zero points in the tensor order above.
+ *   rings:    unchanged; the MixConv of a repeat >= 1 of a residual block holds the previous ADD output, the head ring the
+ *             final map (the ADD output when the last block has a residual); reset fills each with that tensor's zero point.
+ *   pooling:  the pooled value shares the final map's scale and zero point; average: acc = sum of the T_f int8 values,
+ *             (acc > 0 ? acc + T_f / 2 : acc - T_f / 2) / T_f (C division), clamped; max: the int8 maximum. */
 int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_weights, const int32_t* ints, int64_t n_ints,
                              float input_scale, const uint8_t* lut);
 int64_t mww_stream_q8_sizes(const mww_stream* s, int64_t* n_ints);   /* int8 weights expected (n_ints: int32 entries) */

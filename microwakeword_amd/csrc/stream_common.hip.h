@@ -1,7 +1,7 @@
 // Shared by the streaming units.  A stream (mww_stream) has a front every stream has - context, per-call track /
 // segment / tile tables, outputs, float weights and state, int8 parameters and state; its host path is tu_stream.hip - and a
 // model part (SModel): MixedNet (tu_stream.hip float, tu_stream_mixednet.hip float with residuals / pooling / attention,
-// tu_stream_q8.hip int8; its plan is here) or a conv/BN graph
+// tu_stream_q8.hip int8, tu_stream_mixednet_q8.hip int8 with residuals / pooling; its plan is here) or a conv/BN graph
 // (stream_graph.hip.h).  The model's virtual functions are the one place the two kinds are told apart.  The device code all
 // four kernels share is here too: the tile header, the Dense heads, the head-ring write-back and the calibration (REC) folds.
 // The kernels walk the same tiles and the same ring layout; only the element type and the arithmetic differ.
@@ -57,6 +57,8 @@ struct SVar {
   int att, pool;             // spatial attention (non_stream mode only); 0 none, 1 average, 2 max pooling
   int tp;                    // frames the Dense or the pooling reads: tf - 3 with attention, else tf
   int64_t wa;                // attention kernel [4][2] (avg, max)
+  const int* lt;             // [n_layers] calibrated tensor of each layer's output (kind 3: the 1x1 output, the ADD output next)
+  int n_tensors;
 };
 
 struct SStores {
@@ -261,6 +263,7 @@ struct SModel {
   int64_t q8_nw = 0, q8_ni = 0, q8_izp = 0;   // int8 weights / int32 values expected; offset of the zero points
   int64_t q8_tile_bytes = 0;                  // one workgroup's int8 tile
   std::vector<std::pair<int64_t, int>> q8_requant;   // per op and the Dense: (offset of its bias / multiplier / shift, cout)
+  std::vector<int64_t> q8_add;                       // per int8 ADD: offset of its M1, sh1, M2, sh2, Mo, sho
   virtual ~SModel() {}                                // frees the device tables
   virtual int upload() = 0;                           // device tables of the plan (the device is current)
   virtual int64_t fold_weights(const float* h, float* w) const = 0;   // Keras order -> device layout; floats consumed
@@ -353,11 +356,14 @@ struct MixedNet : SModel {
   mww_stream_desc d{};
   int residual[MWW_MAX_BLOCKS] = {};   // mww_stream_create_mixednet: per block; spatial attention; pooling (0 / 1 / 2)
   int att = 0, pool = 0;
+  bool q8_variant = false;             // mww_stream_create_mixednet_q8: a residual / pooled plan takes int8 parameters
   SVar var{};
   bool variant() const { return var.has_res || var.att || var.pool; }   // runs the kernel of tu_stream_mixednet.hip
   SNet net{};
   std::vector<SLayer> layers;   // host copy of net.L
   SLayer* d_layers = nullptr;
+  std::vector<int> lt;          // host copy of var.lt
+  int* d_lt = nullptr;
   // int8 layout (tu_stream_q8.hip): weight / int offsets of conv1, the layers and the Dense; pitches
   struct Q8 {
     const int64_t* lw;     // [n_layers] offset of each layer's weights
@@ -373,6 +379,7 @@ struct MixedNet : SModel {
   ~MixedNet() override {
     if (d_layers) (void)hipFree(d_layers);
     if (d_q8_off) (void)hipFree(d_q8_off);
+    if (d_lt) (void)hipFree(d_lt);
   }
   int upload() override;
   int64_t fold_weights(const float* h, float* w) const override;
@@ -382,8 +389,13 @@ struct MixedNet : SModel {
   void launch_q8(const SStores& S, const SCall& a, const SQ8& q, int grid, size_t lds, hipStream_t hs) const override;
 };
 
-// tu_stream_mixednet.hip: the float kernel of a MixedNet with residuals, a pooled head or attention
+// tu_stream_mixednet.hip: the float kernel of a MixedNet with residuals, a pooled head or attention (a.rec: the <REC> form)
 void launch_mixednet_variant(const SNet& net, const SVar& var, const SStores& S, const SCall& a, int grid, hipStream_t hs);
+// tu_stream_mixednet_q8.hip: its int8 twin (residuals, pooled head); k: the call and the layout, one kernel argument
+struct SQ8Net : SQ8, MixedNet::Q8 {};
+const void* mixednet_variant_q8_kernel();
+void launch_mixednet_variant_q8(const SNet& net, const SVar& var, const SStores& S, const SCall& a, const SQ8Net& k, int grid, size_t lds,
+                                hipStream_t hs);
 
 // topology + weight / state layout, reach of every layer and the call geometry from the description
 inline int MixedNet::plan() {
@@ -394,6 +406,9 @@ inline int MixedNet::plan() {
   if (d.n_blocks <= 0 || d.n_blocks > MWW_MAX_BLOCKS) return unsupported("n_blocks must be 1..8");
   if (d.t_final <= 0) return unsupported("t_final must be positive");
   if (pool < 0 || pool > 2 || att < 0 || att > 1) return unsupported("pool must be 0 (none), 1 (average) or 2 (max), spatial_attention 0 or 1");
+  if (att && q8_variant)
+    return unsupported("mww_stream_create_mixednet_q8 does not cover spatial_attention: the int8 model is a stream-mode model, stream-mode "
+                       "attention has no pinned reading, and TFLite's int8 MUL / Logistic gate is not restated");
   if (att && d.t_final < 4) return unsupported("spatial attention (kernel 4) needs t_final >= 4, not " + std::to_string(d.t_final));
   if (att && d.mode != MWW_STREAM_MODE_NON_STREAM)
     return unsupported("spatial attention runs in non_stream mode only: the reference's streaming clone gates the ring frames with the "
@@ -488,14 +503,28 @@ inline int MixedNet::plan() {
   n_weights = kw;
   n_dev_w = dw;
   n_state = st;
-  n_tensors = nl + 3;
+  // calibrated tensors: input, conv1, every layer's output (a residual block's 1x1 counts twice: before and after the add), logit
+  lt.assign((size_t)nl, 0);
+  int nt = 2;
+  for (int l = 0; l < nl; ++l) {
+    lt[(size_t)l] = nt;
+    nt += layers[l].kind == 3 ? 2 : 1;
+  }
+  n_tensors = nt + 1;
+  var.n_tensors = n_tensors;
   // a tile: the gathered input rows and two activation buffers
   const int64_t rows = g.tile_outputs + g.reach, g_rows = ((rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS;
   if (variant()) {   // + the residual buffer, + per position the channel mean, the channel max and the gate
     scratch_per_wg = (g_rows + (2 + var.has_res) * rows * net.cmax + (att ? 3 * rows : 0) + 255) & ~(int64_t)255;
+    if (q8_variant) {   // residuals / pooling: the int8 kernel of tu_stream_mixednet_q8.hip, one more int8 buffer for r
+      q8_tile_bytes = g_rows + (2 + var.has_res) * rows * r4(net.cmax);
+      plan_q8();
+      return MWW_OK;
+    }
     int8 = false;
     int8_refusal = "the int8 streaming model does not cover MixedNet with residual_connection, pooled or spatial_attention "
-                   "(TFLite's int8 ADD, pooling and MUL are not restated): this stream runs the float model only";
+                   "on a stream of mww_stream_create_mixednet: this stream runs the float model only "
+                   "(mww_stream_create_mixednet_q8 creates one that takes int8 parameters for residual_connection and pooled)";
     return MWW_OK;
   }
   scratch_per_wg = (g_rows + 2 * rows * net.cmax + 255) & ~(int64_t)255;

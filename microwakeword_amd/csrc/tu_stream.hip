@@ -223,7 +223,9 @@ namespace mww_stream_impl {
 int MixedNet::upload() {
   int rc = upload_table(&d_layers, layers);
   if (!rc) rc = upload_table(&d_q8_off, q8_off);
+  if (!rc) rc = upload_table(&d_lt, lt);
   net.L = d_layers;
+  var.lt = d_lt;
   q.lw = d_q8_off;
   q.li = d_q8_off + net.n_layers;
   return rc;
@@ -424,10 +426,11 @@ int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* d, mww_stream** out) 
   return stream_create(ctx, m, m->plan(), out);
 }
 
-int mww_stream_create_mixednet(mww_ctx* ctx, const mww_mixednet_stream_desc* d, mww_stream** out) {
+static int create_mixednet(mww_ctx* ctx, const mww_mixednet_stream_desc* d, bool q8_variant, mww_stream** out) {
   if (!ctx || !d || !out) return mww::set_error(MWW_ERR_INVALID, "null argument");
   *out = nullptr;
   MixedNet* m = new MixedNet();
+  m->q8_variant = q8_variant;
   mww_stream_desc& b = m->d;   // the common part, field by field
   b.conv1_filters = d->conv1_filters;
   b.conv1_kernel = d->conv1_kernel;
@@ -444,6 +447,14 @@ int mww_stream_create_mixednet(mww_ctx* ctx, const mww_mixednet_stream_desc* d, 
   m->att = d->spatial_attention;
   m->pool = d->pool;
   return stream_create(ctx, m, m->plan(), out);
+}
+
+int mww_stream_create_mixednet(mww_ctx* ctx, const mww_mixednet_stream_desc* d, mww_stream** out) {
+  return create_mixednet(ctx, d, false, out);
+}
+
+int mww_stream_create_mixednet_q8(mww_ctx* ctx, const mww_mixednet_stream_desc* d, mww_stream** out) {
+  return create_mixednet(ctx, d, true, out);
 }
 
 void mww_stream_destroy(mww_stream* s) {
@@ -587,6 +598,10 @@ int mww_stream_set_quantized(mww_stream* s, const int8_t* weights, int64_t n_wei
   for (const auto& op : m.q8_requant)
     if (bad_requant(op.first, op.second))
       return mww::set_error(MWW_ERR_INVALID, "requantization multipliers must be >= 0 and shifts lie in [-31, 30]");
+  for (int64_t at : m.q8_add)   // TFLite's int8 Add: three multipliers below one
+    for (int k = 0; k < 3; ++k)
+      if (ints[at + 2 * k] < 0 || ints[at + 2 * k + 1] < -31 || ints[at + 2 * k + 1] > 0)
+        return mww::set_error(MWW_ERR_INVALID, "ADD multipliers must be >= 0 and their shifts lie in [-31, 0]");
   q8_free(s);
   std::vector<int8_t> st0((size_t)m.n_state + 4, 0);
   m.q8_state0(ints + izp, st0.data());

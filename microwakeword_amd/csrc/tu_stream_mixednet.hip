@@ -13,6 +13,11 @@
 //              final-map position the channel mean and max, then the 4-tap gate; the head reads h[q] a[q] at the last T_f - 3.
 //
 // Every sum runs in a fixed order, nothing is atomic: two runs give the same bits.
+//
+// <REC> is the calibration form (mww_stream_calibrate_host on a stream of mww_stream_create_mixednet_q8): every thread keeps the
+// min / max of the tensor it is computing - a kind-2 layer records r, a kind-3 layer the value before the add and the value
+// after add + ReLU as two tensors, the head the logit -, rec_fold runs per layer, one partial row per workgroup.  <false> is the
+// kernel without any of it.
 #include <hip/hip_runtime.h>
 
 #include "stream_common.hip.h"
@@ -22,11 +27,15 @@ using namespace mww_stream_impl;
 namespace {
 
 constexpr int kPoolChannels = 8;   // channels a head thread pools at a time (registers)
+// input, conv1, the logit; per block a residual; per repeat MixConv, 1x1 and ADD
+constexpr int kMaxVarTensors = 3 + MWW_MAX_BLOCKS + 3 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT;
 
 // Head over the last TP positions of the (gated) final map: pooling per channel when `pool`, then the Dense, sigmoid.
 // gate: a[q] at gate[q - g_lo], or NULL.  Positions before the stream start read the head ring [TF - 1][C].
+template <bool REC>
 __device__ inline void variant_head(const SCall& a, const STile& T, const float* fin, int pitch, const float* hring, int64_t wd_at,
-                                    int64_t bd_at, int C, int TF, int TP, int pool, const float* gate, int64_t g_lo) {
+                                    int64_t bd_at, int C, int TF, int TP, int pool, const float* gate, int64_t g_lo, float& lmin,
+                                    float& lmax) {
   for (int o = threadIdx.x; o < T.n; o += kStreamThreads) {
     const int64_t c = T.c0 + o, q0 = c - (TP - 1);
     float acc = a.w[bd_at];
@@ -62,11 +71,19 @@ __device__ inline void variant_head(const SCall& a, const STile& T, const float*
     const int64_t g = T.out0 + o;
     a.logit[g] = acc;
     a.prob[g] = 1.f / (1.f + expf(-acc));
+    if (REC) {
+      lmin = fminf(lmin, acc);
+      lmax = fmaxf(lmax, acc);
+    }
   }
 }
 
+template <bool REC>
 __global__ void __launch_bounds__(kStreamThreads) stream_mixednet_kernel(SNet net, SVar var, SStores S, SCall a) {
   const int tid = threadIdx.x;
+  __shared__ float red[REC ? 2 * kStreamThreads : 1], rmin[REC ? kMaxVarTensors : 1], rmax[REC ? kMaxVarTensors : 1];
+  float lmin = INFINITY, lmax = -INFINITY, lmin2 = INFINITY, lmax2 = -INFINITY;   // (2: the ADD output of a kind-3 layer)
+  if (REC) rec_init(a, rmin, rmax);
   float* G = a.scratch + (int64_t)blockIdx.x * a.scratch_per_wg;            // gathered padded input rows [.][40]
   float* B0 = G + ((a.buf_rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS;   // two activation buffers [rows][cmax]
   float* B1 = B0 + a.buf_rows * net.cmax;
@@ -101,8 +118,17 @@ __global__ void __launch_bounds__(kStreamThreads) stream_mixednet_kernel(SNet ne
       float acc = 0.f;
       for (int r = 0; r < net.k1 * MWW_FEATURE_BINS; ++r) acc = fmaf(g[r], w[(int64_t)r * net.c1], acc);
       B0[i * net.cmax + co] = acc > 0.f ? acc : 0.f;
+      if (REC) {
+        lmin = fminf(lmin, B0[i * net.cmax + co]);
+        lmax = fmaxf(lmax, B0[i * net.cmax + co]);
+      }
     }
     __syncthreads();
+    if (REC) {
+      rec_fold(lmin, lmax, 1, red, rmin, rmax);
+      lmin = INFINITY;
+      lmax = -INFINITY;
+    }
     float* in = B0;
     float* out = B1;
     int64_t in_lo = lo, r_lo = lo;
@@ -119,8 +145,17 @@ __global__ void __launch_bounds__(kStreamThreads) stream_mixednet_kernel(SNet ne
           float acc = a.w[L.b + co];
           for (int ci = 0; ci < Ci; ++ci) acc = fmaf(x[ci], w[(int64_t)ci * Co], acc);
           Rb[(i - r_lo) * net.cmax + co] = acc;
+          if (REC) {
+            lmin = fminf(lmin, acc);
+            lmax = fmaxf(lmax, acc);
+          }
         }
         __syncthreads();
+        if (REC) {
+          rec_fold(lmin, lmax, var.lt[l], red, rmin, rmax);
+          lmin = INFINITY;
+          lmax = -INFINITY;
+        }
         continue;
       }
       int64_t o_lo = c0 - L.reach;
@@ -139,6 +174,10 @@ __global__ void __launch_bounds__(kStreamThreads) stream_mixednet_kernel(SNet ne
             acc = fmaf(a.w[L.w + (int64_t)j * C + c], x, acc);
           }
           out[(i - o_lo) * net.cmax + c] = acc;
+          if (REC) {
+            lmin = fminf(lmin, acc);
+            lmax = fmaxf(lmax, acc);
+          }
         }
         if (last) {   // this layer's ring after the call: its input at positions [N - R, N)
           for (int idx = tid; idx < R * C; idx += kStreamThreads) {
@@ -157,11 +196,27 @@ __global__ void __launch_bounds__(kStreamThreads) stream_mixednet_kernel(SNet ne
           const float* w = a.w + L.w + co;
           float acc = a.w[L.b + co];
           for (int ci = 0; ci < Ci; ++ci) acc = fmaf(x[ci], w[(int64_t)ci * Co], acc);
+          if (REC && res) {   // the 1x1 output before the add is a tensor of its own
+            lmin = fminf(lmin, acc);
+            lmax = fmaxf(lmax, acc);
+          }
           if (res) acc += Rb[(i - r_lo) * net.cmax + co];   // o_lo >= r_lo: the residual covers the block input
           out[(i - o_lo) * net.cmax + co] = acc > 0.f ? acc : 0.f;
+          if (REC) {
+            float& mn = res ? lmin2 : lmin;
+            float& mx = res ? lmax2 : lmax;
+            mn = fminf(mn, out[(i - o_lo) * net.cmax + co]);
+            mx = fmaxf(mx, out[(i - o_lo) * net.cmax + co]);
+          }
         }
       }
       __syncthreads();
+      if (REC) {
+        rec_fold(lmin, lmax, var.lt[l], red, rmin, rmax);
+        if (L.kind == 3) rec_fold(lmin2, lmax2, var.lt[l] + 1, red, rmin, rmax);
+        lmin = lmin2 = INFINITY;
+        lmax = lmax2 = -INFINITY;
+      }
       float* t = in;
       in = out;
       out = t;
@@ -199,14 +254,19 @@ __global__ void __launch_bounds__(kStreamThreads) stream_mixednet_kernel(SNet ne
       gate = gt;
     }
     if (var.att || var.pool) {
-      variant_head(a, T, fin, net.cmax, hring, net.wd, net.bd, net.c_last, net.tf, var.tp, var.pool, gate, in_lo);
+      variant_head<REC>(a, T, fin, net.cmax, hring, net.wd, net.bd, net.c_last, net.tf, var.tp, var.pool, gate, in_lo, lmin, lmax);
     } else {
-      float lmin = 0.f, lmax = 0.f;   // (the calibration form's range: not recorded here)
-      dense_head<false>(a, T, fin, net.cmax, hring, net.wd, net.bd, net.c_last, net.tf, lmin, lmax);
+      dense_head<REC>(a, T, fin, net.cmax, hring, net.wd, net.bd, net.c_last, net.tf, lmin, lmax);
+    }
+    if (REC) {
+      rec_fold(lmin, lmax, var.n_tensors - 1, red, rmin, rmax);
+      lmin = INFINITY;
+      lmax = -INFINITY;
     }
     if (last) head_ring_store(a.st_out + net.ring_head, T, fin, net.cmax, hring, net.c_last, net.tf);
     __syncthreads();   // the next tile reuses the scratch
   }
+  if (REC) rec_flush(a, rmin, rmax);
 }
 
 }  // namespace
@@ -214,7 +274,10 @@ __global__ void __launch_bounds__(kStreamThreads) stream_mixednet_kernel(SNet ne
 namespace mww_stream_impl {
 
 void launch_mixednet_variant(const SNet& net, const SVar& var, const SStores& S, const SCall& a, int grid, hipStream_t hs) {
-  hipLaunchKernelGGL(stream_mixednet_kernel, dim3(grid), dim3(kStreamThreads), 0, hs, net, var, S, a);
+  if (a.rec)
+    hipLaunchKernelGGL(stream_mixednet_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, hs, net, var, S, a);
+  else
+    hipLaunchKernelGGL(stream_mixednet_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, hs, net, var, S, a);
 }
 
 }  // namespace mww_stream_impl

@@ -22,8 +22,6 @@ using namespace mww_stream_impl;
 
 namespace {
 
-struct SQ8Net : SQ8, MixedNet::Q8 {};   // the call and the layout, one kernel argument
-
 __global__ void __launch_bounds__(kStreamThreads) stream_q8_kernel(SNet net, SStores S, SCall a, SQ8Net q) {
   HIP_DYNAMIC_SHARED(int, q8_lds)
   const int tid = threadIdx.x;
@@ -155,37 +153,47 @@ void MixedNet::plan_q8() {
   for (const SLayer& L : layers) {
     q8_off.push_back(w);
     li.push_back(ints(L.cout));
+    if (L.kind == 3) {   // the ADD of a residual block's 1x1: M1, sh1, M2, sh2, Mo, sho
+      q8_add.push_back(i);
+      i += 6;
+    }
     w = r4(w + (L.kind == 0 ? (int64_t)L.k * L.cin : (int64_t)L.cout * r4(L.cin)));
   }
   q8_off.insert(q8_off.end(), li.begin(), li.end());
   q.wd = w;
-  w = r4(w + (int64_t)net.tf * r4(net.c_last));
+  w = r4(w + (int64_t)(var.pool ? 1 : net.tf) * r4(net.c_last));   // a pooled Dense reads the C pooled values
   q.id = ints(1);
   q8_izp = i;
   q8_nw = w;
-  q8_ni = i + net.n_layers + 3;
+  q8_ni = i + n_tensors;
   q.kp1 = net.k1 * MWW_FEATURE_BINS;
   q.cp = (int)r4(net.cmax);
 }
 
-// rings at reset: real zero, i.e. each ring's tensor zero point (conv1: the input, MixConv: its input, head: the last map)
+// rings at reset: real zero, i.e. the zero point of the tensor under each ring (conv1: the input, MixConv: its input - in a
+// residual block's repeat >= 1 the previous ADD output -, head: the final map)
 void MixedNet::q8_state0(const int32_t* zp, int8_t* st0) const {
   for (int64_t k = 0; k < (int64_t)net.r1 * MWW_FEATURE_BINS; ++k) st0[net.ring1 + k] = (int8_t)zp[0];
+  int t_in = 1;   // the tensor the next layer reads
   for (size_t l = 0; l < layers.size(); ++l) {
     const SLayer& L = layers[l];
     if (L.kind == 0)
-      for (int64_t k = 0; k < (int64_t)(L.k - 1) * L.cin; ++k) st0[L.ring + k] = (int8_t)zp[1 + l];
+      for (int64_t k = 0; k < (int64_t)(L.k - 1) * L.cin; ++k) st0[L.ring + k] = (int8_t)zp[t_in];
+    if (L.kind != 2) t_in = lt[l] + (L.kind == 3 ? 1 : 0);   // a residual is kept aside: the next layer still reads the block input
   }
-  for (int64_t k = 0; k < (int64_t)(net.tf - 1) * net.c_last; ++k) st0[net.ring_head + k] = (int8_t)zp[1 + net.n_layers];
+  for (int64_t k = 0; k < (int64_t)(net.tf - 1) * net.c_last; ++k) st0[net.ring_head + k] = (int8_t)zp[t_in];
 }
 
-const void* MixedNet::q8_kernel() const { return (const void*)stream_q8_kernel; }
+const void* MixedNet::q8_kernel() const { return variant() ? mixednet_variant_q8_kernel() : (const void*)stream_q8_kernel; }
 
 void MixedNet::launch_q8(const SStores& S, const SCall& a, const SQ8& c, int grid, size_t lds, hipStream_t hs) const {
   SQ8Net k;
   static_cast<SQ8&>(k) = c;
   static_cast<MixedNet::Q8&>(k) = q;
-  hipLaunchKernelGGL(stream_q8_kernel, dim3(grid), dim3(kStreamThreads), lds, hs, net, S, a, k);
+  if (variant())   // residuals / pooled head: tu_stream_mixednet_q8.hip; a plain plan never leaves the kernel above
+    launch_mixednet_variant_q8(net, var, S, a, k, grid, lds, hs);
+  else
+    hipLaunchKernelGGL(stream_q8_kernel, dim3(grid), dim3(kStreamThreads), lds, hs, net, S, a, k);
 }
 
 }  // namespace mww_stream_impl

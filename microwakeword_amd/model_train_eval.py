@@ -7,8 +7,8 @@ Mirrors microwakeword/model_train_eval.py:
   * ``train_model(config, model, data_processor, restore_checkpoint)``   :99-128
   * ``evaluate_model``                         :131-272 (``--test_tf_nonstreaming``, ``--test_tflite_nonstreaming``,
     ``--test_tflite_streaming`` run natively through streaming.py, after ``--train 1`` or on an existing ``train_dir``; what
-    a requested evaluation does not cover - stream-mode spatial attention, int8 with residual / pooled / attention models -
-    raises before training starts)
+    a requested evaluation does not cover - stream-mode spatial attention, int8 with attention models, int8 with residual /
+    pooled models unless ``--quantized_backend native_ext`` - raises before training starts)
   * argparse surface                          :277-389
 
 Data-parallel over the GPUs of one node (no reference equivalent): launched as
@@ -132,9 +132,10 @@ def build_parser():
     parser.add_argument("--test_tflite_nonstreaming_quantized", type=int, default=0)
     parser.add_argument("--test_tflite_streaming", type=int, default=0)
     parser.add_argument("--test_tflite_streaming_quantized", type=int, default=0)
-    parser.add_argument("--quantized_backend", type=str, default="tflite", choices=("tflite", "native"),
+    parser.add_argument("--quantized_backend", type=str, default="tflite", choices=("tflite", "native", "native_ext"),
                         help="native: run --test_tflite_streaming_quantized on the int8 kernel here, calibrated and quantized "
-                             "by a restatement of TFLite's int8 arithmetic (not TFLite itself)")
+                             "by a restatement of TFLite's int8 arithmetic (not TFLite itself); native_ext: native, plus the "
+                             "restated int8 ADD / AVERAGE_POOL_2D / MAX_POOL_2D of MixedNets with --residual_connection or --pooled")
     parser.add_argument("--restore_checkpoint", type=int, default=0)
     parser.add_argument("--use_weights", type=str, default="best_weights")
     parser.add_argument("--verbosity", type=str, default="INFO")
@@ -173,7 +174,8 @@ def evaluate_model(flags, model_module, config, device=0):
     (its ``.npz`` twin) and is evaluated on the test sets - ``--test_tf_nonstreaming``: ``non_stream/testing_set_metrics.txt``;
     ``--test_tflite_nonstreaming``: ``tflite_non_stream/tflite_streaming_roc.txt``; ``--test_tflite_streaming``:
     ``tflite_stream_state_internal/tflite_streaming_roc.txt`` (streaming.py); ``--test_tflite_streaming_quantized`` with
-    ``--quantized_backend native``: calibration and int8 quantization (quantize.py; Inception: quantize_graph.py), the parameters in
+    ``--quantized_backend native`` or ``native_ext``: calibration and int8 quantization (quantize.py; Inception: quantize_graph.py;
+    with ``native_ext`` a MixedNet with residual connections or a pooled head: quantize_mixednet.py), the parameters in
     ``tflite_stream_state_internal_quant/stream_state_internal_quant.npz`` and the ROC of the int8 streaming model in
     ``tflite_stream_state_internal_quant/tflite_streaming_roc.txt``.  No TFLite file is written: the streaming /
     non-streaming forms run natively from the same weights."""
@@ -194,11 +196,7 @@ def evaluate_model(flags, model_module, config, device=0):
             out[folder] = streaming.streaming_model_roc(config, folder, sm, data_processor, data_set="testing",
                                                         ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt")
     if getattr(flags, "test_tflite_streaming_quantized", 0):
-        from .layout import InceptionLayout
-        if isinstance(model.layout, InceptionLayout):   # the conversion does not depend on the family; the graph here does
-            from . import quantize_graph as quantize
-        else:
-            from . import quantize
+        quantize = quantization_module(model, getattr(flags, "quantized_backend", "native"))
         folder = "tflite_stream_state_internal_quant"
         logging.info("Testing the quantized streaming model: calibrated and quantized by a restatement of TFLite's int8 "
                      "arithmetic (quantize.py / quantize_graph.py, INTEGRATION.md), not by TFLite")
@@ -214,6 +212,19 @@ def evaluate_model(flags, model_module, config, device=0):
     return out
 
 
+def quantization_module(model, backend="native"):
+    """the module that calibrates and quantizes ``model``: the conversion does not depend on the family, the graph here does.
+    ``native_ext`` sends a MixedNet whose flags ask for a residual connection or a pooled head to quantize_mixednet; for a plain
+    MixedNet or an Inception model it is ``native``."""
+    from . import quantize, quantize_graph, quantize_mixednet, streaming
+    from .layout import InceptionLayout
+    if isinstance(model.layout, InceptionLayout):
+        return quantize_graph
+    if backend == "native_ext" and streaming.mixednet_variant_flags(model.flags):
+        return quantize_mixednet
+    return quantize
+
+
 def check_evaluation_flags(flags, model_module, config):
     """The topology check of the requested ``--test_*`` evaluations, from the flags alone: a MixedNet flag set one of them
     does not cover raises NotImplementedError here, not after the training run it would follow."""
@@ -223,7 +234,8 @@ def check_evaluation_flags(flags, model_module, config):
     modes = [mode for flag, mode in ((flags.test_tflite_nonstreaming, "non_stream"), (flags.test_tflite_streaming, "stream")) if flag]
     int8 = bool(getattr(flags, "test_tflite_streaming_quantized", 0))
     if modes or int8:
-        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], modes, int8=int8)
+        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], modes, int8=int8,
+                                            int8_variants=getattr(flags, "quantized_backend", "tflite") == "native_ext")
 
 
 def _evaluate(flags, model_module, config, device, world):
@@ -241,7 +253,7 @@ def _evaluate(flags, model_module, config, device, world):
 
 
 def _run(flags, model_module, rank, local_rank, world):
-    if flags.test_tflite_nonstreaming_quantized or (flags.test_tflite_streaming_quantized and flags.quantized_backend != "native"):
+    if flags.test_tflite_nonstreaming_quantized or (flags.test_tflite_streaming_quantized and flags.quantized_backend not in ("native", "native_ext")):
         msg = ("the int8 *_quantized evaluations need the TFLite converter's calibration (reference "
                "microwakeword.utils); --test_tf_nonstreaming, --test_tflite_nonstreaming and "
                "--test_tflite_streaming run here. --test_tflite_streaming_quantized also runs here with --quantized_backend "

@@ -122,7 +122,7 @@ EXPORTS = [
     "mww_stream_reset", "mww_stream_get_state", "mww_stream_run", "mww_stream_run_host", "mww_stream_read", "mww_stream_set_probs",
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
-    "mww_stream_create_mixednet",
+    "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8",
 ]
 
 
@@ -213,6 +213,7 @@ class NativeLib:
         L.mww_evaluate_windows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int]
         L.mww_stream_create.argtypes = [C.c_void_p, C.POINTER(StreamDesc), C.POINTER(C.c_void_p)]
         L.mww_stream_create_mixednet.argtypes = [C.c_void_p, C.POINTER(MixedNetStreamDesc), C.POINTER(C.c_void_p)]
+        L.mww_stream_create_mixednet_q8.argtypes = [C.c_void_p, C.POINTER(MixedNetStreamDesc), C.POINTER(C.c_void_p)]
         L.mww_stream_create_convnet.argtypes = [C.c_void_p, C.POINTER(ConvNetDesc), C.c_int32, C.POINTER(C.c_void_p)]
         L.mww_stream_create_convnet_q8.argtypes = [C.c_void_p, C.POINTER(ConvNetDesc), C.c_int32, C.POINTER(C.c_void_p)]
         L.mww_stream_destroy.argtypes = [C.c_void_p]
@@ -631,9 +632,11 @@ class Stream:
     stride, blocks = [(repeat, kernel sizes, pointwise filters), ...], t_final, frames, mode ("stream" / "non_stream").
     With any of the optional keys set - residual (0 / 1 per block), attention (0 / 1), pool (0 / "average" / "max") - the
     stream comes from ``mww_stream_create_mixednet`` and ``t_final`` counts the final map's frames before attention and
-    pooling (``streaming.mixednet_stream_description``); the int8 methods raise ``NativeError`` on it."""
+    pooling (``streaming.mixednet_stream_description``); the int8 methods raise ``NativeError`` on it unless the stream was
+    created with ``int8=True`` (``mww_stream_create_mixednet_q8``: the same stream, on which calibration and the int8 kernel
+    of csrc/tu_stream_mixednet_q8.hip work for residual / pooled descriptions; attention is refused there)."""
 
-    def __init__(self, engine: "Engine", desc: dict):
+    def __init__(self, engine: "Engine", desc: dict, int8: bool = False):
         self.engine = engine   # the context is borrowed: keep it alive
         self.nl = engine.nl
         residual = [int(bool(r)) for r in desc.get("residual") or []]
@@ -641,7 +644,7 @@ class Stream:
         if isinstance(pool, str) and pool not in STREAM_POOLS:
             raise ValueError("pool must be 0, 'average' or 'max', not %r" % (pool,))
         pool = STREAM_POOLS[pool] if pool in STREAM_POOLS else int(pool)   # (a number outside 0..2: the library refuses it)
-        extended = any(residual) or attention or pool
+        extended = any(residual) or attention or pool or int8
         d = MixedNetStreamDesc() if extended else StreamDesc()
         d.conv1_filters, d.conv1_kernel, d.stride = int(desc["conv1_filters"]), int(desc["conv1_kernel"]), int(desc["stride"])
         blocks = list(desc["blocks"])
@@ -663,7 +666,8 @@ class Stream:
             for i, r in enumerate(residual):
                 d.residual[i] = r
             d.spatial_attention, d.pool = attention, pool
-            self.nl.check(self.nl.lib.mww_stream_create_mixednet(engine.h, C.byref(d), C.byref(h)))
+            create = self.nl.lib.mww_stream_create_mixednet_q8 if int8 else self.nl.lib.mww_stream_create_mixednet
+            self.nl.check(create(engine.h, C.byref(d), C.byref(h)))
         else:
             self.nl.check(self.nl.lib.mww_stream_create(engine.h, C.byref(d), C.byref(h)))
         self._created(h, int(d.stride))

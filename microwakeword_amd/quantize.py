@@ -338,7 +338,8 @@ def _mixednet_only(model):
     if mixednet_variant_flags(model.flags):   # before any device work: the float stream of such a model takes no int8 parameters
         raise NotImplementedError("the int8 quantized streaming evaluation does not cover MixedNet with "
                                   + ", ".join(mixednet_variant_flags(model.flags))
-                                  + " (TFLite's int8 ADD, pooling and MUL are not restated)")
+                                  + " in this module (quantize_mixednet.calibrate / quantize_mixednet.quantize restate TFLite's int8 "
+                                  "ADD and pooling for residual_connection and pooled; int8 MUL is not restated)")
 
 
 def calibrate(model, data_processor, config) -> np.ndarray:

@@ -105,12 +105,15 @@ def mixednet_stream_description(flags, frames: int, stride: int, mode: str) -> d
                 frames=int(frames), mode=mode, residual=res, attention=attention, pool=pool)
 
 
-def check_evaluation_topology(flags, frames: int, stride: int, modes: Sequence[str], int8: bool = False):
+def check_evaluation_topology(flags, frames: int, stride: int, modes: Sequence[str], int8: bool = False, int8_variants: bool = False):
     """What ``model_train_eval`` asks BEFORE it trains: raises NotImplementedError naming the flag when a requested
-    streaming / non-streaming evaluation (``modes``) or the int8 one does not cover the MixedNet flag set."""
-    if int8 and mixednet_variant_flags(flags):
+    streaming / non-streaming evaluation (``modes``) or the int8 one does not cover the MixedNet flag set.
+    ``int8_variants`` (``--quantized_backend native_ext``): residual_connection and pooled pass the int8 check
+    (quantize_mixednet.py); spatial attention and first_conv_filters = 0 are refused by the stream-mode description below."""
+    if int8 and not int8_variants and mixednet_variant_flags(flags):
         raise NotImplementedError("the int8 quantized streaming evaluation does not cover MixedNet with "
-                                  + ", ".join(mixednet_variant_flags(flags)) + " (TFLite's int8 ADD, pooling and MUL are not restated)")
+                                  + ", ".join(mixednet_variant_flags(flags)) + " (--quantized_backend native_ext adds the restated "
+                                  "int8 ADD, AVERAGE_POOL_2D and MAX_POOL_2D for residual_connection and pooled; int8 MUL is not restated)")
     for mode in list(modes) + (["stream"] if int8 and "stream" not in modes else []):   # the int8 model is a stream-mode model
         mixednet_stream_description(flags, frames, stride, mode)
 
@@ -198,10 +201,13 @@ class StreamingModel:
 
 
 def load_quantized(path):
-    """the ``QuantizedModel`` (MixedNet) or ``QuantizedGraphModel`` (Inception; its file carries ``family``) of an ``.npz``"""
-    from . import quantize, quantize_graph
+    """the ``QuantizedModel`` (MixedNet), ``QuantizedMixedNetModel`` (MixedNet with residuals / a pooled head) or
+    ``QuantizedGraphModel`` (Inception) of an ``.npz``; the files of the last two carry ``family``"""
+    from . import quantize, quantize_graph, quantize_mixednet
     with np.load(path, allow_pickle=False) as z:
         family = str(z["family"]) if "family" in z.files else "mixednet"
+    if family == quantize_mixednet.FAMILY:
+        return quantize_mixednet.QuantizedMixedNetModel.load(path)
     return quantize_graph.QuantizedGraphModel.load(path) if family == quantize_graph.FAMILY else quantize.QuantizedModel.load(path)
 
 
@@ -209,14 +215,17 @@ class QuantizedStreamingModel(StreamingModel):
     """The int8 quantized streaming model (``--test_tflite_streaming_quantized``) with the methods of ``StreamingModel``:
     ``model_or_file`` is a ``quantize.QuantizedModel`` (MixedNet: the int8 kernel of csrc/tu_stream_q8.hip), a
     ``quantize_graph.QuantizedGraphModel`` (Inception: csrc/tu_stream_graph_q8.hip on a stream of
-    ``mww_stream_create_convnet_q8``) or the path of either's ``.npz``; ``context`` is the float ``Model`` whose context
+    ``mww_stream_create_convnet_q8``), a ``quantize_mixednet.QuantizedMixedNetModel`` (MixedNet with residuals / a pooled head:
+    csrc/tu_stream_mixednet_q8.hip on a stream of ``mww_stream_create_mixednet_q8``) or the path of any one's ``.npz``; ``context`` is the float ``Model`` whose context
     (device, HIP stream, resident feature stores) the stream borrows.  Probabilities are ``uint8 / 255`` in float32
     (``read_q8`` gives the uint8 outputs), in the same device buffer the metrics kernel reads."""
 
     def __init__(self, model_or_file, stride: int, mode: str = "stream", context=None):
         from .quantize import QuantizedModel
         from .quantize_graph import QuantizedGraphModel
-        q = model_or_file if isinstance(model_or_file, (QuantizedModel, QuantizedGraphModel)) else load_quantized(model_or_file)
+        from .quantize_mixednet import QuantizedMixedNetModel
+        known = (QuantizedModel, QuantizedGraphModel, QuantizedMixedNetModel)
+        q = model_or_file if isinstance(model_or_file, known) else load_quantized(model_or_file)
         if context is None:
             raise ValueError("QuantizedStreamingModel needs the float model whose context it shares (context=...)")
         if mode not in native.STREAM_MODES:
@@ -231,6 +240,8 @@ class QuantizedStreamingModel(StreamingModel):
         self.desc = dict(q.desc, mode=mode)
         if isinstance(q, QuantizedGraphModel):
             self.native = native.GraphStream(context.engine, self.desc, int8=True)
+        elif isinstance(q, QuantizedMixedNetModel):
+            self.native = native.Stream(context.engine, self.desc, int8=True)
         else:
             self.native = native.Stream(context.engine, self.desc)
         self.native.set_quantized(*q.packed())

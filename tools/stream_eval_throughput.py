@@ -8,6 +8,8 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
     python tools/stream_eval_throughput.py --hours 20 --model inception   # the default Inception flags, T = 176
     python tools/stream_eval_throughput.py --hours 20 --model inception --quantized   # its int8 model (csrc/tu_stream_graph_q8.hip)
     python tools/stream_eval_throughput.py --hours 20 --residual_connection 1,0,1,0 --pooled 1   # csrc/tu_stream_mixednet.hip
+    python tools/stream_eval_throughput.py --hours 20 --residual_connection 1,0,1,0 --pooled 1 --quantized   # its int8 model
+                                                                    # (csrc/tu_stream_mixednet_q8.hip, quantize_mixednet.py)
     python tools/stream_eval_throughput.py --hours 20 --mode non_stream --residual_connection 1,0,1,0 --repeat_in_block 1,2,1,1 \
         --spatial_attention 1 --pooled 1 --max_pool 1     # every window of the non-streaming model (attention: this mode only)
 """
@@ -20,7 +22,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from microwakeword_amd import inception, mixednet, native, quantize, quantize_graph, streaming  # noqa: E402
+from microwakeword_amd import inception, mixednet, native, quantize, quantize_graph, quantize_mixednet, streaming  # noqa: E402
 
 DEF = dict(pointwise_filters="48,48,48,48", residual_connection="0,0,0,0", repeat_in_block="1,1,1,1",
            mixconv_kernel_sizes="[5],[9],[13],[21]", max_pool=0, first_conv_filters=32, first_conv_kernel_size=3,
@@ -87,6 +89,15 @@ def main():
                 st.set_weights(flat)
                 return st
             q = quantize_graph
+        elif streaming.mixednet_variant_flags(flags):   # residual / pooled: the stream that takes the int8 calls, and its contract
+            desc = streaming.mixednet_stream_description(flags, T, 1, "stream")
+            flat = np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in model.get_weights()])
+
+            def calibration_stream():
+                st = native.Stream(model.engine, desc, int8=True)
+                st.set_weights(flat)
+                return st
+            q = quantize_mixednet
         else:
             calibration_stream = lambda: streaming.StreamingModel(model, 1, "stream").native   # noqa: E731
             q = quantize

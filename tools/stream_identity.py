@@ -7,6 +7,7 @@ arithmetic leaves every hash as it was.
     python tools/stream_identity.py --lib B.so > b.jsonl
     python tools/stream_identity.py --compare a.jsonl b.jsonl  # two columns, exit status 1 when a hash differs
     python tools/stream_identity.py --lib tests/hipemu/libmww_emu.so --emulator   # the cases the emulator tests run
+    python tools/stream_identity.py --variants   # after those, the float cases of tests/mixednet_variant_checks.py
 
 The cases: those of tests/stream_sweep.py (the script of each case: several stream-mode calls with resets, zero-output and
 one-output calls between them; its non-stream twin), tests/inception_streaming_checks.py ``stream_cases()`` /
@@ -94,6 +95,40 @@ def sweep_case(lib, c, n_cu):
     return H
 
 
+def variant_case(lib, c, n_cu):
+    """tests/mixednet_variant_checks.py: the case's script on a float stream of mww_stream_create_mixednet (none for a
+    spatial-attention case), then its non-stream twin"""
+    import mixednet_variant_checks as vc
+    import stream_sweep as sw
+    import streaming_checks as sc
+    b, s, H = vc.built(c.id), c.desc["stride"], Hashes()
+    model = sc.context_model(lib)
+    if c.script:
+        st = vc.new_stream(lib, b)
+        for i, step in enumerate(c.script):
+            rng = sw._rng(c.id, 0, i)
+            if step[0] == "reset":
+                st.reset()
+            elif step[0] == "zero":
+                st.run_host(sw.gen_frames(rng, s - 1))
+            elif step[0] == "tracks":
+                st.run(sc.Tracks(model, step[1], step[2], seed=int(rng.integers(1 << 30))).win)
+            elif step[0] in ("host", "outputs"):
+                n = step[1] if step[0] == "host" else ((2 * n_cu + 2) * sw.TILE + 5 if step[1] == "grid" else step[1]) * s + s - 1
+                st.run_host(sw.gen_frames(rng, n, "u16" if i % 2 else "f32"))
+            else:
+                for _ in range(step[1]):
+                    st.run_host(sw.gen_frames(rng, s))
+                    H.add_float(st)
+            H.add_float(st)
+        st.close()
+    st = vc.new_stream(lib, b, "non_stream")
+    st.run(sc.Tracks(model, c.ns[0], c.ns[1], seed=vc.SEED).win)
+    H.add_float(st)
+    st.close()
+    return H
+
+
 def graph_float_case(lib, flags, T, calls, seed, non_stream=None):
     """tests/inception_streaming_checks.py: successive calls on one float graph stream, then non-stream mode"""
     import inception_streaming_checks as ic
@@ -135,7 +170,7 @@ def graph_q8_case(lib, case):
     return H
 
 
-def run(lib, emulator):
+def run(lib, emulator, variants=False):
     import inception_streaming_checks as ic
     import quant_graph_checks as gc
     import stream_sweep as sw
@@ -150,6 +185,10 @@ def run(lib, emulator):
     for name, case in gc.cases().items():
         if small(name) or name.startswith("sweep/"):
             print(graph_q8_case(lib, case).line("quant_graph/" + name), flush=True)
+    if variants:   # after the existing set, whose output stays as it was
+        import mixednet_variant_checks as vc
+        for c in vc._cases():
+            print(variant_case(lib, c, n_cu).line("mixednet_variant/" + c.id), flush=True)
 
 
 def compare(path_a, path_b):
@@ -170,12 +209,13 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--lib", help="library to run (default: the package's own)")
     ap.add_argument("--emulator", action="store_true", help="the emulator-sized part of the cases (a library of tests/hipemu)")
+    ap.add_argument("--variants", action="store_true", help="also the float cases of tests/mixednet_variant_checks.py (residual, pooled, attention)")
     ap.add_argument("--compare", nargs=2, metavar="JSONL")
     a = ap.parse_args()
     if a.compare:
         sys.exit(compare(*a.compare))
     from microwakeword_amd import native
-    run(native.NativeLib.get(a.lib), a.emulator)
+    run(native.NativeLib.get(a.lib), a.emulator, a.variants)
 
 
 if __name__ == "__main__":
