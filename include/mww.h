@@ -528,6 +528,23 @@ int mww_stream_set_probs(mww_stream* s, const float* probs, int64_t n);       /*
  * probabilities after the first `skip`.  ma_len[t]: moving-average values of track t (score is -inf when 0). */
 int mww_stream_metrics(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip,
                        int cooldown, const double* cutoffs, int n_cutoffs, uint64_t* counts, int64_t* ma_len, float* score);
+/* WHERE the moving average crosses ONE cutoff (csrc/tu_stream_detect.hip), on the probabilities held - so on a
+ * stream of any creator, float or int8.  Moving average, kinds, `skip` and the cooldown are those of mww_stream_metrics: a
+ * track of n probabilities has m = n - window + 1 values avg_i (0 when n < window).
+ *   kind 0 (ambient): index i is a detection iff (double)avg_i > cutoff and i >= next_ok, where next_ok starts at
+ *     max(cooldown - 1, 0) and becomes i + max(cooldown, 1) after a detection (the closed form of test.py:119-135: cooldown
+ *     starts at `cooldown`, is decremented with a floor at 0 before each value, a detection resets it).  Events
+ *     (track, index, average) come ordered by track, then index; track_count[t] is the track's detections, complete whatever
+ *     `capacity` is, and sums to what mww_stream_metrics counts at that cutoff; best_index[t] = -1, score[t] = 0.
+ *   kind 1 (positive): after the first `skip` probabilities, score[t] = the maximum moving average (the bits of
+ *     mww_stream_metrics) and best_index[t] = the smallest moving-average index, counted after the skip, that attains it
+ *     (-1 and -inf when there is no value); track_count[t] = 0.
+ * Returns the number of detections of the whole call, which may exceed `capacity`: the first `capacity` events are written
+ * (out may be NULL when capacity is 0), or an error < 0.  Two calls on the same probabilities write the same bytes. */
+typedef struct { int32_t track; int32_t reserved; int64_t index; float average; float reserved2; } mww_detection;
+int64_t mww_stream_detections(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip,
+                              int cooldown, double cutoff, mww_detection* out, int64_t capacity, int64_t* track_count,
+                              int64_t* best_index, float* score);
 
 /* ---- int8 quantized streaming model (the reference's --test_tflite_streaming_quantized; microwakeword_amd/quantize.py
  * derives the parameters, INTEGRATION.md states the contract).

@@ -303,6 +303,11 @@ struct mww_stream {
   std::vector<char> htab;   // host copy of the last call's tables
   float* rec = nullptr;     // calibration partials
   int64_t cap_rec = 0;
+  // detections (tu_stream_detect.hip): the call's tables, its candidates and transfer tables, its events
+  char* det_tab = nullptr;
+  char* det_cand = nullptr;
+  mww_detection* det_out = nullptr;
+  int64_t cap_det_tab = 0, cap_det_cand = 0, cap_det_out = 0;
   // int8 form (mww_stream_set_quantized): runs replace the float kernel with the int8 one
   bool q8 = false;
   int8_t* q8_w = nullptr;

@@ -114,6 +114,57 @@ class MmapFeatureProvider:
         return self.truncation_strategy if requested == "default" else requested
 
 
+class MinedFeatureProvider:
+    """A provider whose ``"training"`` samples ALIAS rows of other providers' resident stores
+    (``FeatureHandler.add_mined_provider``): sample i is (source provider, dtype key, first element, rows) - exactly what
+    ``mww_sampler_desc`` holds per sample -, so it owns no flat image and uploads nothing.  Every other mode is empty.
+    The samples stay in the order given: unlike ``MmapFeatureProvider`` it shuffles nothing, so creating one draws nothing
+    from Python's or numpy's global generators."""
+
+    def __init__(self, sources, samples, label, sampling_weight, penalty_weight, truncation_strategy, step):
+        self.label = float(label)
+        self.sampling_weight = sampling_weight
+        self.penalty_weight = penalty_weight
+        self.truncation_strategy = truncation_strategy
+        self.fixed_right_cutoffs = [0]
+        self.step = step
+        self.sources = list(sources)              # [(provider, dtype key)]: what a sample's store index refers to
+        self.samples = list(samples)              # [(source index, src_elem, rows)]
+        self.flat: Dict[str, np.ndarray] = {}     # nothing of its own to upload
+        self.loaded_features: List[Sequence[np.ndarray]] = []
+        self.feature_sets: Dict[str, List[Tuple[int, int]]] = {m: [] for m in MODES}
+        self.feature_sets["training"] = [(src, i) for i, (src, _, _) in enumerate(self.samples)]
+        self.feature_dtype = list(range(len(self.sources)))   # (fi -> key of store_id)
+        self.sample_start = [{i: e for i, (s, e, _) in enumerate(self.samples) if s == k} for k in range(len(self.sources))]
+        self.sample_len = [{i: r for i, (s, _, r) in enumerate(self.samples) if s == k} for k in range(len(self.sources))]
+        self.stats = {m: {"spectrogram_count": 0, "total_duration": 0.0} for m in MODES}
+        self.stats["training"] = {"spectrogram_count": len(self.samples), "total_duration": sum(step * r for _, _, r in self.samples)}
+
+    @property
+    def store_id(self):
+        """the source stores' CURRENT ids (they are handed out again by every ``FeatureHandler.attach``)"""
+        return {k: p.store_id[key] for k, (p, key) in enumerate(self.sources)}
+
+    def host_rows(self, i):
+        """sample i as the float32 [rows, 40] frames the device serves (u16 stores scaled by 0.0390625)"""
+        src, elem, rows = self.samples[i]
+        p, key = self.sources[src]
+        a = p.flat[key][elem:elem + rows * FEATURE_BINS].reshape(rows, FEATURE_BINS)
+        return a.astype(np.float32) * np.float32(0.0390625) if key == "u16" else a.astype(np.float32)
+
+    def build_flat(self, keep=None):
+        raise NotImplementedError("a mined provider aliases other providers' rows and has no image of its own")
+
+    def get_mode_duration(self, mode):
+        return self.stats[mode]["total_duration"]
+
+    def get_mode_size(self, mode):
+        return self.stats[mode]["spectrogram_count"]
+
+    def strategy(self, requested):
+        return self.truncation_strategy if requested == "default" else requested
+
+
 class FeatureHandler:
     """Drop-in for ``microwakeword.data.FeatureHandler`` (mmap providers)."""
 
@@ -172,6 +223,52 @@ class FeatureHandler:
         self._sampler = None
         self._eval_cache = {}
 
+    def add_mined_provider(self, clips, label=0.0, sampling_weight=1.0, penalty_weight=1.0, truncation_strategy="truncate_start"):
+        """Appends a provider whose ``"training"`` samples are ``clips``: ``mww_window``-style descriptors
+        (store, 0, rows, 0, src_elem) of rows that are ALREADY resident (``streaming.detection_clips`` /
+        ``mining.mine_hard_negatives`` produce them).  Nothing is uploaded (``uploaded_bytes`` stays), the samples keep the
+        order given and NOTHING is drawn from Python's or numpy's global generators: the reference has no such call, so the
+        streams it shares with us stay where they are, and a provider with ``sampling_weight`` 0 leaves every later batch as
+        it was.  The sampler (and a running prefetcher, its streams kept) is rebuilt, so both
+        ``next_training_batch_on_device`` and ``get_data("training", ...)`` serve the clips; ``"truncate_start"`` keeps a
+        clip's last T rows - with ``before = after = 0`` exactly the window that fired.  Returns the provider."""
+        if getattr(self, "_sharded_for", None) is not None and self._sharded_for[1] > 1:
+            raise NotImplementedError("mined providers are not available on a data-parallel sharded handler: a rank holds only "
+                                      "its shard of the training rows, so a clip mined on one rank is not resident on the others")
+        self._need_engine()
+        if truncation_strategy not in native.STRATEGIES or truncation_strategy in ("none", "fixed_right_cutoff", "split"):
+            raise ValueError("truncation strategy %r cannot serve mined clips" % (truncation_strategy,))
+        by_id = {}
+        for p in self.feature_providers:
+            if isinstance(p, MinedFeatureProvider):
+                continue
+            for key, sid in p.store_id.items():
+                by_id[int(sid)] = (p, key)
+        clips = np.ascontiguousarray(clips, native.WINDOW_DTYPE).reshape(-1)
+        sources, at, samples = [], {}, []
+        for i, c in enumerate(clips):
+            sid, rows, elem = int(c["store"]), int(c["copy_rows"]), int(c["src_elem"])
+            src = by_id.get(sid)
+            if src is None:
+                raise ValueError("clip %d names store %d, which this handler has not uploaded" % (i, sid))
+            size = src[0].flat[src[1]].size
+            if int(c["pad_rows"]) != 0 or rows <= 0 or elem < 0 or elem % FEATURE_BINS or elem + rows * FEATURE_BINS > size:
+                raise ValueError("clip %d (store %d, element %d, %d rows) is not a whole-row slice inside the resident store "
+                                 "of %d elements" % (i, sid, elem, rows, size))
+            if sid not in at:
+                at[sid] = len(sources)
+                sources.append(src)
+            samples.append((at[sid], elem, rows))
+        if not samples:
+            raise ValueError("no clips to add")
+        step = self.feature_providers[0].step
+        mined = MinedFeatureProvider(sources, samples, label, sampling_weight, penalty_weight, truncation_strategy, step)
+        self.feature_providers.append(mined)
+        if getattr(self, "_pf", None) is not None:
+            self._drop_prefetcher(keep_streams=True)   # its sampler description does not know the new provider
+        self._sampler = None
+        return mined
+
     def shard_training_lists(self, rank: int, world: int):
         """per provider, training sample i of the CANONICAL (store, sample) order goes to rank i mod W - a partition
         whatever per-rank shuffle produced the list - and only those samples (plus every validation / testing sample: their
@@ -181,6 +278,8 @@ class FeatureHandler:
             return
         if getattr(self, "_sharded_for", None) is not None:
             raise ValueError("feature handler already sharded for rank/world %r" % (self._sharded_for,))
+        if int(world) > 1 and any(isinstance(p, MinedFeatureProvider) for p in self.feature_providers):
+            raise NotImplementedError("a handler with a mined provider cannot be sharded: the clips alias rows that a rank's shard drops")
         if int(world) == 1:   # a world of one keeps everything (and the image it has): only the canonical order of the lists
             for p in self.feature_providers:
                 p.feature_sets["training"] = sorted(p.feature_sets["training"])

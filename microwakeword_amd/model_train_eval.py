@@ -136,6 +136,10 @@ def build_parser():
                         help="native: run --test_tflite_streaming_quantized on the int8 kernel here, calibrated and quantized "
                              "by a restatement of TFLite's int8 arithmetic (not TFLite itself); native_ext: native, plus the "
                              "restated int8 ADD / AVERAGE_POOL_2D / MAX_POOL_2D of MixedNets with --residual_connection or --pooled")
+    parser.add_argument("--detections_cutoff", type=float, default=None,
+                        help="with a --test_tflite_* evaluation that runs here: also write detections.txt / detections.npz next to "
+                             "tflite_streaming_roc.txt - every ambient false accept (track, time, moving average) and every missed "
+                             "positive at this probability cutoff")
     parser.add_argument("--restore_checkpoint", type=int, default=0)
     parser.add_argument("--use_weights", type=str, default="best_weights")
     parser.add_argument("--verbosity", type=str, default="INFO")
@@ -194,7 +198,8 @@ def evaluate_model(flags, model_module, config, device=0):
             logging.info("Testing the %s model false accept per hour and false rejection rates at various cutoffs", mode)
             sm = streaming.StreamingModel(model, config["stride"], mode)
             out[folder] = streaming.streaming_model_roc(config, folder, sm, data_processor, data_set="testing",
-                                                        ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt")
+                                                        ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt",
+                                                        detections_cutoff=getattr(flags, "detections_cutoff", None))
     if getattr(flags, "test_tflite_streaming_quantized", 0):
         quantize = quantization_module(model, getattr(flags, "quantized_backend", "native"))
         folder = "tflite_stream_state_internal_quant"
@@ -208,7 +213,8 @@ def evaluate_model(flags, model_module, config, device=0):
         logging.info("int8 parameters:\n%s", qm.summary())
         qsm = streaming.QuantizedStreamingModel(qm, config["stride"], "stream", context=model)
         out[folder] = streaming.streaming_model_roc(config, folder, qsm, data_processor, data_set="testing",
-                                                    ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt")
+                                                    ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt",
+                                                    detections_cutoff=getattr(flags, "detections_cutoff", None))
     return out
 
 

@@ -63,6 +63,10 @@ class Window(C.Structure):
 WINDOW_DTYPE = np.dtype([("store", np.int32), ("pad_rows", np.int32), ("copy_rows", np.int32), ("reserved", np.int32),
                          ("src_elem", np.int64)])
 assert WINDOW_DTYPE.itemsize == C.sizeof(Window)
+# mww_detection as the library writes it, and the structured array Stream.detections returns
+DETECTION_RAW = np.dtype([("track", np.int32), ("reserved", np.int32), ("index", np.int64), ("average", np.float32), ("reserved2", np.float32)])
+DETECTION_DTYPE = np.dtype([("track", np.int32), ("index", np.int64), ("average", np.float32)])
+assert DETECTION_RAW.itemsize == 24
 
 
 class MetricsRaw(C.Structure):
@@ -122,7 +126,7 @@ EXPORTS = [
     "mww_stream_reset", "mww_stream_get_state", "mww_stream_run", "mww_stream_run_host", "mww_stream_read", "mww_stream_set_probs",
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
-    "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8",
+    "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections",
 ]
 
 
@@ -231,6 +235,9 @@ class NativeLib:
         L.mww_stream_read.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64]
         L.mww_stream_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mww_stream_detections.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
+                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mww_stream_detections.restype = C.c_int64
         L.mww_stream_num_tensors.argtypes = [C.c_void_p]
         L.mww_stream_calibrate_host.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float)]
         L.mww_stream_set_quantized.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
@@ -743,6 +750,37 @@ class Stream:
         self.nl.check(self.nl.lib.mww_stream_metrics(self.h, vp(off), vp(kd), n, int(window), int(skip), int(cooldown), vp(cut),
                                                      cut.size, vp(counts), vp(ma_len), vp(score)))
         return counts, ma_len, score
+
+    def detections(self, offsets, kind, cutoff, window, skip, cooldown, capacity=None):
+        """``mww_stream_detections`` on the probabilities held: where the moving average crosses ``cutoff`` on the ambient
+        (kind 0) tracks, and where a positive (kind 1) track reaches its score.  -> (events DETECTION_DTYPE in (track, index)
+        order, track_count int64 [n], best_index int64 [n], score float32 [n]).  ``capacity=None`` calls once to count and
+        once to fetch; a given capacity fetches at most that many events (track_count stays complete)."""
+        off = np.ascontiguousarray(offsets, np.int64)
+        kd = np.ascontiguousarray(kind, np.int32)
+        n = kd.size
+        if off.size != n + 1:
+            raise ValueError("offsets must have one entry more than kind")
+        track_count = np.zeros(n, np.int64)
+        best_index = np.zeros(n, np.int64)
+        score = np.zeros(n, np.float32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+
+        def call(events):
+            return int(self.nl.check(self.nl.lib.mww_stream_detections(
+                self.h, vp(off), vp(kd), n, int(window), int(skip), int(cooldown), float(cutoff),
+                vp(events) if events.size else None, events.size, vp(track_count), vp(best_index), vp(score))))
+
+        counted = capacity is None
+        if counted:
+            capacity = call(np.zeros(0, DETECTION_RAW))
+        raw = np.zeros(int(capacity), DETECTION_RAW)
+        if raw.size or not counted:   # (nothing to fetch after a count of 0)
+            raw = raw[:min(call(raw), raw.size)]
+        events = np.zeros(raw.size, DETECTION_DTYPE)
+        for name in DETECTION_DTYPE.names:
+            events[name] = raw[name]
+        return events, track_count, best_index, score
 
     # ---- int8 form (include/mww.h, mww_stream_set_quantized)
     def num_tensors(self) -> int:

@@ -199,6 +199,13 @@ class StreamingModel:
         """Device-side detection metrics on the probabilities of the last call (see mww_stream_metrics)."""
         return self.native.metrics(offsets, kind, cutoffs, sliding_window_length, ignore_slices_after_accept, ignore_slices_after_accept)
 
+    def detections(self, offsets, kind, cutoff, sliding_window_length=5, ignore_slices_after_accept=25):
+        """Where the probabilities of the last call fire at ONE cutoff (mww_stream_detections; ``detection_positions`` is the
+        host restatement): ``(events, track_count, best_index, score)`` - ``events`` a structured array (track, index,
+        average) of the ambient (kind 0) tracks' false accepts in (track, index) order, ``best_index`` / ``score`` where a
+        positive (kind 1) track reaches its maximum after the first ``ignore_slices_after_accept`` probabilities."""
+        return self.native.detections(offsets, kind, cutoff, sliding_window_length, ignore_slices_after_accept, ignore_slices_after_accept)
+
 
 def load_quantized(path):
     """the ``QuantizedModel`` (MixedNet), ``QuantizedMixedNetModel`` (MixedNet with residuals / a pooled head) or
@@ -281,6 +288,64 @@ def false_accept_counts(moving_averages: List[np.ndarray], cutoffs, ignore_slice
             counts += hit.astype(np.uint64)
             cooldown[hit] = ignore_slices_after_accept
     return counts
+
+
+def moving_average_in_order(probabilities, sliding_window_length=5) -> np.ndarray:
+    """The moving average as the kernels compute it, spelled out: the float32 sum p[i] + p[i+1] + ... taken in that order,
+    then one float32 division by the window length.  Fewer than w probabilities give an empty array."""
+    p = np.asarray(probabilities, np.float32)
+    w = int(sliding_window_length)
+    m = p.size - w + 1
+    if m <= 0:
+        return np.zeros(0, np.float32)
+    s = np.zeros(m, np.float32)
+    for k in range(w):
+        s = s + p[k:k + m]
+    return s / np.float32(w)
+
+
+def detection_positions(moving_averages: List[np.ndarray], cutoff, ignore_slices_after_accept=25) -> List[np.ndarray]:
+    """The loop of test.py:119-135 at one cutoff, recording WHERE it counts: per track the int64 indices of the moving
+    average at which a false accept is counted (cooldown restarted per track).  ``len`` of each equals that track's share of
+    ``false_accept_counts`` at the cutoff."""
+    cutoff = float(cutoff)
+    out = []
+    for track in moving_averages:
+        cooldown = ignore_slices_after_accept
+        hits = []
+        for i, value in enumerate(np.asarray(track, np.float32)):
+            cooldown = max(cooldown - 1, 0)
+            if cooldown == 0 and float(value) > cutoff:
+                hits.append(i)
+                cooldown = ignore_slices_after_accept
+        out.append(np.array(hits, np.int64))
+    return out
+
+
+def detection_clips(windows, events, frames, stride, mode, sliding_window_length, before=0, after=0, return_kept=False):
+    """The feature rows behind each detection as slices of the resident stores.  ``windows``: the tracks that were run
+    (``FeatureHandler.track_windows``), ``events``: what ``detections`` returned for them.  The last probability of the
+    event's averaging window is output n = index + w - 1 of its track; it was computed from the track rows ending at
+    e = (n + 1) * stride (``mode="stream"``) or e = frames + n * stride (``"non_stream"``).  The clip is the track rows
+    [e - frames - before, e + after) - with before = after = 0 exactly the window that fired - clipped to the rows the store
+    holds: a track's ``pad_rows`` leading zero frames exist in no store.  Returns ``mww_window`` descriptors
+    (store, 0, rows, 0, src_elem), empty clips dropped; with ``return_kept`` also the positions in ``events`` of the clips
+    kept."""
+    if mode not in native.STREAM_MODES:
+        raise ValueError("mode must be 'stream' or 'non_stream'")
+    win = np.ascontiguousarray(windows, native.WINDOW_DTYPE).reshape(-1)
+    trk = np.asarray(events["track"], np.int64)
+    n = np.asarray(events["index"], np.int64) + int(sliding_window_length) - 1
+    end = (n + 1) * int(stride) if mode == "stream" else int(frames) + n * int(stride)
+    pad = win["pad_rows"][trk].astype(np.int64)
+    lo = np.maximum(end - int(frames) - int(before) - pad, 0)
+    hi = np.minimum(end + int(after) - pad, win["copy_rows"][trk].astype(np.int64))
+    keep = np.nonzero(hi > lo)[0]
+    clips = np.zeros(keep.size, native.WINDOW_DTYPE)
+    clips["store"] = win["store"][trk[keep]]
+    clips["copy_rows"] = hi[keep] - lo[keep]
+    clips["src_elem"] = win["src_elem"][trk[keep]] + lo[keep] * FEATURE_BINS
+    return (clips, keep) if return_kept else clips
 
 
 def track_hours(ma_lengths, stride=1, step_s=0.02) -> float:
@@ -378,11 +443,14 @@ def _finish(counts, faph, scores, cutoffs):
 
 def streaming_model_roc(config, folder, streaming_model: StreamingModel, data_processor, data_set="testing",
                         ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt", sliding_window_length=5,
-                        ignore_slices_after_accept=25):
+                        ignore_slices_after_accept=25, detections_cutoff=None):
     """test.py:293-403 ``tflite_streaming_model_roc`` on the device: the ambient tracks, then the positive tracks of
     ``data_set``, through one stream whose state carries over (stream mode; starting from the state it has - a fresh
     ``StreamingModel`` starts from zeros, as the reference's interpreter does), the moving averages / cooldown counts /
-    scores by the metrics kernel.  Writes ``<train_dir>/<folder>/<accuracy_name>`` and returns the AUC."""
+    scores by the metrics kernel.  Writes ``<train_dir>/<folder>/<accuracy_name>`` and returns the AUC.
+    ``detections_cutoff`` (``--detections_cutoff``): additionally locates, on the same probabilities, every ambient false
+    accept and every positive whose score is not above that cutoff (``detections_report``) and writes ``detections.txt`` /
+    ``detections.npz`` into the same folder; the ROC file does not change."""
     stride = int(config["stride"])
     step_s = config["window_step_ms"] / 1000
     sm = streaming_model
@@ -396,6 +464,9 @@ def streaming_model_roc(config, folder, streaming_model: StreamingModel, data_pr
         if bad.size:
             raise ValueError("ambient track %d of %r has fewer than %d probabilities" % (bad[0], ambient_set, sliding_window_length))
         hours = track_hours(ma_len, stride, step_s)
+    located = {}
+    if detections_cutoff is not None and n_amb:
+        located["ambient"] = sm.detections(off, np.zeros(n_amb, np.int32), detections_cutoff, sliding_window_length, ignore_slices_after_accept)
     faph = counts.astype(np.float64) / hours
     off, _ = sm.predict_tracks(data_processor, data_set, only_label=1.0)
     n_pos = off.size - 1
@@ -407,12 +478,41 @@ def streaming_model_roc(config, folder, streaming_model: StreamingModel, data_pr
             raise ValueError("positive track %d of %r has no moving-average value after skipping %d probabilities"
                              % (bad[0], data_set, ignore_slices_after_accept))
         scores = list(score)
+        if detections_cutoff is not None:
+            located["positive"] = sm.detections(off, np.ones(n_pos, np.int32), detections_cutoff, sliding_window_length, ignore_slices_after_accept)
     res = _finish(counts, faph, scores, CUTOFFS)
     path = os.path.join(config["train_dir"], folder)
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, accuracy_name), "wt") as fd:
         fd.write(res["text"])
+    if detections_cutoff is not None:
+        text, arrays = detections_report(located.get("ambient"), located.get("positive"), detections_cutoff, stride, step_s)
+        with open(os.path.join(path, "detections.txt"), "wt") as fd:
+            fd.write(text)
+        np.savez(os.path.join(path, "detections.npz"), **arrays)
     return res["auc"]
+
+
+def detections_report(ambient, positive, cutoff, stride=1, step_s=0.02):
+    """``detections.txt`` and the arrays of ``detections.npz``: ``ambient`` / ``positive`` are what ``detections`` returned
+    for the ambient tracks and for the positive tracks (or None).  Lists every ambient false accept - track number, time of
+    the moving-average index in seconds (index * stride * step), moving average - and every positive track whose score is
+    not above the cutoff (the test of test.py:380) with the time at which it came closest."""
+    ev = ambient[0] if ambient is not None else np.zeros(0, native.DETECTION_DTYPE)
+    n_pos = positive[3].size if positive is not None else 0
+    best = positive[2] if positive is not None else np.zeros(0, np.int64)
+    score = positive[3] if positive is not None else np.zeros(0, np.float32)
+    missed = np.array([t for t in range(n_pos) if not score[t] > cutoff], np.int64)
+    seconds = ev["index"].astype(np.float64) * stride * step_s
+    lines = ["Cutoff {:.4f}: {} ambient false accepts, {} of {} positives missed".format(float(cutoff), ev.size, missed.size, n_pos)]
+    for j in range(ev.size):
+        lines.append("ambient track {}: t={:.3f} s; average={:.6f}".format(int(ev["track"][j]), seconds[j], float(ev["average"][j])))
+    for t in missed:
+        lines.append("missed positive track {}: score={:.6f}; t={:.3f} s".format(int(t), float(score[t]), float(best[t]) * stride * step_s))
+    arrays = dict(cutoff=np.float64(cutoff), ambient_track=ev["track"].copy(), ambient_index=ev["index"].copy(), ambient_seconds=seconds,
+                  ambient_average=ev["average"].copy(), positive_score=np.asarray(score, np.float32),
+                  positive_best_index=np.asarray(best, np.int64), missed_positive_track=missed)
+    return "".join(line + "\n" for line in lines), arrays
 
 
 def compute_metrics(true_positives, true_negatives, false_positives, false_negatives):

@@ -12,6 +12,9 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
                                                                     # (csrc/tu_stream_mixednet_q8.hip, quantize_mixednet.py)
     python tools/stream_eval_throughput.py --hours 20 --mode non_stream --residual_connection 1,0,1,0 --repeat_in_block 1,2,1,1 \
         --spatial_attention 1 --pooled 1 --max_pool 1     # every window of the non-streaming model (attention: this mode only)
+    python tools/stream_eval_throughput.py --hours 20 --detections 0.5 --detections_out profiles/stream_detections_throughput.txt
+        # adds, on the ambient probabilities of the same session: mww_stream_metrics at the 101 cutoffs (the yardstick),
+        # mww_stream_detections at the cutoff and at 0.0 (every index a candidate); medians of --detections_reps calls
 """
 import argparse
 import json
@@ -46,6 +49,10 @@ def main():
         ap.add_argument("--" + flag, default=DEF[flag], help="mixednet flag (default %s)" % DEF[flag])
     for flag in ("spatial_attention", "pooled", "max_pool"):
         ap.add_argument("--" + flag, type=int, default=0, help="mixednet flag")
+    ap.add_argument("--detections", type=float, default=None, metavar="CUTOFF",
+                    help="also time mww_stream_detections at this cutoff and at 0.0 against mww_stream_metrics on the ambient probabilities")
+    ap.add_argument("--detections_reps", type=int, default=15)
+    ap.add_argument("--detections_out", default=None, help="write the detection leg's times and event counts to this text file")
     a = ap.parse_args()
     if a.model == "inception":
         T = a.frames or 176
@@ -145,7 +152,60 @@ def main():
            "outputs_per_s": round(n_out / t, 1), "audio_hours_per_s": round(hours / t, 3),
            "windowed_outputs": nw, "windowed_seconds": round(tw, 4), "windowed_outputs_per_s": round(nw / tw, 1),
            "speedup_vs_windowed": round((n_out / t) / (nw / tw), 2), "library": model.engine.nl.version()}
+    if a.detections is not None:
+        rec["detections"] = detections_leg(sm, amb_win, a.detections, a.detections_reps)
+        if a.detections_out:
+            with open(a.detections_out, "wt") as fd:
+                fd.write(detections_text(rec))
     print(json.dumps(rec), flush=True)
+
+
+def detections_leg(sm, amb_win, cutoff, reps):
+    """One session, the same ambient probabilities: the median wall time of `reps` calls (after one warm-up call each) of
+    mww_stream_metrics at the 101 cutoffs and of mww_stream_detections (one call, capacity = the count) at `cutoff`, at
+    0.0 and at the median moving average, window 5, cooldown 25."""
+    off = sm.native.run(amb_win)
+    kind = np.zeros(amb_win.size, np.int32)
+
+    def median_ms(fn):
+        fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return round(float(np.median(ts)) * 1e3, 3)
+
+    out = {"probabilities": int(off[-1]), "tracks": int(amb_win.size), "reps": reps, "window": 5, "cooldown": 25,
+           "metrics_101_cutoffs_ms": median_ms(lambda: sm.metrics(off, kind))}
+    counts, _, _ = sm.metrics(off, kind)
+    # a model with random weights may put every probability on one side of `cutoff`: the median of the moving averages makes
+    # about half of the indices candidates
+    p = sm.read_probabilities()
+    med = float(np.median(np.concatenate([streaming.moving_average_in_order(p[off[t]:off[t + 1]], 5) for t in range(amb_win.size)])))
+    for name, c in (("cutoff", float(cutoff)), ("worst_case", 0.0), ("median", med)):
+        events, track_count, _, _ = sm.detections(off, kind, c)
+        n = int(track_count.sum())
+        at = int(np.argmin(np.abs(streaming.CUTOFFS - c)))
+        assert events.size == n and (abs(streaming.CUTOFFS[at] - c) > 1e-9 or n == int(counts[at])), (n, counts[at])
+        out[name] = {"cutoff": c, "events": n,
+                     "detections_ms": median_ms(lambda: sm.native.detections(off, kind, c, 5, 25, 25, capacity=n)),
+                     "count_only_ms": median_ms(lambda: sm.native.detections(off, kind, c, 5, 25, 25, capacity=0))}
+    return out
+
+
+def detections_text(rec):
+    d = rec["detections"]
+    lines = ["mww_stream_detections against mww_stream_metrics, one session (tools/stream_eval_throughput.py --detections)",
+             "library: %s" % rec["library"], "model: %s%s" % (rec["model"], ", int8" if rec.get("quantized") else ""),
+             "%d probabilities in %d ambient tracks (%.1f h at 20 ms), window %d, cooldown %d; median wall time of %d calls each"
+             % (d["probabilities"], d["tracks"], d["probabilities"] * 0.02 / 3600, d["window"], d["cooldown"], d["reps"]),
+             "mww_stream_metrics, 101 cutoffs:          %9.3f ms" % d["metrics_101_cutoffs_ms"]]
+    for name in ("cutoff", "worst_case", "median"):
+        c = d[name]
+        lines.append("mww_stream_detections, cutoff %.4f:      %9.3f ms  (%d events; counting only, capacity 0: %.3f ms)"
+                     % (c["cutoff"], c["detections_ms"], c["events"], c["count_only_ms"]))
+    return "".join(line + "\n" for line in lines)
 
 
 if __name__ == "__main__":
