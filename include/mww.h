@@ -545,6 +545,17 @@ typedef struct { int32_t track; int32_t reserved; int64_t index; float average; 
 int64_t mww_stream_detections(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip,
                               int cooldown, double cutoff, mww_detection* out, int64_t capacity, int64_t* track_count,
                               int64_t* best_index, float* score);
+/* The grid a deployment is chosen from (csrc/tu_stream_oppoints.hip): row k of counts [n_windows][n_cutoffs],
+ * ma_len [n_windows][n_tracks] and score [n_windows][n_tracks] is exactly what mww_stream_metrics returns for window = windows[k]
+ * with the same other arguments - the same integers, the same score bits - with the semantics its comment states (moving
+ * average, comparison, cooldown, `skip`, empty tracks).  `windows` may be unsorted and may repeat; each lies in
+ * 1..MWW_OP_MAX_WINDOW, n_windows in 1..MWW_OP_MAX_WINDOWS, n_cutoffs in 1..128.  On the probabilities held, so on a stream
+ * of any creator, float or int8.  Two calls on the same probabilities write the same bytes. */
+#define MWW_OP_MAX_WINDOWS 32
+#define MWW_OP_MAX_WINDOW 256
+int mww_stream_operating_points(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, const int32_t* windows,
+                                int n_windows, int skip, int cooldown, const double* cutoffs, int n_cutoffs, uint64_t* counts,
+                                int64_t* ma_len, float* score);
 
 /* ---- int8 quantized streaming model (the reference's --test_tflite_streaming_quantized; microwakeword_amd/quantize.py
  * derives the parameters, INTEGRATION.md states the contract).

@@ -308,6 +308,10 @@ struct mww_stream {
   char* det_cand = nullptr;
   mww_detection* det_out = nullptr;
   int64_t cap_det_tab = 0, cap_det_cand = 0, cap_det_out = 0;
+  // operating points (tu_stream_oppoints.hip): the call's tables, the transfer tables of one pass over the windows
+  char* op_tab = nullptr;
+  char* op_scr = nullptr;
+  int64_t cap_op_tab = 0, cap_op_scr = 0;
   // int8 form (mww_stream_set_quantized): runs replace the float kernel with the int8 one
   bool q8 = false;
   int8_t* q8_w = nullptr;

@@ -29,6 +29,7 @@ import yaml
 
 from . import inception
 from . import mixednet
+from . import native
 from .data import FeatureHandler
 from . import train as train_mod
 
@@ -140,6 +141,12 @@ def build_parser():
                         help="with a --test_tflite_* evaluation that runs here: also write detections.txt / detections.npz next to "
                              "tflite_streaming_roc.txt - every ambient false accept (track, time, moving average) and every missed "
                              "positive at this probability cutoff")
+    parser.add_argument("--operating_point_faph", type=float, default=None,
+                        help="with a --test_tflite_* evaluation that runs here: also write operating_points.txt / operating_points.npz / "
+                             "operating_point.json next to tflite_streaming_roc.txt - FAPH and FRR at every (sliding window, cutoff) "
+                             "and the window and cutoff with the fewest false rejections at no more than this many false accepts per hour")
+    parser.add_argument("--operating_point_windows", type=str, default=",".join(str(w) for w in range(1, 11)),
+                        help="the sliding-window sizes of --operating_point_faph (comma separated, each 1..256, at most 32)")
     parser.add_argument("--restore_checkpoint", type=int, default=0)
     parser.add_argument("--use_weights", type=str, default="best_weights")
     parser.add_argument("--verbosity", type=str, default="INFO")
@@ -182,7 +189,8 @@ def evaluate_model(flags, model_module, config, device=0):
     with ``native_ext`` a MixedNet with residual connections or a pooled head: quantize_mixednet.py), the parameters in
     ``tflite_stream_state_internal_quant/stream_state_internal_quant.npz`` and the ROC of the int8 streaming model in
     ``tflite_stream_state_internal_quant/tflite_streaming_roc.txt``.  No TFLite file is written: the streaming /
-    non-streaming forms run natively from the same weights."""
+    non-streaming forms run natively from the same weights.  ``--operating_point_faph``: each of these ROC evaluations also
+    writes the operating-point grid of ``streaming.operating_point_grid`` into its folder."""
     from . import streaming
     model = model_module.model(flags, config["training_input_shape"], config["batch_size"], device=device)
     model.load_weights(os.path.join(config["train_dir"], flags.use_weights + ".weights.h5"))
@@ -200,6 +208,7 @@ def evaluate_model(flags, model_module, config, device=0):
             out[folder] = streaming.streaming_model_roc(config, folder, sm, data_processor, data_set="testing",
                                                         ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt",
                                                         detections_cutoff=getattr(flags, "detections_cutoff", None))
+            _operating_points(flags, config, folder, sm, data_processor)
     if getattr(flags, "test_tflite_streaming_quantized", 0):
         quantize = quantization_module(model, getattr(flags, "quantized_backend", "native"))
         folder = "tflite_stream_state_internal_quant"
@@ -215,7 +224,41 @@ def evaluate_model(flags, model_module, config, device=0):
         out[folder] = streaming.streaming_model_roc(config, folder, qsm, data_processor, data_set="testing",
                                                     ambient_set="testing_ambient", accuracy_name="tflite_streaming_roc.txt",
                                                     detections_cutoff=getattr(flags, "detections_cutoff", None))
+        _operating_points(flags, config, folder, qsm, data_processor)
     return out
+
+
+def operating_point_windows(flags):
+    """The windows of ``--operating_point_faph`` (None without the flag), checked from the flags alone: ValueError for a target
+    <= 0, a window outside 1..256, more than 32 windows, or no evaluation that runs here to attach the grid to."""
+    target = getattr(flags, "operating_point_faph", None)
+    if target is None:
+        return None
+    if not target > 0:
+        raise ValueError("--operating_point_faph must be positive")
+    try:
+        windows = [int(w) for w in str(flags.operating_point_windows).split(",")]
+    except ValueError:
+        raise ValueError("--operating_point_windows must be comma-separated integers") from None
+    if not 1 <= len(windows) <= native.OP_MAX_WINDOWS or any(not 1 <= w <= native.OP_MAX_WINDOW for w in windows):
+        raise ValueError("--operating_point_windows takes 1..%d windows, each in 1..%d" % (native.OP_MAX_WINDOWS, native.OP_MAX_WINDOW))
+    runs_here = getattr(flags, "test_tflite_streaming_quantized", 0) and getattr(flags, "quantized_backend", "tflite") in ("native", "native_ext")
+    if not (flags.test_tflite_nonstreaming or flags.test_tflite_streaming or runs_here):
+        raise ValueError("--operating_point_faph needs --test_tflite_nonstreaming, --test_tflite_streaming or a native "
+                         "--test_tflite_streaming_quantized evaluation")
+    return windows
+
+
+def _operating_points(flags, config, folder, sm, data_processor):
+    """``--operating_point_faph``: the grid of the evaluation ``folder`` just ran, on the same tracks from the same start"""
+    windows = operating_point_windows(flags)
+    if windows is None:
+        return
+    from . import streaming
+    sm.reset()   # the ROC started from a fresh stream
+    grid = streaming.operating_point_grid(config, folder, sm, data_processor, flags.operating_point_faph, windows, data_set="testing",
+                                          ambient_set="testing_ambient")
+    logging.info("%s: %s", folder, streaming.operating_point_text(grid).splitlines()[-1])
 
 
 def quantization_module(model, backend="native"):
@@ -269,6 +312,7 @@ def _run(flags, model_module, rank, local_rank, world):
                     "yields stride-row chunks, which do not fit the non-streaming model's T-row input, so there is no "
                     "well-defined calibration to restate")
         raise NotImplementedError(msg)
+    operating_point_windows(flags)
     config = load_config(flags, model_module)
     check_evaluation_flags(flags, model_module, config)   # before training and before train_dir is claimed
     device = flags.device if local_rank is None else local_rank

@@ -85,6 +85,7 @@ class SamplerDesc(C.Structure):
 STREAM_MAX_KERNELS = 8
 STREAM_MAX_REPEAT = 8
 STREAM_MODES = {"stream": 0, "non_stream": 1}
+OP_MAX_WINDOWS, OP_MAX_WINDOW = 32, 256   # MWW_OP_MAX_WINDOWS, MWW_OP_MAX_WINDOW (include/mww.h)
 
 
 class StreamDesc(C.Structure):
@@ -126,7 +127,7 @@ EXPORTS = [
     "mww_stream_reset", "mww_stream_get_state", "mww_stream_run", "mww_stream_run_host", "mww_stream_read", "mww_stream_set_probs",
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
-    "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections",
+    "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections", "mww_stream_operating_points",
 ]
 
 
@@ -238,6 +239,8 @@ class NativeLib:
         L.mww_stream_detections.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mww_stream_detections.restype = C.c_int64
+        L.mww_stream_operating_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mww_stream_num_tensors.argtypes = [C.c_void_p]
         L.mww_stream_calibrate_host.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float)]
         L.mww_stream_set_quantized.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
@@ -781,6 +784,24 @@ class Stream:
         for name in DETECTION_DTYPE.names:
             events[name] = raw[name]
         return events, track_count, best_index, score
+
+    def operating_points(self, offsets, kind, windows, cutoffs, skip=25, cooldown=25):
+        """``mww_stream_operating_points`` on the probabilities held: row k is ``metrics`` at ``windows[k]``.
+        -> (counts uint64 [W, C] summed over the kind-0 tracks, ma_len int64 [W, n], score float32 [W, n])"""
+        off = np.ascontiguousarray(offsets, np.int64)
+        kd = np.ascontiguousarray(kind, np.int32)
+        win = np.ascontiguousarray(windows, np.int32).reshape(-1)
+        cut = np.ascontiguousarray(cutoffs, np.float64).reshape(-1)
+        n = kd.size
+        if off.size != n + 1:
+            raise ValueError("offsets must have one entry more than kind")
+        counts = np.zeros((win.size, cut.size), np.uint64)
+        ma_len = np.zeros((win.size, n), np.int64)
+        score = np.zeros((win.size, n), np.float32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self.nl.check(self.nl.lib.mww_stream_operating_points(self.h, vp(off), vp(kd), n, vp(win), win.size, int(skip), int(cooldown),
+                                                              vp(cut), cut.size, vp(counts), vp(ma_len), vp(score)))
+        return counts, ma_len, score
 
     # ---- int8 form (include/mww.h, mww_stream_set_quantized)
     def num_tensors(self) -> int:

@@ -28,6 +28,7 @@ from .layout import FEATURE_BINS, InceptionLayout, _flag, parse
 
 SCALE_U16 = np.float32(0.0390625)
 CUTOFFS = np.arange(0, 1.01, 0.01)   # test.py:331
+OP_WINDOWS = tuple(range(1, 11))     # sliding-window sizes of the operating-point grid (the reference evaluates 5 alone)
 
 
 def stream_description(flags, t_final: int, frames: int, stride: int, mode: str) -> dict:
@@ -205,6 +206,12 @@ class StreamingModel:
         average) of the ambient (kind 0) tracks' false accepts in (track, index) order, ``best_index`` / ``score`` where a
         positive (kind 1) track reaches its maximum after the first ``ignore_slices_after_accept`` probabilities."""
         return self.native.detections(offsets, kind, cutoff, sliding_window_length, ignore_slices_after_accept, ignore_slices_after_accept)
+
+    def operating_points(self, offsets, kind, windows=OP_WINDOWS, cutoffs=CUTOFFS, ignore_slices_after_accept=25):
+        """``metrics`` at every sliding-window size of ``windows`` in one call (mww_stream_operating_points;
+        ``operating_points_host`` is the host restatement): ``(counts [W, C], ma_len [W, n], score [W, n])``, row k what
+        ``metrics`` returns for ``sliding_window_length=windows[k]``."""
+        return self.native.operating_points(offsets, kind, windows, cutoffs, ignore_slices_after_accept, ignore_slices_after_accept)
 
 
 def load_quantized(path):
@@ -491,6 +498,145 @@ def streaming_model_roc(config, folder, streaming_model: StreamingModel, data_pr
             fd.write(text)
         np.savez(os.path.join(path, "detections.npz"), **arrays)
     return res["auc"]
+
+
+# ------------------------------------------------------------------------------------------ choosing what to ship
+
+def select_operating_points(faph, frr, usable, target_faph, windows=None):
+    """The selection rule of the operating-point grid, on ``faph [W, C]`` / ``frr [W, C]`` (cutoffs ascending along C),
+    ``usable [W]`` and the rows' window sizes (default: ascending with the row).  Per usable window the chosen cutoff is the
+    smallest one with ``faph <= target_faph`` there AND at every larger cutoff of the grid (under a cooldown the counts need
+    not fall monotonically with the cutoff, so the first crossing is not enough); -1 when even the largest cutoff exceeds
+    the target, and for an unusable window.  The recommendation is the window whose chosen cutoff has the smallest FRR; ties
+    go to the smaller FAPH, then to the smaller window (then the earlier row).  Returns ``(chosen [W] int64, recommended)``,
+    ``recommended`` a row or -1 when no window meets the target; raises ValueError when no window is usable."""
+    faph, frr, usable = np.asarray(faph, np.float64), np.asarray(frr, np.float64), np.asarray(usable, bool)
+    if not usable.any():
+        raise ValueError("no window of the grid is usable: every one is longer than an ambient track or leaves a positive track without a value")
+    chosen = np.full(faph.shape[0], -1, np.int64)
+    for k in np.nonzero(usable)[0]:
+        above = np.nonzero(~(faph[k] <= target_faph))[0]
+        first = above[-1] + 1 if above.size else 0
+        if first < faph.shape[1]:
+            chosen[k] = first
+    windows = np.arange(chosen.size) if windows is None else np.asarray(windows, np.int64)
+    best = [(frr[k, chosen[k]], faph[k, chosen[k]], int(windows[k]), k) for k in range(chosen.size) if chosen[k] >= 0]
+    return chosen, (min(best)[3] if best else -1)
+
+
+def _operating_grid(counts, ambient_ma_len, positive_ma_len, score, windows, cutoffs, stride, step_s, target_faph):
+    """counts [W, C], ambient_ma_len [W, n_amb], positive_ma_len / score [W, n_pos] -> the grid's dict (both paths end here)"""
+    windows, cutoffs = np.asarray(windows, np.int64).reshape(-1), np.asarray(cutoffs, np.float64).reshape(-1)
+    if score.shape[1] == 0:
+        raise ValueError("the test set has no positive track")
+    W = windows.size
+    hours = np.array([track_hours(ambient_ma_len[k], stride, step_s) for k in range(W)], np.float64)
+    usable = np.array([ambient_ma_len.shape[1] > 0 and bool(np.all(ambient_ma_len[k] > 0)) and bool(np.all(positive_ma_len[k] > 0))
+                       for k in range(W)])
+    faph = np.full((W, cutoffs.size), np.nan)
+    frr = np.full((W, cutoffs.size), np.nan)
+    for k in np.nonzero(usable)[0]:
+        faph[k] = counts[k].astype(np.float64) / hours[k]
+        frr[k] = false_rejection_rates(list(score[k]), cutoffs)
+    out = dict(windows=windows, cutoffs=cutoffs, counts=np.asarray(counts, np.uint64), hours=hours, usable=usable, faph=faph, frr=frr,
+               ambient_ma_len=np.asarray(ambient_ma_len, np.int64), positive_ma_len=np.asarray(positive_ma_len, np.int64),
+               score=np.asarray(score, np.float32))
+    if target_faph is not None:
+        chosen, rec = select_operating_points(faph, frr, usable, target_faph, windows)
+        out.update(target_faph=float(target_faph), chosen=chosen, recommended=int(rec),
+                   chosen_cutoff=np.array([cutoffs[c] if c >= 0 else np.nan for c in chosen], np.float64))
+    return out
+
+
+def operating_points_host(ambient_probabilities, positive_probabilities, windows=OP_WINDOWS, cutoffs=CUTOFFS, stride=1, step_s=0.02,
+                          ignore_slices_after_accept=25, target_faph=None, skip=None):
+    """Host restatement of the operating-point grid on given per-track probabilities, from ``moving_average_in_order``,
+    ``false_accept_counts`` and ``false_rejection_rates``: per window of ``windows`` the ambient tracks' cooldown counts at
+    each cutoff, the positive tracks' scores after the first ``skip`` (default: ``ignore_slices_after_accept``)
+    probabilities, FAPH and FRR; with ``target_faph`` also the selection (``select_operating_points``).  Returns the dict
+    ``operating_point_grid`` returns."""
+    skip = ignore_slices_after_accept if skip is None else skip
+    windows = [int(w) for w in windows]
+    n_amb, n_pos = len(ambient_probabilities), len(positive_probabilities)
+    counts = np.zeros((len(windows), len(cutoffs)), np.uint64)
+    amb_len, pos_len = np.zeros((len(windows), n_amb), np.int64), np.zeros((len(windows), n_pos), np.int64)
+    score = np.zeros((len(windows), n_pos), np.float32)
+    done = {}
+    for k, w in enumerate(windows):
+        if w not in done:   # a window may repeat
+            amb = [moving_average_in_order(p, w) for p in ambient_probabilities]
+            pos = [moving_average_in_order(np.asarray(p, np.float32)[skip:], w) for p in positive_probabilities]
+            done[w] = (false_accept_counts(amb, cutoffs, ignore_slices_after_accept), [a.size for a in amb], [a.size for a in pos],
+                       [np.max(a) if a.size else np.float32(-np.inf) for a in pos])
+        counts[k], amb_len[k], pos_len[k], score[k] = done[w]
+    return _operating_grid(counts, amb_len, pos_len, score, windows, cutoffs, stride, step_s, target_faph)
+
+
+def operating_point_text(grid):
+    """``operating_points.txt``: one line per window, then the recommendation"""
+    lines = []
+    for k, w in enumerate(grid["windows"]):
+        c = grid["chosen"][k]
+        if not grid["usable"][k]:
+            lines.append("Window {}: unusable (longer than an ambient track, or no value left on a positive track)".format(w))
+        elif c < 0:
+            lines.append("Window {}: no cutoff of the grid keeps faph <= {:g}".format(w, grid["target_faph"]))
+        else:
+            lines.append("Window {}: cutoff={:.2f}; faph={:.3f}; frr={:.4f}".format(w, grid["cutoffs"][c], grid["faph"][k, c], grid["frr"][k, c]))
+    r = grid["recommended"]
+    if r < 0:
+        lines.append("Recommended: none (no window keeps faph <= {:g})".format(grid["target_faph"]))
+    else:
+        c = grid["chosen"][r]
+        lines.append("Recommended: window {}, cutoff {:.2f} (faph={:.3f}; frr={:.4f}) for faph <= {:g}".format(
+            grid["windows"][r], grid["cutoffs"][c], grid["faph"][r, c], grid["frr"][r, c], grid["target_faph"]))
+    return "".join(line + "\n" for line in lines)
+
+
+def operating_point_settings(grid, mode, quantized):
+    """``operating_point.json``: the recommendation as plain settings (None where no window meets the target)"""
+    r = grid["recommended"]
+    c = grid["chosen"][r] if r >= 0 else -1
+    return {"probability_cutoff": float(grid["cutoffs"][c]) if r >= 0 else None,
+            "sliding_window_size": int(grid["windows"][r]) if r >= 0 else None,
+            "false_accepts_per_hour": float(grid["faph"][r, c]) if r >= 0 else None,
+            "false_rejection_rate": float(grid["frr"][r, c]) if r >= 0 else None,
+            "target_false_accepts_per_hour": float(grid["target_faph"]), "mode": mode, "quantized": bool(quantized)}
+
+
+def operating_point_grid(config, folder, sm, data_processor, target_faph, windows=OP_WINDOWS, data_set="testing",
+                         ambient_set="testing_ambient", ignore_slices_after_accept=25):
+    """FAPH / FRR at every (sliding window, cutoff) of ``windows`` x ``CUTOFFS`` and the operating point for
+    ``target_faph``: the tracks are fed as ``streaming_model_roc`` feeds them (the ambient tracks, then the positive tracks
+    of ``data_set``, the ring state carried over, from the state the stream has), with one grid call per kind
+    (``StreamingModel.operating_points``).  Writes ``operating_points.txt`` / ``operating_points.npz`` /
+    ``operating_point.json`` into ``<train_dir>/<folder>`` and returns the grid (``operating_points_host`` is its host
+    restatement); a window no track set supports is reported unusable and left out of the choice."""
+    import json
+    stride = int(config["stride"])
+    step_s = config["window_step_ms"] / 1000
+    windows = [int(w) for w in windows]
+    off, _ = sm.predict_tracks(data_processor, ambient_set)
+    n_amb = off.size - 1
+    counts, amb_len = np.zeros((len(windows), CUTOFFS.size), np.uint64), np.zeros((len(windows), 0), np.int64)
+    if n_amb:
+        counts, amb_len, _ = sm.operating_points(off, np.zeros(n_amb, np.int32), windows, CUTOFFS, ignore_slices_after_accept)
+    off, _ = sm.predict_tracks(data_processor, data_set, only_label=1.0)
+    n_pos = off.size - 1
+    pos_len, score = np.zeros((len(windows), 0), np.int64), np.zeros((len(windows), 0), np.float32)
+    if n_pos:
+        _, pos_len, score = sm.operating_points(off, np.ones(n_pos, np.int32), windows, CUTOFFS, ignore_slices_after_accept)
+    grid = _operating_grid(counts, amb_len, pos_len, score, windows, CUTOFFS, stride, step_s, target_faph)
+    path = os.path.join(config["train_dir"], folder)
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, "operating_points.txt"), "wt") as fd:
+        fd.write(operating_point_text(grid))
+    np.savez(os.path.join(path, "operating_points.npz"), **{k: grid[k] for k in
+             ("windows", "cutoffs", "counts", "faph", "frr", "hours", "chosen_cutoff")}, recommended=np.int64(grid["recommended"]))
+    with open(os.path.join(path, "operating_point.json"), "wt") as fd:
+        json.dump(operating_point_settings(grid, sm.mode, isinstance(sm, QuantizedStreamingModel)), fd, indent=2)
+        fd.write("\n")
+    return grid
 
 
 def detections_report(ambient, positive, cutoff, stride=1, step_s=0.02):

@@ -15,6 +15,10 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
     python tools/stream_eval_throughput.py --hours 20 --detections 0.5 --detections_out profiles/stream_detections_throughput.txt
         # adds, on the ambient probabilities of the same session: mww_stream_metrics at the 101 cutoffs (the yardstick),
         # mww_stream_detections at the cutoff and at 0.0 (every index a candidate); medians of --detections_reps calls
+    python tools/stream_eval_throughput.py --hours 20 --operating_points --operating_points_out profiles/stream_operating_points_throughput.txt
+        # adds, on the same ambient probabilities: mww_stream_metrics at one window (the yardstick) against ONE
+        # mww_stream_operating_points call for 10 windows x 101 cutoffs, on CUTOFFS (cutoff 0: every index a candidate) and on
+        # 101 quantiles of the moving averages (every cutoff splits the indices differently)
 """
 import argparse
 import json
@@ -53,6 +57,9 @@ def main():
                     help="also time mww_stream_detections at this cutoff and at 0.0 against mww_stream_metrics on the ambient probabilities")
     ap.add_argument("--detections_reps", type=int, default=15)
     ap.add_argument("--detections_out", default=None, help="write the detection leg's times and event counts to this text file")
+    ap.add_argument("--operating_points", action="store_true",
+                    help="also time one mww_stream_operating_points call (10 windows x 101 cutoffs) against mww_stream_metrics at one window")
+    ap.add_argument("--operating_points_out", default=None, help="write the operating-point leg's times and scratch size to this text file")
     a = ap.parse_args()
     if a.model == "inception":
         T = a.frames or 176
@@ -157,6 +164,11 @@ def main():
         if a.detections_out:
             with open(a.detections_out, "wt") as fd:
                 fd.write(detections_text(rec))
+    if a.operating_points:
+        rec["operating_points"] = operating_points_leg(sm, amb_win, a.detections_reps)
+        if a.operating_points_out:
+            with open(a.operating_points_out, "wt") as fd:
+                fd.write(operating_points_text(rec))
     print(json.dumps(rec), flush=True)
 
 
@@ -192,6 +204,64 @@ def detections_leg(sm, amb_win, cutoff, reps):
                      "detections_ms": median_ms(lambda: sm.native.detections(off, kind, c, 5, 25, 25, capacity=n)),
                      "count_only_ms": median_ms(lambda: sm.native.detections(off, kind, c, 5, 25, 25, capacity=0))}
     return out
+
+
+def operating_points_scratch(ma_lengths, n_windows, n_cutoffs, cooldown, seg=1024, budget=96 << 20):
+    """bytes of transfer tables resident at a time (ma_lengths: per track, at the smallest window)"""
+    n_seg = sum((int(m) + seg - 1) // seg for m in ma_lengths)
+    per_window = max(n_seg, 1) * min(max(cooldown, 1), seg) * n_cutoffs * 4
+    return per_window * min(n_windows, max(budget // per_window, 1))
+
+
+def operating_points_leg(sm, amb_win, reps, cooldown=25):
+    """One session, the same ambient probabilities: the median wall time of `reps` calls (after one warm-up call each) of
+    mww_stream_metrics at the 101 cutoffs and window 5 (the yardstick) and of one mww_stream_operating_points call for windows
+    1..10 at the 101 cutoffs of CUTOFFS (0.0 among them: every index a candidate) and at 101 quantiles of the window-5
+    moving averages; host round trips included.  Every row is checked against the metrics call of its window."""
+    off = sm.native.run(amb_win)
+    kind = np.zeros(amb_win.size, np.int32)
+    windows = streaming.OP_WINDOWS
+
+    def median_ms(fn):
+        fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return round(float(np.median(ts)) * 1e3, 3)
+
+    p = sm.read_probabilities()
+    mas = np.concatenate([streaming.moving_average_in_order(p[off[t]:off[t + 1]], 5) for t in range(amb_win.size)])
+    quantiles = np.quantile(mas.astype(np.float64), np.linspace(0, 1, streaming.CUTOFFS.size))
+    out = {"probabilities": int(off[-1]), "tracks": int(amb_win.size), "reps": reps, "windows": list(windows), "cooldown": cooldown,
+           "scratch_bytes": operating_points_scratch(np.diff(off) - min(windows) + 1, len(windows), streaming.CUTOFFS.size, cooldown)}
+    for name, cut in (("cutoffs", streaming.CUTOFFS), ("quantiles", quantiles)):
+        counts, ma_len, _ = sm.operating_points(off, kind, windows, cut, cooldown)
+        for k, w in enumerate(windows):
+            m = sm.metrics(off, kind, cut, w, cooldown)
+            assert np.array_equal(counts[k], m[0]) and np.array_equal(ma_len[k], m[1]), (name, w)
+        out[name] = {"metrics_one_window_ms": median_ms(lambda: sm.metrics(off, kind, cut, 5, cooldown)),
+                     "grid_ms": median_ms(lambda: sm.operating_points(off, kind, windows, cut, cooldown)),
+                     "false_accepts_window_5": [int(counts[4, 0]), int(counts[4, cut.size // 2]), int(counts[4, -1])]}
+    return out
+
+
+def operating_points_text(rec):
+    d = rec["operating_points"]
+    lines = ["mww_stream_operating_points against mww_stream_metrics, one session (tools/stream_eval_throughput.py --operating_points)",
+             "library: %s" % rec["library"], "model: %s%s" % (rec["model"], ", int8" if rec.get("quantized") else ""),
+             "%d probabilities in %d ambient tracks (%.1f h at 20 ms), cooldown %d; median wall time of %d calls each, host round trips included"
+             % (d["probabilities"], d["tracks"], d["probabilities"] * 0.02 / 3600, d["cooldown"], d["reps"]),
+             "grid: windows %s x 101 cutoffs in one call; transfer tables resident: %d bytes (%.1f MB)"
+             % (",".join(str(w) for w in d["windows"]), d["scratch_bytes"], d["scratch_bytes"] / 1e6)]
+    for name, what in (("cutoffs", "cutoffs 0.00 .. 1.00 (0.00: every index a candidate)"), ("quantiles", "cutoffs = 101 quantiles of the moving averages")):
+        c = d[name]
+        lines.append("%s:" % what)
+        lines.append("  mww_stream_metrics, window 5 (the yardstick):      %9.3f ms" % c["metrics_one_window_ms"])
+        lines.append("  mww_stream_operating_points, 10 windows:           %9.3f ms  (false accepts at window 5, first / middle / last cutoff: %s)"
+                     % (c["grid_ms"], " / ".join(str(v) for v in c["false_accepts_window_5"])))
+    return "".join(line + "\n" for line in lines)
 
 
 def detections_text(rec):
