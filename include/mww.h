@@ -422,7 +422,7 @@ typedef struct {
 typedef struct mww_stream mww_stream;
 /* MWW_ERR_UNSUPPORTED (+ message) for a malformed description or a topology outside the list above */
 int mww_stream_create(mww_ctx* ctx, const mww_stream_desc* desc, mww_stream** out);
-/* The same handle for a MixedNet with residual connections, a pooled head or spatial attention (csrc/tu_stream_mixednet.hip).
+/* The same handle for a MixedNet with residual connections, a pooled head or spatial attention (csrc/tu_stream.hip, the kernel's <VAR> form).
  * The description is the superset of mww_stream_desc; with no option set the stream is the one of mww_stream_create.  It is a
  * creator of its own because the test-suite pins what mww_stream_create takes and refuses: the old name keeps its behaviour.
  *   residual[b] (--residual_connection; mixednet.py:340-358): r = BN(Conv1x1(block input)), no bias, no ring and no state, is
@@ -458,8 +458,8 @@ typedef struct {
 } mww_mixednet_stream_desc;
 int mww_stream_create_mixednet(mww_ctx* ctx, const mww_mixednet_stream_desc* desc, mww_stream** out);
 /* The same MixedNet stream (same description, plan, float weights, state layout, same handle type) on which the six int8 entry
- * points work when the description uses residual or pool: calibration on the float kernel of csrc/tu_stream_mixednet.hip, then
- * the int8 kernel of csrc/tu_stream_mixednet_q8.hip once mww_stream_set_quantized has loaded parameters (layout: next to
+ * points work when the description uses residual or pool: calibration on the float kernel's <VAR, REC> form (csrc/tu_stream.hip), then
+ * the int8 kernel's <VAR> form (csrc/tu_stream_q8.hip) once mww_stream_set_quantized has loaded parameters (layout: next to
  * mww_stream_set_quantized below; contract: INTEGRATION.md 6, "residual and pooled MixedNets").  A creator of its own for the
  * reason mww_stream_create_convnet_q8 gives: the refusal of the int8 calls on a stream of mww_stream_create_mixednet is pinned
  * by the test-suite (tests/mixednet_variant_checks.py).  spatial_attention is refused here in BOTH modes

@@ -1,9 +1,9 @@
 // Shared by the streaming units.  A stream (mww_stream) has a front every stream has - context, per-call track /
 // segment / tile tables, outputs, float weights and state, int8 parameters and state; its host path is tu_stream.hip - and a
-// model part (SModel): MixedNet (tu_stream.hip float, tu_stream_mixednet.hip float with residuals / pooling / attention,
-// tu_stream_q8.hip int8, tu_stream_mixednet_q8.hip int8 with residuals / pooling; its plan is here) or a conv/BN graph
-// (stream_graph.hip.h).  The model's virtual functions are the one place the two kinds are told apart.  The device code all
-// four kernels share is here too: the tile header, the Dense heads, the head-ring write-back and the calibration (REC) folds.
+// model part (SModel): MixedNet (tu_stream.hip float, tu_stream_q8.hip int8, each kernel with a <VAR> form for residuals /
+// pooling / attention; its plan is here) or a conv/BN graph (stream_graph.hip.h).  The model's virtual functions are the one
+// place the two kinds are told apart.  The device code all four kernels share is here too: the tile header, the Dense heads,
+// the head-ring write-back and the calibration (REC) folds.
 // The kernels walk the same tiles and the same ring layout; only the element type and the arithmetic differ.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,7 +35,7 @@ inline int64_t r4(int64_t n) { return (n + 3) & ~(int64_t)3; }   // int8 rows an
 
 struct SLayer {
   int kind;          // 0: depthwise K taps + bias (fused MixConv groups, zero leading taps); 1: 1x1 + folded BN + ReLU;
-                     // (tu_stream_mixednet.hip only) 2: a block's residual 1x1 + folded BN, linear, of the block input, kept
+                     // (the kernels' <VAR> form only) 2: a block's residual 1x1 + folded BN, linear, of the block input, kept
                      // aside; 3: kind 1 with that residual added at equal positions before the ReLU
   int cin, cout, k;
   int64_t w, b;      // offsets into the weight buffer
@@ -51,7 +51,7 @@ struct SNet {
   const SLayer* L;           // [n_layers], device memory (the kernel argument stays small)
 };
 
-// What a MixedNet with residual connections, a pooled head or spatial attention adds to SNet (tu_stream_mixednet.hip)
+// What a MixedNet with residual connections, a pooled head or spatial attention adds to SNet (read by the kernels' <VAR> form only)
 struct SVar {
   int has_res;               // a third activation buffer holds the current block's residual
   int att, pool;             // spatial attention (non_stream mode only); 0 none, 1 average, 2 max pooling
@@ -367,7 +367,7 @@ struct MixedNet : SModel {
   int att = 0, pool = 0;
   bool q8_variant = false;             // mww_stream_create_mixednet_q8: a residual / pooled plan takes int8 parameters
   SVar var{};
-  bool variant() const { return var.has_res || var.att || var.pool; }   // runs the kernel of tu_stream_mixednet.hip
+  bool variant() const { return var.has_res || var.att || var.pool; }   // runs the kernels' <VAR> form
   SNet net{};
   std::vector<SLayer> layers;   // host copy of net.L
   SLayer* d_layers = nullptr;
@@ -398,13 +398,8 @@ struct MixedNet : SModel {
   void launch_q8(const SStores& S, const SCall& a, const SQ8& q, int grid, size_t lds, hipStream_t hs) const override;
 };
 
-// tu_stream_mixednet.hip: the float kernel of a MixedNet with residuals, a pooled head or attention (a.rec: the <REC> form)
-void launch_mixednet_variant(const SNet& net, const SVar& var, const SStores& S, const SCall& a, int grid, hipStream_t hs);
-// tu_stream_mixednet_q8.hip: its int8 twin (residuals, pooled head); k: the call and the layout, one kernel argument
+// tu_stream_q8.hip: the call and the layout, one kernel argument
 struct SQ8Net : SQ8, MixedNet::Q8 {};
-const void* mixednet_variant_q8_kernel();
-void launch_mixednet_variant_q8(const SNet& net, const SVar& var, const SStores& S, const SCall& a, const SQ8Net& k, int grid, size_t lds,
-                                hipStream_t hs);
 
 // topology + weight / state layout, reach of every layer and the call geometry from the description
 inline int MixedNet::plan() {
@@ -525,7 +520,7 @@ inline int MixedNet::plan() {
   const int64_t rows = g.tile_outputs + g.reach, g_rows = ((rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS;
   if (variant()) {   // + the residual buffer, + per position the channel mean, the channel max and the gate
     scratch_per_wg = (g_rows + (2 + var.has_res) * rows * net.cmax + (att ? 3 * rows : 0) + 255) & ~(int64_t)255;
-    if (q8_variant) {   // residuals / pooling: the int8 kernel of tu_stream_mixednet_q8.hip, one more int8 buffer for r
+    if (q8_variant) {   // residuals / pooling: the int8 kernel's <VAR> form, one more int8 buffer for r
       q8_tile_bytes = g_rows + (2 + var.has_res) * rows * r4(net.cmax);
       plan_q8();
       return MWW_OK;

@@ -23,8 +23,8 @@
 // detection-metrics kernels, and the host path of EVERY stream - creation, reset, the float and the int8 launch epilogue,
 // calibration, mww_stream_set_quantized - written once against SModel (stream_common.hip.h); the conv/BN graph model part
 // and its two creators are tu_stream_graph.hip / tu_stream_graph_q8.hip.  A MixedNet with residual connections, a pooled head or
-// spatial attention (mww_stream_create_mixednet) is the same model part with three more plan inputs; its float kernel is
-// tu_stream_mixednet.hip, a plain plan never leaves the kernel below.
+// spatial attention (mww_stream_create_mixednet) is the same model part with three more plan inputs and the <VAR> form of the
+// kernel below; a plain plan runs the form without VAR.
 #include <hip/hip_runtime.h>
 
 #include "stream_common.hip.h"
@@ -34,16 +34,87 @@ using namespace mww_stream_impl;
 namespace {
 
 constexpr int kMaxTensors = 3 + 2 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT;
+// VAR: input, conv1, the logit; per block a residual; per repeat MixConv, 1x1 and ADD
+constexpr int kMaxVarTensors = 3 + MWW_MAX_BLOCKS + 3 * MWW_MAX_BLOCKS * MWW_STREAM_MAX_REPEAT;
+constexpr int kPoolChannels = 8;   // channels a head thread pools at a time (registers)
 
+// Head over the last TP positions of the (gated) final map: pooling per channel when `pool`, then the Dense, sigmoid.
+// gate: a[q] at gate[q - g_lo], or NULL.  Positions before the stream start read the head ring [TF - 1][C].
 template <bool REC>
-__global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net, SStores S, SCall a) {
+__device__ inline void variant_head(const SCall& a, const STile& T, const float* fin, int pitch, const float* hring, int64_t wd_at,
+                                    int64_t bd_at, int C, int TF, int TP, int pool, const float* gate, int64_t g_lo, float& lmin,
+                                    float& lmax) {
+  for (int o = threadIdx.x; o < T.n; o += kStreamThreads) {
+    const int64_t c = T.c0 + o, q0 = c - (TP - 1);
+    float acc = a.w[bd_at];
+    if (pool) {   // kPoolChannels channels at a time: a row is visited C / kPoolChannels times, not C times
+      for (int ch0 = 0; ch0 < C; ch0 += kPoolChannels) {
+        const int nc = C - ch0 < kPoolChannels ? C - ch0 : kPoolChannels;
+        float p[kPoolChannels];
+        for (int t = 0; t < TP; ++t) {   // every channel's frames in order
+          const int64_t q = q0 + t;
+          const float* x = (q >= 0 ? fin + q * pitch : hring + (TF - 1 + q) * C) + ch0;
+          const float g = gate ? gate[q - g_lo] : 1.f;
+#pragma unroll
+          for (int j = 0; j < kPoolChannels; ++j) {
+            if (j < nc) {
+              const float v = gate ? x[j] * g : x[j];
+              p[j] = t == 0 ? v : (pool == 1 ? p[j] + v : fmaxf(p[j], v));
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < kPoolChannels; ++j)
+          if (j < nc) acc = fmaf(pool == 1 ? p[j] / (float)TP : p[j], a.w[wd_at + ch0 + j], acc);
+      }
+    } else {
+      for (int t = 0; t < TP; ++t) {
+        const int64_t q = q0 + t;
+        const float* wd = a.w + wd_at + (int64_t)t * C;
+        const float* x = q >= 0 ? fin + q * pitch : hring + (TF - 1 + q) * C;
+        const float g = gate ? gate[q - g_lo] : 1.f;
+        for (int ch = 0; ch < C; ++ch) acc = fmaf(x[ch] * g, wd[ch], acc);
+      }
+    }
+    const int64_t g = T.out0 + o;
+    a.logit[g] = acc;
+    a.prob[g] = 1.f / (1.f + expf(-acc));
+    if (REC) {
+      lmin = fminf(lmin, acc);
+      lmax = fmaxf(lmax, acc);
+    }
+  }
+}
+
+// The float MixedNet kernel: one tile walk, four instantiations.  <VAR> is the form of a plan with residual connections, a
+// pooled head or spatial attention (mixednet.py:234-275 SpatialAttention, :340-358 residual, :362-381 pooled head); all it adds
+// sits behind the compile-time VAR, so <false, *> - the kernel a plain plan runs (MixedNet::launch) - holds none of it:
+//
+//   residual   layer kind 2: r = folded BN(1x1(block input)), linear, over the block-input range [in_lo, c1) of the tile, in a
+//              third activation buffer of the workgroup (allocated only when a block has a residual).  It has no ring: an
+//              output position >= 0 reads the block input at the same position, which the tile holds.  Layer kind 3 - the 1x1
+//              layers of that block, every repeat over its own output range - adds r at equal positions before the ReLU.
+//   pooling    the head reduces the T_f frames it holds (head ring before the stream start: cold zeros take part) per channel,
+//              average (sum in frame order, divided by the frames) or max, and the Dense reads the C pooled values.
+//   attention  non_stream mode only.  a[q] depends on positions only, so it is one more right-aligned layer of reach 3: per
+//              final-map position the channel mean and max, then the 4-tap gate; the head reads h[q] a[q] at the last T_f - 3.
+//
+// <REC> is the calibration form (mww_stream_calibrate_host): every thread keeps the min / max of the tensor it is computing - a
+// kind-2 layer records r, a kind-3 layer the value before the add and the value after add + ReLU as two tensors, the head the
+// logit -, rec_fold runs per layer, one partial row per workgroup.  <*, false> is the kernel without any of it.  The calibrated
+// tensor of layer l is var.lt[l]; without VAR that is 2 + l, which needs no table.
+template <bool VAR, bool REC>
+__global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net, SVar var, SStores S, SCall a) {
   const int tid = threadIdx.x;
-  __shared__ float red[REC ? 2 * kStreamThreads : 1], rmin[REC ? kMaxTensors : 1], rmax[REC ? kMaxTensors : 1];
-  float lmin = INFINITY, lmax = -INFINITY;
+  constexpr int kRec = VAR ? kMaxVarTensors : kMaxTensors;
+  __shared__ float red[REC ? 2 * kStreamThreads : 1], rmin[REC ? kRec : 1], rmax[REC ? kRec : 1];
+  float lmin = INFINITY, lmax = -INFINITY, lmin2 = INFINITY, lmax2 = -INFINITY;   // (2, VAR: the ADD output of a kind-3 layer)
   if (REC) rec_init(a, rmin, rmax);
   float* G = a.scratch + (int64_t)blockIdx.x * a.scratch_per_wg;            // gathered padded input rows [.][40]
   float* B0 = G + ((a.buf_rows - 1) * net.s + net.k1) * MWW_FEATURE_BINS;   // two activation buffers [rows][cmax]
   float* B1 = B0 + a.buf_rows * net.cmax;
+  float* Rb = B1 + a.buf_rows * net.cmax;                                   // VAR: the block's residual [rows][cmax] (has_res)
+  float* At = Rb + (VAR && var.has_res ? a.buf_rows * net.cmax : 0);        // VAR: attention mean, max, gate [rows] each (att)
   const int r1 = a.use_state ? net.r1 : 0;
   for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const STile T = tile_of(a, tile);
@@ -86,9 +157,34 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
     }
     float* in = B0;
     float* out = B1;
-    int64_t in_lo = lo;
+    int64_t in_lo = lo, r_lo = lo;   // (r_lo, VAR: the position of Rb's first row)
     for (int l = 0; l < net.n_layers; ++l) {
       const SLayer& L = net.L[l];
+      const int lt = VAR ? var.lt[l] : 2 + l;   // the calibrated tensor (REC)
+      if (VAR && L.kind == 2) {   // the block's residual over the block-input range; the buffers are not swapped
+        const int Ci = L.cin, Co = L.cout;
+        r_lo = in_lo;
+        for (int64_t idx = tid; idx < (c1 - in_lo) * Co; idx += kStreamThreads) {
+          const int64_t i = in_lo + idx / Co;
+          const int co = (int)(idx % Co);
+          const float* x = in + (i - in_lo) * net.cmax;
+          const float* w = a.w + L.w + co;
+          float acc = a.w[L.b + co];
+          for (int ci = 0; ci < Ci; ++ci) acc = fmaf(x[ci], w[(int64_t)ci * Co], acc);
+          Rb[(i - r_lo) * net.cmax + co] = acc;
+          if (REC) {
+            lmin = fminf(lmin, acc);
+            lmax = fmaxf(lmax, acc);
+          }
+        }
+        __syncthreads();
+        if (REC) {
+          rec_fold(lmin, lmax, lt, red, rmin, rmax);
+          lmin = INFINITY;
+          lmax = -INFINITY;
+        }
+        continue;
+      }
       int64_t o_lo = c0 - L.reach;
       if (o_lo < 0) o_lo = 0;
       const int64_t no = c1 - o_lo;
@@ -119,6 +215,7 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
         }
       } else {
         const int Ci = L.cin, Co = L.cout;
+        const bool res = VAR && L.kind == 3;
         for (int64_t idx = tid; idx < no * Co; idx += kStreamThreads) {
           const int64_t i = o_lo + idx / Co;
           const int co = (int)(idx % Co);
@@ -126,8 +223,16 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
           const float* w = a.w + L.w + co;
           float acc = a.w[L.b + co];
           for (int ci = 0; ci < Ci; ++ci) acc = fmaf(x[ci], w[(int64_t)ci * Co], acc);
+          if (REC && res) {   // the 1x1 output before the add is a tensor of its own
+            lmin = fminf(lmin, acc);
+            lmax = fmaxf(lmax, acc);
+          }
+          if (res) acc += Rb[(i - r_lo) * net.cmax + co];   // o_lo >= r_lo: the residual covers the block input
           out[(i - o_lo) * net.cmax + co] = acc > 0.f ? acc : 0.f;
-          if (REC) {
+          if (REC && res) {   // (no reference picking one of the two pairs: that put them on the stack)
+            lmin2 = fminf(lmin2, out[(i - o_lo) * net.cmax + co]);
+            lmax2 = fmaxf(lmax2, out[(i - o_lo) * net.cmax + co]);
+          } else if (REC) {
             lmin = fminf(lmin, out[(i - o_lo) * net.cmax + co]);
             lmax = fmaxf(lmax, out[(i - o_lo) * net.cmax + co]);
           }
@@ -135,21 +240,54 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
       }
       __syncthreads();
       if (REC) {
-        rec_fold(lmin, lmax, 2 + l, red, rmin, rmax);
-        lmin = INFINITY;
-        lmax = -INFINITY;
+        rec_fold(lmin, lmax, lt, red, rmin, rmax);
+        if (VAR && L.kind == 3) rec_fold(lmin2, lmax2, lt + 1, red, rmin, rmax);
+        lmin = lmin2 = INFINITY;
+        lmax = lmax2 = -INFINITY;
       }
       float* t = in;
       in = out;
       out = t;
       in_lo = o_lo;
     }
-    // ---- head: Dense over the last T_f frames of the final map at every output position
+    // ---- head: Dense over the last T_f frames of the final map at every output position; VAR: gated and / or pooled first
     const float* fin = in - in_lo * net.cmax;
     const float* hring = a.st_in + net.ring_head;
-    dense_head<REC>(a, T, fin, net.cmax, hring, net.wd, net.bd, net.c_last, net.tf, lmin, lmax);
+    const float* gate = nullptr;
+    if (VAR && var.att) {   // non_stream: every position the head reads is >= 0 and in the tile, in_lo = c0 - (tf - 1)
+      const int C = net.c_last;
+      const int64_t nq = c1 - in_lo;
+      float *avg = At, *mx = At + a.buf_rows, *gt = mx + a.buf_rows;
+      for (int64_t i = tid; i < nq; i += kStreamThreads) {
+        const float* x = in + i * net.cmax;
+        float s = 0.f, m = x[0];
+        for (int ch = 0; ch < C; ++ch) {
+          s += x[ch];
+          m = fmaxf(m, x[ch]);
+        }
+        avg[i] = s / (float)C;
+        mx[i] = m;
+      }
+      __syncthreads();
+      const float* wa = a.w + var.wa;
+      for (int64_t i = 3 + tid; i < nq; i += kStreamThreads) {
+        float s = 0.f;
+        for (int j = 0; j < 4; ++j) {
+          s = fmaf(wa[2 * j], avg[i - 3 + j], s);
+          s = fmaf(wa[2 * j + 1], mx[i - 3 + j], s);
+        }
+        gt[i] = 1.f / (1.f + expf(-s));
+      }
+      __syncthreads();
+      gate = gt;
+    }
+    if (VAR && (var.att || var.pool)) {
+      variant_head<REC>(a, T, fin, net.cmax, hring, net.wd, net.bd, net.c_last, net.tf, var.tp, var.pool, gate, in_lo, lmin, lmax);
+    } else {
+      dense_head<REC>(a, T, fin, net.cmax, hring, net.wd, net.bd, net.c_last, net.tf, lmin, lmax);
+    }
     if (REC) {
-      rec_fold(lmin, lmax, 2 + net.n_layers, red, rmin, rmax);
+      rec_fold(lmin, lmax, VAR ? var.n_tensors - 1 : 2 + net.n_layers, red, rmin, rmax);
       lmin = INFINITY;
       lmax = -INFINITY;
     }
@@ -284,12 +422,9 @@ int64_t MixedNet::fold_weights(const float* h, float* w) const {
 }
 
 void MixedNet::launch(const SStores& S, const SCall& a, int grid, hipStream_t hs) const {
-  if (variant())
-    launch_mixednet_variant(net, var, S, a, grid, hs);
-  else if (a.rec)
-    hipLaunchKernelGGL(stream_forward_kernel<true>, dim3(grid), dim3(kStreamThreads), 0, hs, net, S, a);
-  else
-    hipLaunchKernelGGL(stream_forward_kernel<false>, dim3(grid), dim3(kStreamThreads), 0, hs, net, S, a);
+  auto kernel = variant() ? (a.rec ? stream_forward_kernel<true, true> : stream_forward_kernel<true, false>)
+                          : (a.rec ? stream_forward_kernel<false, true> : stream_forward_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kStreamThreads), 0, hs, net, var, S, a);
 }
 
 // ---- the host path of every stream: the front of mww_stream; whatever differs between the models is behind SModel

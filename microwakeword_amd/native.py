@@ -644,7 +644,7 @@ class Stream:
     stream comes from ``mww_stream_create_mixednet`` and ``t_final`` counts the final map's frames before attention and
     pooling (``streaming.mixednet_stream_description``); the int8 methods raise ``NativeError`` on it unless the stream was
     created with ``int8=True`` (``mww_stream_create_mixednet_q8``: the same stream, on which calibration and the int8 kernel
-    of csrc/tu_stream_mixednet_q8.hip work for residual / pooled descriptions; attention is refused there)."""
+    of csrc/tu_stream_q8.hip (its <VAR> form) work for residual / pooled descriptions; attention is refused there)."""
 
     def __init__(self, engine: "Engine", desc: dict, int8: bool = False):
         self.engine = engine   # the context is borrowed: keep it alive

@@ -14,7 +14,8 @@
   * ``QuantizedModel``  those parameters, ``save`` / ``load`` as a data-only ``.npz`` and a readable ``summary``.
 
 Nothing here is pinned to TFLite (no TensorFlow on this path); the int8 kernel is pinned to tests/quant_oracle.py.
-The Inception twin (a graph with concatenations) is ``quantize_graph.py``, which imports the fixed-point helpers below.
+``quantize_mixednet.py`` (residual connections, a pooled head) and ``quantize_graph.py`` (Inception: a graph with
+concatenations) build on the fixed-point helpers, the op builders and the ``QuantizedModel`` class below.
 """
 from __future__ import annotations
 
@@ -163,92 +164,188 @@ def _r4(n):
     return (n + 3) & ~3
 
 
+OP_KEYS = ("weights", "weight_scales", "bias", "multiplier", "shift")
+
+
+def checked_ranges(ranges, n) -> np.ndarray:
+    """the calibrated ranges as float64 [n, 2], finite"""
+    ranges = np.asarray(ranges, np.float64).reshape(-1, 2)
+    if ranges.shape[0] != n:
+        raise ValueError("expected %d calibrated ranges, got %d" % (n, ranges.shape[0]))
+    if not np.all(np.isfinite(ranges)):
+        raise ValueError("a calibrated range is not finite (was the calibration set empty?)")
+    return ranges
+
+
+def activation_table(ranges):
+    """``activation_params`` of every range: (float32 scales, int32 zero points)"""
+    params = [activation_params(lo, hi) for lo, hi in ranges]
+    return np.array([p[0] for p in params], np.float32), np.array([p[1] for p in params], np.int32)
+
+
+def requant_op(scales, kind, wq, ws, b, t_in, t_out, tensors=None):
+    """the dict of one op (``QuantizedModel``): its bias in units of s_in * s_w and, per output channel, the
+    ``quantize_multiplier`` of s_in * s_w / s_out in double"""
+    s_in, s_out = np.float64(scales[t_in]), np.float64(scales[t_out])
+    mult = [quantize_multiplier(s_in * np.float64(sw) / s_out) for sw in ws]
+    return dict(kind=kind, weights=wq, weight_scales=ws, bias=bias_q(b, scales[t_in], ws).astype(np.int32),
+                multiplier=np.array([m for m, _ in mult], np.int32), shift=np.array([s for _, s in mult], np.int32),
+                tensors=tensors or (t_in, t_out))
+
+
+def fold_mixconv(it, ks, ci):
+    """the next MixConv groups of ``it`` (per group kernel [k,1,gc,1] and bias) as one [K, ci] table, taps right-aligned, and
+    the bias [ci]"""
+    K = max(ks)
+    fw = np.zeros((K, ci), np.float32)
+    fb = np.zeros(ci, np.float32)
+    c0 = 0
+    for gc, kk in zip(split_channels(ci, len(ks)), ks):
+        fw[K - kk:, c0:c0 + gc] = next(it).reshape(kk, gc)
+        fb[c0:c0 + gc] = next(it).reshape(gc)
+        c0 += gc
+    return fw, fb
+
+
+def pointwise_op(scales, it, kind, ci, co, t_in, t_out):
+    """the next 1x1 layer of ``it`` (kernel [1,1,ci,co], BN gamma / beta / moving mean / moving variance), BN folded"""
+    kern = next(it).reshape(ci, co)
+    gamma, beta, mean, var = (next(it).reshape(co) for _ in range(4))
+    fw, fb = fold_bn(kern, gamma, beta, mean, var)
+    wq, ws = weight_params(fw, 1)
+    return requant_op(scales, kind, wq, ws, fb, t_in, t_out)
+
+
+def dense_op(scales, it, c_last, t_in, t_out, tensors=None, td=None):
+    """the Dense of ``it`` (kernel [td * c_last, 1], bias; the last weights) over ``td`` frames (default: what the kernel holds)"""
+    dk = next(it).reshape(-1)
+    db = next(it).reshape(1)
+    if td is not None and dk.size != td * c_last:
+        raise ValueError("the dense kernel has %d weights, the description asks for %d" % (dk.size, td * c_last))
+    wq, ws = weight_params(dk.reshape(-1, 1), 1)
+    return requant_op(scales, "dense", wq.reshape(td or dk.size // c_last, c_last), ws, db, t_in, t_out, tensors)
+
+
+def _rows_r4(w):
+    """int8 rows padded to 32-bit words, flat"""
+    n, c = w.shape
+    blk = np.zeros((n, _r4(c)), np.int8)
+    blk[:, :c] = w
+    return blk.reshape(-1)
+
+
 class QuantizedModel:
     """int8 parameters of a streaming MixedNet.  Per tensor (``names``): ``scales`` float32, ``zero_points`` int32.  Per op
     (conv1, the plan's layers, dense) in ``ops``: dict(kind, weights int8 in the op's natural layout - conv1 [k1*40, C1],
     mix [K, C] (taps right-aligned), pw [Ci, Co], dense [T_f, C] -, weight_scales float32 [cout], bias int32 [cout]
-    (without the input zero point), multiplier int32 [cout], shift int32 [cout], tensors (in, out)); ``lut`` uint8 [256]."""
+    (without the input zero point), multiplier int32 [cout], shift int32 [cout], tensors (in, out)); ``lut`` uint8 [256].
+
+    Also the base of ``quantize_mixednet.QuantizedMixedNetModel`` (kinds res and pw_add, the latter with ``add`` /
+    ``add_tensors``) and ``quantize_graph.QuantizedGraphModel`` (its own ``packed``): a subclass sets ``FAMILY`` (the file's
+    ``family`` key; a plain MixedNet file has none) and overrides ``_describe`` / ``_check_family`` / ``_summary_notes``."""
+
+    FAMILY = None
+    NAME_WIDTH = 24   # of ``summary``
 
     def __init__(self, desc, scales, zero_points, ops, lut, ranges=None):
-        self.desc = dict(desc)
-        self.names = tensor_names(self.desc)
+        self.desc, self.names = self._describe(desc)
         self.scales = np.asarray(scales, np.float32)
         self.zero_points = np.asarray(zero_points, np.int32)
         self.ops = ops
         self.lut = np.asarray(lut, np.uint8)
         self.ranges = None if ranges is None else np.asarray(ranges, np.float32)
 
-    # -- the native layout (include/mww.h, mww_stream_set_quantized)
+    @staticmethod
+    def _describe(desc):
+        """(the description as the model keeps it, the tensor names)"""
+        desc = dict(desc)
+        return desc, tensor_names(desc)
+
+    # -- the native layout (include/mww.h, mww_stream_set_quantized; residual / pooled: on a stream of mww_stream_create_mixednet_q8)
     def packed(self):
         """(int8 weights, int32 values, input scale, lut) in the layout of mww_stream_set_quantized"""
         wparts, iparts, at = [], [], 0
         for op in self.ops:
             w = op["weights"]
+            wsum = w.astype(np.int64).sum(axis=0)
             if op["kind"] == "conv1":
                 blk = np.ascontiguousarray(w.T).reshape(-1)                       # [C1][k1*40]
             elif op["kind"] == "mix":
                 blk = w.reshape(-1)                                               # [K][C]
-            elif op["kind"] == "pw":
-                ci, co = w.shape
-                blk = np.zeros((co, _r4(ci)), np.int8)
-                blk[:, :ci] = w.T
-                blk = blk.reshape(-1)                                             # [Co][r4(Ci)]
+            elif op["kind"] in ("pw", "pw_add", "res"):
+                blk = _rows_r4(w.T)                                               # [Co][r4(Ci)]
             else:
-                tf, c = w.shape
-                blk = np.zeros((tf, _r4(c)), np.int8)
-                blk[:, :c] = w
-                blk = blk.reshape(-1)                                             # [T_f][r4(C)]
+                blk = _rows_r4(w)                                                 # [T_f or 1][r4(C)]
+                wsum = np.array([wsum.sum()], np.int64)
             pad = _r4(at + blk.size) - (at + blk.size)
             wparts += [blk, np.zeros(pad, np.int8)]
             at += blk.size + pad
-            zp_in = int(self.zero_points[op["tensors"][0]])
-            wsum = self._channel_sums(op)
-            folded = op["bias"].astype(np.int64) - zp_in * wsum
-            if folded.min(initial=0) < INT32_MIN or folded.max(initial=0) > INT32_MAX:
-                raise OverflowError("folded bias of %s exceeds int32" % op["kind"])
+            folded = self._int32(op["bias"].astype(np.int64) - int(self.zero_points[op["tensors"][0]]) * wsum, op["kind"])
             iparts += [folded, op["multiplier"].astype(np.int64), op["shift"].astype(np.int64)]
-        iparts.append(self.zero_points.astype(np.int64))
+            if "add" in op:
+                iparts.append(op["add"].astype(np.int64))
+        return self._packed(wparts, iparts)
+
+    def _packed(self, wparts, iparts):
+        iparts = iparts + [self.zero_points.astype(np.int64)]
         return (np.concatenate(wparts).astype(np.int8), np.concatenate(iparts).astype(np.int32), np.float32(self.scales[0]),
                 self.lut)
 
     @staticmethod
-    def _channel_sums(op):
-        w = op["weights"].astype(np.int64)
-        if op["kind"] in ("conv1", "mix", "pw"):
-            return w.sum(axis=0)
-        return np.array([w.sum()], np.int64)
+    def _int32(v, what):
+        if v.min(initial=0) < INT32_MIN or v.max(initial=0) > INT32_MAX:
+            raise OverflowError("folded bias of %s exceeds int32" % what)
+        return v
 
     # -- file
     def save(self, path):
-        arrays = {"desc": np.array(json.dumps(self.desc)), "names": np.array(self.names), "scales": self.scales,
-                  "zero_points": self.zero_points, "lut": self.lut}
+        arrays = {"family": np.array(self.FAMILY)} if self.FAMILY else {}
+        arrays.update({"desc": np.array(json.dumps(self.desc)), "names": np.array(self.names), "scales": self.scales,
+                       "zero_points": self.zero_points, "lut": self.lut})
         if self.ranges is not None:
             arrays["ranges"] = self.ranges
         for i, op in enumerate(self.ops):
             arrays["op%d/kind" % i] = np.array(op["kind"])
             arrays["op%d/tensors" % i] = np.asarray(op["tensors"], np.int32)
-            for k in ("weights", "weight_scales", "bias", "multiplier", "shift"):
+            for k in OP_KEYS:
                 arrays["op%d/%s" % (i, k)] = op[k]
+            if "add" in op:
+                arrays["op%d/add" % i] = op["add"]
+                arrays["op%d/add_tensors" % i] = np.asarray(op["add_tensors"], np.int32)
         np.savez(path, **arrays)
+
+    @classmethod
+    def _check_family(cls, path, family):
+        """raises when the file's ``family`` (None: it has no such key) is not this class's; a plain MixedNet file is not checked"""
 
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
+            cls._check_family(path, str(z["family"]) if "family" in z.files else None)
             desc = json.loads(str(z["desc"]))
             ops, i = [], 0
             while "op%d/kind" % i in z.files:
                 op = {"kind": str(z["op%d/kind" % i]), "tensors": tuple(int(t) for t in z["op%d/tensors" % i])}
-                for k in ("weights", "weight_scales", "bias", "multiplier", "shift"):
+                for k in OP_KEYS:
                     op[k] = z["op%d/%s" % (i, k)]
+                if "op%d/add" % i in z.files:
+                    op["add"] = z["op%d/add" % i]
+                    op["add_tensors"] = tuple(int(t) for t in z["op%d/add_tensors" % i])
                 ops.append(op)
                 i += 1
             return cls(desc, z["scales"], z["zero_points"], ops, z["lut"], z["ranges"] if "ranges" in z.files else None)
 
+    def _summary_notes(self) -> List[str]:
+        """lines between the tensors and the output"""
+        return []
+
     def summary(self) -> str:
-        lines = ["%-24s %14s %11s" % ("tensor", "scale", "zero_point")]
+        name = "%%-%ds" % self.NAME_WIDTH
+        lines = [(name + " %14s %11s") % ("tensor", "scale", "zero_point")]
         for n, s, z in zip(self.names, self.scales, self.zero_points):
-            lines.append("%-24s %14.8g %11d" % (n, float(s), int(z)))
-        lines.append("output (uint8)           %14.8g %11d" % (1.0 / 256.0, 0))
+            lines.append((name + " %14.8g %11d") % (n, float(s), int(z)))
+        lines += self._summary_notes()
+        lines.append((name + " %14.8g %11d") % ("output (uint8)", 1.0 / 256.0, 0))
         return "\n".join(lines)
 
 
@@ -256,57 +353,23 @@ def quantize_weights(desc: dict, weights: Sequence[np.ndarray], ranges) -> Quant
     """The int8 model of a stream description, its Keras-order float weights (``Model.get_weights()``: conv1 kernel; per
     block and repeat: each MixConv group's kernel [k,1,gc,1] and bias, the 1x1 kernel, BN gamma / beta / moving mean /
     moving variance; dense kernel [T_f*C, 1] and bias) and the calibrated ranges [n_tensors, 2]."""
-    w = [np.asarray(a, np.float32) for a in weights]
-    ranges = np.asarray(ranges, np.float64).reshape(-1, 2)
-    names = tensor_names(desc)
-    if ranges.shape[0] != len(names):
-        raise ValueError("expected %d calibrated ranges, got %d" % (len(names), ranges.shape[0]))
-    if not np.all(np.isfinite(ranges)):
-        raise ValueError("a calibrated range is not finite (was the calibration set empty?)")
-    params = [activation_params(lo, hi) for lo, hi in ranges]
-    scales = np.array([p[0] for p in params], np.float32)
-    zps = np.array([p[1] for p in params], np.int32)
-    ops = []
-
-    def op(kind, wq, ws, b, t_in, t_out):
-        s_in, s_out = np.float64(scales[t_in]), np.float64(scales[t_out])
-        mult = [quantize_multiplier(s_in * np.float64(sw) / s_out) for sw in ws]
-        ops.append(dict(kind=kind, weights=wq, weight_scales=ws, bias=bias_q(b, scales[t_in], ws).astype(np.int32),
-                        multiplier=np.array([m for m, _ in mult], np.int32), shift=np.array([s for _, s in mult], np.int32),
-                        tensors=(t_in, t_out)))
-
-    it = iter(w)
+    ranges = checked_ranges(ranges, len(tensor_names(desc)))
+    scales, zps = activation_table(ranges)
+    it = iter(np.asarray(a, np.float32) for a in weights)
     k1 = int(desc["conv1_kernel"])
     c1 = int(desc["conv1_filters"])
-    k = next(it).reshape(k1 * FEATURE_BINS, c1)                                   # [k1,1,40,C1]
-    wq, ws = weight_params(k, 1)
-    op("conv1", wq, ws, np.zeros(c1, np.float32), 0, 1)
-    for li, (kind, b, r, ks, ci, co) in enumerate(plan_ops(desc)):
-        t_in, t_out = 1 + li, 2 + li
+    wq, ws = weight_params(next(it).reshape(k1 * FEATURE_BINS, c1), 1)            # [k1,1,40,C1]
+    ops = [requant_op(scales, "conv1", wq, ws, np.zeros(c1, np.float32), 0, 1)]
+    t = 1   # the tensor the next layer reads
+    for kind, b, r, ks, ci, co in plan_ops(desc):
         if kind == "mix":
-            K = max(ks)
-            fw = np.zeros((K, ci), np.float32)
-            fb = np.zeros(ci, np.float32)
-            c0 = 0
-            for gc, kk in zip(split_channels(ci, len(ks)), ks):
-                fw[K - kk:, c0:c0 + gc] = next(it).reshape(kk, gc)
-                fb[c0:c0 + gc] = next(it).reshape(gc)
-                c0 += gc
+            fw, fb = fold_mixconv(it, ks, ci)
             wq, ws = weight_params(fw, 1)
-            op("mix", wq, ws, fb, t_in, t_out)
+            ops.append(requant_op(scales, "mix", wq, ws, fb, t, t + 1))
         else:
-            kern = next(it).reshape(ci, co)
-            gamma, beta, mean, var = (next(it).reshape(co) for _ in range(4))
-            fw, fb = fold_bn(kern, gamma, beta, mean, var)
-            wq, ws = weight_params(fw, 1)
-            op("pw", wq, ws, fb, t_in, t_out)
-    n_l = len(plan_ops(desc))
-    dk = next(it).reshape(-1)
-    db = next(it).reshape(1)
-    c_last = int(desc["blocks"][-1][2])
-    tf = dk.size // c_last
-    wq, ws = weight_params(dk.reshape(-1, 1), 1)
-    op("dense", wq.reshape(tf, c_last), ws, db, 1 + n_l, 2 + n_l)
+            ops.append(pointwise_op(scales, it, "pw", ci, co, t, t + 1))
+        t += 1
+    ops.append(dense_op(scales, it, int(desc["blocks"][-1][2]), t, t + 1))
     if next(it, None) is not None:
         raise ValueError("more weights than the stream description holds")
     lut = logistic_table(scales[-1], zps[-1])

@@ -1,7 +1,7 @@
 """int8 quantization of the streaming Inception model - any conv -> BN/SSN -> ReLU graph of ``native.GraphStream`` - the
 model the reference converts with ``quantize=True`` (microwakeword/utils.py:288-360; the conversion does not depend on the
-model family) and evaluates with ``--test_tflite_streaming_quantized``.  The MixedNet twin is ``quantize.py``; the
-fixed-point helpers are imported from it.
+model family) and evaluates with ``--test_tflite_streaming_quantized``.  The MixedNet form is ``quantize.py``; the
+fixed-point helpers, the op builders and the model class it extends are imported from it.
 
   * ``calibrate``   the representative-dataset pass as one stream-mode run from zero rings over
                     ``quantize.calibration_frames`` at stride 1 (an Inception model has no ``--stride``), on the float graph
@@ -31,8 +31,8 @@ from typing import List, Sequence
 import numpy as np
 
 from .layout import FEATURE_BINS
-from .quantize import (BN_EPS, INT32_MAX, INT32_MIN, activation_params, bias_q, logistic_table, quantize_multiplier,
-                       round_half_away, weight_params)
+from .quantize import (BN_EPS, QuantizedModel, _rows_r4, activation_table, checked_ranges, dense_op, logistic_table,
+                       requant_op, round_half_away, weight_params)
 from . import quantize as _mixednet
 
 FAMILY = "graph"
@@ -92,25 +92,25 @@ def fold_op(op: dict, cin: int, kernel, gamma, beta, mean, var):
     return w, b
 
 
-class QuantizedGraphModel:
+class QuantizedGraphModel(QuantizedModel):
     """int8 parameters of a streaming conv/BN graph.  Per tensor (``names``: input, every op's output, dense): ``scales``
     float32, ``zero_points`` int32, ``classes`` (the concatenation class of each activation tensor).  Per op in ``ops``:
     dict(kind "conv" / "dense", weights int8 - conv [k, Cin, Co] (sources concatenated along Cin), dense [T_f, C] -,
     weight_scales float32 [cout], bias int32 [cout] (without the input zero point), multiplier, shift int32 [cout],
-    tensors = the source tensors then the output tensor); ``lut`` uint8 [256]."""
+    tensors = the source tensors then the output tensor); ``lut`` uint8 [256].  ``save`` / ``load`` are the base class's."""
 
-    family = FAMILY
+    FAMILY = family = FAMILY
+    NAME_WIDTH = 28
 
     def __init__(self, desc, scales, zero_points, ops, lut, ranges=None):
-        self.desc = json.loads(json.dumps(desc))   # a plain copy: tuples become lists, as a loaded file has them
-        self.names = tensor_names(self.desc)
-        self.scales = np.asarray(scales, np.float32)
-        self.zero_points = np.asarray(zero_points, np.int32)
-        self.ops = ops
-        self.lut = np.asarray(lut, np.uint8)
-        self.ranges = None if ranges is None else np.asarray(ranges, np.float32)
+        super().__init__(desc, scales, zero_points, ops, lut, ranges)
         self.classes = concat_classes(self.desc)
         self.sources = op_sources(self.desc)
+
+    @staticmethod
+    def _describe(desc):
+        desc = json.loads(json.dumps(desc))   # a plain copy: tuples become lists, as a loaded file has them
+        return desc, tensor_names(desc)
 
     # -- the native layout (include/mww.h, mww_stream_set_quantized on a stream of mww_stream_create_convnet_q8)
     def packed(self):
@@ -130,103 +130,45 @@ class QuantizedGraphModel:
             wparts.append(np.ascontiguousarray(np.concatenate(cols, 1).transpose(2, 0, 1)).reshape(-1))   # [Co][k][kp]
             iparts += [self._int32(folded, "op"), op["multiplier"].astype(np.int64), op["shift"].astype(np.int64)]
         d = self.ops[-1]
-        tf, c = d["weights"].shape
-        blk = np.zeros((tf, _r4(c)), np.int8)
-        blk[:, :c] = d["weights"]
-        wparts.append(blk.reshape(-1))
-        zp_in = int(self.zero_points[d["tensors"][0]])
-        folded = d["bias"].astype(np.int64) - zp_in * d["weights"].astype(np.int64).sum()
+        wparts.append(_rows_r4(d["weights"]))
+        folded = d["bias"].astype(np.int64) - int(self.zero_points[d["tensors"][0]]) * d["weights"].astype(np.int64).sum()
         iparts += [self._int32(folded, "dense"), d["multiplier"].astype(np.int64), d["shift"].astype(np.int64)]
-        iparts.append(self.zero_points.astype(np.int64))
-        return (np.concatenate(wparts).astype(np.int8), np.concatenate(iparts).astype(np.int32), np.float32(self.scales[0]),
-                self.lut)
-
-    @staticmethod
-    def _int32(v, what):
-        if v.min(initial=0) < INT32_MIN or v.max(initial=0) > INT32_MAX:
-            raise OverflowError("folded bias of %s exceeds int32" % what)
-        return v
-
-    # -- file
-    def save(self, path):
-        arrays = {"family": np.array(FAMILY), "desc": np.array(json.dumps(self.desc)), "names": np.array(self.names),
-                  "scales": self.scales, "zero_points": self.zero_points, "lut": self.lut}
-        if self.ranges is not None:
-            arrays["ranges"] = self.ranges
-        for i, op in enumerate(self.ops):
-            arrays["op%d/kind" % i] = np.array(op["kind"])
-            arrays["op%d/tensors" % i] = np.asarray(op["tensors"], np.int32)
-            for k in ("weights", "weight_scales", "bias", "multiplier", "shift"):
-                arrays["op%d/%s" % (i, k)] = op[k]
-        np.savez(path, **arrays)
+        return self._packed(wparts, iparts)
 
     @classmethod
-    def load(cls, path):
-        with np.load(path, allow_pickle=False) as z:
-            if "family" not in z.files or str(z["family"]) != FAMILY:
-                raise ValueError("%s does not hold a quantized graph model (quantize.QuantizedModel.load reads a MixedNet file)" % path)
-            desc = json.loads(str(z["desc"]))
-            ops, i = [], 0
-            while "op%d/kind" % i in z.files:
-                op = {"kind": str(z["op%d/kind" % i]), "tensors": tuple(int(t) for t in z["op%d/tensors" % i])}
-                for k in ("weights", "weight_scales", "bias", "multiplier", "shift"):
-                    op[k] = z["op%d/%s" % (i, k)]
-                ops.append(op)
-                i += 1
-            return cls(desc, z["scales"], z["zero_points"], ops, z["lut"], z["ranges"] if "ranges" in z.files else None)
+    def _check_family(cls, path, family):
+        if family != FAMILY:
+            raise ValueError("%s does not hold a quantized graph model (quantize.QuantizedModel.load reads a MixedNet file)" % path)
 
     def summary(self) -> str:
-        lines = ["%-28s %14s %11s %6s" % ("tensor", "scale", "zero_point", "class")]
-        for t, (n, s, z) in enumerate(zip(self.names, self.scales, self.zero_points)):
-            lines.append("%-28s %14.8g %11d %6s" % (n, float(s), int(z), self.classes[t] if t < len(self.classes) else "-"))
-        lines.append("%-28s %14.8g %11d" % ("output (uint8)", 1.0 / 256.0, 0))
-        return "\n".join(lines)
+        lines = super().summary().split("\n")   # + the class column on the header and on every tensor's line
+        col = ["class"] + [self.classes[t] if t < len(self.classes) else "-" for t in range(len(self.names))]
+        return "\n".join(["%s %6s" % lc for lc in zip(lines, col)] + lines[-1:])
 
 
 def quantize_weights(desc: dict, weights: Sequence[np.ndarray], ranges) -> QuantizedGraphModel:
     """The int8 model of a graph stream description (``streaming.graph_stream_description``), its Keras-order float weights
     (per op kernel [k,1,Cin,F], gamma, beta, moving mean, moving variance [slots]; dense kernel [T_f*C, 1] and bias) and the
     calibrated ranges [n_ops + 2, 2]."""
-    w = [np.asarray(a, np.float32) for a in weights]
     ops_d = desc["conv_ops"]
     n = len(ops_d)
-    ranges = np.asarray(ranges, np.float64).reshape(-1, 2)
-    if ranges.shape[0] != n + 2:
-        raise ValueError("expected %d calibrated ranges, got %d" % (n + 2, ranges.shape[0]))
-    if not np.all(np.isfinite(ranges)):
-        raise ValueError("a calibrated range is not finite (was the calibration set empty?)")
+    ranges = checked_ranges(ranges, n + 2)
     # one (scale, zero point) per concatenation class, from the union of its members' ranges
     cls = concat_classes(desc)
-    params = []
+    union = ranges.copy()
     for t in range(n + 1):
         members = [m for m in range(n + 1) if cls[m] == cls[t]]
-        params.append(activation_params(ranges[members, 0].min(), ranges[members, 1].max()))
-    params.append(activation_params(*ranges[n + 1]))
-    scales = np.array([p[0] for p in params], np.float32)
-    zps = np.array([p[1] for p in params], np.int32)
-    sources = op_sources(desc)
+        union[t] = ranges[members, 0].min(), ranges[members, 1].max()
+    scales, zps = activation_table(union)
     ops = []
-
-    def op(kind, wq, ws, b, t_in, t_out):
-        s_in, s_out = np.float64(scales[t_in[0]]), np.float64(scales[t_out])
-        mult = [quantize_multiplier(s_in * np.float64(sw) / s_out) for sw in ws]
-        ops.append(dict(kind=kind, weights=wq, weight_scales=ws, bias=bias_q(b, scales[t_in[0]], ws).astype(np.int32),
-                        multiplier=np.array([m for m, _ in mult], np.int32), shift=np.array([s for _, s in mult], np.int32),
-                        tensors=tuple(t_in) + (t_out,)))
-
-    it = iter(w)
-    for i, (o, srcs) in enumerate(zip(ops_d, sources)):
+    it = iter(np.asarray(a, np.float32) for a in weights)
+    for i, (o, srcs) in enumerate(zip(ops_d, op_sources(desc))):
         cin = sum(cn for _, _, cn in srcs)
         kern, gamma, beta, mean, var = (next(it) for _ in range(5))
         fw, fb = fold_op(o, cin, kern, gamma, beta, mean, var)
         wq, ws = weight_params(fw, 2)
-        op("conv", wq, ws, fb, [t for t, _, _ in srcs], 1 + i)
-    dk = next(it).reshape(-1)
-    db = next(it).reshape(1)
-    c_last = int(ops_d[-1]["filters"])
-    tf = dk.size // c_last
-    wq, ws = weight_params(dk.reshape(-1, 1), 1)
-    op("dense", wq.reshape(tf, c_last), ws, db, [n], n + 1)
+        ops.append(requant_op(scales, "conv", wq, ws, fb, srcs[0][0], 1 + i, tuple(t for t, _, _ in srcs) + (1 + i,)))
+    ops.append(dense_op(scales, it, int(ops_d[-1]["filters"]), n, n + 1, (n, n + 1)))
     if next(it, None) is not None:
         raise ValueError("more weights than the graph description holds")
     lut = logistic_table(scales[-1], zps[-1])

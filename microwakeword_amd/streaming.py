@@ -139,7 +139,7 @@ def graph_stream_description(flags, frames: int, stride: int, mode: str) -> dict
 class StreamingModel:
     """The streaming (``mode="stream"``) or non-streaming (``mode="non_stream"``) form of a trained MixedNet or Inception
     ``model`` (``microwakeword_amd.model.Model``, any kernel family; MixedNet on csrc/tu_stream.hip - with residual
-    connections, a pooled head or, in non_stream mode, spatial attention on csrc/tu_stream_mixednet.hip -, Inception on
+    connections, a pooled head or, in non_stream mode, spatial attention on that kernel's <VAR> form -, Inception on
     csrc/tu_stream_graph.hip), sharing the model's context: its device, HIP stream and the
     feature stores a ``FeatureHandler`` uploaded there.  The weights are taken from ``model`` when this object is created
     (``set_weights`` takes new ones)."""
@@ -230,7 +230,7 @@ class QuantizedStreamingModel(StreamingModel):
     ``model_or_file`` is a ``quantize.QuantizedModel`` (MixedNet: the int8 kernel of csrc/tu_stream_q8.hip), a
     ``quantize_graph.QuantizedGraphModel`` (Inception: csrc/tu_stream_graph_q8.hip on a stream of
     ``mww_stream_create_convnet_q8``), a ``quantize_mixednet.QuantizedMixedNetModel`` (MixedNet with residuals / a pooled head:
-    csrc/tu_stream_mixednet_q8.hip on a stream of ``mww_stream_create_mixednet_q8``) or the path of any one's ``.npz``; ``context`` is the float ``Model`` whose context
+    the <VAR> form of that kernel on a stream of ``mww_stream_create_mixednet_q8``) or the path of any one's ``.npz``; ``context`` is the float ``Model`` whose context
     (device, HIP stream, resident feature stores) the stream borrows.  Probabilities are ``uint8 / 255`` in float32
     (``read_q8`` gives the uint8 outputs), in the same device buffer the metrics kernel reads."""
 

@@ -1,5 +1,5 @@
 """Checks of the streaming evaluation of MixedNets with residual connections, a pooled head or spatial attention
-(``mww_stream_create_mixednet``, csrc/tu_stream_mixednet.hip) shared by the emulator tests
+(``mww_stream_create_mixednet``, stream_forward_kernel<true, *> of csrc/tu_stream.hip) shared by the emulator tests
 (tests/test_mixednet_variant_emulated.py) and the GPU tests (tests/test_mixednet_variant_gpu.py), in the manner of
 tests/stream_sweep.py:
 

@@ -1,5 +1,5 @@
 """Checks of the int8 streaming evaluation of MixedNets with residual connections or a pooled head
-(``mww_stream_create_mixednet_q8``, csrc/tu_stream_mixednet_q8.hip through microwakeword_amd.quantize_mixednet / streaming)
+(``mww_stream_create_mixednet_q8``, stream_q8_kernel<true> of csrc/tu_stream_q8.hip through microwakeword_amd.quantize_mixednet / streaming)
 shared by the emulator tests (tests/test_mixednet_q8_emulated.py) and the GPU tests (tests/test_mixednet_q8_gpu.py).
 
 - ``case_ids()``: every non-attention case of ``mixednet_variant_checks.cases()`` (imported, not edited: their stream scripts

@@ -1,5 +1,5 @@
-"""A covering sweep of the two run-time-shape streaming kernels - ``stream_forward_kernel`` (csrc/tu_stream.hip, with its
-calibration form ``<REC = true>``) and ``stream_q8_kernel`` (csrc/tu_stream_q8.hip) - shared by the GPU sweep
+"""A covering sweep of the two run-time-shape streaming kernels - ``stream_forward_kernel<false, *>`` (csrc/tu_stream.hip, with its
+calibration form ``<REC = true>``) and ``stream_q8_kernel<false>`` (csrc/tu_stream_q8.hip), the forms a plain MixedNet runs - shared by the GPU sweep
 (tests/test_stream_sweep_gpu.py) and its CPU-side checks (tests/test_stream_sweep_emulated.py).
 
 ``plan()`` in csrc/stream_common.hip.h accepts far more than the topologies the realistic tests run (widths that are no

@@ -1,4 +1,4 @@
-"""int8 streaming evaluation of MixedNets with residual connections or a pooled head (csrc/tu_stream_mixednet_q8.hip,
+"""int8 streaming evaluation of MixedNets with residual connections or a pooled head (stream_q8_kernel<true> of csrc/tu_stream_q8.hip,
 mww_stream_create_mixednet_q8) under the host-side emulator of tests/hipemu: every case of tests/quant_mixednet_checks.py -
 calibration on the device, then outputs, logits and rings bit for bit against tests/quant_mixednet_oracle.py - and the ABI."""
 import pytest

@@ -1,5 +1,5 @@
 """int8 streaming evaluation of MixedNets with residual connections or a pooled head on the MI355X
-(csrc/tu_stream_mixednet_q8.hip): every case of tests/quant_mixednet_checks.py - calibration on the device against the old
+(stream_q8_kernel<true> of csrc/tu_stream_q8.hip): every case of tests/quant_mixednet_checks.py - calibration on the device against the old
 creator's run and the float64 oracle, resident u16 / f32 tracks, host calls, one-output chains against the literal ring form,
 tile edges and the grid-stride loop, the three placements of the tile (LDS below and above 64 KB, global scratch), chunked
 calls, reruns and the non_stream twin: uint8 outputs, int8 logits and int8 rings bit for bit against the NumPy restatement."""

@@ -1,4 +1,4 @@
-"""Streaming evaluation of MixedNets with residual connections, a pooled head or spatial attention (csrc/tu_stream_mixednet.hip,
+"""Streaming evaluation of MixedNets with residual connections, a pooled head or spatial attention (stream_forward_kernel<true, *> of csrc/tu_stream.hip,
 mww_stream_create_mixednet) under the host-side emulator of tests/hipemu: every case of tests/mixednet_variant_checks.py,
 the reference-graph fixture, the refusals of the ABI and ``StreamingModel`` on such models."""
 import numpy as np

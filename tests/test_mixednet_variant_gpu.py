@@ -1,5 +1,5 @@
 """Streaming evaluation of MixedNets with residual connections, a pooled head or spatial attention on the MI355X
-(csrc/tu_stream_mixednet.hip): every case of tests/mixednet_variant_checks.py - resident u16 / f32 tracks with pads and empty
+(stream_forward_kernel<true, *> of csrc/tu_stream.hip): every case of tests/mixednet_variant_checks.py - resident u16 / f32 tracks with pads and empty
 tracks, host calls, one-output chains against the literal ring form, tile edges and the grid-stride loop, the non_stream twin,
 outputs, logits and rings against the float64 oracles, chunked predict_spectrogram and reruns bit for bit -, the
 reference-graph fixture and the refusals of the ABI."""

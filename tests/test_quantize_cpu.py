@@ -172,7 +172,8 @@ def test_gfx950_build_runs_int8_dot_products(tmp_path):
                     "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "microwakeword_amd", "csrc", "tu_stream_q8.hip"),
                     "-o", out], check=True)
     asm = open(out).read()
-    m = re.search(r"^(_Z\w*stream_q8_kernel\w*):", asm, re.M)
-    assert m, "stream_q8_kernel not found in the gfx950 assembly"
-    body = asm[m.end():asm.index(".size\t" + m.group(1), m.end())]
-    assert re.search(r"\bv_dot4c?_i32_i8|\bv_mfma_i32_16x16x64_i8", body), "no int8 dot / MFMA instruction in the int8 kernel"
+    for var in ("Lb0E", "Lb1E"):   # stream_q8_kernel<false> (a plain plan) and <true> (residuals / a pooled head)
+        m = re.search(r"^(_Z\w*stream_q8_kernelI%s\w*):" % var, asm, re.M)
+        assert m, "stream_q8_kernel<%s> not found in the gfx950 assembly" % var
+        body = asm[m.end():asm.index(".size\t" + m.group(1), m.end())]
+        assert re.search(r"\bv_dot4c?_i32_i8|\bv_mfma_i32_16x16x64_i8", body), "no int8 dot / MFMA instruction in the int8 kernel <%s>" % var

@@ -7,9 +7,9 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
                                                                     # the calibration pass (500 spectrograms) + quantization
     python tools/stream_eval_throughput.py --hours 20 --model inception   # the default Inception flags, T = 176
     python tools/stream_eval_throughput.py --hours 20 --model inception --quantized   # its int8 model (csrc/tu_stream_graph_q8.hip)
-    python tools/stream_eval_throughput.py --hours 20 --residual_connection 1,0,1,0 --pooled 1   # csrc/tu_stream_mixednet.hip
+    python tools/stream_eval_throughput.py --hours 20 --residual_connection 1,0,1,0 --pooled 1   # the float kernel's <VAR> form
     python tools/stream_eval_throughput.py --hours 20 --residual_connection 1,0,1,0 --pooled 1 --quantized   # its int8 model
-                                                                    # (csrc/tu_stream_mixednet_q8.hip, quantize_mixednet.py)
+                                                                    # (the int8 kernel's <VAR> form, quantize_mixednet.py)
     python tools/stream_eval_throughput.py --hours 20 --mode non_stream --residual_connection 1,0,1,0 --repeat_in_block 1,2,1,1 \
         --spatial_attention 1 --pooled 1 --max_pool 1     # every window of the non-streaming model (attention: this mode only)
     python tools/stream_eval_throughput.py --hours 20 --detections 0.5 --detections_out profiles/stream_detections_throughput.txt

@@ -7,7 +7,8 @@ arithmetic leaves every hash as it was.
     python tools/stream_identity.py --lib B.so > b.jsonl
     python tools/stream_identity.py --compare a.jsonl b.jsonl  # two columns, exit status 1 when a hash differs
     python tools/stream_identity.py --lib tests/hipemu/libmww_emu.so --emulator   # the cases the emulator tests run
-    python tools/stream_identity.py --variants   # after those, the float cases of tests/mixednet_variant_checks.py
+    python tools/stream_identity.py --variants   # after those, the float cases of tests/mixednet_variant_checks.py and the
+                                                 # calibration + int8 cases of tests/quant_mixednet_checks.py
 
 The cases: those of tests/stream_sweep.py (the script of each case: several stream-mode calls with resets, zero-output and
 one-output calls between them; its non-stream twin), tests/inception_streaming_checks.py ``stream_cases()`` /
@@ -47,12 +48,35 @@ class Hashes:
         return json.dumps(dict(case=name, **{f: self.h[f].hexdigest()[:32] for f in FIELDS}))
 
 
+def run_script(st, model, c, n_cu, add, gen_frames=None):
+    """the script of a case (tests/stream_sweep.py) on stream ``st``; ``add(st)`` after every call"""
+    import stream_sweep as sw
+    import streaming_checks as sc
+    gen_frames, s = gen_frames or sw.gen_frames, c.desc["stride"]
+    for i, step in enumerate(c.script):
+        rng = sw._rng(c.id, 0, i)
+        if step[0] == "reset":
+            st.reset()
+        elif step[0] == "zero":
+            st.run_host(gen_frames(rng, s - 1))
+        elif step[0] == "tracks":
+            st.run(sc.Tracks(model, step[1], step[2], seed=int(rng.integers(1 << 30))).win)
+        elif step[0] in ("host", "outputs"):
+            n = step[1] if step[0] == "host" else ((2 * n_cu + 2) * sw.TILE + 5 if step[1] == "grid" else step[1]) * s + s - 1
+            st.run_host(gen_frames(rng, n, "u16" if i % 2 else "f32"))
+        else:
+            for _ in range(step[1]):
+                st.run_host(gen_frames(rng, s))
+                add(st)
+        add(st)
+
+
 def sweep_case(lib, c, n_cu):
     """tests/stream_sweep.py: the case's script on a float and an int8 stream, calibration, the non-stream twin"""
     import stream_sweep as sw
     import streaming_checks as sc
     from microwakeword_amd import native, streaming
-    b, s, H = sw.built(c.id), c.desc["stride"], Hashes()
+    b, H = sw.built(c.id), Hashes()
     model = sc.context_model(lib)
     for kind in ("float", "q8"):
         if kind == "float":
@@ -61,22 +85,7 @@ def sweep_case(lib, c, n_cu):
         else:
             st = streaming.QuantizedStreamingModel(b.qm, b.s, "stream", context=model).native
         add = H.add_float if kind == "float" else H.add_q8
-        for i, step in enumerate(c.script):
-            rng = sw._rng(c.id, 0, i)
-            if step[0] == "reset":
-                st.reset()
-            elif step[0] == "zero":
-                st.run_host(sw.gen_frames(rng, s - 1))
-            elif step[0] == "tracks":
-                st.run(sc.Tracks(model, step[1], step[2], seed=int(rng.integers(1 << 30))).win)
-            elif step[0] in ("host", "outputs"):
-                n = step[1] if step[0] == "host" else ((2 * n_cu + 2) * sw.TILE + 5 if step[1] == "grid" else step[1]) * s + s - 1
-                st.run_host(sw.gen_frames(rng, n, "u16" if i % 2 else "f32"))
-            else:
-                for _ in range(step[1]):
-                    st.run_host(sw.gen_frames(rng, s))
-                    add(st)
-            add(st)
+        run_script(st, model, c, n_cu, add)
         if kind == "float":
             st.reset()
             H.add(ranges=st.calibrate_host(b.seq))
@@ -99,32 +108,41 @@ def variant_case(lib, c, n_cu):
     """tests/mixednet_variant_checks.py: the case's script on a float stream of mww_stream_create_mixednet (none for a
     spatial-attention case), then its non-stream twin"""
     import mixednet_variant_checks as vc
-    import stream_sweep as sw
     import streaming_checks as sc
-    b, s, H = vc.built(c.id), c.desc["stride"], Hashes()
+    b, H = vc.built(c.id), Hashes()
     model = sc.context_model(lib)
     if c.script:
         st = vc.new_stream(lib, b)
-        for i, step in enumerate(c.script):
-            rng = sw._rng(c.id, 0, i)
-            if step[0] == "reset":
-                st.reset()
-            elif step[0] == "zero":
-                st.run_host(sw.gen_frames(rng, s - 1))
-            elif step[0] == "tracks":
-                st.run(sc.Tracks(model, step[1], step[2], seed=int(rng.integers(1 << 30))).win)
-            elif step[0] in ("host", "outputs"):
-                n = step[1] if step[0] == "host" else ((2 * n_cu + 2) * sw.TILE + 5 if step[1] == "grid" else step[1]) * s + s - 1
-                st.run_host(sw.gen_frames(rng, n, "u16" if i % 2 else "f32"))
-            else:
-                for _ in range(step[1]):
-                    st.run_host(sw.gen_frames(rng, s))
-                    H.add_float(st)
-            H.add_float(st)
+        run_script(st, model, c, n_cu, H.add_float)
         st.close()
     st = vc.new_stream(lib, b, "non_stream")
     st.run(sc.Tracks(model, c.ns[0], c.ns[1], seed=vc.SEED).win)
     H.add_float(st)
+    st.close()
+    return H
+
+
+def variant_q8_case(lib, cid, n_cu):
+    """tests/quant_mixednet_checks.py: calibration on a float stream of mww_stream_create_mixednet_q8, the int8 model of those
+    ranges, the case's script on the int8 stream, then its non-stream twin"""
+    import mixednet_variant_checks as vc
+    import quant_mixednet_checks as qx
+    import streaming_checks as sc
+    from microwakeword_amd import quantize_mixednet as qmx
+    b, H = qx.built(cid), Hashes()
+    model = sc.context_model(lib)
+    st = qx.new_float_stream(lib, b, True)
+    ranges = st.calibrate_host(qx.calibration_frames(cid))
+    H.add(ranges=ranges)
+    H.add_float(st)
+    st.close()
+    qm = qmx.quantize_weights(qx.desc_of(b), b.weights, qx._final_ranges(cid, ranges))
+    st = qx.new_q8_stream(lib, qm)
+    run_script(st, model, b.case, n_cu, H.add_q8, qx.gen_frames)
+    st.close()
+    st = qx.new_q8_stream(lib, qm, "non_stream")
+    st.run(sc.Tracks(model, b.case.ns[0], b.case.ns[1], seed=vc.SEED).win)
+    H.add_q8(st)
     st.close()
     return H
 
@@ -189,6 +207,9 @@ def run(lib, emulator, variants=False):
         import mixednet_variant_checks as vc
         for c in vc._cases():
             print(variant_case(lib, c, n_cu).line("mixednet_variant/" + c.id), flush=True)
+        import quant_mixednet_checks as qx
+        for cid in qx.case_ids():
+            print(variant_q8_case(lib, cid, n_cu).line("quant_mixednet/" + cid), flush=True)
 
 
 def compare(path_a, path_b):
@@ -209,7 +230,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--lib", help="library to run (default: the package's own)")
     ap.add_argument("--emulator", action="store_true", help="the emulator-sized part of the cases (a library of tests/hipemu)")
-    ap.add_argument("--variants", action="store_true", help="also the float cases of tests/mixednet_variant_checks.py (residual, pooled, attention)")
+    ap.add_argument("--variants", action="store_true", help="also the float cases of tests/mixednet_variant_checks.py (residual, pooled, attention) and the calibration + int8 "
+                    "cases of tests/quant_mixednet_checks.py (residual, pooled)")
     ap.add_argument("--compare", nargs=2, metavar="JSONL")
     a = ap.parse_args()
     if a.compare:
