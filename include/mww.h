@@ -545,6 +545,25 @@ typedef struct { int32_t track; int32_t reserved; int64_t index; float average; 
 int64_t mww_stream_detections(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip,
                               int cooldown, double cutoff, mww_detection* out, int64_t capacity, int64_t* track_count,
                               int64_t* best_index, float* score);
+/* One mining round on the probabilities held (csrc/tu_stream_mine.hip): the hard negatives of the `tracks` that
+ * were run (their `offsets` as mww_stream_run returned them), every track ambient (kind 0), selected and cut into clips on the
+ * device.  Byte for byte the chain it replaces:
+ *   detections  those of mww_stream_detections at `window`, `cooldown`, `cutoff` (skip does not apply to ambient tracks);
+ *   selection   max_new < 0 keeps every event, else the max_new highest moving averages (compared as floats: -0 == +0), ties
+ *               to the earlier event in (track, index) order - a stable descending sort - returned in (track, index) order;
+ *   clips       streaming.detection_clips: output n = index + window - 1 was computed from the track rows ending at
+ *               e = (n + 1) * stride (stream mode) or frames + n * stride (non_stream mode; frames, stride and mode are the
+ *               stream's own); the clip is rows [e - frames - before, e + after) minus the track's pad_rows, clipped to
+ *               [0, copy_rows), as (store, 0, rows, 0, src_elem + 40 * first row).  A selected event without a row is dropped
+ *               AFTER the selection, so fewer than max_new clips may remain.
+ * clips / events [capacity] receive the first `capacity` kept clips and their events in (track, index) order (both may be NULL
+ * when capacity is 0); *n_detections the detections before the selection; track_count [n_tracks] each track's detections.
+ * Returns the number of clips kept, which may exceed `capacity`, or an error < 0.  The host reads back at most
+ * min(max_new, capacity) clips and events and the counts, never the event list.  Two calls on the same probabilities write the
+ * same bytes. */
+int64_t mww_stream_mine(mww_stream* s, const mww_window* tracks, const int64_t* offsets, int64_t n_tracks, int window, int cooldown,
+                        double cutoff, int before, int after, int64_t max_new, mww_window* clips, mww_detection* events,
+                        int64_t capacity, int64_t* n_detections, int64_t* track_count);
 /* The grid a deployment is chosen from (csrc/tu_stream_oppoints.hip): row k of counts [n_windows][n_cutoffs],
  * ma_len [n_windows][n_tracks] and score [n_windows][n_tracks] is exactly what mww_stream_metrics returns for window = windows[k]
  * with the same other arguments - the same integers, the same score bits - with the semantics its comment states (moving

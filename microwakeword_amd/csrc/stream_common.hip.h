@@ -308,6 +308,9 @@ struct mww_stream {
   char* det_cand = nullptr;
   mww_detection* det_out = nullptr;
   int64_t cap_det_tab = 0, cap_det_cand = 0, cap_det_out = 0;
+  // mining (tu_stream_mine.hip): the tracks' windows, the radix histograms, the per-workgroup counts, the kept clips and events
+  char* mine_buf = nullptr;
+  int64_t cap_mine_buf = 0;
   // operating points (tu_stream_oppoints.hip): the call's tables, the transfer tables of one pass over the windows
   char* op_tab = nullptr;
   char* op_scr = nullptr;

@@ -598,7 +598,7 @@ void mww_stream_destroy(mww_stream* s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (void* p : {(void*)s->w, (void*)s->st[0], (void*)s->st[1], (void*)s->prob, (void*)s->logit, (void*)s->scratch,
                   (void*)s->tables, (void*)s->host_frames, (void*)s->mtab, (void*)s->rec,
-                  (void*)s->det_tab, (void*)s->det_cand, (void*)s->det_out, (void*)s->op_tab, (void*)s->op_scr})
+                  (void*)s->det_tab, (void*)s->det_cand, (void*)s->det_out, (void*)s->mine_buf, (void*)s->op_tab, (void*)s->op_scr})
     if (p) (void)hipFree(p);
   q8_free(s);
   delete s->model;

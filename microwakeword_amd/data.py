@@ -238,6 +238,17 @@ class FeatureHandler:
         self._need_engine()
         if truncation_strategy not in native.STRATEGIES or truncation_strategy in ("none", "fixed_right_cutoff", "split"):
             raise ValueError("truncation strategy %r cannot serve mined clips" % (truncation_strategy,))
+        sources, samples = self._mined_samples(clips)
+        step = self.feature_providers[0].step
+        mined = MinedFeatureProvider(sources, samples, label, sampling_weight, penalty_weight, truncation_strategy, step)
+        self.feature_providers.append(mined)
+        if getattr(self, "_pf", None) is not None:
+            self._drop_prefetcher(keep_streams=True)   # its sampler description does not know the new provider
+        self._sampler = None
+        return mined
+
+    def _mined_samples(self, clips):
+        """``clips`` checked against the resident stores -> (sources, samples) of a ``MinedFeatureProvider``"""
         by_id = {}
         for p in self.feature_providers:
             if isinstance(p, MinedFeatureProvider):
@@ -261,13 +272,23 @@ class FeatureHandler:
             samples.append((at[sid], elem, rows))
         if not samples:
             raise ValueError("no clips to add")
-        step = self.feature_providers[0].step
-        mined = MinedFeatureProvider(sources, samples, label, sampling_weight, penalty_weight, truncation_strategy, step)
-        self.feature_providers.append(mined)
+        return sources, samples
+
+    def set_mined_clips(self, provider, clips):
+        """Replaces, in place, the samples of ``provider`` (what ``add_mined_provider`` returned) with ``clips``: the same
+        validation, the provider keeps its place in ``feature_providers``, its label, weights and strategy.  Nothing is
+        uploaded and nothing is drawn from Python's or numpy's generators; the sampler (and a running prefetcher, its streams
+        kept) is rebuilt, so at ``sampling_weight`` 0 every later batch is the batch without the call."""
+        if not isinstance(provider, MinedFeatureProvider) or not any(p is provider for p in self.feature_providers):
+            raise ValueError("set_mined_clips needs a mined provider of this handler (add_mined_provider returns it)")
+        self._need_engine()
+        sources, samples = self._mined_samples(clips)
+        provider.__init__(sources, samples, provider.label, provider.sampling_weight, provider.penalty_weight,
+                          provider.truncation_strategy, provider.step)
         if getattr(self, "_pf", None) is not None:
-            self._drop_prefetcher(keep_streams=True)   # its sampler description does not know the new provider
+            self._drop_prefetcher(keep_streams=True)   # its sampler description holds the old samples
         self._sampler = None
-        return mined
+        return provider
 
     def shard_training_lists(self, rank: int, world: int):
         """per provider, training sample i of the CANONICAL (store, sample) order goes to rank i mod W - a partition

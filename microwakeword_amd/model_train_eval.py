@@ -287,6 +287,16 @@ def check_evaluation_flags(flags, model_module, config):
                                             int8_variants=getattr(flags, "quantized_backend", "tflite") == "native_ext")
 
 
+def check_mining_config(flags, model_module, config, world):
+    """The ``hard_negative_mining`` mapping of the configuration (mining.mining_config) and the topology of the stream its
+    rounds run on: a refusal is raised here, not at the first round of the training run."""
+    from . import mining, streaming
+    from .train import process_group
+    m = mining.mining_config(config, max(int(world), process_group()[1]))
+    if m is not None and model_module is mixednet:
+        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], [m["mode"]])
+
+
 def _evaluate(flags, model_module, config, device, world):
     """rank 0 evaluates, the other ranks of a data-parallel job wait at a barrier"""
     if not any((flags.test_tf_nonstreaming, flags.test_tflite_nonstreaming, flags.test_tflite_streaming,
@@ -315,6 +325,8 @@ def _run(flags, model_module, rank, local_rank, world):
     operating_point_windows(flags)
     config = load_config(flags, model_module)
     check_evaluation_flags(flags, model_module, config)   # before training and before train_dir is claimed
+    if flags.train:
+        check_mining_config(flags, model_module, config, world)   # likewise
     device = flags.device if local_rank is None else local_rank
     if flags.train:
         device = flags.device if local_rank is None else local_rank

@@ -128,6 +128,7 @@ EXPORTS = [
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
     "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections", "mww_stream_operating_points",
+    "mww_stream_mine",
 ]
 
 
@@ -239,6 +240,9 @@ class NativeLib:
         L.mww_stream_detections.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mww_stream_detections.restype = C.c_int64
+        L.mww_stream_mine.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mww_stream_mine.restype = C.c_int64
         L.mww_stream_operating_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mww_stream_num_tensors.argtypes = [C.c_void_p]
@@ -784,6 +788,40 @@ class Stream:
         for name in DETECTION_DTYPE.names:
             events[name] = raw[name]
         return events, track_count, best_index, score
+
+    def mine(self, tracks, offsets, cutoff, window=5, cooldown=25, before=0, after=0, max_new=None, capacity=None):
+        """``mww_stream_mine`` on the probabilities held: the detections of ``tracks`` (every one ambient), the ``max_new``
+        highest moving averages of them (``None``: all; ties to the earlier event) and their clips, selected and cut on the
+        device.  -> (clips WINDOW_DTYPE, events DETECTION_DTYPE, both in (track, index) order, detections before the selection,
+        track_count int64 [n]).  ``capacity=None`` sizes the outputs for the result (one call when ``max_new`` bounds it, else
+        one to count and one to fetch); a given capacity fetches at most that many clips."""
+        tr = np.ascontiguousarray(tracks, WINDOW_DTYPE).reshape(-1)
+        off = np.ascontiguousarray(offsets, np.int64)
+        if off.size != tr.size + 1:
+            raise ValueError("offsets must have one entry more than tracks")
+        want = -1 if max_new is None else max(int(max_new), 0)
+        track_count = np.zeros(tr.size, np.int64)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+
+        def call(cap):
+            clips, raw = np.zeros(cap, WINDOW_DTYPE), np.zeros(cap, DETECTION_RAW)
+            n = int(self.nl.check(self.nl.lib.mww_stream_mine(
+                self.h, vp(tr), vp(off), tr.size, int(window), int(cooldown), float(cutoff), int(before), int(after), want,
+                vp(clips) if cap else None, vp(raw) if cap else None, cap, C.byref(total), vp(track_count))))
+            return n, clips, raw
+
+        if capacity is None:
+            n, clips, raw = call(want if want >= 0 else 0)
+            if n > clips.size:
+                n, clips, raw = call(n)
+        else:
+            n, clips, raw = call(int(capacity))
+        n = min(n, clips.size)
+        events = np.zeros(n, DETECTION_DTYPE)
+        for name in DETECTION_DTYPE.names:
+            events[name] = raw[name][:n]
+        return clips[:n].copy(), events, int(total.value), track_count
 
     def operating_points(self, offsets, kind, windows, cutoffs, skip=25, cooldown=25):
         """``mww_stream_operating_points`` on the probabilities held: row k is ``metrics`` at ``windows[k]``.

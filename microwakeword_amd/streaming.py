@@ -207,6 +207,13 @@ class StreamingModel:
         positive (kind 1) track reaches its maximum after the first ``ignore_slices_after_accept`` probabilities."""
         return self.native.detections(offsets, kind, cutoff, sliding_window_length, ignore_slices_after_accept, ignore_slices_after_accept)
 
+    def mine(self, windows, offsets, cutoff, sliding_window_length=5, ignore_slices_after_accept=25, before=0, after=0, max_new=None):
+        """The hard negatives of the tracks ``windows`` on the probabilities of the last call, selected and cut into clips on
+        the device (mww_stream_mine): what ``detections`` on all-ambient tracks, a stable descending sort cut at ``max_new``
+        and ``detection_clips`` give, without the event list crossing to the host.  -> (clips, events, detections before the
+        selection, track_count)."""
+        return self.native.mine(windows, offsets, cutoff, sliding_window_length, ignore_slices_after_accept, before, after, max_new)
+
     def operating_points(self, offsets, kind, windows=OP_WINDOWS, cutoffs=CUTOFFS, ignore_slices_after_accept=25):
         """``metrics`` at every sliding-window size of ``windows`` in one call (mww_stream_operating_points;
         ``operating_points_host`` is the host restatement): ``(counts [W, C], ma_len [W, n], score [W, n])``, row k what

@@ -189,6 +189,8 @@ def train(model, config, data_processor, verbose=True):
     model.make_train_function()
     rank, world = process_group()
     chief = rank == 0
+    from .mining import MiningRounds, mining_config
+    mining = mining_config(config, world)   # refusals come before the first step
     fast = hasattr(data_processor, "next_training_batch_on_device") and hasattr(model, "train_on_device_batch") \
         and getattr(data_processor, "engine", None) is getattr(model, "engine", object())
     prefetch = int(config.get("prefetch_batches", 4))
@@ -235,6 +237,11 @@ def train(model, config, data_processor, verbose=True):
 
     train_writer = _JsonSummary(os.path.join(config["summaries_dir"], "train"), "scalars") if chief else _NoSummary()
     val_writer = _JsonSummary(os.path.join(config["summaries_dir"], "validation"), "scalars") if chief else _NoSummary()
+    # hard_negative_mining (mining.MiningRounds): rounds at evaluation boundaries; a restored run takes the list up again
+    miner = None
+    if mining is not None:
+        miner = MiningRounds(mining, model, data_processor, config,
+                             _JsonSummary(os.path.join(config["summaries_dir"], "mining"), "scalars") if chief else None)
 
     warned_weights = False
     steps_max = int(np.sum(ph["training_steps"]))
@@ -305,7 +312,7 @@ def train(model, config, data_processor, verbose=True):
             if private_streams:
                 data_processor.release_private_rng()   # validation shuffles on the global numpy stream (data.py:593-595) ...
             nm = validate_nonstreaming(config, data_processor, model, "validation")
-            if private_streams:
+            if private_streams and miner is None:
                 data_processor.use_private_rng(prefetch=prefetch)   # ... and the training draws continue behind them
             model.reset_metrics()
             info("Step %d (nonstreaming): Validation: recall at no faph = %.3f with cutoff %.2f, accuracy = %.2f%%, recall = %.2f%%, "
@@ -326,6 +333,13 @@ def train(model, config, data_processor, verbose=True):
                 save_ckpt()
             info("So far the best minimization quantity is %.3f with best maximization quantity of %.5f%%; no faph cutoff is %.2f",
                  best_min, best_max * 100, best_cutoff)
+            if miner is not None:
+                # after validation, the best-weights rule and the checkpoint, and before the private streams are taken up again: a
+                # round draws nothing, so the draws continue where they would without it
+                if miner.due(step, is_last):
+                    miner.round(step)
+                if private_streams:
+                    data_processor.use_private_rng(prefetch=prefetch)
     save_ckpt()
     save_weights(os.path.join(config["train_dir"], "last_weights.weights.h5"))
     if dp is not None:

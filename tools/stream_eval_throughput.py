@@ -19,6 +19,10 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
         # adds, on the same ambient probabilities: mww_stream_metrics at one window (the yardstick) against ONE
         # mww_stream_operating_points call for 10 windows x 101 cutoffs, on CUTOFFS (cutoff 0: every index a candidate) and on
         # 101 quantiles of the moving averages (every cutoff splits the indices differently)
+    python tools/stream_eval_throughput.py --hours 20 --mine 2000 --mine_out profiles/stream_mine_throughput.txt
+        # adds, on the same ambient probabilities: ONE mww_stream_mine call keeping MAX_NEW clips against the chain it replaces
+        # (mww_stream_detections at full capacity, the host argsort, detection_clips), at cutoff 0.0 (every index a candidate)
+        # and at a cutoff that leaves fewer than MAX_NEW events; byte equality is checked before anything is timed
 """
 import argparse
 import json
@@ -60,6 +64,9 @@ def main():
     ap.add_argument("--operating_points", action="store_true",
                     help="also time one mww_stream_operating_points call (10 windows x 101 cutoffs) against mww_stream_metrics at one window")
     ap.add_argument("--operating_points_out", default=None, help="write the operating-point leg's times and scratch size to this text file")
+    ap.add_argument("--mine", type=int, default=None, metavar="MAX_NEW",
+                    help="also time mww_stream_mine keeping MAX_NEW clips against mww_stream_detections + argsort + detection_clips")
+    ap.add_argument("--mine_out", default=None, help="write the mining leg's times and read-back sizes to this text file")
     a = ap.parse_args()
     if a.model == "inception":
         T = a.frames or 176
@@ -169,6 +176,11 @@ def main():
         if a.operating_points_out:
             with open(a.operating_points_out, "wt") as fd:
                 fd.write(operating_points_text(rec))
+    if a.mine is not None:
+        rec["mine"] = mine_leg(sm, amb_win, a.mine, a.detections_reps)
+        if a.mine_out:
+            with open(a.mine_out, "wt") as fd:
+                fd.write(mine_text(rec))
     print(json.dumps(rec), flush=True)
 
 
@@ -261,6 +273,75 @@ def operating_points_text(rec):
         lines.append("  mww_stream_metrics, window 5 (the yardstick):      %9.3f ms" % c["metrics_one_window_ms"])
         lines.append("  mww_stream_operating_points, 10 windows:           %9.3f ms  (false accepts at window 5, first / middle / last cutoff: %s)"
                      % (c["grid_ms"], " / ".join(str(v) for v in c["false_accepts_window_5"])))
+    return "".join(line + "\n" for line in lines)
+
+
+def mine_leg(sm, amb_win, max_new, reps, window=5, cooldown=25):
+    """One session, the same ambient probabilities: the median wall time of `reps` calls (after one warm-up call each) of ONE
+    mww_stream_mine call keeping `max_new` clips and of the chain it replaces - mww_stream_detections at full capacity (the
+    count known: one call), the stable host argsort, streaming.detection_clips - at cutoff 0.0 (every index a candidate) and at
+    a cutoff that leaves fewer than `max_new` events.  Clips and events are compared byte for byte before anything is timed.
+    The bytes are what each side copies from the device: events (24 B) and per-track results for the chain; the kept clips
+    and events (24 B each, three 256-B-aligned blocks) and the per-track counts for the call."""
+    off = sm.native.run(amb_win)
+    n_trk = int(amb_win.size)
+    kind = np.zeros(n_trk, np.int32)
+
+    def median_ms(fn):
+        fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return round(float(np.median(ts)) * 1e3, 3)
+
+    def chain(c, n):
+        events, _, _, _ = sm.native.detections(off, kind, c, window, cooldown, cooldown, capacity=n)
+        if events.size > max_new:
+            best = np.argsort(-events["average"].astype(np.float64), kind="stable")[:max_new]
+            events = events[np.sort(best)]
+        clips, kept = streaming.detection_clips(amb_win, events, sm.frames, sm.stride, sm.mode, window, return_kept=True)
+        return clips, events[kept]
+
+    p = sm.read_probabilities()
+    mas = np.concatenate([streaming.moving_average_in_order(p[off[t]:off[t + 1]], window) for t in range(n_trk)])
+    few = float(np.sort(mas)[-max(max_new // 2, 2)])   # at most max_new / 2 - 1 values lie above it
+    al = lambda b: (b + 255) & ~255   # noqa: E731
+    out = {"probabilities": int(off[-1]), "tracks": n_trk, "reps": reps, "window": window, "cooldown": cooldown, "max_new": int(max_new)}
+    for name, c in (("all_candidates", 0.0), ("few_events", few)):
+        _, track_count, _, _ = sm.native.detections(off, kind, c, window, cooldown, cooldown, capacity=0)
+        n = int(track_count.sum())
+        want_clips, want_events = chain(c, n)
+        clips, events, total, counts = sm.native.mine(amb_win, off, c, window, cooldown, 0, 0, max_new)
+        assert clips.tobytes() == want_clips.tobytes() and events.tobytes() == want_events.tobytes(), name
+        assert total == n and np.array_equal(counts, track_count), name
+        k = min(n, max_new)
+        out[name] = {"cutoff": c, "events": n, "clips": int(clips.size),
+                     "chain_ms": median_ms(lambda: chain(c, n)),
+                     "mine_ms": median_ms(lambda: sm.native.mine(amb_win, off, c, window, cooldown, 0, 0, max_new)),
+                     "chain_bytes": 8 + n * 24 + n_trk * 20,
+                     "mine_bytes": 8 + n_trk * 8 + (al(al(8) + al(k * 24) + k * 24) if k else 0)}
+    assert out["all_candidates"]["events"] > max_new > out["few_events"]["events"], out
+    return out
+
+
+def mine_text(rec):
+    d = rec["mine"]
+    lines = ["mww_stream_mine against the chain it replaces, one session (tools/stream_eval_throughput.py --mine %d)" % d["max_new"],
+             "library: %s" % rec["library"], "model: %s%s" % (rec["model"], ", int8" if rec.get("quantized") else ""),
+             "%d probabilities in %d ambient tracks (%.1f h at 20 ms), window %d, cooldown %d, max_new %d; median wall time of %d calls each, "
+             "host work included; clips and events byte-identical on both sides"
+             % (d["probabilities"], d["tracks"], d["probabilities"] * 0.02 / 3600, d["window"], d["cooldown"], d["max_new"], d["reps"])]
+    for name, what in (("all_candidates", "every index a candidate"), ("few_events", "fewer than max_new events")):
+        c = d[name]
+        lines.append("cutoff %.6f (%s): %d events, %d clips kept" % (c["cutoff"], what, c["events"], c["clips"]))
+        lines.append("  mww_stream_detections + argsort + detection_clips: %9.3f ms, %9d bytes read back" % (c["chain_ms"], c["chain_bytes"]))
+        lines.append("  mww_stream_mine:                                    %9.3f ms, %9d bytes read back (1/%.1f)"
+                     % (c["mine_ms"], c["mine_bytes"], c["chain_bytes"] / c["mine_bytes"]))
+    a = d["all_candidates"]
+    lines.append("the bar (all candidates): mine <= chain: %s; read-back <= 1/20 of the chain's: %s"
+                 % ("met" if a["mine_ms"] <= a["chain_ms"] else "MISSED", "met" if 20 * a["mine_bytes"] <= a["chain_bytes"] else "MISSED"))
     return "".join(line + "\n" for line in lines)
 
 
