@@ -575,6 +575,25 @@ int64_t mww_stream_mine(mww_stream* s, const mww_window* tracks, const int64_t* 
 int mww_stream_operating_points(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, const int32_t* windows,
                                 int n_windows, int skip, int cooldown, const double* cutoffs, int n_cutoffs, uint64_t* counts,
                                 int64_t* ma_len, float* score);
+/* The same grid summarised on the device (csrc/tu_stream_oppoints.hip): what a choice of operating point reads,
+ * whatever the number of tracks.  With score[k][t] and ma_len[k][t] the values mww_stream_operating_points returns (the skip
+ * applies to kind 1; an empty track has score -inf and length 0) - they stay on the device -:
+ *   counts [n_windows][n_cutoffs]        exactly the counts of mww_stream_operating_points (the kind-0 tracks);
+ *   accepts [n_windows][n_cutoffs]       the kind-1 tracks with (double)score[k][t] > cutoffs[c], strict: a score equal to the
+ *                                        cutoff is not accepted, -inf never; frr = 1 - accepts / n_kind[1] on the host;
+ *   hours [n_windows]                    the float64 sum over the kind-0 tracks, in track order, of
+ *                                        ((double)(ma_len[k][t] * stride) * step_s) / 3600.0: product, division and add are
+ *                                        separate IEEE operations (streaming.track_hours, bit for bit);
+ *   short_tracks [n_windows][2]          the kind-0 / kind-1 tracks with ma_len[k][t] == 0: a window is usable when n_kind[0] > 0
+ *                                        and both are 0;
+ *   n_kind [2]                           the kind-0 / kind-1 tracks.
+ * A kind-1 track takes no part in the per-cutoff walk and has no per-track count row; its score is compared with the cutoffs in
+ * an integer reduction of fixed order.  The host reads back n_windows * n_cutoffs * 16 + n_windows * 24 + 16 bytes.  Arguments
+ * and limits are those of mww_stream_operating_points; in addition stride >= 1 and step_s > 0.  On the probabilities held, so on
+ * a stream of any creator, float or int8.  Two calls on the same probabilities write the same bytes. */
+int mww_stream_operating_summary(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, const int32_t* windows,
+                                 int n_windows, int skip, int cooldown, const double* cutoffs, int n_cutoffs, int stride, double step_s,
+                                 uint64_t* counts, uint64_t* accepts, double* hours, int64_t* short_tracks, int64_t* n_kind);
 
 /* ---- int8 quantized streaming model (the reference's --test_tflite_streaming_quantized; microwakeword_amd/quantize.py
  * derives the parameters, INTEGRATION.md states the contract).

@@ -297,6 +297,16 @@ def check_mining_config(flags, model_module, config, world):
         streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], [m["mode"]])
 
 
+def check_streaming_validation_config(flags, model_module, config, world):
+    """The ``streaming_validation`` mapping of the configuration (streaming.streaming_validation_config) and the topology of
+    the stream it validates on: a refusal is raised here, not at the dry validation of the training run."""
+    from . import streaming
+    from .train import process_group
+    v = streaming.streaming_validation_config(config, max(int(world), process_group()[1]))
+    if v is not None and model_module is mixednet:
+        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], [v["mode"]])
+
+
 def _evaluate(flags, model_module, config, device, world):
     """rank 0 evaluates, the other ranks of a data-parallel job wait at a barrier"""
     if not any((flags.test_tf_nonstreaming, flags.test_tflite_nonstreaming, flags.test_tflite_streaming,
@@ -327,6 +337,7 @@ def _run(flags, model_module, rank, local_rank, world):
     check_evaluation_flags(flags, model_module, config)   # before training and before train_dir is claimed
     if flags.train:
         check_mining_config(flags, model_module, config, world)   # likewise
+        check_streaming_validation_config(flags, model_module, config, world)
     device = flags.device if local_rank is None else local_rank
     if flags.train:
         device = flags.device if local_rank is None else local_rank

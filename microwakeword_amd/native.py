@@ -128,7 +128,7 @@ EXPORTS = [
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
     "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections", "mww_stream_operating_points",
-    "mww_stream_mine",
+    "mww_stream_mine", "mww_stream_operating_summary",
 ]
 
 
@@ -245,6 +245,9 @@ class NativeLib:
         L.mww_stream_mine.restype = C.c_int64
         L.mww_stream_operating_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mww_stream_operating_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]
         L.mww_stream_num_tensors.argtypes = [C.c_void_p]
         L.mww_stream_calibrate_host.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float)]
         L.mww_stream_set_quantized.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
@@ -840,6 +843,26 @@ class Stream:
         self.nl.check(self.nl.lib.mww_stream_operating_points(self.h, vp(off), vp(kd), n, vp(win), win.size, int(skip), int(cooldown),
                                                               vp(cut), cut.size, vp(counts), vp(ma_len), vp(score)))
         return counts, ma_len, score
+
+    def operating_summary(self, offsets, kind, windows, cutoffs, skip=25, cooldown=25, stride=None, step_s=0.02):
+        """``mww_stream_operating_summary`` on the probabilities held: the grid of ``operating_points`` reduced on the device.
+        -> (counts uint64 [W, C] of the kind-0 tracks, accepts uint64 [W, C] kind-1 tracks whose score is above the cutoff,
+        hours float64 [W], short_tracks int64 [W, 2] kind-0 / kind-1 tracks without a moving-average value, n_kind int64 [2]).
+        ``stride`` defaults to the stream's own."""
+        off = np.ascontiguousarray(offsets, np.int64)
+        kd = np.ascontiguousarray(kind, np.int32)
+        win = np.ascontiguousarray(windows, np.int32).reshape(-1)
+        cut = np.ascontiguousarray(cutoffs, np.float64).reshape(-1)
+        n = kd.size
+        if off.size != n + 1:
+            raise ValueError("offsets must have one entry more than kind")
+        counts, accepts = np.zeros((win.size, cut.size), np.uint64), np.zeros((win.size, cut.size), np.uint64)
+        hours, short, n_kind = np.zeros(win.size, np.float64), np.zeros((win.size, 2), np.int64), np.zeros(2, np.int64)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self.nl.check(self.nl.lib.mww_stream_operating_summary(
+            self.h, vp(off), vp(kd), n, vp(win), win.size, int(skip), int(cooldown), vp(cut), cut.size,
+            int(self.stride if stride is None else stride), float(step_s), vp(counts), vp(accepts), vp(hours), vp(short), vp(n_kind)))
+        return counts, accepts, hours, short, n_kind
 
     # ---- int8 form (include/mww.h, mww_stream_set_quantized)
     def num_tensors(self) -> int:

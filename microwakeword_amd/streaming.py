@@ -220,6 +220,18 @@ class StreamingModel:
         ``metrics`` returns for ``sliding_window_length=windows[k]``."""
         return self.native.operating_points(offsets, kind, windows, cutoffs, ignore_slices_after_accept, ignore_slices_after_accept)
 
+    def operating_summary(self, offsets, kind, windows=OP_WINDOWS, cutoffs=CUTOFFS, ignore_slices_after_accept=25, stride=None, step_s=0.02,
+                          target_faph=None):
+        """The grid of ``operating_points`` summarised on the device (mww_stream_operating_summary; ``operating_summary_host`` is
+        the host restatement): the dict of the operating-point grid without its per-track arrays - ``windows, cutoffs, counts,
+        accepts, hours, usable, faph, frr, n_ambient, n_positive`` and, with ``target_faph``, ``target_faph, chosen,
+        recommended, chosen_cutoff`` (``select_operating_points``).  What is read back does not grow with the tracks.
+        ``stride`` defaults to the stream's own.  Raises ValueError without a positive (kind 1) track."""
+        stride = self.stride if stride is None else int(stride)
+        counts, accepts, hours, short, n_kind = self.native.operating_summary(
+            offsets, kind, windows, cutoffs, ignore_slices_after_accept, ignore_slices_after_accept, stride, step_s)
+        return _operating_summary(counts, accepts, hours, short, n_kind, windows, cutoffs, target_faph)
+
 
 def load_quantized(path):
     """the ``QuantizedModel`` (MixedNet), ``QuantizedMixedNetModel`` (MixedNet with residuals / a pooled head) or
@@ -579,6 +591,46 @@ def operating_points_host(ambient_probabilities, positive_probabilities, windows
     return _operating_grid(counts, amb_len, pos_len, score, windows, cutoffs, stride, step_s, target_faph)
 
 
+SUMMARY_KEYS = ("windows", "cutoffs", "counts", "accepts", "hours", "usable", "faph", "frr", "n_ambient", "n_positive")
+SELECTION_KEYS = ("target_faph", "chosen", "recommended", "chosen_cutoff")
+
+
+def _operating_summary(counts, accepts, hours, short_tracks, n_kind, windows, cutoffs, target_faph):
+    """what mww_stream_operating_summary returns -> the summary's dict: the rules of ``_operating_grid`` on the reduced numbers"""
+    windows, cutoffs = np.asarray(windows, np.int64).reshape(-1), np.asarray(cutoffs, np.float64).reshape(-1)
+    n_amb, n_pos = int(n_kind[0]), int(n_kind[1])
+    if n_pos == 0:
+        raise ValueError("the test set has no positive track")
+    usable = np.array([n_amb > 0 and short_tracks[k, 0] == 0 and short_tracks[k, 1] == 0 for k in range(windows.size)], bool)
+    faph = np.full((windows.size, cutoffs.size), np.nan)
+    frr = np.full((windows.size, cutoffs.size), np.nan)
+    for k in np.nonzero(usable)[0]:
+        faph[k] = counts[k].astype(np.float64) / hours[k]
+        frr[k] = 1 - accepts[k].astype(np.float64) / n_pos   # false_rejection_rates: 1 - true_accepts / len(scores)
+    out = dict(windows=windows, cutoffs=cutoffs, counts=np.asarray(counts, np.uint64), accepts=np.asarray(accepts, np.uint64),
+               hours=np.asarray(hours, np.float64), usable=usable, faph=faph, frr=frr, n_ambient=n_amb, n_positive=n_pos)
+    if target_faph is not None:
+        chosen, rec = select_operating_points(faph, frr, usable, target_faph, windows)
+        out.update(target_faph=float(target_faph), chosen=chosen, recommended=int(rec),
+                   chosen_cutoff=np.array([cutoffs[c] if c >= 0 else np.nan for c in chosen], np.float64))
+    return out
+
+
+def operating_summary_host(ambient_probabilities, positive_probabilities, windows=OP_WINDOWS, cutoffs=CUTOFFS, stride=1, step_s=0.02,
+                           ignore_slices_after_accept=25, target_faph=None, skip=None):
+    """Host restatement of ``StreamingModel.operating_summary`` on given per-track probabilities: ``operating_points_host``
+    with the per-track arrays reduced - ``accepts[k, c]`` counts the scores of window k with ``float64(score) > cutoffs[c]`` -
+    and its counts, hours, usable, faph and frr (so ``false_rejection_rates`` and ``track_hours``) taken as they are."""
+    g = operating_points_host(ambient_probabilities, positive_probabilities, windows, cutoffs, stride, step_s, ignore_slices_after_accept,
+                              target_faph, skip)
+    score = g["score"].astype(np.float64)
+    accepts = np.array([[np.count_nonzero(score[k] > c) for c in g["cutoffs"]] for k in range(score.shape[0])], np.uint64)
+    out = {k: g[k] for k in ("windows", "cutoffs", "counts", "hours", "usable", "faph", "frr")}
+    out.update(accepts=accepts.reshape(g["counts"].shape), n_ambient=len(ambient_probabilities), n_positive=len(positive_probabilities))
+    out.update({k: g[k] for k in SELECTION_KEYS if k in g})
+    return out
+
+
 def operating_point_text(grid):
     """``operating_points.txt``: one line per window, then the recommendation"""
     lines = []
@@ -644,6 +696,137 @@ def operating_point_grid(config, folder, sm, data_processor, target_faph, window
         json.dump(operating_point_settings(grid, sm.mode, isinstance(sm, QuantizedStreamingModel)), fd, indent=2)
         fd.write("\n")
     return grid
+
+
+# ---- the training-loop option (train.train)
+VALIDATION_KEY = "streaming_validation"
+VALIDATION_DEFAULTS = dict(windows=[5], mode="stream", ignore_slices_after_accept=25, data_set="validation", ambient_set="validation_ambient",
+                           every_evals=1)
+STREAMING_METRICS = ("streaming_recall", "streaming_false_rejection_rate", "streaming_false_accepts_per_hour", "streaming_cutoff",
+                     "streaming_window", "streaming_hours", "streaming_positives")
+
+
+def streaming_validation_config(config, world=1):
+    """The ``streaming_validation`` mapping of a training configuration with its defaults filled in, or None without the key.
+    Unknown keys, out-of-range values and a world size above 1 are ``ValueError``s that name the key; so is a
+    ``minimization_metric`` / ``maximization_metric`` that names a streaming metric without the key."""
+    key = VALIDATION_KEY
+    given = config.get(key)
+    if given is None:
+        named = [config.get(k) for k in ("minimization_metric", "maximization_metric") if config.get(k) in STREAMING_METRICS]
+        if named:
+            raise ValueError("%s: the metric %s needs the %s mapping (target_faph, ...)" % (key, ", ".join(named), key))
+        return None
+    if not isinstance(given, dict):
+        raise ValueError("%s must be a mapping (target_faph, windows, ...)" % key)
+    unknown = sorted(set(given) - set(VALIDATION_DEFAULTS) - {"target_faph"}, key=str)
+    if unknown:
+        raise ValueError("%s: unknown key(s) %s; known: target_faph, %s" % (key, ", ".join(map(str, unknown)), ", ".join(VALIDATION_DEFAULTS)))
+    if "target_faph" not in given:
+        raise ValueError("%s: target_faph is required" % key)
+    v = dict(VALIDATION_DEFAULTS, **given)
+    try:
+        v["target_faph"] = float(v["target_faph"])
+        v["windows"] = [int(w) for w in (v["windows"] if isinstance(v["windows"], (list, tuple)) else [v["windows"]])]
+        v["ignore_slices_after_accept"], v["every_evals"] = int(v["ignore_slices_after_accept"]), int(v["every_evals"])
+    except (TypeError, ValueError):
+        raise ValueError("%s: target_faph is a number, windows a list of integers, ignore_slices_after_accept and every_evals "
+                         "integers (mode: stream / non_stream)" % key) from None
+    bad = [k for k, ok in (("target_faph", v["target_faph"] == v["target_faph"]),   # any number: the grid ends at cutoff 1.0, where
+                           # every count is 0, so only a target below 0 is met by no window
+                           ("windows", 1 <= len(v["windows"]) <= native.OP_MAX_WINDOWS and all(1 <= w <= native.OP_MAX_WINDOW for w in v["windows"])),
+                           ("mode", v["mode"] in native.STREAM_MODES), ("ignore_slices_after_accept", v["ignore_slices_after_accept"] >= 0),
+                           ("data_set", isinstance(v["data_set"], str) and bool(v["data_set"])),
+                           ("ambient_set", isinstance(v["ambient_set"], str) and bool(v["ambient_set"])),
+                           ("every_evals", v["every_evals"] >= 1)) if not ok]
+    if bad:
+        raise ValueError("%s: %s out of range (target_faph a number; ignore_slices_after_accept >= 0; 1..%d windows of 1..%d; every_evals >= 1; "
+                         "mode stream or non_stream; data_set, ambient_set names of modes)"
+                         % (key, ", ".join(bad), native.OP_MAX_WINDOWS, native.OP_MAX_WINDOW))
+    if int(world) > 1:
+        raise ValueError("%s is not available under data parallelism (world size %d): a rank holds its shard of the validation "
+                         "stores only" % (key, int(world)))
+    return v
+
+
+def streaming_metrics(summary):
+    """The summary of one streaming validation (``operating_summary`` with ``target_faph``) -> the ``streaming_*`` metrics.
+    When no window meets the target: recall 0, FRR 1, and as FAPH the closest the grid gets - the smallest FAPH at the
+    largest cutoff over the usable windows -, so a minimisation towards the target keeps improving."""
+    r = summary["recommended"]
+    usable = np.nonzero(summary["usable"])[0]
+    if r >= 0:
+        c = summary["chosen"][r]
+        frr, faph = float(summary["frr"][r, c]), float(summary["faph"][r, c])
+        out = dict(streaming_recall=1 - frr, streaming_false_rejection_rate=frr, streaming_false_accepts_per_hour=faph,
+                   streaming_cutoff=float(summary["cutoffs"][c]), streaming_window=int(summary["windows"][r]))
+    else:
+        out = dict(streaming_recall=0.0, streaming_false_rejection_rate=1.0,
+                   streaming_false_accepts_per_hour=float(min(summary["faph"][k, -1] for k in usable)),
+                   streaming_cutoff=float("nan"), streaming_window=-1)
+    out.update(streaming_hours=float(summary["hours"][r if r >= 0 else usable[0]]), streaming_positives=int(summary["n_positive"]))
+    return out
+
+
+class StreamingValidation:
+    """What ``train.train`` does with a ``streaming_validation`` mapping: at the evaluation boundaries that are due, the
+    streaming FAPH / FRR of the model's current weights at the operating point ``target_faph`` selects, added to the
+    validation metrics.  A validation draws nothing from Python's or numpy's generators."""
+
+    def __init__(self, settings, model, data_processor, config, writer=None):
+        if getattr(data_processor, "engine", None) is not getattr(model, "engine", object()) or not hasattr(data_processor, "track_windows"):
+            raise ValueError("%s needs this package's Model and FeatureHandler on one engine: the tracks are windows of the stores "
+                             "resident in the model's context" % VALIDATION_KEY)
+        flags = getattr(model, "flags", None)
+        if flags is not None and not isinstance(model.layout, InceptionLayout):
+            check_evaluation_topology(flags, config["spectrogram_length"], config["stride"], [settings["mode"]])
+        self.v, self.model, self.fh, self.config, self.writer = settings, model, data_processor, config, writer
+        self.sm = None
+        self.boundaries = 0
+        self.last = None   # the summary of the last validation
+
+    def due(self, is_last):
+        """called once per evaluation boundary: whether a validation runs at this one (always at the last step)"""
+        self.boundaries += 1
+        return is_last or self.boundaries % self.v["every_evals"] == 0
+
+    def validate(self, step):
+        metrics, self.last = validate_streaming(self.config, self.fh, self.model, self)
+        if self.writer is not None:
+            self.writer.scalars(step, **metrics)
+        import logging
+        logging.getLogger("microwakeword_amd.train").info(
+            "Step %d (streaming): Validation: recall = %.2f%% at %.3f false accepts per hour (target %g) with window %d and cutoff %.2f; "
+            "%.3f ambient hours, %d positives", step, metrics["streaming_recall"] * 100, metrics["streaming_false_accepts_per_hour"],
+            self.v["target_faph"], metrics["streaming_window"], metrics["streaming_cutoff"], metrics["streaming_hours"],
+            metrics["streaming_positives"])
+        return metrics
+
+
+def validate_streaming(config, data_processor, model, state):
+    """One streaming validation of ``model``'s current weights (``state``: the ``StreamingValidation`` that keeps the settings
+    and the stream): the ambient tracks of ``ambient_set``, then the label-1 tracks of ``data_set``, through one native run
+    from zeroed rings with the state carried from track to track (the order of ``streaming_model_roc``), one
+    ``operating_summary`` and the selection at ``target_faph``.  Returns ``(streaming_* metrics, summary)``; raises ValueError
+    without a positive track or a usable window."""
+    v = state.v
+    if state.sm is None:
+        state.sm = StreamingModel(model, int(config["stride"]), v["mode"])   # on the model's own context
+    sm = state.sm
+    sm.set_weights(model.get_weights())
+    sm.reset()
+    amb, _ = data_processor.track_windows(v["ambient_set"], sm.frames)
+    pos, _ = data_processor.track_windows(v["data_set"], sm.frames, only_label=1.0)
+    if pos.size == 0:
+        raise ValueError("%s: %r has no positive track" % (VALIDATION_KEY, v["data_set"]))
+    offsets = sm.native.run(np.concatenate([amb, pos]))
+    kind = np.concatenate([np.zeros(amb.size, np.int32), np.ones(pos.size, np.int32)])
+    try:
+        summary = sm.operating_summary(offsets, kind, v["windows"], CUTOFFS, v["ignore_slices_after_accept"], sm.stride,
+                                       config["window_step_ms"] / 1000, v["target_faph"])
+    except ValueError as e:
+        raise ValueError("%s: %s" % (VALIDATION_KEY, e)) from None
+    return streaming_metrics(summary), summary
 
 
 def detections_report(ambient, positive, cutoff, stride=1, step_s=0.02):

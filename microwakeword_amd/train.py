@@ -11,6 +11,9 @@
     best-weights rule, checkpoint                                   train.py:315-451
 and ``validate_nonstreaming`` reproduces train.py:41-163 (validation set + 100 ms-stride split of
 the ambient set accumulated into the same counters, FAPH / recall-at-cutoff / average viable recall).
+With a ``streaming_validation`` mapping in the configuration every evaluation boundary that is due also measures the streaming
+FAPH / recall at the operating point its ``target_faph`` selects (``streaming.validate_streaming``) and adds the
+``streaming_*`` metrics to those the best-weights rule may name; without the key nothing changes.
 
 When both objects come from this package the spectrogram batch never leaves HBM
 (``FeatureHandler.next_training_batch_on_device`` + ``Model.train_on_device_batch``); with any other
@@ -191,6 +194,8 @@ def train(model, config, data_processor, verbose=True):
     chief = rank == 0
     from .mining import MiningRounds, mining_config
     mining = mining_config(config, world)   # refusals come before the first step
+    from .streaming import STREAMING_METRICS, StreamingValidation, streaming_validation_config
+    streaming_settings = streaming_validation_config(config, world)   # likewise
     fast = hasattr(data_processor, "next_training_batch_on_device") and hasattr(model, "train_on_device_batch") \
         and getattr(data_processor, "engine", None) is getattr(model, "engine", object())
     prefetch = int(config.get("prefetch_batches", 4))
@@ -201,6 +206,17 @@ def train(model, config, data_processor, verbose=True):
         # hands weights, moving statistics and Adam state to the other ranks
         model.load_weights(ckpt + ".weights")
         model.load_optimizer_state(ckpt + ".opt.npz")
+
+    # streaming_validation (streaming.StreamingValidation): the streaming FAPH / recall among the validation metrics.
+    # One dry validation with the initial weights before step 1: a set-up without a usable window or a positive track fails
+    # here, not at the first boundary.  It draws nothing, and runs before the sampler streams are made private.
+    streamer = None
+    if streaming_settings is not None:
+        streamer = StreamingValidation(streaming_settings, model, data_processor, config)   # its refusals, before any file is made
+        if chief:
+            streamer.writer = _JsonSummary(os.path.join(config["summaries_dir"], "validation_streaming"), "scalars")
+        streamer.validate(0)
+    streaming_named = [k for k in ("minimization_metric", "maximization_metric") if config.get(k) in STREAMING_METRICS]
 
     dp = None
     if world > 1 or config.get("data_parallel"):
@@ -312,6 +328,9 @@ def train(model, config, data_processor, verbose=True):
             if private_streams:
                 data_processor.release_private_rng()   # validation shuffles on the global numpy stream (data.py:593-595) ...
             nm = validate_nonstreaming(config, data_processor, model, "validation")
+            streamed = streamer is not None and streamer.due(is_last)
+            if streamed:
+                nm.update(streamer.validate(step))   # while the private streams are released; it draws nothing
             if private_streams and miner is None:
                 data_processor.use_private_rng(prefetch=prefetch)   # ... and the training draws continue behind them
             model.reset_metrics()
@@ -325,9 +344,11 @@ def train(model, config, data_processor, verbose=True):
             if chief:
                 os.makedirs(os.path.join(config["train_dir"], "train"), exist_ok=True)
             save_weights(os.path.join(config["train_dir"], "train", f"{int(best_min * 10000)}_weights_{step}.weights.h5"))
-            cur_min = 0.0 if config["minimization_metric"] is None else nm[config["minimization_metric"]]
-            cur_max = nm[config["maximization_metric"]]
-            if _is_better(cur_min, cur_max, best_min, best_max, config["target_minimization"]):
+            # a boundary without a streaming validation (every_evals > 1) has no value for a streaming metric: the rule waits
+            judged = streamed or not streaming_named
+            cur_min = 0.0 if config["minimization_metric"] is None or not judged else nm[config["minimization_metric"]]
+            cur_max = nm[config["maximization_metric"]] if judged else 0.0
+            if judged and _is_better(cur_min, cur_max, best_min, best_max, config["target_minimization"]):
                 best_min, best_max, best_cutoff = cur_min, cur_max, nm["cutoff_for_no_faph"]
                 save_weights(os.path.join(config["train_dir"], "best_weights.weights.h5"))
                 save_ckpt()

@@ -23,6 +23,10 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
         # adds, on the same ambient probabilities: ONE mww_stream_mine call keeping MAX_NEW clips against the chain it replaces
         # (mww_stream_detections at full capacity, the host argsort, detection_clips), at cutoff 0.0 (every index a candidate)
         # and at a cutoff that leaves fewer than MAX_NEW events; byte equality is checked before anything is timed
+    python tools/stream_eval_throughput.py --hours 20 --summary --summary_out profiles/stream_operating_summary_throughput.txt
+        # adds, on the probabilities of the ambient tracks followed by the positives: ONE mww_stream_operating_summary call for
+        # 10 windows x 101 cutoffs with the selection against the chain it replaces (mww_stream_operating_points + the host's
+        # _operating_grid); equality is checked before anything is timed.  --positives 50000: the validation-sized case
 """
 import argparse
 import json
@@ -67,6 +71,10 @@ def main():
     ap.add_argument("--mine", type=int, default=None, metavar="MAX_NEW",
                     help="also time mww_stream_mine keeping MAX_NEW clips against mww_stream_detections + argsort + detection_clips")
     ap.add_argument("--mine_out", default=None, help="write the mining leg's times and read-back sizes to this text file")
+    ap.add_argument("--summary", action="store_true",
+                    help="also time one mww_stream_operating_summary call (10 windows x 101 cutoffs) against mww_stream_operating_points + the host grid")
+    ap.add_argument("--summary_out", default=None, help="append the summary leg's times, read-back and scratch sizes to this text file")
+    ap.add_argument("--summary_target", type=float, default=0.5, help="target FAPH of the summary leg's selection")
     a = ap.parse_args()
     if a.model == "inception":
         T = a.frames or 176
@@ -181,7 +189,80 @@ def main():
         if a.mine_out:
             with open(a.mine_out, "wt") as fd:
                 fd.write(mine_text(rec))
+    if a.summary:
+        rec["summary"] = summary_leg(sm, amb_win, pos_win, a.detections_reps, a.summary_target)
+        if a.summary_out:
+            with open(a.summary_out, "at") as fd:
+                fd.write(summary_text(rec))
     print(json.dumps(rec), flush=True)
+
+
+def summary_leg(sm, amb_win, pos_win, reps, target, cooldown=25, step_s=0.02):
+    """One session, the probabilities of the ambient tracks followed by the positives (one native run): the median wall time of
+    `reps` calls (after one warm-up call each) of ONE StreamingModel.operating_summary call - windows 1..10 x the 101 cutoffs,
+    the selection at `target` included - and of the chain it replaces: mww_stream_operating_points, then the host's
+    _operating_grid (track_hours, false_rejection_rates, select_operating_points).  Counts, hours, usable, FAPH, FRR and the
+    selection are compared bit for bit before anything is timed.  Bytes: what each side copies from the device, and the device
+    memory each call needs next to the transfer tables (both from the sizes)."""
+    n_amb, n_pos = int(amb_win.size), int(pos_win.size)
+    off = sm.native.run(np.concatenate([amb_win, pos_win]))
+    kind = np.concatenate([np.zeros(n_amb, np.int32), np.ones(n_pos, np.int32)])
+    windows, cut = streaming.OP_WINDOWS, streaming.CUTOFFS
+    W, C, n = len(windows), cut.size, n_amb + n_pos
+
+    def median_ms(fn):
+        fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return round(float(np.median(ts)) * 1e3, 3)
+
+    def chain():
+        counts, ma_len, score = sm.operating_points(off, kind, windows, cut, cooldown)
+        return streaming._operating_grid(counts, ma_len[:, :n_amb], ma_len[:, n_amb:], score[:, n_amb:], windows, cut, sm.stride, step_s, target)
+
+    def call():
+        return sm.operating_summary(off, kind, windows, cut, cooldown, sm.stride, step_s, target)
+
+    want, got = chain(), call()
+    for k in ("counts", "hours", "usable", "faph", "frr", "chosen", "chosen_cutoff"):
+        assert np.asarray(got[k]).tobytes() == np.asarray(want[k]).tobytes(), k
+    assert got["recommended"] == want["recommended"] and got["n_positive"] == n_pos and got["usable"].all()
+    lengths = np.diff(off) - np.where(kind == 1, cooldown, 0)
+    n_seg = int(sum((max(int(m) - min(windows) + 1, 0) + 1023) // 1024 for m in lengths))
+    ma = np.maximum(lengths - min(windows) + 1, 0)
+    tables, tables_ambient = operating_points_scratch(ma, W, C, cooldown), operating_points_scratch(ma[:n_amb], W, C, cooldown)
+    n_blk = (n_pos + 255) // 256
+    r = got["recommended"]
+    return {"probabilities": int(off[-1]), "ambient_tracks": n_amb, "positives": n_pos, "reps": reps, "windows": list(windows),
+            "cooldown": cooldown, "target_faph": target, "recommended_window": int(windows[r]) if r >= 0 else None,
+            "chain_ms": median_ms(chain), "grid_call_ms": median_ms(lambda: sm.operating_points(off, kind, windows, cut, cooldown)),
+            "summary_ms": median_ms(call),
+            "chain_bytes": W * C * 8 + W * n * 12, "summary_bytes": W * C * 16 + W * 24 + 16,
+            "chain_table_bytes": tables, "summary_table_bytes": tables_ambient,
+            "chain_scratch_bytes": W * C * 8 + W * n * 12 + W * n * C * 8 + W * n_seg * 4,
+            "summary_scratch_bytes": W * C * 16 + W * 24 + 16 + W * n_amb * C * 8 + W * n_blk * (C + 1) * 4 + W * n_seg * 4}
+
+
+def summary_text(rec):
+    d = rec["summary"]
+    lines = ["mww_stream_operating_summary against the chain it replaces, one session (tools/stream_eval_throughput.py --summary --positives %d)"
+             % d["positives"],
+             "library: %s" % rec["library"], "model: %s%s" % (rec["model"], ", int8" if rec.get("quantized") else ""),
+             "%d probabilities: %d ambient tracks + %d positives, windows %s x 101 cutoffs, cooldown %d, target %g FAPH; median wall time "
+             "of %d calls each, host work included; counts, hours, FAPH, FRR and the selection bit-identical on both sides"
+             % (d["probabilities"], d["ambient_tracks"], d["positives"], ",".join(str(w) for w in d["windows"]), d["cooldown"],
+                d["target_faph"], d["reps"]),
+             "  mww_stream_operating_points + _operating_grid on the host: %10.3f ms (the call alone %.3f ms), %10d bytes read back, %11d bytes of device scratch"
+             % (d["chain_ms"], d["grid_call_ms"], d["chain_bytes"], d["chain_scratch_bytes"]),
+             "  mww_stream_operating_summary + the selection:              %10.3f ms, %31d bytes read back, %11d bytes of device scratch"
+             % (d["summary_ms"], d["summary_bytes"], d["summary_scratch_bytes"]),
+             "  transfer tables resident at a time: %d bytes (a row per segment) against %d bytes (the ambient segments alone)"
+             % (d["chain_table_bytes"], d["summary_table_bytes"]),
+             "the bar: summary <= chain: %s" % ("met" if d["summary_ms"] <= d["chain_ms"] else "MISSED"), ""]
+    return "".join(line + "\n" for line in lines)
 
 
 def detections_leg(sm, amb_win, cutoff, reps):

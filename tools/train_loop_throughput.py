@@ -1,6 +1,8 @@
 """Throughput of the PRODUCT train loop (microwakeword_amd.train.train on the package's own Model / FeatureHandler) on the
 synthetic benchmark stores, next to bench.py's figure for the same step: what a user of the CLI gets.
-usage: python tools/train_loop_throughput.py [steps] [batch] [mixednet|inception]"""
+usage: python tools/train_loop_throughput.py [steps] [batch] [mixednet|inception] [streaming_validation]
+With the fourth argument the configuration carries ``streaming_validation: {target_faph: 0.5}`` and the wall time of
+the evaluation boundary is printed in its parts: validate_nonstreaming and each streaming validation (the dry one first)."""
 import random
 import sys
 import tempfile
@@ -16,7 +18,25 @@ from microwakeword_amd.data import FeatureHandler   # noqa: E402
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 600
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 kind = sys.argv[3] if len(sys.argv) > 3 else "mixednet"
+with_streaming = len(sys.argv) > 4 and sys.argv[4] == "streaming_validation"
 T = 194
+timed = {}
+
+
+def _timed(module, name):
+    fn = getattr(module, name)
+
+    def wrapper(*a, **kw):
+        t0 = time.perf_counter()
+        out = fn(*a, **kw)
+        timed.setdefault(name, []).append(time.perf_counter() - t0)
+        return out
+    setattr(module, name, wrapper)
+
+
+from microwakeword_amd import streaming   # noqa: E402
+_timed(tr, "validate_nonstreaming")
+_timed(streaming, "validate_streaming")
 for verbose in (False, True):
     cfg, _ = synthetic.benchmark_config(4096, 1234, n_val=256, n_ambient=32)
     d = tempfile.mkdtemp(prefix="mww_loop_")
@@ -24,6 +44,9 @@ for verbose in (False, True):
                time_mask_max_size=[5], time_mask_count=[2], freq_mask_max_size=[5], freq_mask_count=[2], positive_class_weight=[1.0],
                negative_class_weight=[1.0], eval_step_interval=steps, target_minimization=0.9, minimization_metric=None,
                maximization_metric="accuracy")
+    if with_streaming:
+        cfg["streaming_validation"] = dict(target_faph=0.5)
+    timed.clear()
     random.seed(0)
     np.random.seed(0)
     if kind == "inception":
@@ -37,4 +60,5 @@ for verbose in (False, True):
     sys.stdout.write("\n")
     print("train.train (%s) verbose=%s: %d steps of batch %d in %.3f s = %.4f ms/step = %.2f M windows/s (one validation pass and the "
           "checkpoint writes at the end included)" % (kind, verbose, steps, B, dt, 1e3 * dt / steps, steps * B / dt / 1e6), flush=True)
+    print("evaluation boundary: " + "; ".join("%s %s ms" % (k, ", ".join("%.1f" % (1e3 * t) for t in v)) for k, v in timed.items()), flush=True)
     model.engine.close()
