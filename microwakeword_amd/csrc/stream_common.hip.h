@@ -297,24 +297,20 @@ struct mww_stream {
   int64_t cap_host_frames = 0;
   int64_t n_out = 0;       // outputs held in prob (last run or set_probs)
   int grid = 0;            // workgroups of the last launch
-  // metrics
-  char* mtab = nullptr;
-  int64_t cap_mtab = 0;
   std::vector<char> htab;   // host copy of the last call's tables
   float* rec = nullptr;     // calibration partials
   int64_t cap_rec = 0;
-  // detections (tu_stream_detect.hip): the call's tables, its candidates and transfer tables, its events
-  char* det_tab = nullptr;
-  char* det_cand = nullptr;
+  // the entry points on the probabilities held (stream_post.hip.h): no two run at once, so they share a call's tables and
+  // its transfer tables / candidates
+  char* post_tab = nullptr;
+  char* post_scr = nullptr;
+  int64_t cap_post_tab = 0, cap_post_scr = 0;
+  // detections (stream_detect.hip.h): the events; live together with the tables above inside mww_stream_mine, as is mine_buf
   mww_detection* det_out = nullptr;
-  int64_t cap_det_tab = 0, cap_det_cand = 0, cap_det_out = 0;
+  int64_t cap_det_out = 0;
   // mining (tu_stream_mine.hip): the tracks' windows, the radix histograms, the per-workgroup counts, the kept clips and events
   char* mine_buf = nullptr;
   int64_t cap_mine_buf = 0;
-  // operating points (tu_stream_oppoints.hip): the call's tables, the transfer tables of one pass over the windows
-  char* op_tab = nullptr;
-  char* op_scr = nullptr;
-  int64_t cap_op_tab = 0, cap_op_scr = 0;
   // int8 form (mww_stream_set_quantized): runs replace the float kernel with the int8 one
   bool q8 = false;
   int8_t* q8_w = nullptr;

@@ -2,7 +2,9 @@
 // mww_stream_detections (include/mww.h): WHERE the moving average of the probabilities a stream holds crosses one
 // cutoff, in the cooldown semantics of test.py:119-135, and which moving-average index gives a positive track its score.
 //
-// The cooldown walk is the only sequential part, and it is cut into segments of DET_SEG moving-average values:
+// The moving average, the values of a track, the segment plan and the table packing are those of stream_post.hip.h.
+//
+// The cooldown walk is the only sequential part, and it is cut into segments of POST_SEG moving-average values:
 //   detect_segment_kernel  one workgroup per segment: moving averages and candidate flags (avg > cutoff) in parallel, the
 //                          candidate offsets compacted IN INDEX ORDER by an LDS prefix scan over the threads' counts (thread j
 //                          owns the DET_ITEMS consecutive values j * DET_ITEMS ..., so position = values before it: no atomic
@@ -17,21 +19,13 @@
 //                          (track, index, average) at the positions the scans fixed, below `capacity`.
 // Every position is a function of the data alone, so two runs write the same bytes.
 #pragma once
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "stream_common.hip.h"
-
-using namespace mww_stream_impl;
+#include "stream_post.hip.h"
 
 namespace {
 
 constexpr int DET_THREADS = 256;
 constexpr int DET_ITEMS = 4;
-constexpr int DET_SEG = DET_THREADS * DET_ITEMS;   // 1024 moving-average values per segment (tests/stream_detect_checks.py names it)
+static_assert(DET_THREADS * DET_ITEMS == POST_SEG, "thread j owns the DET_ITEMS consecutive values of a segment from j * DET_ITEMS");
 
 struct DetArgs {
   const float* prob;
@@ -42,9 +36,9 @@ struct DetArgs {
   int win, skip;
   int cdp;                  // max(cooldown, 1): distance from an accept to the next index that may be accepted
   int first_ok;             // max(cooldown - 1, 0): the first index of a track that may be accepted
-  int n_entry;              // min(cdp, DET_SEG): entry states a segment tabulates
+  int n_entry;              // min(cdp, POST_SEG): entry states a segment tabulates
   double cutoff;
-  unsigned short* cand;     // [n_seg][DET_SEG] candidate offsets of each segment, ascending
+  unsigned short* cand;     // [n_seg][POST_SEG] candidate offsets of each segment, ascending
   int* seg_ncand;           // [n_seg]
   int* tab_exit;            // [n_seg][n_entry]
   int* tab_cnt;             // [n_seg][n_entry]
@@ -60,41 +54,22 @@ struct DetArgs {
   int64_t capacity;
 };
 
-// the moving average of mww_stream_metrics: float32 sum in order, then one division
-__device__ __forceinline__ float det_avg(const float* p, int win) {
-  float s = 0.f;
-  for (int k = 0; k < win; ++k) s += p[k];
-  return s / (float)win;
-}
-
-// track of segment `seg`: the last t with seg_first[t] <= seg (tracks without a segment share their successor's entry)
-__device__ __forceinline__ int det_track_of(const int* seg_first, int n_trk, int seg) {
-  int lo = 0, hi = n_trk;   // seg_first[lo] <= seg < seg_first[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (seg_first[mid] <= seg) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 struct DetSeg {
   int t;
   int64_t b;     // first probability of the track's moving-average sequence (after the skip of a positive track)
   int64_t i0;    // first moving-average index of the segment
-  int len;       // values in the segment (1 .. DET_SEG)
+  int len;       // values in the segment (1 .. POST_SEG)
   int kind;
 };
 
 __device__ __forceinline__ DetSeg det_segment(const DetArgs& a, int seg) {
   DetSeg g;
-  g.t = det_track_of(a.seg_first, a.n_trk, seg);
+  g.t = post_track_of(a.seg_first, a.n_trk, seg);
   g.kind = a.kind[g.t];
-  const int64_t sk = g.kind ? a.skip : 0;
-  const int64_t n = a.off[g.t + 1] - a.off[g.t] - sk;   // >= win: the track has a segment
-  const int64_t m = n - a.win + 1;
-  g.b = a.off[g.t] + sk;
-  g.i0 = (int64_t)(seg - a.seg_first[g.t]) * DET_SEG;
-  g.len = (int)(m - g.i0 < DET_SEG ? m - g.i0 : DET_SEG);
+  const PostValues v = post_values(a.off, a.kind, a.skip, g.t, a.win);   // m > 0: the track has a segment
+  g.b = v.b;
+  g.i0 = (int64_t)(seg - a.seg_first[g.t]) * POST_SEG;
+  g.len = (int)(v.m - g.i0 < POST_SEG ? v.m - g.i0 : POST_SEG);
   return g;
 }
 
@@ -122,7 +97,7 @@ __device__ __forceinline__ int det_walk(const unsigned short* cand, int n_cand, 
     if (cnt) next = (int64_t)cand[n_cand - 1] + 1;
   } else {
     int p = 0;
-    while (next < DET_SEG) {
+    while (next < POST_SEG) {
       p += det_lower_bound(cand + p, n_cand - p, next);
       if (p >= n_cand) break;
       if (acc) acc[cnt] = cand[p];
@@ -131,13 +106,13 @@ __device__ __forceinline__ int det_walk(const unsigned short* cand, int n_cand, 
       ++p;
     }
   }
-  *exit_state = next > DET_SEG ? (int)(next - DET_SEG) : 0;
+  *exit_state = next > POST_SEG ? (int)(next - POST_SEG) : 0;
   return cnt;
 }
 
 __global__ void __launch_bounds__(DET_THREADS) detect_segment_kernel(DetArgs a) {
   __shared__ int s_scan[DET_THREADS];
-  __shared__ unsigned short s_cand[DET_SEG];
+  __shared__ unsigned short s_cand[POST_SEG];
   __shared__ float s_best[DET_THREADS];
   __shared__ int s_bidx[DET_THREADS];
   const int seg = blockIdx.x, j = threadIdx.x;
@@ -147,7 +122,7 @@ __global__ void __launch_bounds__(DET_THREADS) detect_segment_kernel(DetArgs a) 
   float avg[DET_ITEMS];
   for (int k = 0; k < DET_ITEMS; ++k) {
     const int o = j * DET_ITEMS + k;
-    avg[k] = o < g.len ? det_avg(p + o, a.win) : 0.f;
+    avg[k] = o < g.len ? post_avg(p + o, a.win) : 0.f;
   }
   if (g.kind == 0) {
     bool flag[DET_ITEMS];
@@ -170,7 +145,7 @@ __global__ void __launch_bounds__(DET_THREADS) detect_segment_kernel(DetArgs a) 
     for (int k = 0; k < DET_ITEMS; ++k)
       if (flag[k]) s_cand[at++] = (unsigned short)(j * DET_ITEMS + k);
     __syncthreads();
-    unsigned short* gc = a.cand + (int64_t)seg * DET_SEG;
+    unsigned short* gc = a.cand + (int64_t)seg * POST_SEG;
     for (int q = j; q < n_cand; q += DET_THREADS) gc[q] = s_cand[q];
     if (j == 0) a.seg_ncand[seg] = n_cand;
     for (int e = j; e < a.n_entry; e += DET_THREADS) {
@@ -208,9 +183,9 @@ __global__ void __launch_bounds__(64) detect_track_kernel(DetArgs a) {
     int64_t state = a.first_ok, total = 0;
     for (int s = s0; s < s1; ++s) {
       a.seg_base[s] = total;
-      if (state >= DET_SEG) {   // still cooling down beyond this segment
-        a.seg_entry[s] = DET_SEG;
-        state -= DET_SEG;
+      if (state >= POST_SEG) {   // still cooling down beyond this segment
+        a.seg_entry[s] = POST_SEG;
+        state -= POST_SEG;
       } else {
         a.seg_entry[s] = (int)state;
         total += a.tab_cnt[(int64_t)s * a.n_entry + state];
@@ -256,8 +231,8 @@ __global__ void __launch_bounds__(DET_THREADS) detect_scan_kernel(DetArgs a) {
 }
 
 __global__ void __launch_bounds__(DET_THREADS) detect_write_kernel(DetArgs a) {
-  __shared__ unsigned short s_cand[DET_SEG];
-  __shared__ unsigned short s_acc[DET_SEG];
+  __shared__ unsigned short s_cand[POST_SEG];
+  __shared__ unsigned short s_acc[POST_SEG];
   __shared__ int s_n;
   const int seg = blockIdx.x, j = threadIdx.x;
   if (seg >= a.n_seg) return;
@@ -266,8 +241,8 @@ __global__ void __launch_bounds__(DET_THREADS) detect_write_kernel(DetArgs a) {
   const int entry = a.seg_entry[seg];
   const int64_t base = a.trk_base[g.t] + a.seg_base[seg];
   const int n_cand = a.seg_ncand[seg];
-  if (entry >= DET_SEG || n_cand == 0 || base >= a.capacity) return;   // uniform over the workgroup
-  const unsigned short* gc = a.cand + (int64_t)seg * DET_SEG;
+  if (entry >= POST_SEG || n_cand == 0 || base >= a.capacity) return;   // uniform over the workgroup
+  const unsigned short* gc = a.cand + (int64_t)seg * POST_SEG;
   for (int q = j; q < n_cand; q += DET_THREADS) s_cand[q] = gc[q];
   __syncthreads();
   if (j == 0) {
@@ -283,7 +258,7 @@ __global__ void __launch_bounds__(DET_THREADS) detect_write_kernel(DetArgs a) {
     d.track = g.t;
     d.reserved = 0;
     d.index = g.i0 + o;
-    d.average = det_avg(a.prob + g.b + g.i0 + o, a.win);
+    d.average = post_avg(a.prob + g.b + g.i0 + o, a.win);
     d.reserved2 = 0.f;
     a.out[base + q] = d;
   }
@@ -293,48 +268,37 @@ __global__ void __launch_bounds__(DET_THREADS) detect_write_kernel(DetArgs a) {
 // (a->trk_count, a->trk_base, the segments' entry states) and nothing is written yet.  `kind` null: every track is ambient.
 inline int det_locate(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip, int cooldown,
                       double cutoff, DetArgs* out) {
-  if (n_tracks <= 0 || n_tracks > INT32_MAX || window <= 0 || skip < 0 || cooldown < 0)
-    return mww::set_error(MWW_ERR_INVALID, "bad detection arguments");
-  if (offsets[0] < 0 || offsets[n_tracks] > s->n_out) return mww::set_error(MWW_ERR_INVALID, "track offsets exceed the probabilities held");
-  for (int64_t t = 0; t < n_tracks; ++t)
-    if (offsets[t + 1] < offsets[t]) return mww::set_error(MWW_ERR_INVALID, "track offsets must not decrease");
-  for (int64_t t = 0; kind && t < n_tracks; ++t)
-    if (kind[t] != 0 && kind[t] != 1) return mww::set_error(MWW_ERR_INVALID, "track kind must be 0 (ambient) or 1 (positive)");
-  std::vector<int32_t> seg_first((size_t)n_tracks + 1);
-  int64_t n_seg = 0;
-  for (int64_t t = 0; t < n_tracks; ++t) {
-    seg_first[(size_t)t] = (int32_t)n_seg;
-    const int64_t n = offsets[t + 1] - offsets[t] - (kind && kind[t] ? skip : 0);
-    const int64_t m = n >= window ? n - window + 1 : 0;
-    n_seg += (m + DET_SEG - 1) / DET_SEG;
-    if (n_seg > INT32_MAX) return mww::set_error(MWW_ERR_INVALID, "too many probabilities for one call");
-  }
-  seg_first[(size_t)n_tracks] = (int32_t)n_seg;
-  const int cdp = std::max(cooldown, 1), n_entry = std::min(cdp, DET_SEG);
-  auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-  // inputs, per-track results, per-segment results: one table
-  const int64_t o_off = 0, o_kind = al((n_tracks + 1) * 8), o_sf = al(o_kind + n_tracks * 4), o_in_end = al(o_sf + (n_tracks + 1) * 4),
-                o_cnt = o_in_end, o_base = al(o_cnt + n_tracks * 8), o_bidx = al(o_base + (n_tracks + 1) * 8),
-                o_sc = al(o_bidx + n_tracks * 8), o_nc = al(o_sc + n_tracks * 4), o_ent = al(o_nc + n_seg * 4),
-                o_sbase = al(o_ent + n_seg * 4), o_sbest = al(o_sbase + n_seg * 8), o_sbidx = al(o_sbest + n_seg * 4),
-                bytes = al(o_sbidx + n_seg * 8);
-  // candidates and transfer tables: sized from this call's segments and cooldown
-  const int64_t c_cand = 0, c_exit = al(n_seg * DET_SEG * 2), c_tcnt = al(c_exit + n_seg * n_entry * 4),
-                c_bytes = al(c_tcnt + n_seg * n_entry * 4);
-  SCHK(hipSetDevice(s->device));
-  int rc = grow(&s->det_tab, &s->cap_det_tab, bytes);
-  if (!rc) rc = grow(&s->det_cand, &s->cap_det_cand, c_bytes);
-  if (rc) return rc;
-  std::vector<char> h((size_t)o_in_end, 0);
-  std::memcpy(&h[o_off], offsets, (size_t)(n_tracks + 1) * 8);
-  if (kind) std::memcpy(&h[o_kind], kind, (size_t)n_tracks * 4);
-  std::memcpy(&h[o_sf], seg_first.data(), (size_t)(n_tracks + 1) * 4);
-  SCHK(hipMemcpyAsync(s->det_tab, h.data(), (size_t)o_in_end, hipMemcpyHostToDevice, s->stream));
+  if (int rc = post_check_tracks(s, offsets, kind, n_tracks, window > 0 && skip >= 0 && cooldown >= 0, "bad detection arguments", true)) return rc;
+  PostPlan plan;
+  if (int rc = post_plan(offsets, kind, n_tracks, skip, window, false, &plan)) return rc;
+  const int64_t n_seg = plan.n_seg;
+  const int cdp = std::max(cooldown, 1), n_entry = std::min(cdp, POST_SEG);
   DetArgs a{};
+  // inputs, per-track results, per-segment results: one table
+  PostTable tab;
+  tab.add(&a.off, n_tracks + 1, offsets);
+  tab.add(&a.kind, n_tracks, kind);
+  tab.add(&a.seg_first, n_tracks + 1, plan.seg_first.data());
+  tab.end_host();
+  tab.add(&a.trk_count, n_tracks);
+  tab.add(&a.trk_base, n_tracks + 1);
+  tab.add(&a.trk_bidx, n_tracks);
+  tab.add(&a.trk_score, n_tracks);
+  tab.add(&a.seg_ncand, n_seg);
+  tab.add(&a.seg_entry, n_seg);
+  tab.add(&a.seg_base, n_seg);
+  tab.add(&a.seg_best, n_seg);
+  tab.add(&a.seg_bidx, n_seg);
+  // candidates and transfer tables: sized from this call's segments and cooldown
+  PostTable scr;
+  scr.add(&a.cand, n_seg * POST_SEG);
+  scr.add(&a.tab_exit, n_seg * n_entry);
+  scr.add(&a.tab_cnt, n_seg * n_entry);
+  SCHK(hipSetDevice(s->device));
+  int rc = tab.commit(&s->post_tab, &s->cap_post_tab, s->stream);
+  if (!rc) rc = scr.commit(&s->post_scr, &s->cap_post_scr, s->stream);
+  if (rc) return rc;
   a.prob = s->prob;
-  a.off = reinterpret_cast<const int64_t*>(s->det_tab + o_off);
-  a.kind = reinterpret_cast<const int*>(s->det_tab + o_kind);
-  a.seg_first = reinterpret_cast<const int*>(s->det_tab + o_sf);
   a.n_trk = (int)n_tracks;
   a.n_seg = (int)n_seg;
   a.win = window;
@@ -343,18 +307,6 @@ inline int det_locate(mww_stream* s, const int64_t* offsets, const int32_t* kind
   a.first_ok = std::max(cooldown - 1, 0);
   a.n_entry = n_entry;
   a.cutoff = cutoff;
-  a.cand = reinterpret_cast<unsigned short*>(s->det_cand + c_cand);
-  a.tab_exit = reinterpret_cast<int*>(s->det_cand + c_exit);
-  a.tab_cnt = reinterpret_cast<int*>(s->det_cand + c_tcnt);
-  a.seg_ncand = reinterpret_cast<int*>(s->det_tab + o_nc);
-  a.seg_entry = reinterpret_cast<int*>(s->det_tab + o_ent);
-  a.seg_base = reinterpret_cast<int64_t*>(s->det_tab + o_sbase);
-  a.seg_best = reinterpret_cast<float*>(s->det_tab + o_sbest);
-  a.seg_bidx = reinterpret_cast<int64_t*>(s->det_tab + o_sbidx);
-  a.trk_count = reinterpret_cast<int64_t*>(s->det_tab + o_cnt);
-  a.trk_base = reinterpret_cast<int64_t*>(s->det_tab + o_base);
-  a.trk_bidx = reinterpret_cast<int64_t*>(s->det_tab + o_bidx);
-  a.trk_score = reinterpret_cast<float*>(s->det_tab + o_sc);
   a.out = nullptr;
   a.capacity = 0;
   if (n_seg) {

@@ -1,4 +1,4 @@
-// Streaming inference and detection metrics (mww_stream_*, include/mww.h): the evaluation that follows training in the
+// Streaming inference (mww_stream_*, include/mww.h): the evaluation that follows training in the
 // reference (model_train_eval.py:131-272 evaluate_model -> test.py:293-403 tflite_streaming_model_roc, inference.py:82-125
 // Model.predict_spectrogram), computed from the HBM-resident feature stores of a context.
 //
@@ -19,10 +19,12 @@
 // stream read the layers' rings instead.  The tile that ends the call also writes the final rings (double-buffered
 // state, so no tile reads a ring another tile writes).  Every sum runs in a fixed order: no atomics, runs are bit-identical.
 //
-// Here: the float MixedNet kernel and the float half of the MixedNet model part (Keras-order weight folding, launch), the
-// detection-metrics kernels, and the host path of EVERY stream - creation, reset, the float and the int8 launch epilogue,
-// calibration, mww_stream_set_quantized - written once against SModel (stream_common.hip.h); the conv/BN graph model part
-// and its two creators are tu_stream_graph.hip / tu_stream_graph_q8.hip.  A MixedNet with residual connections, a pooled head or
+// Here: the float MixedNet kernel and the float half of the MixedNet model part (Keras-order weight folding, launch), and
+// the host path of EVERY stream - creation, reset, the float and the int8 launch epilogue, calibration,
+// mww_stream_set_quantized - written once against SModel (stream_common.hip.h); the conv/BN graph model part and its two
+// creators are tu_stream_graph.hip / tu_stream_graph_q8.hip.  What is computed FROM the probabilities a stream holds - the
+// detection metrics (mww_stream_metrics), the operating-point grid, detections, mining - is tu_stream_oppoints.hip,
+// tu_stream_detect.hip and tu_stream_mine.hip over stream_post.hip.h.  A MixedNet with residual connections, a pooled head or
 // spatial attention (mww_stream_create_mixednet) is the same model part with three more plan inputs and the <VAR> form of the
 // kernel below; a plain plan runs the form without VAR.
 #include <hip/hip_runtime.h>
@@ -297,62 +299,6 @@ __global__ void __launch_bounds__(kStreamThreads) stream_forward_kernel(SNet net
   if (REC) rec_flush(a, rmin, rmax);
 }
 
-// Detection metrics (test.py:94-137 compute_false_accepts_per_hour, :329-376).  One workgroup per track: thread j < n_cut
-// scans the ambient track's moving average sequentially with the cooldown of cutoff j; one thread takes the positive
-// track's score.  Moving average: float32, summed in order then divided (numpy .mean of the float32 sliding window).
-__global__ void __launch_bounds__(128) stream_metrics_kernel(const float* prob, const int64_t* off, const int* kind, int n_trk,
-                                                             int win, int skip, int cooldown, const double* cut, int n_cut,
-                                                             unsigned long long* counts, int64_t* ma_len, float* score) {
-  const int t = blockIdx.x;
-  if (t >= n_trk) return;
-  const int j = threadIdx.x;
-  const int64_t b = off[t], n = off[t + 1] - off[t];
-  if (kind[t] == 0) {
-    const int64_t m = n >= win ? n - win + 1 : 0;
-    if (j == 0) { ma_len[t] = m; score[t] = 0.f; }
-    if (j < n_cut) {
-      const double c = cut[j];
-      int cd = cooldown;
-      unsigned long long fa = 0;
-      for (int64_t i = 0; i < m; ++i) {
-        float s = 0.f;
-        for (int k = 0; k < win; ++k) s += prob[b + i + k];
-        const float avg = s / (float)win;
-        cd = cd > 0 ? cd - 1 : 0;
-        if (cd == 0 && (double)avg > c) {
-          ++fa;
-          cd = cooldown;
-        }
-      }
-      counts[(int64_t)t * n_cut + j] = fa;
-    }
-  } else {
-    if (j < n_cut) counts[(int64_t)t * n_cut + j] = 0;
-    if (j == 0) {
-      const int64_t r = n > skip ? n - skip : 0;
-      const int64_t m = r >= win ? r - win + 1 : 0;
-      float best = -INFINITY;
-      for (int64_t i = 0; i < m; ++i) {
-        float s = 0.f;
-        for (int k = 0; k < win; ++k) s += prob[b + skip + i + k];
-        const float avg = s / (float)win;
-        best = avg > best ? avg : best;
-      }
-      ma_len[t] = m;
-      score[t] = best;
-    }
-  }
-}
-
-// per-cutoff sum over the tracks, in track order
-__global__ void stream_counts_sum_kernel(const unsigned long long* counts, int n_trk, int n_cut, unsigned long long* total) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n_cut) return;
-  unsigned long long s = 0;
-  for (int t = 0; t < n_trk; ++t) s += counts[(int64_t)t * n_cut + j];
-  total[j] = s;
-}
-
 }  // namespace
 
 // ---- MixedNet, float half of the model part (tu_stream_q8.hip has the int8 half)
@@ -597,8 +543,8 @@ void mww_stream_destroy(mww_stream* s) {
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (void* p : {(void*)s->w, (void*)s->st[0], (void*)s->st[1], (void*)s->prob, (void*)s->logit, (void*)s->scratch,
-                  (void*)s->tables, (void*)s->host_frames, (void*)s->mtab, (void*)s->rec,
-                  (void*)s->det_tab, (void*)s->det_cand, (void*)s->det_out, (void*)s->mine_buf, (void*)s->op_tab, (void*)s->op_scr})
+                  (void*)s->tables, (void*)s->host_frames, (void*)s->rec,
+                  (void*)s->post_tab, (void*)s->post_scr, (void*)s->det_out, (void*)s->mine_buf})
     if (p) (void)hipFree(p);
   q8_free(s);
   delete s->model;
@@ -774,43 +720,6 @@ int mww_stream_get_state_q8(mww_stream* s, int8_t* h, int64_t n) {
   if (!s || !s->q8 || !h || n != s->model->n_state) return mww::set_error(MWW_ERR_INVALID, "state size mismatch (or no int8 parameters)");
   SCHK(hipSetDevice(s->device));
   SCHK(hipMemcpyAsync(h, s->q8_st[s->q8_cur], (size_t)n, hipMemcpyDeviceToHost, s->stream));
-  SCHK(hipStreamSynchronize(s->stream));
-  return MWW_OK;
-}
-
-int mww_stream_metrics(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip,
-                       int cooldown, const double* cutoffs, int n_cutoffs, uint64_t* counts, int64_t* ma_len, float* score) {
-  if (!s || !offsets || !kind || !cutoffs || !counts || !ma_len || !score) return mww::set_error(MWW_ERR_INVALID, "null argument");
-  if (n_tracks <= 0 || n_tracks > INT32_MAX || window <= 0 || skip < 0 || cooldown < 0 || n_cutoffs <= 0 || n_cutoffs > 128)
-    return mww::set_error(MWW_ERR_INVALID, "bad metric arguments (1..128 cutoffs)");
-  if (offsets[0] < 0 || offsets[n_tracks] > s->n_out) return mww::set_error(MWW_ERR_INVALID, "track offsets exceed the probabilities held");
-  for (int64_t t = 0; t < n_tracks; ++t)
-    if (offsets[t + 1] < offsets[t]) return mww::set_error(MWW_ERR_INVALID, "track offsets must not decrease");
-  auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-  const int64_t o_off = 0, o_kind = al((n_tracks + 1) * 8), o_cut = al(o_kind + n_tracks * 4), o_cnt = al(o_cut + n_cutoffs * 8),
-                o_len = al(o_cnt + n_tracks * n_cutoffs * 8), o_sc = al(o_len + n_tracks * 8), o_tot = al(o_sc + n_tracks * 4),
-                bytes = al(o_tot + n_cutoffs * 8);
-  SCHK(hipSetDevice(s->device));
-  int rc = grow(&s->mtab, &s->cap_mtab, bytes);
-  if (rc) return rc;
-  std::vector<char> h((size_t)o_cnt, 0);
-  std::memcpy(&h[o_off], offsets, (size_t)(n_tracks + 1) * 8);
-  std::memcpy(&h[o_kind], kind, (size_t)n_tracks * 4);
-  std::memcpy(&h[o_cut], cutoffs, (size_t)n_cutoffs * 8);
-  SCHK(hipMemcpyAsync(s->mtab, h.data(), (size_t)o_cnt, hipMemcpyHostToDevice, s->stream));
-  auto* cnt = reinterpret_cast<unsigned long long*>(s->mtab + o_cnt);
-  auto* len = reinterpret_cast<int64_t*>(s->mtab + o_len);
-  auto* sc = reinterpret_cast<float*>(s->mtab + o_sc);
-  auto* tot = reinterpret_cast<unsigned long long*>(s->mtab + o_tot);
-  hipLaunchKernelGGL(stream_metrics_kernel, dim3((unsigned)n_tracks), dim3(128), 0, s->stream, (const float*)s->prob,
-                     reinterpret_cast<const int64_t*>(s->mtab + o_off), reinterpret_cast<const int*>(s->mtab + o_kind), (int)n_tracks,
-                     window, skip, cooldown, reinterpret_cast<const double*>(s->mtab + o_cut), n_cutoffs, cnt, len, sc);
-  SCHK(hipGetLastError());
-  hipLaunchKernelGGL(stream_counts_sum_kernel, dim3(1), dim3(128), 0, s->stream, (const unsigned long long*)cnt, (int)n_tracks, n_cutoffs, tot);
-  SCHK(hipGetLastError());
-  SCHK(hipMemcpyAsync(counts, tot, (size_t)n_cutoffs * 8, hipMemcpyDeviceToHost, s->stream));
-  SCHK(hipMemcpyAsync(ma_len, len, (size_t)n_tracks * 8, hipMemcpyDeviceToHost, s->stream));
-  SCHK(hipMemcpyAsync(score, sc, (size_t)n_tracks * 4, hipMemcpyDeviceToHost, s->stream));
   SCHK(hipStreamSynchronize(s->stream));
   return MWW_OK;
 }

@@ -1,4 +1,5 @@
-// mww_stream_detections (include/mww.h): the launches are in stream_detect.hip.h, shared with tu_stream_mine.hip.
+// mww_stream_detections (include/mww.h): the launches are in stream_detect.hip.h, shared with tu_stream_mine.hip; what
+// they share with the metric entry points of tu_stream_oppoints.hip is stream_post.hip.h.
 #include "stream_detect.hip.h"
 
 extern "C" {

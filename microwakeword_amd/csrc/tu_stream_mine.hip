@@ -1,6 +1,7 @@
 // mww_stream_mine (include/mww.h): the hard negatives of one mining round, selected and cut into clips on the device.
 //
-// The events come from the launches of stream_detect.hip.h (every track ambient) and stay in s->det_out.  What follows keeps
+// The events come from the launches of stream_detect.hip.h (every track ambient) and stay in s->det_out; the tables of this
+// unit are packed by stream_post.hip.h's PostTable into s->mine_buf.  What follows keeps
 // the `max_new` highest moving averages (ties to the earlier event), drops the clips without a row and writes the rest in event
 // order - the chain mww_stream_detections -> stable argsort -> streaming.detection_clips, byte for byte:
 //   mine_hist_kernel   x 4  radix select of the max_new-th largest key, 8 bits per launch, most significant first.  The key is
@@ -251,16 +252,17 @@ int64_t mww_stream_mine(mww_stream* s, const mww_window* tracks, const int64_t* 
   }
   if ((rc = det_events(s, &d, total))) return rc;
   const int64_t n_blk = (total + MINE_CHUNK - 1) / MINE_CHUNK, n_read = std::min(k, capacity);
-  auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
   // what the host reads back comes first: the count, the clips, the events
-  const int64_t o_kept = 0, o_clip = al(8), o_ev = al(o_clip + n_read * (int64_t)sizeof(mww_window)),
-                o_read_end = al(o_ev + n_read * (int64_t)sizeof(mww_detection)), o_hist = o_read_end,
-                o_ties = al(o_hist + MINE_PASSES * 256 * 4), o_keep = al(o_ties + n_blk * 4), o_trk = al(o_keep + n_blk * 4),
-                bytes = al(o_trk + n_tracks * (int64_t)sizeof(mww_window));
-  if ((rc = grow(&s->mine_buf, &s->cap_mine_buf, bytes))) return rc;
   MineArgs a{};
+  PostTable tab;
+  const int64_t kept_at = tab.add(&a.n_kept, 1), clip_at = tab.add(&a.out_clip, n_read), ev_at = tab.add(&a.out_ev, n_read);
+  const int64_t read_end = tab.size;
+  tab.add(&a.hist, MINE_PASSES * 256);
+  tab.add(&a.blk_ties, n_blk);
+  tab.add(&a.blk_keep, n_blk);
+  tab.add(&a.trk, n_tracks);
+  if ((rc = tab.commit(&s->mine_buf, &s->cap_mine_buf, s->stream))) return rc;
   a.ev = s->det_out;
-  a.trk = reinterpret_cast<const mww_window*>(s->mine_buf + o_trk);
   a.n_ev = (int)total;
   a.n_blk = (int)n_blk;
   a.select = k < total ? 1 : 0;
@@ -271,14 +273,8 @@ int64_t mww_stream_mine(mww_stream* s, const mww_window* tracks, const int64_t* 
   a.stream_mode = g.mode == MWW_STREAM_MODE_STREAM ? 1 : 0;
   a.before = before;
   a.after = after;
-  a.hist = reinterpret_cast<unsigned*>(s->mine_buf + o_hist);
-  a.blk_ties = reinterpret_cast<int*>(s->mine_buf + o_ties);
-  a.blk_keep = reinterpret_cast<int*>(s->mine_buf + o_keep);
-  a.n_kept = reinterpret_cast<long long*>(s->mine_buf + o_kept);
-  a.out_clip = reinterpret_cast<mww_window*>(s->mine_buf + o_clip);
-  a.out_ev = reinterpret_cast<mww_detection*>(s->mine_buf + o_ev);
   a.capacity = n_read;
-  SCHK(hipMemcpyAsync(s->mine_buf + o_trk, tracks, (size_t)n_tracks * sizeof(mww_window), hipMemcpyHostToDevice, s->stream));
+  SCHK(hipMemcpyAsync(const_cast<mww_window*>(a.trk), tracks, (size_t)n_tracks * sizeof(mww_window), hipMemcpyHostToDevice, s->stream));
   const dim3 grid((unsigned)n_blk), block(MINE_THREADS);
   if (a.select) {
     SCHK(hipMemsetAsync(a.hist, 0, MINE_PASSES * 256 * 4, s->stream));
@@ -294,16 +290,16 @@ int64_t mww_stream_mine(mww_stream* s, const mww_window* tracks, const int64_t* 
   hipLaunchKernelGGL(mine_compact_kernel<true>, grid, block, 0, s->stream, a);
   SCHK(hipGetLastError());
   // the kept clips and events (at most min(max_new, capacity) of each) and the per-track counts: never the event list
-  std::vector<char> h((size_t)o_read_end);
-  SCHK(hipMemcpyAsync(h.data(), s->mine_buf, (size_t)o_read_end, hipMemcpyDeviceToHost, s->stream));
+  std::vector<char> h((size_t)read_end);
+  SCHK(hipMemcpyAsync(h.data(), s->mine_buf, (size_t)read_end, hipMemcpyDeviceToHost, s->stream));
   SCHK(hipMemcpyAsync(track_count, d.trk_count, (size_t)n_tracks * 8, hipMemcpyDeviceToHost, s->stream));
   SCHK(hipStreamSynchronize(s->stream));
   long long kept = 0;
-  std::memcpy(&kept, &h[o_kept], 8);
+  std::memcpy(&kept, &h[(size_t)kept_at], 8);
   const int64_t n_copy = std::min<int64_t>(kept, n_read);
   if (n_copy > 0) {
-    std::memcpy(clips, &h[o_clip], (size_t)n_copy * sizeof(mww_window));
-    std::memcpy(events, &h[o_ev], (size_t)n_copy * sizeof(mww_detection));
+    std::memcpy(clips, &h[(size_t)clip_at], (size_t)n_copy * sizeof(mww_window));
+    std::memcpy(events, &h[(size_t)ev_at], (size_t)n_copy * sizeof(mww_detection));
   }
   return kept;
 }

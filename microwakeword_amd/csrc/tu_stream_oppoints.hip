@@ -1,17 +1,29 @@
+// The metrics of the probabilities a stream holds: at one window (mww_stream_metrics), on a grid of windows
+// (mww_stream_operating_points) and the grid reduced on the device (mww_stream_operating_summary).  The moving average, the
+// values of a track, the segment plan, the track-table check and the table packing are those of stream_post.hip.h, shared
+// with the detection launches.
+//
+// mww_stream_metrics: test.py:94-137 compute_false_accepts_per_hour, :329-376.  The independent form the grid is
+// tested against, and deliberately the simple one:
+//   stream_metrics_kernel     one workgroup per track: thread j < n_cut scans the ambient track's moving average sequentially
+//                             with the cooldown of cutoff j; one thread takes the positive track's score.
+//   stream_counts_sum_kernel  one thread per cutoff: the tracks' counts summed in track order.
+//
 // mww_stream_operating_points (include/mww.h): the false-accept counts of every (window, cutoff) pair and the
 // positive scores of every window in one call, on the probabilities a stream holds.  Row k is mww_stream_metrics at windows[k].
 //
-// The cooldown walk is cut into segments of OP_SEG moving-average values, as in tu_stream_detect.hip, and the work is parallel
+// The cooldown walk is cut into segments of POST_SEG moving-average values, as in stream_detect.hip.h, and the work is parallel
 // over (segment, window):
-//   op_segment_kernel  one workgroup per (segment, window): stages the OP_SEG + w - 1 probabilities in LDS once, forms the
+//   op_segment_kernel  one workgroup per (segment, window): stages the POST_SEG + w - 1 probabilities in LDS once, forms the
 //                      averages there (the expression of the metrics kernel), and thread j < n_cutoffs builds cutoff j's
 //                      transfer table from them: entry state e (next_ok - segment start) -> (accepts, last accepted offset).
 //                      One BACKWARD sweep serves all entry states: F(i), the walk that enters with next_ok = i, is
 //                      F(i + 1) when i is no candidate and 1 + F(i + cdp) when it is, so a ring of cdp slots (slot i mod cdp
 //                      holds F(i + cdp) until F(i) replaces it) ends holding F(0 .. cdp - 1): the table.  A positive track's
 //                      segment reduces its maximum instead.
-//   op_track_kernel    one thread per (track, window, cutoff): composes the tables in segment order, one dependent load per
-//                      segment; thread 0 of a (track, window) takes the length and the positive score (segments in order).
+//   op_track_kernel    one thread per (track, window, cutoff): composes the tables in segment order (op_compose), one
+//                      dependent load per segment; thread 0 of a (track, window) takes the length and the positive score
+//                      (op_score: the segments' maxima in order).
 //   op_sum_kernel      one thread per (window, cutoff): the tracks' counts summed in track order.
 // The tables of `pw` windows are resident at a time (OP_SCRATCH bytes at most, one window at least): the windows run in passes.
 // Nothing depends on an arrival order, so two calls write the same bytes.
@@ -20,35 +32,78 @@
 // per (window, cutoff) the ambient count and the number of positive tracks accepted, per window the ambient hours and the
 // tracks without a value.  It shares op_segment_kernel; the tables have rows for the ambient tracks' segments alone (tab_first:
 // a positive track's segment only reduces its maximum), so their size does not grow with the positives.  What follows differs:
-//   ops_ambient_kernel   op_track_kernel's walk for the kind-0 tracks alone: one thread per (ambient track, window, cutoff),
+//   ops_ambient_kernel   op_compose for the kind-0 tracks alone: one thread per (ambient track, window, cutoff),
 //                        count rows [W][n_ambient][C].  A positive track has no thread and no row here.
-//   ops_positive_kernel  one workgroup per (OPS_POS positive tracks, window): thread i takes track i's score (its segments'
-//                        maxima in order) into LDS, then thread c counts the scores above cutoff c: an integer partial per
-//                        (window, workgroup, cutoff), and the workgroup's tracks without a value.
+//   ops_positive_kernel  one workgroup per (OPS_POS positive tracks, window): thread i takes track i's score (op_score) into
+//                        LDS, then thread c counts the scores above cutoff c: an integer partial per (window, workgroup,
+//                        cutoff), and the workgroup's tracks without a value.
 //   ops_final_kernel     one thread per (window, cutoff) sums the ambient rows in track order and the partials in workgroup
 //                        order; one thread per window walks the ambient tracks in order for the hours (float64: product,
 //                        division, add, uncontracted) and the short-track counts.
 // Every sum is an integer sum in a fixed order (no atomics), the hours a serial float64 sum: two calls write the same bytes.
 // The host reads back the result block alone: W * C * 16 + W * 24 + 16 bytes.
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "stream_common.hip.h"
-
-using namespace mww_stream_impl;
+//
+// Both grid entry points are an OpCall: begin() checks, plans and packs the common inputs, the entry point adds the sections
+// that are its own, commit() uploads and fills OpArgs, passes() runs op_segment_kernel and the entry point's launches per pass.
+#include "stream_post.hip.h"
 
 namespace {
 
 constexpr int OP_THREADS = 128;                     // >= the 128 cutoffs of a call: one thread per cutoff
-constexpr int OP_SEG = 1024;                        // moving-average values per segment (tests/operating_point_checks.py names it)
-constexpr int OP_CNT_BITS = 11;                     // a table entry: accepts (<= OP_SEG) | last accepted offset << OP_CNT_BITS
+constexpr int OP_CNT_BITS = 11;                     // a table entry: accepts (<= POST_SEG) | last accepted offset << OP_CNT_BITS
+static_assert(OP_THREADS >= POST_MAX_CUTOFFS && POST_SEG < (1 << OP_CNT_BITS), "a thread per cutoff; a count fits its bits");
 constexpr int64_t OP_SCRATCH = (int64_t)96 << 20;   // transfer tables resident at a time
 constexpr int OP_RING_LDS = 32 * 1024;              // a ring of n_cutoffs * n_entry words up to this size lives in LDS
 constexpr int OPS_POS = 256;                        // positive tracks per workgroup of ops_positive_kernel (>= the 128 cutoffs)
 
+// ---- mww_stream_metrics: one workgroup per track, a sequential scan per cutoff
+__global__ void __launch_bounds__(128) stream_metrics_kernel(const float* prob, const int64_t* off, const int* kind, int n_trk,
+                                                             int win, int skip, int cooldown, const double* cut, int n_cut,
+                                                             unsigned long long* counts, int64_t* ma_len, float* score) {
+  const int t = blockIdx.x;
+  if (t >= n_trk) return;
+  const int j = threadIdx.x;
+  const PostValues v = post_values(off, kind, skip, t, win);
+  const float* p = prob + v.b;
+  const int64_t m = v.m;
+  if (kind[t] == 0) {
+    if (j == 0) { ma_len[t] = m; score[t] = 0.f; }
+    if (j < n_cut) {
+      const double c = cut[j];
+      int cd = cooldown;
+      unsigned long long fa = 0;
+      for (int64_t i = 0; i < m; ++i) {
+        const float avg = post_avg(p + i, win);
+        cd = cd > 0 ? cd - 1 : 0;
+        if (cd == 0 && (double)avg > c) {
+          ++fa;
+          cd = cooldown;
+        }
+      }
+      counts[(int64_t)t * n_cut + j] = fa;
+    }
+  } else {
+    if (j < n_cut) counts[(int64_t)t * n_cut + j] = 0;
+    if (j == 0) {
+      float best = -INFINITY;
+      for (int64_t i = 0; i < m; ++i) {
+        const float avg = post_avg(p + i, win);
+        best = avg > best ? avg : best;
+      }
+      ma_len[t] = m;
+      score[t] = best;
+    }
+  }
+}
+
+// per-cutoff sum over the tracks, in track order
+__global__ void stream_counts_sum_kernel(const unsigned long long* counts, int n_trk, int n_cut, unsigned long long* total) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_cut) return;
+  total[j] = post_sum_rows(counts + j, n_trk, n_cut);
+}
+
+// ---- mww_stream_operating_points
 struct OpArgs {
   const float* prob;
   const int64_t* off;        // [n_trk + 1]
@@ -61,7 +116,7 @@ struct OpArgs {
   int skip;
   int cdp;                   // max(cooldown, 1): distance from an accept to the next index that may be accepted
   int first_ok;              // max(cooldown - 1, 0): the first index of a track that may be accepted
-  int n_entry;               // min(cdp, OP_SEG): entry states a segment tabulates = slots of the ring
+  int n_entry;               // min(cdp, POST_SEG): entry states a segment tabulates = slots of the ring
   int w0, pw;                // this pass: windows w0 .. w0 + pw - 1
   int ring_lds;              // the ring is in LDS (else it is the table itself)
   unsigned* tab;             // [table rows][pw][n_entry][n_cut]
@@ -72,45 +127,55 @@ struct OpArgs {
   unsigned long long* total; // [n_win][n_cut]
 };
 
-// track of segment `seg`: the last t with seg_first[t] <= seg (tracks without a segment share their successor's entry)
-__device__ __forceinline__ int op_track_of(const int* seg_first, int n_trk, int seg) {
-  int lo = 0, hi = n_trk;   // seg_first[lo] <= seg < seg_first[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (seg_first[mid] <= seg) lo = mid; else hi = mid;
+// moving-average values of track t at window index wi
+__device__ __forceinline__ int64_t op_len(const OpArgs& a, int t, int wi) { return post_values(a.off, a.kind, a.skip, t, a.win[wi]).m; }
+
+// An ambient track's count at pass window wk and cutoff c: the transfer tables of its `n_rows` segments from table row `row0`
+// composed in order, one dependent load per segment.
+__device__ __forceinline__ unsigned long long op_compose(const OpArgs& a, int row0, int n_rows, int wk, int c) {
+  unsigned long long total = 0;
+  int64_t state = a.first_ok;
+  for (int s = row0; s < row0 + n_rows; ++s) {
+    if (state >= POST_SEG) {   // still cooling down beyond this segment
+      state -= POST_SEG;
+      continue;
+    }
+    const unsigned v = a.tab[(((int64_t)s * a.pw + wk) * a.n_entry + state) * a.n_cut + c];
+    const unsigned cnt = v & ((1u << OP_CNT_BITS) - 1);
+    total += cnt;
+    const int64_t next = cnt ? (int64_t)(v >> OP_CNT_BITS) + a.cdp : state;
+    state = next > POST_SEG ? next - POST_SEG : 0;
   }
-  return lo;
+  return total;
 }
 
-// moving-average values of track t at window w (after the skip of a positive track); *b: its first probability
-__device__ __forceinline__ int64_t op_values(const OpArgs& a, int t, int w, int64_t* b) {
-  const int64_t sk = a.kind[t] ? a.skip : 0;
-  const int64_t n = a.off[t + 1] - a.off[t] - sk;
-  *b = a.off[t] + sk;
-  return n >= w ? n - w + 1 : 0;
+// A positive track's score at window wi: the maxima of its `n` segments from segment s0, in order; no value: -inf
+__device__ __forceinline__ float op_score(const OpArgs& a, int wi, int s0, int n) {
+  float best = -INFINITY;
+  for (int s = s0; s < s0 + n; ++s) {
+    const float v = a.seg_best[(int64_t)wi * a.n_seg + s];
+    best = v > best ? v : best;
+  }
+  return best;
 }
 
 __global__ void __launch_bounds__(OP_THREADS) op_segment_kernel(OpArgs a) {
-  __shared__ float s_p[OP_SEG + MWW_OP_MAX_WINDOW - 1];
-  __shared__ float s_avg[OP_SEG];
+  __shared__ float s_p[POST_SEG + MWW_OP_MAX_WINDOW - 1];
+  __shared__ float s_avg[POST_SEG];
   __shared__ float s_best[OP_THREADS];
   HIP_DYNAMIC_SHARED(unsigned, s_ring)
   const int seg = blockIdx.x, wk = blockIdx.y, j = threadIdx.x;
   const int w = a.win[a.w0 + wk];
-  const int t = op_track_of(a.seg_first, a.n_trk, seg);
-  int64_t b;
-  const int64_t m = op_values(a, t, w, &b);
-  const int64_t i0 = (int64_t)(seg - a.seg_first[t]) * OP_SEG;
+  const int t = post_track_of(a.seg_first, a.n_trk, seg);
+  const PostValues tv = post_values(a.off, a.kind, a.skip, t, w);
+  const int64_t b = tv.b, m = tv.m;
+  const int64_t i0 = (int64_t)(seg - a.seg_first[t]) * POST_SEG;
   if (m <= i0) return;   // this window has fewer segments than the smallest one (uniform over the workgroup)
-  const int len = (int)(m - i0 < OP_SEG ? m - i0 : OP_SEG);
+  const int len = (int)(m - i0 < POST_SEG ? m - i0 : POST_SEG);
   const float* p = a.prob + b + i0;
   for (int q = j; q < len + w - 1; q += OP_THREADS) s_p[q] = p[q];   // ends at the track's last probability
   __syncthreads();
-  for (int q = j; q < len; q += OP_THREADS) {   // the moving average of mww_stream_metrics: float32 sum in order, one division
-    float s = 0.f;
-    for (int k = 0; k < w; ++k) s += s_p[q + k];
-    s_avg[q] = s / (float)w;
-  }
+  for (int q = j; q < len; q += OP_THREADS) s_avg[q] = post_avg(s_p + q, w);
   __syncthreads();
   if (a.kind[t] != 0) {
     float best = -INFINITY;
@@ -150,35 +215,13 @@ __global__ void __launch_bounds__(256) op_track_kernel(OpArgs a) {
   if (id >= (int64_t)a.n_trk * a.pw * a.n_cut) return;
   const int c = (int)(id % a.n_cut), wk = (int)(id / a.n_cut % a.pw), t = (int)(id / a.n_cut / a.pw);
   const int wi = a.w0 + wk;
-  int64_t b;
-  const int64_t m = op_values(a, t, a.win[wi], &b);
-  const int s0 = a.seg_first[t], s1 = s0 + (int)((m + OP_SEG - 1) / OP_SEG);
+  const int64_t m = op_len(a, t, wi);
+  const int n_segs = (int)((m + POST_SEG - 1) / POST_SEG);
   const bool positive = a.kind[t] != 0;
-  unsigned long long total = 0;
-  if (!positive) {
-    int64_t state = a.first_ok;
-    for (int s = s0; s < s1; ++s) {
-      if (state >= OP_SEG) {   // still cooling down beyond this segment
-        state -= OP_SEG;
-        continue;
-      }
-      const unsigned v = a.tab[(((int64_t)s * a.pw + wk) * a.n_entry + state) * a.n_cut + c];
-      const unsigned cnt = v & ((1u << OP_CNT_BITS) - 1);
-      total += cnt;
-      const int64_t next = cnt ? (int64_t)(v >> OP_CNT_BITS) + a.cdp : state;
-      state = next > OP_SEG ? next - OP_SEG : 0;
-    }
-  }
-  a.trk_cnt[((int64_t)wi * a.n_trk + t) * a.n_cut + c] = total;
+  a.trk_cnt[((int64_t)wi * a.n_trk + t) * a.n_cut + c] = positive ? 0ull : op_compose(a, a.tab_first[t], n_segs, wk, c);
   if (c == 0) {
-    float best = positive ? -INFINITY : 0.f;
-    if (positive)
-      for (int s = s0; s < s1; ++s) {
-        const float v = a.seg_best[(int64_t)wi * a.n_seg + s];
-        best = v > best ? v : best;
-      }
     a.ma_len[(int64_t)wi * a.n_trk + t] = m;
-    a.score[(int64_t)wi * a.n_trk + t] = best;
+    a.score[(int64_t)wi * a.n_trk + t] = positive ? op_score(a, wi, a.seg_first[t], n_segs) : 0.f;
   }
 }
 
@@ -187,9 +230,7 @@ __global__ void __launch_bounds__(256) op_sum_kernel(OpArgs a) {
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= a.pw * a.n_cut) return;
   const int c = id % a.n_cut, wi = a.w0 + id / a.n_cut;
-  unsigned long long s = 0;
-  for (int t = 0; t < a.n_trk; ++t) s += a.trk_cnt[((int64_t)wi * a.n_trk + t) * a.n_cut + c];
-  a.total[(int64_t)wi * a.n_cut + c] = s;
+  a.total[(int64_t)wi * a.n_cut + c] = post_sum_rows(a.trk_cnt + (int64_t)wi * a.n_trk * a.n_cut + c, a.n_trk, a.n_cut);
 }
 
 // ---- mww_stream_operating_summary
@@ -209,29 +250,14 @@ struct OpsArgs {
   int64_t* n_kind;               // [2]
 };
 
-// op_track_kernel's walk, for the ambient tracks alone
+// op_compose for the ambient tracks alone: count rows [W][n_ambient][C]
 __global__ void __launch_bounds__(256) ops_ambient_kernel(OpArgs a, OpsArgs o) {
   const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (int64_t)o.n_amb * a.pw * a.n_cut) return;
   const int c = (int)(id % a.n_cut), wk = (int)(id / a.n_cut % a.pw), j = (int)(id / a.n_cut / a.pw);
   const int wi = a.w0 + wk, t = o.amb[j];
-  int64_t b;
-  const int64_t m = op_values(a, t, a.win[wi], &b);
-  const int s0 = a.tab_first[t], s1 = s0 + (int)((m + OP_SEG - 1) / OP_SEG);   // table rows: a positive track has none
-  unsigned long long total = 0;
-  int64_t state = a.first_ok;
-  for (int s = s0; s < s1; ++s) {
-    if (state >= OP_SEG) {   // still cooling down beyond this segment
-      state -= OP_SEG;
-      continue;
-    }
-    const unsigned v = a.tab[(((int64_t)s * a.pw + wk) * a.n_entry + state) * a.n_cut + c];
-    const unsigned cnt = v & ((1u << OP_CNT_BITS) - 1);
-    total += cnt;
-    const int64_t next = cnt ? (int64_t)(v >> OP_CNT_BITS) + a.cdp : state;
-    state = next > OP_SEG ? next - OP_SEG : 0;
-  }
-  o.amb_cnt[((int64_t)wi * o.n_amb + j) * a.n_cut + c] = total;
+  const int n_segs = (int)((op_len(a, t, wi) + POST_SEG - 1) / POST_SEG);
+  o.amb_cnt[((int64_t)wi * o.n_amb + j) * a.n_cut + c] = op_compose(a, a.tab_first[t], n_segs, wk, c);   // table rows: a positive track has none
 }
 
 __global__ void __launch_bounds__(OPS_POS) ops_positive_kernel(OpArgs a, OpsArgs o) {
@@ -242,15 +268,8 @@ __global__ void __launch_bounds__(OPS_POS) ops_positive_kernel(OpArgs a, OpsArgs
   const int n = o.n_pos - first < OPS_POS ? o.n_pos - first : OPS_POS;
   if (i < n) {
     const int t = o.pos[first + i];
-    int64_t b;
-    const int64_t m = op_values(a, t, a.win[wi], &b);
-    const int s0 = a.seg_first[t], s1 = s0 + (int)((m + OP_SEG - 1) / OP_SEG);
-    float best = -INFINITY;   // the score of op_track_kernel: the segments in order; no value: -inf
-    for (int s = s0; s < s1; ++s) {
-      const float v = a.seg_best[(int64_t)wi * a.n_seg + s];
-      best = v > best ? v : best;
-    }
-    s_score[i] = best;
+    const int64_t m = op_len(a, t, wi);
+    s_score[i] = op_score(a, wi, a.seg_first[t], (int)((m + POST_SEG - 1) / POST_SEG));
     s_short[i] = m == 0;
   }
   __syncthreads();
@@ -272,10 +291,9 @@ __global__ void __launch_bounds__(256) ops_final_kernel(OpArgs a, OpsArgs o) {
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= a.pw * a.n_cut) return;
   const int c = id % a.n_cut, wi = a.w0 + id / a.n_cut;
-  unsigned long long cnt = 0, acc = 0;
-  for (int j = 0; j < o.n_amb; ++j) cnt += o.amb_cnt[((int64_t)wi * o.n_amb + j) * a.n_cut + c];
+  unsigned long long acc = 0;
   for (int b = 0; b < o.n_pblk; ++b) acc += o.part_acc[((int64_t)wi * o.n_pblk + b) * a.n_cut + c];
-  o.counts[(int64_t)wi * a.n_cut + c] = cnt;
+  o.counts[(int64_t)wi * a.n_cut + c] = post_sum_rows(o.amb_cnt + (int64_t)wi * o.n_amb * a.n_cut + c, o.n_amb, a.n_cut);
   o.accepts[(int64_t)wi * a.n_cut + c] = acc;
   if (c != 0) return;
   // streaming.track_hours: h += ((n * stride) * step_s) / 3600.0 in track order, three separate float64 operations
@@ -283,8 +301,7 @@ __global__ void __launch_bounds__(256) ops_final_kernel(OpArgs a, OpsArgs o) {
   int64_t short_amb = 0, short_pos = 0;
   for (int j = 0; j < o.n_amb; ++j) {
 #pragma clang fp contract(off)
-    int64_t b;
-    const int64_t m = op_values(a, o.amb[j], a.win[wi], &b);
+    const int64_t m = op_len(a, o.amb[j], wi);
     const double prod = (double)(m * (int64_t)o.stride) * o.step_s;
     const double quot = prod / 3600.0;
     h = h + quot;
@@ -300,120 +317,147 @@ __global__ void __launch_bounds__(256) ops_final_kernel(OpArgs a, OpsArgs o) {
   }
 }
 
-// what both entry points check and derive from their arguments (after the null-pointer check)
-struct OpPlan {
-  std::vector<int32_t> seg_first;   // [n_tracks + 1]
-  std::vector<int32_t> tab_first;   // [n_tracks + 1] with ambient_tables: the first table row of each track, kind-1 tracks taking none
-  int64_t n_seg, per_window;        // segments of the smallest window; bytes of one window's transfer tables
-  int cdp, n_entry, pw;             // pw: windows per pass
-};
+// What the two grid entry points share, in the order a call goes through it.
+struct OpCall {
+  PostPlan plan;
+  PostTable tab;
+  OpArgs a{};
+  int n_windows = 0, pw = 0;   // pw: windows per pass
+  int64_t per_window = 0;      // bytes of one window's transfer tables
+  size_t lds = 0;              // of op_segment_kernel: the ring, when it fits
 
-int op_plan(const mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, const int32_t* windows, int n_windows,
-            int skip, int cooldown, int n_cutoffs, bool ambient_tables, OpPlan* p) {
-  if (n_tracks <= 0 || n_tracks > INT32_MAX || skip < 0 || cooldown < 0 || n_cutoffs <= 0 || n_cutoffs > 128)
-    return mww::set_error(MWW_ERR_INVALID, "bad operating-point arguments (1..128 cutoffs)");
-  if (n_windows <= 0 || n_windows > MWW_OP_MAX_WINDOWS)
-    return mww::set_error(MWW_ERR_INVALID, ("1.." + std::to_string(MWW_OP_MAX_WINDOWS) + " windows per call").c_str());
-  int wmin = MWW_OP_MAX_WINDOW;
-  for (int k = 0; k < n_windows; ++k) {
-    if (windows[k] <= 0 || windows[k] > MWW_OP_MAX_WINDOW)
-      return mww::set_error(MWW_ERR_INVALID, ("a window must lie in 1.." + std::to_string(MWW_OP_MAX_WINDOW)).c_str());
-    wmin = std::min(wmin, (int)windows[k]);
+  // checks the arguments (after the entry point's null check), plans the segments and the passes, and opens the table with
+  // the inputs both entry points have.  The entry point goes on with its own inputs, tab.end_host(), its result sections.
+  int begin(const mww_stream* s, const int64_t* offsets, const int32_t* knd, int64_t n_tracks, const int32_t* windows, int n_win,
+            int skip, int cooldown, const double* cutoffs, int n_cutoffs, bool ambient_tables) {
+    const std::string bad = "bad operating-point arguments (1.." + std::to_string(POST_MAX_CUTOFFS) + " cutoffs)";
+    if (n_tracks <= 0 || n_tracks > INT32_MAX || skip < 0 || cooldown < 0 || n_cutoffs <= 0 || n_cutoffs > POST_MAX_CUTOFFS)
+      return mww::set_error(MWW_ERR_INVALID, bad.c_str());
+    if (n_win <= 0 || n_win > MWW_OP_MAX_WINDOWS)
+      return mww::set_error(MWW_ERR_INVALID, ("1.." + std::to_string(MWW_OP_MAX_WINDOWS) + " windows per call").c_str());
+    int wmin = MWW_OP_MAX_WINDOW;
+    for (int k = 0; k < n_win; ++k) {
+      if (windows[k] <= 0 || windows[k] > MWW_OP_MAX_WINDOW)
+        return mww::set_error(MWW_ERR_INVALID, ("a window must lie in 1.." + std::to_string(MWW_OP_MAX_WINDOW)).c_str());
+      wmin = std::min(wmin, (int)windows[k]);
+    }
+    if (int rc = post_check_tracks(s, offsets, knd, n_tracks, true, bad, false)) return rc;
+    if (int rc = post_plan(offsets, knd, n_tracks, skip, wmin, ambient_tables, &plan)) return rc;   // the smallest window has the most segments
+    n_windows = n_win;
+    a.prob = s->prob;
+    a.n_trk = (int)n_tracks;
+    a.n_seg = (int)plan.n_seg;
+    a.n_cut = n_cutoffs;
+    a.skip = skip;
+    a.cdp = std::max(cooldown, 1);
+    a.first_ok = std::max(cooldown - 1, 0);
+    a.n_entry = std::min(a.cdp, POST_SEG);
+    a.ring_lds = (int64_t)n_cutoffs * a.n_entry * 4 <= OP_RING_LDS;
+    lds = a.ring_lds ? (size_t)n_cutoffs * a.n_entry * 4 : 0;
+    per_window = std::max<int64_t>(ambient_tables ? plan.n_rows : plan.n_seg, 1) * a.n_entry * n_cutoffs * 4;
+    pw = (int)std::min<int64_t>(n_win, std::max<int64_t>(OP_SCRATCH / per_window, 1));
+    tab.add(&a.off, n_tracks + 1, offsets);
+    tab.add(&a.kind, n_tracks, knd);
+    tab.add(&a.seg_first, n_tracks + 1, plan.seg_first.data());
+    tab.add(&a.win, n_win, windows);
+    tab.add(&a.cut, n_cutoffs, cutoffs);
+    return MWW_OK;
   }
-  if (offsets[0] < 0 || offsets[n_tracks] > s->n_out) return mww::set_error(MWW_ERR_INVALID, "track offsets exceed the probabilities held");
-  for (int64_t t = 0; t < n_tracks; ++t)
-    if (offsets[t + 1] < offsets[t]) return mww::set_error(MWW_ERR_INVALID, "track offsets must not decrease");
-  p->seg_first.resize((size_t)n_tracks + 1);
-  if (ambient_tables) p->tab_first.resize((size_t)n_tracks + 1);
-  int64_t n_seg = 0, n_rows = 0;
-  for (int64_t t = 0; t < n_tracks; ++t) {
-    p->seg_first[(size_t)t] = (int32_t)n_seg;
-    if (ambient_tables) p->tab_first[(size_t)t] = (int32_t)n_rows;
-    const int64_t n = offsets[t + 1] - offsets[t] - (kind[t] ? skip : 0);
-    const int64_t m = n >= wmin ? n - wmin + 1 : 0;
-    n_seg += (m + OP_SEG - 1) / OP_SEG;
-    if (!kind[t]) n_rows += (m + OP_SEG - 1) / OP_SEG;
-    if (n_seg > INT32_MAX) return mww::set_error(MWW_ERR_INVALID, "too many probabilities for one call");
+
+  // closes the table with the segments' maxima, uploads it and so points OpArgs at it (a table row per segment, unless the
+  // entry point added a tab_first of its own)
+  int commit(mww_stream* s) {
+    tab.add(&a.seg_best, (int64_t)n_windows * plan.n_seg);
+    SCHK(hipSetDevice(s->device));
+    int rc = tab.commit(&s->post_tab, &s->cap_post_tab, s->stream);
+    if (!rc) rc = grow(&s->post_scr, &s->cap_post_scr, per_window * pw);
+    if (rc) return rc;
+    if (!a.tab_first) a.tab_first = a.seg_first;
+    a.tab = reinterpret_cast<unsigned*>(s->post_scr);
+    return MWW_OK;
   }
-  p->seg_first[(size_t)n_tracks] = (int32_t)n_seg;
-  if (ambient_tables) p->tab_first[(size_t)n_tracks] = (int32_t)n_rows;
-  p->n_seg = n_seg;
-  p->cdp = std::max(cooldown, 1);
-  p->n_entry = std::min(p->cdp, OP_SEG);
-  p->per_window = std::max<int64_t>(ambient_tables ? n_rows : n_seg, 1) * p->n_entry * n_cutoffs * 4;
-  p->pw = (int)std::min<int64_t>(n_windows, std::max<int64_t>(OP_SCRATCH / p->per_window, 1));
-  return MWW_OK;
-}
+
+  // the windows in passes of pw, in stream order (a pass reuses the tables of the one before): op_segment_kernel, then the
+  // entry point's launches `follow(a)`
+  template <class F>
+  int passes(mww_stream* s, F&& follow) {
+    for (int w0 = 0; w0 < n_windows; w0 += pw) {
+      a.w0 = w0;
+      a.pw = std::min(pw, n_windows - w0);
+      if (a.n_seg) {
+        hipLaunchKernelGGL(op_segment_kernel, dim3((unsigned)a.n_seg, (unsigned)a.pw), dim3(OP_THREADS), lds, s->stream, a);
+        SCHK(hipGetLastError());
+      }
+      if (int rc = follow(a)) return rc;
+    }
+    return MWW_OK;
+  }
+};
 
 }  // namespace
 
 extern "C" {
 
+int mww_stream_metrics(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, int window, int skip,
+                       int cooldown, const double* cutoffs, int n_cutoffs, uint64_t* counts, int64_t* ma_len, float* score) {
+  if (!s || !offsets || !kind || !cutoffs || !counts || !ma_len || !score) return mww::set_error(MWW_ERR_INVALID, "null argument");
+  const bool args_ok = window > 0 && skip >= 0 && cooldown >= 0 && n_cutoffs > 0 && n_cutoffs <= POST_MAX_CUTOFFS;
+  if (int rc = post_check_tracks(s, offsets, kind, n_tracks, args_ok, "bad metric arguments (1.." + std::to_string(POST_MAX_CUTOFFS) + " cutoffs)", false))
+    return rc;
+  const int64_t* off;
+  const int* knd;
+  const double* cut;
+  unsigned long long *cnt, *tot;
+  int64_t* len;
+  float* sc;
+  PostTable tab;
+  tab.add(&off, n_tracks + 1, offsets);
+  tab.add(&knd, n_tracks, kind);
+  tab.add(&cut, n_cutoffs, cutoffs);
+  tab.end_host();
+  tab.add(&cnt, n_tracks * n_cutoffs);
+  tab.add(&len, n_tracks);
+  tab.add(&sc, n_tracks);
+  tab.add(&tot, n_cutoffs);
+  SCHK(hipSetDevice(s->device));
+  if (int rc = tab.commit(&s->post_tab, &s->cap_post_tab, s->stream)) return rc;
+  hipLaunchKernelGGL(stream_metrics_kernel, dim3((unsigned)n_tracks), dim3(128), 0, s->stream, (const float*)s->prob, off, knd,
+                     (int)n_tracks, window, skip, cooldown, cut, n_cutoffs, cnt, len, sc);
+  SCHK(hipGetLastError());
+  hipLaunchKernelGGL(stream_counts_sum_kernel, dim3(1), dim3(128), 0, s->stream, (const unsigned long long*)cnt, (int)n_tracks, n_cutoffs, tot);
+  SCHK(hipGetLastError());
+  SCHK(hipMemcpyAsync(counts, tot, (size_t)n_cutoffs * 8, hipMemcpyDeviceToHost, s->stream));
+  SCHK(hipMemcpyAsync(ma_len, len, (size_t)n_tracks * 8, hipMemcpyDeviceToHost, s->stream));
+  SCHK(hipMemcpyAsync(score, sc, (size_t)n_tracks * 4, hipMemcpyDeviceToHost, s->stream));
+  SCHK(hipStreamSynchronize(s->stream));
+  return MWW_OK;
+}
+
 int mww_stream_operating_points(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, const int32_t* windows,
                                 int n_windows, int skip, int cooldown, const double* cutoffs, int n_cutoffs, uint64_t* counts,
                                 int64_t* ma_len, float* score) {
   if (!s || !offsets || !kind || !windows || !cutoffs || !counts || !ma_len || !score) return mww::set_error(MWW_ERR_INVALID, "null argument");
-  OpPlan plan;
-  if (int rc = op_plan(s, offsets, kind, n_tracks, windows, n_windows, skip, cooldown, n_cutoffs, false, &plan)) return rc;
-  const std::vector<int32_t>& seg_first = plan.seg_first;
-  const int64_t n_seg = plan.n_seg, per_window = plan.per_window;
-  const int cdp = plan.cdp, n_entry = plan.n_entry, pw = plan.pw;
-  auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+  OpCall c;
+  if (int rc = c.begin(s, offsets, kind, n_tracks, windows, n_windows, skip, cooldown, cutoffs, n_cutoffs, false)) return rc;
   const int64_t W = n_windows;
-  const int64_t o_off = 0, o_kind = al((n_tracks + 1) * 8), o_sf = al(o_kind + n_tracks * 4), o_win = al(o_sf + (n_tracks + 1) * 4),
-                o_cut = al(o_win + W * 4), o_in_end = al(o_cut + n_cutoffs * 8), o_tot = o_in_end, o_len = al(o_tot + W * n_cutoffs * 8),
-                o_sc = al(o_len + W * n_tracks * 8), o_cnt = al(o_sc + W * n_tracks * 4), o_best = al(o_cnt + W * n_tracks * n_cutoffs * 8),
-                bytes = al(o_best + W * n_seg * 4);
-  SCHK(hipSetDevice(s->device));
-  int rc = grow(&s->op_tab, &s->cap_op_tab, bytes);
-  if (!rc) rc = grow(&s->op_scr, &s->cap_op_scr, per_window * pw);
-  if (rc) return rc;
-  std::vector<char> h((size_t)o_in_end, 0);
-  std::memcpy(&h[o_off], offsets, (size_t)(n_tracks + 1) * 8);
-  std::memcpy(&h[o_kind], kind, (size_t)n_tracks * 4);
-  std::memcpy(&h[o_sf], seg_first.data(), (size_t)(n_tracks + 1) * 4);
-  std::memcpy(&h[o_win], windows, (size_t)W * 4);
-  std::memcpy(&h[o_cut], cutoffs, (size_t)n_cutoffs * 8);
-  SCHK(hipMemcpyAsync(s->op_tab, h.data(), (size_t)o_in_end, hipMemcpyHostToDevice, s->stream));
-  OpArgs a{};
-  a.prob = s->prob;
-  a.off = reinterpret_cast<const int64_t*>(s->op_tab + o_off);
-  a.kind = reinterpret_cast<const int*>(s->op_tab + o_kind);
-  a.seg_first = reinterpret_cast<const int*>(s->op_tab + o_sf);
-  a.tab_first = a.seg_first;   // a table row per segment
-  a.win = reinterpret_cast<const int*>(s->op_tab + o_win);
-  a.cut = reinterpret_cast<const double*>(s->op_tab + o_cut);
-  a.n_trk = (int)n_tracks;
-  a.n_seg = (int)n_seg;
-  a.n_cut = n_cutoffs;
-  a.skip = skip;
-  a.cdp = cdp;
-  a.first_ok = std::max(cooldown - 1, 0);
-  a.n_entry = n_entry;
-  a.ring_lds = (int64_t)n_cutoffs * n_entry * 4 <= OP_RING_LDS;
-  a.tab = reinterpret_cast<unsigned*>(s->op_scr);
-  a.total = reinterpret_cast<unsigned long long*>(s->op_tab + o_tot);
-  a.ma_len = reinterpret_cast<int64_t*>(s->op_tab + o_len);
-  a.score = reinterpret_cast<float*>(s->op_tab + o_sc);
-  a.trk_cnt = reinterpret_cast<unsigned long long*>(s->op_tab + o_cnt);
-  a.seg_best = reinterpret_cast<float*>(s->op_tab + o_best);
-  const size_t lds = a.ring_lds ? (size_t)n_cutoffs * n_entry * 4 : 0;
-  for (int w0 = 0; w0 < n_windows; w0 += pw) {   // stream order: a pass reuses the tables of the one before
-    a.w0 = w0;
-    a.pw = std::min(pw, n_windows - w0);
-    if (n_seg) {
-      hipLaunchKernelGGL(op_segment_kernel, dim3((unsigned)n_seg, (unsigned)a.pw), dim3(OP_THREADS), lds, s->stream, a);
-      SCHK(hipGetLastError());
-    }
+  c.tab.end_host();
+  c.tab.add(&c.a.total, W * n_cutoffs);
+  c.tab.add(&c.a.ma_len, W * n_tracks);
+  c.tab.add(&c.a.score, W * n_tracks);
+  c.tab.add(&c.a.trk_cnt, W * n_tracks * n_cutoffs);
+  if (int rc = c.commit(s)) return rc;
+  const int rc = c.passes(s, [&](const OpArgs& a) {
     const int64_t n_thr = n_tracks * a.pw * n_cutoffs;
     hipLaunchKernelGGL(op_track_kernel, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, s->stream, a);
     SCHK(hipGetLastError());
     hipLaunchKernelGGL(op_sum_kernel, dim3((unsigned)((a.pw * n_cutoffs + 255) / 256)), dim3(256), 0, s->stream, a);
     SCHK(hipGetLastError());
-  }
-  SCHK(hipMemcpyAsync(counts, a.total, (size_t)(W * n_cutoffs) * 8, hipMemcpyDeviceToHost, s->stream));
-  SCHK(hipMemcpyAsync(ma_len, a.ma_len, (size_t)(W * n_tracks) * 8, hipMemcpyDeviceToHost, s->stream));
-  SCHK(hipMemcpyAsync(score, a.score, (size_t)(W * n_tracks) * 4, hipMemcpyDeviceToHost, s->stream));
+    return (int)MWW_OK;
+  });
+  if (rc) return rc;
+  SCHK(hipMemcpyAsync(counts, c.a.total, (size_t)(W * n_cutoffs) * 8, hipMemcpyDeviceToHost, s->stream));
+  SCHK(hipMemcpyAsync(ma_len, c.a.ma_len, (size_t)(W * n_tracks) * 8, hipMemcpyDeviceToHost, s->stream));
+  SCHK(hipMemcpyAsync(score, c.a.score, (size_t)(W * n_tracks) * 4, hipMemcpyDeviceToHost, s->stream));
   SCHK(hipStreamSynchronize(s->stream));
   return MWW_OK;
 }
@@ -424,78 +468,37 @@ int mww_stream_operating_summary(mww_stream* s, const int64_t* offsets, const in
   if (!s || !offsets || !kind || !windows || !cutoffs || !counts || !accepts || !hours || !short_tracks || !n_kind)
     return mww::set_error(MWW_ERR_INVALID, "null argument");
   if (stride < 1 || !(step_s > 0)) return mww::set_error(MWW_ERR_INVALID, "bad operating-summary arguments (stride >= 1, step_s > 0)");
-  OpPlan plan;
-  if (int rc = op_plan(s, offsets, kind, n_tracks, windows, n_windows, skip, cooldown, n_cutoffs, true, &plan)) return rc;
+  OpCall c;
+  if (int rc = c.begin(s, offsets, kind, n_tracks, windows, n_windows, skip, cooldown, cutoffs, n_cutoffs, true)) return rc;
   std::vector<int32_t> amb, pos;
   for (int64_t t = 0; t < n_tracks; ++t) (kind[t] ? pos : amb).push_back((int32_t)t);
   const int64_t n_amb = (int64_t)amb.size(), n_pos = (int64_t)pos.size(), n_pblk = (n_pos + OPS_POS - 1) / OPS_POS;
-  const int64_t n_seg = plan.n_seg, W = n_windows, C = n_cutoffs;
-  const int pw = plan.pw;
-  auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+  const int64_t W = n_windows, C = n_cutoffs;
   // inputs, then the result block (counts, accepts, hours, short_tracks, n_kind: contiguous, read back in one copy), then scratch
-  const int64_t o_off = 0, o_kind = al((n_tracks + 1) * 8), o_sf = al(o_kind + n_tracks * 4), o_win = al(o_sf + (n_tracks + 1) * 4),
-                o_cut = al(o_win + W * 4), o_amb = al(o_cut + C * 8), o_pos = al(o_amb + n_amb * 4), o_tf = al(o_pos + n_pos * 4), o_in_end = al(o_tf + (n_tracks + 1) * 4);
+  OpsArgs o{};
+  char* res;
+  c.tab.add(&o.amb, n_amb, amb.data());
+  c.tab.add(&o.pos, n_pos, pos.data());
+  c.tab.add(&c.a.tab_first, n_tracks + 1, c.plan.tab_first.data());   // table rows for the ambient tracks' segments alone
+  c.tab.end_host();
   const int64_t r_cnt = 0, r_acc = r_cnt + W * C * 8, r_hours = r_acc + W * C * 8, r_short = r_hours + W * 8, r_kind = r_short + W * 16,
                 r_bytes = r_kind + 16;
-  const int64_t o_res = o_in_end, o_acnt = al(o_res + r_bytes), o_pacc = al(o_acnt + W * n_amb * C * 8), o_pshort = al(o_pacc + W * n_pblk * C * 4),
-                o_best = al(o_pshort + W * n_pblk * 4), bytes = al(o_best + W * n_seg * 4);
-  SCHK(hipSetDevice(s->device));
-  int rc = grow(&s->op_tab, &s->cap_op_tab, bytes);
-  if (!rc) rc = grow(&s->op_scr, &s->cap_op_scr, plan.per_window * pw);
-  if (rc) return rc;
-  std::vector<char> h((size_t)o_in_end, 0);
-  std::memcpy(&h[o_off], offsets, (size_t)(n_tracks + 1) * 8);
-  std::memcpy(&h[o_kind], kind, (size_t)n_tracks * 4);
-  std::memcpy(&h[o_sf], plan.seg_first.data(), (size_t)(n_tracks + 1) * 4);
-  std::memcpy(&h[o_win], windows, (size_t)W * 4);
-  std::memcpy(&h[o_cut], cutoffs, (size_t)C * 8);
-  if (n_amb) std::memcpy(&h[o_amb], amb.data(), (size_t)n_amb * 4);
-  if (n_pos) std::memcpy(&h[o_pos], pos.data(), (size_t)n_pos * 4);
-  std::memcpy(&h[o_tf], plan.tab_first.data(), (size_t)(n_tracks + 1) * 4);
-  SCHK(hipMemcpyAsync(s->op_tab, h.data(), (size_t)o_in_end, hipMemcpyHostToDevice, s->stream));
-  OpArgs a{};
-  a.prob = s->prob;
-  a.off = reinterpret_cast<const int64_t*>(s->op_tab + o_off);
-  a.kind = reinterpret_cast<const int*>(s->op_tab + o_kind);
-  a.seg_first = reinterpret_cast<const int*>(s->op_tab + o_sf);
-  a.tab_first = reinterpret_cast<const int*>(s->op_tab + o_tf);   // table rows for the ambient tracks' segments alone
-  a.win = reinterpret_cast<const int*>(s->op_tab + o_win);
-  a.cut = reinterpret_cast<const double*>(s->op_tab + o_cut);
-  a.n_trk = (int)n_tracks;
-  a.n_seg = (int)n_seg;
-  a.n_cut = n_cutoffs;
-  a.skip = skip;
-  a.cdp = plan.cdp;
-  a.first_ok = std::max(cooldown - 1, 0);
-  a.n_entry = plan.n_entry;
-  a.ring_lds = C * plan.n_entry * 4 <= OP_RING_LDS;
-  a.tab = reinterpret_cast<unsigned*>(s->op_scr);
-  a.seg_best = reinterpret_cast<float*>(s->op_tab + o_best);
-  OpsArgs o{};
-  o.amb = reinterpret_cast<const int*>(s->op_tab + o_amb);
-  o.pos = reinterpret_cast<const int*>(s->op_tab + o_pos);
+  c.tab.add(&res, r_bytes);
+  c.tab.add(&o.amb_cnt, W * n_amb * C);
+  c.tab.add(&o.part_acc, W * n_pblk * C);
+  c.tab.add(&o.part_short, W * n_pblk);
+  if (int rc = c.commit(s)) return rc;
   o.n_amb = (int)n_amb;
   o.n_pos = (int)n_pos;
   o.n_pblk = (int)n_pblk;
   o.stride = stride;
   o.step_s = step_s;
-  o.amb_cnt = reinterpret_cast<unsigned long long*>(s->op_tab + o_acnt);
-  o.part_acc = reinterpret_cast<unsigned*>(s->op_tab + o_pacc);
-  o.part_short = reinterpret_cast<unsigned*>(s->op_tab + o_pshort);
-  char* res = s->op_tab + o_res;
   o.counts = reinterpret_cast<unsigned long long*>(res + r_cnt);
   o.accepts = reinterpret_cast<unsigned long long*>(res + r_acc);
   o.hours = reinterpret_cast<double*>(res + r_hours);
   o.short_tracks = reinterpret_cast<int64_t*>(res + r_short);
   o.n_kind = reinterpret_cast<int64_t*>(res + r_kind);
-  const size_t lds = a.ring_lds ? (size_t)C * plan.n_entry * 4 : 0;
-  for (int w0 = 0; w0 < n_windows; w0 += pw) {   // stream order: a pass reuses the tables of the one before
-    a.w0 = w0;
-    a.pw = std::min(pw, n_windows - w0);
-    if (n_seg) {
-      hipLaunchKernelGGL(op_segment_kernel, dim3((unsigned)n_seg, (unsigned)a.pw), dim3(OP_THREADS), lds, s->stream, a);
-      SCHK(hipGetLastError());
-    }
+  const int rc = c.passes(s, [&](const OpArgs& a) {
     if (n_amb) {
       const int64_t n_thr = n_amb * a.pw * C;
       hipLaunchKernelGGL(ops_ambient_kernel, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, s->stream, a, o);
@@ -507,7 +510,9 @@ int mww_stream_operating_summary(mww_stream* s, const int64_t* offsets, const in
     }
     hipLaunchKernelGGL(ops_final_kernel, dim3((unsigned)((a.pw * C + 255) / 256)), dim3(256), 0, s->stream, a, o);
     SCHK(hipGetLastError());
-  }
+    return (int)MWW_OK;
+  });
+  if (rc) return rc;
   std::vector<char> r((size_t)r_bytes);
   SCHK(hipMemcpyAsync(r.data(), res, (size_t)r_bytes, hipMemcpyDeviceToHost, s->stream));   // W * C * 16 + W * 24 + 16 bytes
   SCHK(hipStreamSynchronize(s->stream));

@@ -132,6 +132,20 @@ EXPORTS = [
 ]
 
 
+def vp(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _track_table(offsets, per_track, dtype=np.int32, name="kind"):
+    """the track table of the calls on the probabilities a stream holds: contiguous ``offsets`` int64 [n + 1] and one entry per
+    track (its kind; for mining its window) -> (offsets, entries, n)"""
+    off = np.ascontiguousarray(offsets, np.int64)
+    per = np.ascontiguousarray(per_track, dtype).reshape(-1)
+    if off.size != per.size + 1:
+        raise ValueError("offsets must have one entry more than " + name)
+    return off, per, per.size
+
+
 def _fptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
@@ -747,16 +761,11 @@ class Stream:
 
     def metrics(self, offsets, kind, cutoffs, window=5, skip=25, cooldown=25):
         """-> (counts uint64 [n_cutoffs] summed over the kind-0 tracks, ma_len int64 [n], score float32 [n])"""
-        off = np.ascontiguousarray(offsets, np.int64)
-        kd = np.ascontiguousarray(kind, np.int32)
+        off, kd, n = _track_table(offsets, kind)
         cut = np.ascontiguousarray(cutoffs, np.float64)
-        n = kd.size
-        if off.size != n + 1:
-            raise ValueError("offsets must have one entry more than kind")
         counts = np.zeros(cut.size, np.uint64)
         ma_len = np.zeros(n, np.int64)
         score = np.zeros(n, np.float32)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         self.nl.check(self.nl.lib.mww_stream_metrics(self.h, vp(off), vp(kd), n, int(window), int(skip), int(cooldown), vp(cut),
                                                      cut.size, vp(counts), vp(ma_len), vp(score)))
         return counts, ma_len, score
@@ -766,15 +775,10 @@ class Stream:
         (kind 0) tracks, and where a positive (kind 1) track reaches its score.  -> (events DETECTION_DTYPE in (track, index)
         order, track_count int64 [n], best_index int64 [n], score float32 [n]).  ``capacity=None`` calls once to count and
         once to fetch; a given capacity fetches at most that many events (track_count stays complete)."""
-        off = np.ascontiguousarray(offsets, np.int64)
-        kd = np.ascontiguousarray(kind, np.int32)
-        n = kd.size
-        if off.size != n + 1:
-            raise ValueError("offsets must have one entry more than kind")
+        off, kd, n = _track_table(offsets, kind)
         track_count = np.zeros(n, np.int64)
         best_index = np.zeros(n, np.int64)
         score = np.zeros(n, np.float32)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
 
         def call(events):
             return int(self.nl.check(self.nl.lib.mww_stream_detections(
@@ -798,14 +802,10 @@ class Stream:
         device.  -> (clips WINDOW_DTYPE, events DETECTION_DTYPE, both in (track, index) order, detections before the selection,
         track_count int64 [n]).  ``capacity=None`` sizes the outputs for the result (one call when ``max_new`` bounds it, else
         one to count and one to fetch); a given capacity fetches at most that many clips."""
-        tr = np.ascontiguousarray(tracks, WINDOW_DTYPE).reshape(-1)
-        off = np.ascontiguousarray(offsets, np.int64)
-        if off.size != tr.size + 1:
-            raise ValueError("offsets must have one entry more than tracks")
+        off, tr, _ = _track_table(offsets, tracks, WINDOW_DTYPE, "tracks")
         want = -1 if max_new is None else max(int(max_new), 0)
         track_count = np.zeros(tr.size, np.int64)
         total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
 
         def call(cap):
             clips, raw = np.zeros(cap, WINDOW_DTYPE), np.zeros(cap, DETECTION_RAW)
@@ -829,17 +829,12 @@ class Stream:
     def operating_points(self, offsets, kind, windows, cutoffs, skip=25, cooldown=25):
         """``mww_stream_operating_points`` on the probabilities held: row k is ``metrics`` at ``windows[k]``.
         -> (counts uint64 [W, C] summed over the kind-0 tracks, ma_len int64 [W, n], score float32 [W, n])"""
-        off = np.ascontiguousarray(offsets, np.int64)
-        kd = np.ascontiguousarray(kind, np.int32)
+        off, kd, n = _track_table(offsets, kind)
         win = np.ascontiguousarray(windows, np.int32).reshape(-1)
         cut = np.ascontiguousarray(cutoffs, np.float64).reshape(-1)
-        n = kd.size
-        if off.size != n + 1:
-            raise ValueError("offsets must have one entry more than kind")
         counts = np.zeros((win.size, cut.size), np.uint64)
         ma_len = np.zeros((win.size, n), np.int64)
         score = np.zeros((win.size, n), np.float32)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         self.nl.check(self.nl.lib.mww_stream_operating_points(self.h, vp(off), vp(kd), n, vp(win), win.size, int(skip), int(cooldown),
                                                               vp(cut), cut.size, vp(counts), vp(ma_len), vp(score)))
         return counts, ma_len, score
@@ -849,16 +844,11 @@ class Stream:
         -> (counts uint64 [W, C] of the kind-0 tracks, accepts uint64 [W, C] kind-1 tracks whose score is above the cutoff,
         hours float64 [W], short_tracks int64 [W, 2] kind-0 / kind-1 tracks without a moving-average value, n_kind int64 [2]).
         ``stride`` defaults to the stream's own."""
-        off = np.ascontiguousarray(offsets, np.int64)
-        kd = np.ascontiguousarray(kind, np.int32)
+        off, kd, n = _track_table(offsets, kind)
         win = np.ascontiguousarray(windows, np.int32).reshape(-1)
         cut = np.ascontiguousarray(cutoffs, np.float64).reshape(-1)
-        n = kd.size
-        if off.size != n + 1:
-            raise ValueError("offsets must have one entry more than kind")
         counts, accepts = np.zeros((win.size, cut.size), np.uint64), np.zeros((win.size, cut.size), np.uint64)
         hours, short, n_kind = np.zeros(win.size, np.float64), np.zeros((win.size, 2), np.int64), np.zeros(2, np.int64)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         self.nl.check(self.nl.lib.mww_stream_operating_summary(
             self.h, vp(off), vp(kd), n, vp(win), win.size, int(skip), int(cooldown), vp(cut), cut.size,
             int(self.stride if stride is None else stride), float(step_s), vp(counts), vp(accepts), vp(hours), vp(short), vp(n_kind)))
@@ -887,7 +877,6 @@ class Stream:
         lt = np.ascontiguousarray(lut, np.uint8).reshape(-1)
         if lt.size != 256:
             raise ValueError("the logistic table has 256 entries")
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         self.nl.check(self.nl.lib.mww_stream_set_quantized(self.h, vp(w), w.size, vp(iv), iv.size, float(input_scale), vp(lt)))
 
     def read_q8(self, n=None) -> np.ndarray:

@@ -31,11 +31,8 @@ CUTOFFS = np.arange(0, 1.01, 0.01)   # test.py:331
 OP_WINDOWS = tuple(range(1, 11))     # sliding-window sizes of the operating-point grid (the reference evaluates 5 alone)
 
 
-def stream_description(flags, t_final: int, frames: int, stride: int, mode: str) -> dict:
-    """The ``mww_stream_desc`` of a MixedNet flag set (mixednet.py:307-386).  Topologies outside the streaming kernel raise
-    NotImplementedError naming the flag."""
-    if mode not in native.STREAM_MODES:
-        raise ValueError("mode must be 'stream' or 'non_stream'")
+def _block_lists(flags):
+    """the per-block lists of a MixedNet flag set: pointwise filters, repeats, kernel-size tuples, residual flags (as given)"""
     pf = [int(f) for f in parse(_flag(flags, "pointwise_filters"))]
     rep = [int(r) for r in parse(_flag(flags, "repeat_in_block"))]
     ksz = [tuple(int(k) for k in (ks if isinstance(ks, (list, tuple)) else (ks,))) for ks in parse(_flag(flags, "mixconv_kernel_sizes"))]
@@ -43,6 +40,15 @@ def stream_description(flags, t_final: int, frames: int, stride: int, mode: str)
     for lst in (rep, ksz, res):
         if len(pf) != len(lst):
             raise ValueError("all input lists have to be the same length")   # mixednet.py:298-305
+    return pf, rep, ksz, res
+
+
+def stream_description(flags, t_final: int, frames: int, stride: int, mode: str) -> dict:
+    """The ``mww_stream_desc`` of a MixedNet flag set (mixednet.py:307-386).  Topologies outside the streaming kernel raise
+    NotImplementedError naming the flag."""
+    if mode not in native.STREAM_MODES:
+        raise ValueError("mode must be 'stream' or 'non_stream'")
+    pf, rep, ksz, res = _block_lists(flags)
     unsupported = []
     if int(_flag(flags, "first_conv_filters")) <= 0:
         unsupported.append("first_conv_filters = 0")
@@ -81,13 +87,8 @@ def mixednet_stream_description(flags, frames: int, stride: int, mode: str) -> d
     itself cannot be built."""
     if mode not in native.STREAM_MODES:
         raise ValueError("mode must be 'stream' or 'non_stream'")
-    pf = [int(f) for f in parse(_flag(flags, "pointwise_filters"))]
-    rep = [int(r) for r in parse(_flag(flags, "repeat_in_block"))]
-    ksz = [tuple(int(k) for k in (ks if isinstance(ks, (list, tuple)) else (ks,))) for ks in parse(_flag(flags, "mixconv_kernel_sizes"))]
-    res = [int(bool(r)) for r in parse(_flag(flags, "residual_connection"))]
-    for lst in (rep, ksz, res):
-        if len(pf) != len(lst):
-            raise ValueError("all input lists have to be the same length")   # mixednet.py:298-305
+    pf, rep, ksz, res = _block_lists(flags)
+    res = [int(bool(r)) for r in res]
     f0, k1 = int(_flag(flags, "first_conv_filters")), int(_flag(flags, "first_conv_kernel_size"))
     if f0 <= 0:
         raise NotImplementedError("streaming evaluation does not cover MixedNet with first_conv_filters = 0")
@@ -543,28 +544,37 @@ def select_operating_points(faph, frr, usable, target_faph, windows=None):
     return chosen, (min(best)[3] if best else -1)
 
 
-def _operating_grid(counts, ambient_ma_len, positive_ma_len, score, windows, cutoffs, stride, step_s, target_faph):
-    """counts [W, C], ambient_ma_len [W, n_amb], positive_ma_len / score [W, n_pos] -> the grid's dict (both paths end here)"""
-    windows, cutoffs = np.asarray(windows, np.int64).reshape(-1), np.asarray(cutoffs, np.float64).reshape(-1)
-    if score.shape[1] == 0:
+def _rates_and_selection(windows, cutoffs, counts, hours, usable, frr_row, target_faph, n_pos, after_counts=(), last=()):
+    """Where the grid and the summary end, on ``windows`` int64 [W] and ``cutoffs`` float64 [C]: FAPH and FRR of the usable
+    windows (``frr_row(k)``: the FRR of window k at every cutoff), the dict - the caller's own entries ``after_counts`` behind
+    ``counts`` and ``last`` at the end, the order the two dicts always had - and with ``target_faph`` the selection."""
+    if n_pos == 0:
         raise ValueError("the test set has no positive track")
-    W = windows.size
-    hours = np.array([track_hours(ambient_ma_len[k], stride, step_s) for k in range(W)], np.float64)
-    usable = np.array([ambient_ma_len.shape[1] > 0 and bool(np.all(ambient_ma_len[k] > 0)) and bool(np.all(positive_ma_len[k] > 0))
-                       for k in range(W)])
-    faph = np.full((W, cutoffs.size), np.nan)
-    frr = np.full((W, cutoffs.size), np.nan)
+    usable = np.asarray(usable, bool)
+    faph = np.full((windows.size, cutoffs.size), np.nan)
+    frr = np.full((windows.size, cutoffs.size), np.nan)
     for k in np.nonzero(usable)[0]:
         faph[k] = counts[k].astype(np.float64) / hours[k]
-        frr[k] = false_rejection_rates(list(score[k]), cutoffs)
-    out = dict(windows=windows, cutoffs=cutoffs, counts=np.asarray(counts, np.uint64), hours=hours, usable=usable, faph=faph, frr=frr,
-               ambient_ma_len=np.asarray(ambient_ma_len, np.int64), positive_ma_len=np.asarray(positive_ma_len, np.int64),
-               score=np.asarray(score, np.float32))
+        frr[k] = frr_row(k)
+    out = dict(windows=windows, cutoffs=cutoffs, counts=np.asarray(counts, np.uint64), **dict(after_counts))
+    out.update(hours=np.asarray(hours, np.float64), usable=usable, faph=faph, frr=frr, **dict(last))
     if target_faph is not None:
         chosen, rec = select_operating_points(faph, frr, usable, target_faph, windows)
         out.update(target_faph=float(target_faph), chosen=chosen, recommended=int(rec),
                    chosen_cutoff=np.array([cutoffs[c] if c >= 0 else np.nan for c in chosen], np.float64))
     return out
+
+
+def _operating_grid(counts, ambient_ma_len, positive_ma_len, score, windows, cutoffs, stride, step_s, target_faph):
+    """counts [W, C], ambient_ma_len [W, n_amb], positive_ma_len / score [W, n_pos] -> the grid's dict (both paths end here)"""
+    windows, cutoffs = np.asarray(windows, np.int64).reshape(-1), np.asarray(cutoffs, np.float64).reshape(-1)
+    W = windows.size
+    hours = np.array([track_hours(ambient_ma_len[k], stride, step_s) for k in range(W)], np.float64)
+    usable = [ambient_ma_len.shape[1] > 0 and bool(np.all(ambient_ma_len[k] > 0)) and bool(np.all(positive_ma_len[k] > 0)) for k in range(W)]
+    return _rates_and_selection(windows, cutoffs, counts, hours, usable, lambda k: false_rejection_rates(list(score[k]), cutoffs),
+                                target_faph, score.shape[1],
+                                last=dict(ambient_ma_len=np.asarray(ambient_ma_len, np.int64),
+                                          positive_ma_len=np.asarray(positive_ma_len, np.int64), score=np.asarray(score, np.float32)))
 
 
 def operating_points_host(ambient_probabilities, positive_probabilities, windows=OP_WINDOWS, cutoffs=CUTOFFS, stride=1, step_s=0.02,
@@ -599,21 +609,11 @@ def _operating_summary(counts, accepts, hours, short_tracks, n_kind, windows, cu
     """what mww_stream_operating_summary returns -> the summary's dict: the rules of ``_operating_grid`` on the reduced numbers"""
     windows, cutoffs = np.asarray(windows, np.int64).reshape(-1), np.asarray(cutoffs, np.float64).reshape(-1)
     n_amb, n_pos = int(n_kind[0]), int(n_kind[1])
-    if n_pos == 0:
-        raise ValueError("the test set has no positive track")
-    usable = np.array([n_amb > 0 and short_tracks[k, 0] == 0 and short_tracks[k, 1] == 0 for k in range(windows.size)], bool)
-    faph = np.full((windows.size, cutoffs.size), np.nan)
-    frr = np.full((windows.size, cutoffs.size), np.nan)
-    for k in np.nonzero(usable)[0]:
-        faph[k] = counts[k].astype(np.float64) / hours[k]
-        frr[k] = 1 - accepts[k].astype(np.float64) / n_pos   # false_rejection_rates: 1 - true_accepts / len(scores)
-    out = dict(windows=windows, cutoffs=cutoffs, counts=np.asarray(counts, np.uint64), accepts=np.asarray(accepts, np.uint64),
-               hours=np.asarray(hours, np.float64), usable=usable, faph=faph, frr=frr, n_ambient=n_amb, n_positive=n_pos)
-    if target_faph is not None:
-        chosen, rec = select_operating_points(faph, frr, usable, target_faph, windows)
-        out.update(target_faph=float(target_faph), chosen=chosen, recommended=int(rec),
-                   chosen_cutoff=np.array([cutoffs[c] if c >= 0 else np.nan for c in chosen], np.float64))
-    return out
+    usable = [n_amb > 0 and short_tracks[k, 0] == 0 and short_tracks[k, 1] == 0 for k in range(windows.size)]
+    # false_rejection_rates: 1 - true_accepts / len(scores)
+    return _rates_and_selection(windows, cutoffs, counts, hours, usable, lambda k: 1 - accepts[k].astype(np.float64) / n_pos,
+                                target_faph, n_pos, after_counts=dict(accepts=np.asarray(accepts, np.uint64)),
+                                last=dict(n_ambient=n_amb, n_positive=n_pos))
 
 
 def operating_summary_host(ambient_probabilities, positive_probabilities, windows=OP_WINDOWS, cutoffs=CUTOFFS, stride=1, step_s=0.02,

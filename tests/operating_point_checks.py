@@ -10,7 +10,7 @@ import engine_checks as ec
 import stream_detect_checks as dc
 import streaming_checks as sc
 
-S = 1024   # moving-average values per kernel segment (OP_SEG of csrc/tu_stream_oppoints.hip)
+S = 1024   # moving-average values per kernel segment (POST_SEG of csrc/stream_post.hip.h)
 assert S == dc.SEG   # sweep_lengths places its boundary tracks around the detect kernel's segment: the same size
 
 WINDOWS = (1, 2, 5, 10, 256, 5)   # unsorted tail, a repeat, the largest window of the ABI

@@ -12,7 +12,7 @@ import operating_point_checks as oc
 import stream_detect_checks as dc
 import streaming_checks as sc
 
-S = oc.S            # moving-average values per kernel segment (OP_SEG)
+S = oc.S            # moving-average values per kernel segment (POST_SEG)
 P = 256             # positive tracks per workgroup of the accept reduction (OPS_POS of csrc/tu_stream_oppoints.hip)
 STRIDE, STEP = 3, 0.02   # hours: (n * 3) * 0.02 / 3600 has rounding in the product, the division and the sum
 
@@ -203,6 +203,36 @@ def check_validation(sm):
     counts, accepts, hours, short, n_kind = check_equals_grid(sm.native, off, kind, [native.OP_MAX_WINDOW] * native.OP_MAX_WINDOWS,
                                                               np.linspace(0, 1, 128), 3, 2)
     assert not counts.any() and not accepts.any() and not hours.any() and np.all(short == 1)
+
+
+def check_shared_buffers(sm):
+    """The five entry points keep their device tables in buffers of the stream that they share (csrc/stream_post.hip.h).
+    Interleaved on one stream, with sizes going large -> small -> large, every call returns byte for byte what it returns on
+    a fresh stream that made only that call: what a larger or a different call left in a buffer changes nothing."""
+    big = oc.inputs()   # ~56 tracks up to 3001 probabilities, with the S - 1 / S / S + 1 / 2 S + 1 boundary tracks
+    big_kind = np.array([t % 2 for t in range(len(big.lengths))], np.int32)
+    small = np.linspace(0, 1, 50, dtype=np.float32)   # the set of check_validation
+    small_off, small_kind = np.array([0, 20, 50], np.int64), np.array([0, 1], np.int32)
+    small_win = np.array([(0, 0, 60, 0, 0), (0, 2, 90, 0, 40 * 7)], native.WINDOW_DTYPE)
+    calls = [
+        (big.flat, lambda st: st.metrics(big.off, big_kind, streaming.CUTOFFS, 5, 25, 25)),
+        (small, lambda st: st.detections(small_off, small_kind, 0.3, 3, 3, 2)),
+        (big.flat, lambda st: st.operating_points(big.off, big_kind, oc.WINDOWS, streaming.CUTOFFS, 25, 25)),
+        (small, lambda st: st.mine(small_win, small_off, 0.3, 3, 2, 1, 1, 4)),   # every track ambient
+        (big.flat, lambda st: st.operating_summary(big.off, big_kind, oc.WINDOWS, streaming.CUTOFFS, 25, 25, STRIDE, STEP)),
+        (big.flat, lambda st: st.detections(big.off, big_kind, 0.37, 5, 25, 25)),
+        (small, lambda st: st.metrics(small_off, small_kind, [0.2, 0.5], 5, 3, 2)),
+    ]
+    flat = lambda out: [np.asarray(o) for o in out]   # noqa: E731  (mine also returns its detection count)
+    for i, (probs, call) in enumerate(calls):
+        sm.native.set_probs(probs)
+        got = flat(call(sm.native))
+        fresh = streaming.StreamingModel(sm.model, sm.stride, sm.mode)
+        fresh.native.set_probs(probs)
+        want = flat(call(fresh.native))
+        fresh.native.close()
+        assert len(got) == len(want) and all(same(g, w) for g, w in zip(got, want)), (i, got, want)
+        assert any(np.frombuffer(g.tobytes(), np.uint8).any() for g in got), i   # no call of the sequence comes back empty
 
 
 def check_on(sm, off, kind, p, windows=streaming.OP_WINDOWS, ignore=25, target=None):

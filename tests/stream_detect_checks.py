@@ -10,7 +10,7 @@ from microwakeword_amd import native, streaming
 import engine_checks as ec
 import streaming_checks as sc
 
-SEG = 1024   # moving-average values per kernel segment (DET_SEG of csrc/tu_stream_detect.hip)
+SEG = 1024   # moving-average values per kernel segment (POST_SEG of csrc/stream_post.hip.h)
 
 WINDOWS, COOLDOWNS, SKIPS, CUTOFFS = (1, 5), (0, 1, 25), (0, 25), (0.0, 0.5, 0.37, 1.0)
 

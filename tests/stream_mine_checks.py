@@ -18,7 +18,7 @@ import stream_detect_checks as dc
 import stream_sweep as ss
 import streaming_checks as sc
 
-SEG = dc.SEG          # moving-average values per detect segment (DET_SEG)
+SEG = dc.SEG          # moving-average values per detect segment (POST_SEG)
 W_MAX = 5
 # moving-average counts at window 5: 0, 0 (length = window - 1), 1, both sides of a segment boundary, several workgroups of events
 LENGTHS = [0, W_MAX - 1, W_MAX, SEG - 1 + W_MAX - 1, SEG + W_MAX - 1, SEG + 1 + W_MAX - 1, 3001, 700, 700]

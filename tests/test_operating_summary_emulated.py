@@ -40,6 +40,10 @@ def test_operating_summary_arguments_are_validated(sm):
     osc.check_validation(sm)
 
 
+def test_interleaved_calls_share_buffers_without_a_trace(sm):
+    osc.check_shared_buffers(sm)
+
+
 @pytest.mark.parametrize("mode", ["stream", "non_stream"])
 def test_summary_on_the_kernels_own_probabilities(emu_lib, mode):
     osc.check_own_probabilities(emu_lib, mode)

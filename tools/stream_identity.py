@@ -9,6 +9,8 @@ arithmetic leaves every hash as it was.
     python tools/stream_identity.py --lib tests/hipemu/libmww_emu.so --emulator   # the cases the emulator tests run
     python tools/stream_identity.py --variants   # after those, the float cases of tests/mixednet_variant_checks.py and the
                                                  # calibration + int8 cases of tests/quant_mixednet_checks.py
+    python tools/stream_identity.py --post       # instead of those: what the five entry points on the probabilities held
+                                                 # (csrc/stream_post.hip.h) hand back; the same cases on the GPU and the emulator
 
 The cases: those of tests/stream_sweep.py (the script of each case: several stream-mode calls with resets, zero-output and
 one-output calls between them; its non-stream twin), tests/inception_streaming_checks.py ``stream_cases()`` /
@@ -29,8 +31,8 @@ FIELDS = ("prob", "logit", "state", "ranges", "u8", "state_q8")
 
 
 class Hashes:
-    def __init__(self):
-        self.h = {f: hashlib.sha256() for f in FIELDS}
+    def __init__(self, fields=FIELDS):
+        self.h = {f: hashlib.sha256() for f in fields}
 
     def add(self, **arrays):
         for f, a in arrays.items():
@@ -45,7 +47,7 @@ class Hashes:
         self.add(u8=st.read_q8(), prob=p, logit=z, state_q8=st.get_state_q8())
 
     def line(self, name):
-        return json.dumps(dict(case=name, **{f: self.h[f].hexdigest()[:32] for f in FIELDS}))
+        return json.dumps(dict(case=name, **{f: h.hexdigest()[:32] for f, h in self.h.items()}))
 
 
 def run_script(st, model, c, n_cu, add, gen_frames=None):
@@ -212,17 +214,64 @@ def run(lib, emulator, variants=False):
             print(variant_q8_case(lib, cid, n_cu).line("quant_mixednet/" + cid), flush=True)
 
 
+def run_post(lib):
+    """mww_stream_metrics, _operating_points, _operating_summary, _detections and _mine on the probability set of
+    tests/operating_point_checks.py: one line per case of its CASES table (metrics at every window, the grid, the summary),
+    one per (window, cooldown, skip, cutoff) of the detection sweep of tests/stream_detect_checks.py (events, track counts,
+    best indices, score bits; the clips, events and counts of mining at two max_new, every track ambient)."""
+    import itertools
+    import engine_checks as ec
+    import operating_point_checks as oc
+    import stream_detect_checks as dc
+    import streaming_checks as sc
+    from microwakeword_amd import native
+    print(json.dumps(dict(library=lib.version())), flush=True)   # the stamp of the library the hashes are of: not compared
+    st = sc.streaming.StreamingModel(sc.make_model(lib, ec.DEF, 52)[1], 1, "stream").native
+    inp = oc.inputs()
+    n = len(inp.lengths)
+    st.set_probs(inp.flat)
+
+    def add(H, field, out):
+        for a in out:
+            H.h[field].update(np.ascontiguousarray(a).tobytes())
+
+    for name, (cooldown, skip, parity, cutoffs) in oc.CASES.items():
+        H = Hashes(("metrics", "points", "summary"))
+        kind = np.array([(t + parity) % 2 for t in range(n)], np.int32)
+        for w in oc.WINDOWS:
+            add(H, "metrics", st.metrics(inp.off, kind, cutoffs, w, skip, cooldown))
+        add(H, "points", st.operating_points(inp.off, kind, oc.WINDOWS, cutoffs, skip, cooldown))
+        add(H, "summary", st.operating_summary(inp.off, kind, oc.WINDOWS, cutoffs, skip, cooldown, 3, 0.02))
+        print(H.line("post/grid/" + name), flush=True)
+    win = np.array([(0, t % 3, max(length - t % 3, 0), 0, 40 * int(inp.off[t])) for t, length in enumerate(inp.lengths)], native.WINDOW_DTYPE)
+    sweep = list(itertools.product(dc.WINDOWS, dc.COOLDOWNS, dc.SKIPS, dc.CUTOFFS)) + [
+        (1, dc.SEG - 1, 0, 0.0), (5, dc.SEG, 25, 0.37), (1, dc.SEG + 1, 0, 0.5), (1, 2500, 0, 0.0)]   # check_against_restatement's
+    for window, cooldown, skip, cutoff in sweep:
+        H = Hashes(("detections", "mine"))
+        kind = np.array([(t + dc.CUTOFFS.index(cutoff)) % 2 for t in range(n)], np.int32)
+        add(H, "detections", st.detections(inp.off, kind, cutoff, window, skip, cooldown))
+        for max_new in (7, 2000):
+            clips, events, total, counts = st.mine(win, inp.off, cutoff, window, cooldown, 2, 3, max_new)
+            add(H, "mine", (clips, events, np.int64(total), counts))
+        print(H.line("post/events/w%d_cd%d_skip%d_cut%g" % (window, cooldown, skip, cutoff)), flush=True)
+    st.close()
+
+
 def compare(path_a, path_b):
-    a, b = ({r["case"]: r for r in map(json.loads, open(p))} for p in (path_a, path_b))
+    for p in (path_a, path_b):
+        for r in map(json.loads, open(p)):
+            if "library" in r:
+                print("%s: %s" % (p, r["library"]))
+    a, b = ({r["case"]: r for r in map(json.loads, open(p)) if "case" in r} for p in (path_a, path_b))
     bad = sorted(set(a) ^ set(b))
     for name in a:
         if name in b:
-            for f in FIELDS:
+            for f in (k for k in a[name] if k != "case"):
                 same = a[name][f] == b[name][f]
                 print("%-44s %-9s %s %s %s" % (name, f, a[name][f], b[name][f], "equal" if same else "DIFFERENT"))
                 if not same:
                     bad.append(name + " " + f)
-    print("%d cases, %d hashes: %s" % (len(a), len(a) * len(FIELDS), "all equal" if not bad else "NOT equal: " + ", ".join(bad)))
+    print("%d cases, %d hashes: %s" % (len(a), sum(len(r) - 1 for r in a.values()), "all equal" if not bad else "NOT equal: " + ", ".join(bad)))
     return 1 if bad else 0
 
 
@@ -232,12 +281,16 @@ def main():
     ap.add_argument("--emulator", action="store_true", help="the emulator-sized part of the cases (a library of tests/hipemu)")
     ap.add_argument("--variants", action="store_true", help="also the float cases of tests/mixednet_variant_checks.py (residual, pooled, attention) and the calibration + int8 "
                     "cases of tests/quant_mixednet_checks.py (residual, pooled)")
+    ap.add_argument("--post", action="store_true", help="the five entry points on the probabilities a stream holds, instead of the kernels' cases")
     ap.add_argument("--compare", nargs=2, metavar="JSONL")
     a = ap.parse_args()
     if a.compare:
         sys.exit(compare(*a.compare))
     from microwakeword_amd import native
-    run(native.NativeLib.get(a.lib), a.emulator, a.variants)
+    if a.post:
+        run_post(native.NativeLib.get(a.lib))
+    else:
+        run(native.NativeLib.get(a.lib), a.emulator, a.variants)
 
 
 if __name__ == "__main__":
