@@ -14,8 +14,11 @@
   * ``QuantizedModel``  those parameters, ``save`` / ``load`` as a data-only ``.npz`` and a readable ``summary``.
 
 Nothing here is pinned to TFLite (no TensorFlow on this path); the int8 kernel is pinned to tests/quant_oracle.py.
-``quantize_mixednet.py`` (residual connections, a pooled head) and ``quantize_graph.py`` (Inception: a graph with
-concatenations) build on the fixed-point helpers, the op builders and the ``QuantizedModel`` class below.
+``plan_ops`` / ``tensor_names`` / ``quantize_weights`` are the one walk over a MixedNet description, residual blocks (kinds
+``res`` / ``pw_add``) included: its layer sequence is ``layout.mixednet_layers``, its MixConv fusion ``layout.mixconv_fuse``.
+``quantize_mixednet.py`` (residual connections, a pooled head: the normalised description, the refusals, TFLite's int8 Add and
+its model class) and ``quantize_graph.py`` (Inception: a graph with concatenations) build on it, on the fixed-point helpers, the
+op builders and the ``QuantizedModel`` class below.
 """
 from __future__ import annotations
 
@@ -25,7 +28,7 @@ from typing import List, Sequence
 
 import numpy as np
 
-from .layout import FEATURE_BINS
+from .layout import FEATURE_BINS, mixconv_fuse, mixednet_layers, split_channels   # noqa: F401 - split_channels: by this name too
 
 BN_EPS = 1e-3
 INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
@@ -136,28 +139,26 @@ def fold_bn(kernel, gamma, beta, mean, var):
 # ---------------------------------------------------------------------------------------------------- the graph
 
 def plan_ops(desc: dict):
-    """The plan's layers of a stream description: [(kind, block, repeat, kernel sizes, cin, cout)], kind "mix" (MixConv,
-    only when its largest kernel exceeds 1) or "pw"."""
-    ops, c = [], int(desc["conv1_filters"])
-    for b, (rep, ks, f) in enumerate(desc["blocks"]):
-        ks = [int(k) for k in ks]
-        for r in range(int(rep)):
-            if max(ks) > 1:
-                ops.append(("mix", b, r, ks, c, c))
-            ops.append(("pw", b, r, ks, c, int(f)))
-            c = int(f)
-    return ops
+    """The plan's layers of a stream description (``layout.mixednet_layers`` behind conv1; ``residual`` defaults to none):
+    [(kind, block, repeat, kernel sizes, cin, cout)], kind "res" (a block's residual 1x1, repeat None), "mix" (MixConv, only
+    when its largest kernel exceeds 1), "pw" (1x1 + ReLU) or "pw_add" (linear 1x1, then ADD + ReLU)."""
+    blocks = [(int(rep), [int(k) for k in ks], int(f)) for rep, ks, f in desc["blocks"]]
+    return mixednet_layers(int(desc["conv1_filters"]), blocks, desc.get("residual") or [0] * len(blocks))
 
 
 def tensor_names(desc: dict) -> List[str]:
+    """the calibrated tensors in order: a "res" adds ``block{b}.residual``, a "pw_add" its ADD output behind its 1x1's"""
     names = ["input", "conv1"]
     for kind, b, r, _, _, _ in plan_ops(desc):
-        names.append("block%d.r%d.%s" % (b, r, "mixconv" if kind == "mix" else "pointwise"))
+        if kind == "res":
+            names.append("block%d.residual" % b)
+        elif kind == "mix":
+            names.append("block%d.r%d.mixconv" % (b, r))
+        else:
+            names.append("block%d.r%d.pointwise" % (b, r))
+            if kind == "pw_add":
+                names.append("block%d.r%d.add" % (b, r))
     return names + ["dense"]
-
-
-def split_channels(C, n):
-    return [C // n + (C % n if g == 0 else 0) for g in range(n)]
 
 
 def _r4(n):
@@ -196,15 +197,7 @@ def requant_op(scales, kind, wq, ws, b, t_in, t_out, tensors=None):
 def fold_mixconv(it, ks, ci):
     """the next MixConv groups of ``it`` (per group kernel [k,1,gc,1] and bias) as one [K, ci] table, taps right-aligned, and
     the bias [ci]"""
-    K = max(ks)
-    fw = np.zeros((K, ci), np.float32)
-    fb = np.zeros(ci, np.float32)
-    c0 = 0
-    for gc, kk in zip(split_channels(ci, len(ks)), ks):
-        fw[K - kk:, c0:c0 + gc] = next(it).reshape(kk, gc)
-        fb[c0:c0 + gc] = next(it).reshape(gc)
-        c0 += gc
-    return fw, fb
+    return mixconv_fuse(list(zip(split_channels(ci, len(ks)), ks)), it)
 
 
 def pointwise_op(scales, it, kind, ci, co, t_in, t_out):
@@ -349,31 +342,45 @@ class QuantizedModel:
         return "\n".join(lines)
 
 
-def quantize_weights(desc: dict, weights: Sequence[np.ndarray], ranges) -> QuantizedModel:
-    """The int8 model of a stream description, its Keras-order float weights (``Model.get_weights()``: conv1 kernel; per
-    block and repeat: each MixConv group's kernel [k,1,gc,1] and bias, the 1x1 kernel, BN gamma / beta / moving mean /
-    moving variance; dense kernel [T_f*C, 1] and bias) and the calibrated ranges [n_tensors, 2]."""
-    ranges = checked_ranges(ranges, len(tensor_names(desc)))
+def quantize_weights(desc: dict, weights: Sequence[np.ndarray], ranges, model_class=QuantizedModel, dense_frames=None) -> QuantizedModel:
+    """The int8 model (a ``model_class``) of a stream description, its Keras-order float weights (``Model.get_weights()``: conv1
+    kernel; per block: the residual's 1x1 kernel and BN gamma / beta / moving mean / moving variance when it has one, then per
+    repeat each MixConv group's kernel [k,1,gc,1] and bias, the 1x1 kernel and its BN; dense kernel [T_f*C, 1] and bias) and
+    the calibrated ranges [n_tensors, 2].  ``dense_frames``: the frames the Dense must cover (default: what its kernel holds)."""
+    from .quantize_mixednet import add_params   # (that module imports this one)
+    names = tensor_names(desc)
+    ranges = checked_ranges(ranges, len(names))
     scales, zps = activation_table(ranges)
     it = iter(np.asarray(a, np.float32) for a in weights)
     k1 = int(desc["conv1_kernel"])
     c1 = int(desc["conv1_filters"])
     wq, ws = weight_params(next(it).reshape(k1 * FEATURE_BINS, c1), 1)            # [k1,1,40,C1]
     ops = [requant_op(scales, "conv1", wq, ws, np.zeros(c1, np.float32), 0, 1)]
-    t = 1   # the tensor the next layer reads
+    t_in, t, t_res = 1, 2, None   # the tensor the next layer reads, the next tensor, the current block's residual
     for kind, b, r, ks, ci, co in plan_ops(desc):
+        if kind == "res":
+            ops.append(pointwise_op(scales, it, "res", ci, co, t_in, t))
+            t_res = t
+            t += 1
+            continue
         if kind == "mix":
             fw, fb = fold_mixconv(it, ks, ci)
             wq, ws = weight_params(fw, 1)
-            ops.append(requant_op(scales, "mix", wq, ws, fb, t, t + 1))
+            ops.append(requant_op(scales, "mix", wq, ws, fb, t_in, t))
         else:
-            ops.append(pointwise_op(scales, it, "pw", ci, co, t, t + 1))
+            ops.append(pointwise_op(scales, it, kind, ci, co, t_in, t))
+        if kind == "pw_add":
+            ops[-1]["add_tensors"] = (t, t_res, t + 1)
+            ops[-1]["add"] = add_params(scales[t], scales[t_res], scales[t + 1], names[t + 1])
+            t += 1
+        t_in = t
         t += 1
-    ops.append(dense_op(scales, it, int(desc["blocks"][-1][2]), t, t + 1))
+    ops.append(dense_op(scales, it, int(desc["blocks"][-1][2]), t_in, t, td=dense_frames))
+    assert t == len(names) - 1
     if next(it, None) is not None:
         raise ValueError("more weights than the stream description holds")
     lut = logistic_table(scales[-1], zps[-1])
-    return QuantizedModel(desc, scales, zps, ops, lut, ranges.astype(np.float32))
+    return model_class(desc, scales, zps, ops, lut, ranges.astype(np.float32))
 
 
 # ---------------------------------------------------------------------------------------- calibration / public API
@@ -392,12 +399,16 @@ def calibration_frames(data_processor, config) -> np.ndarray:
     return np.concatenate(parts + [np.zeros((0, FEATURE_BINS), np.float32)], 0)
 
 
-def _mixednet_only(model):
+def refuse_inception(model):
     from .layout import InceptionLayout
     if isinstance(getattr(model, "layout", None), InceptionLayout):
         raise NotImplementedError("this module's int8 evaluation covers MixedNet only (an Inception model is calibrated and quantized by "
                                   "quantize_graph.calibrate / quantize_graph.quantize)")
+
+
+def _mixednet_only(model):
     from .streaming import mixednet_variant_flags
+    refuse_inception(model)
     if mixednet_variant_flags(model.flags):   # before any device work: the float stream of such a model takes no int8 parameters
         raise NotImplementedError("the int8 quantized streaming evaluation does not cover MixedNet with "
                                   + ", ".join(mixednet_variant_flags(model.flags))

@@ -31,17 +31,13 @@ from typing import List, Sequence
 import numpy as np
 
 from .layout import FEATURE_BINS
-from .quantize import (BN_EPS, QuantizedModel, _rows_r4, activation_table, checked_ranges, dense_op, logistic_table,
+from .quantize import (BN_EPS, QuantizedModel, _r4, _rows_r4, activation_table, checked_ranges, dense_op, logistic_table,
                        requant_op, round_half_away, weight_params)
 from . import quantize as _mixednet
 
 FAMILY = "graph"
 __all__ = ["FAMILY", "QuantizedGraphModel", "calibrate", "calibration_frames", "concat_classes", "fold_op", "op_sources",
            "quantize", "quantize_weights", "round_half_away", "tensor_names"]
-
-
-def _r4(n):
-    return (int(n) + 3) & ~3
 
 
 def op_sources(desc: dict):
@@ -99,7 +95,7 @@ class QuantizedGraphModel(QuantizedModel):
     weight_scales float32 [cout], bias int32 [cout] (without the input zero point), multiplier, shift int32 [cout],
     tensors = the source tensors then the output tensor); ``lut`` uint8 [256].  ``save`` / ``load`` are the base class's."""
 
-    FAMILY = family = FAMILY
+    FAMILY = FAMILY
     NAME_WIDTH = 28
 
     def __init__(self, desc, scales, zero_points, ops, lut, ranges=None):

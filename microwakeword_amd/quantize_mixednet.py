@@ -1,13 +1,13 @@
 """int8 quantization of a streaming MixedNet with residual connections or a pooled head - ``quantize.py`` extended to the
 models ``mww_stream_create_mixednet_q8`` serves (the <VAR> kernel of csrc/tu_stream_q8.hip), on its helpers and its model class:
 
-  * ``tensor_names``   the calibrated tensors in order: ``input``, ``conv1``; per block ``block{b}.residual`` (when the block
-                       has a residual, in front of its repeats); per repeat ``block{b}.r{r}.mixconv`` (when max(ks) > 1),
+  * ``tensor_names``   (``quantize.tensor_names``; like ``plan_ops`` the one definition) the calibrated tensors in order:
+                       ``input``, ``conv1``; per block ``block{b}.residual`` (when the block has a residual, in front of its repeats); per repeat ``block{b}.r{r}.mixconv`` (when max(ks) > 1),
                        ``block{b}.r{r}.pointwise`` and, in a residual block, ``block{b}.r{r}.add``; ``dense``.
   * ``calibrate``      ``quantize.calibration_frames`` in one stream-mode pass from zero rings on the float kernel with range
                        recording (a kind-3 layer records the 1x1 output before the add and the ADD output as two tensors).
-  * ``quantize``       the int8 parameters (the contract: INTEGRATION.md 6, "residual and pooled MixedNets"; every item our
-                       reading, not pinned to TFLite): everything of the plain MixedNet contract, a residual block's 1x1 and its
+  * ``quantize``       (``quantize.quantize_weights`` on the normalised description) the int8 parameters (the contract:
+                       INTEGRATION.md 6, "residual and pooled MixedNets"; every item our reading, not pinned to TFLite): everything of the plain MixedNet contract, a residual block's 1x1 and its
                        ``r`` linear with their own ranges, TFLite's int8 ``Add`` (left_shift 20) with the ReLU fused, and
                        AVERAGE_POOL_2D / MAX_POOL_2D, which share their input's parameters and add no tensor.
   * ``QuantizedMixedNetModel``  those parameters, ``save`` / ``load`` as a data-only ``.npz`` (``family = "mixednet_variant"``).
@@ -16,13 +16,12 @@ Spatial attention and ``first_conv_filters = 0`` are refused before any device w
 tests/quant_mixednet_oracle.py."""
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import Sequence
 
 import numpy as np
 
-from .layout import FEATURE_BINS
-from .quantize import (QuantizedModel, activation_table, calibration_frames, checked_ranges, dense_op, fold_mixconv,
-                       logistic_table, pointwise_op, quantize_multiplier, requant_op, weight_params)
+from . import quantize as _plain
+from .quantize import QuantizedModel, calibration_frames, plan_ops, quantize_multiplier, refuse_inception, tensor_names   # noqa: F401
 
 FAMILY = "mixednet_variant"
 ADD_LEFT_SHIFT = 20   # TFLite int8 Add
@@ -54,36 +53,6 @@ def _refuse(desc):
         raise NotImplementedError("the int8 quantized streaming evaluation does not cover MixedNet with spatial_attention (the int8 "
                                   "model is a stream-mode model, stream-mode attention has no pinned reading, and TFLite's int8 MUL / "
                                   "Logistic gate is not restated)")
-
-
-def plan_ops(desc: dict):
-    """The plan's layers: [(kind, block, repeat, kernel sizes, cin, cout)], kind "res" (a block's residual 1x1, repeat None),
-    "mix" (MixConv, only when its largest kernel exceeds 1), "pw" (1x1 + ReLU) or "pw_add" (linear 1x1, then ADD + ReLU)."""
-    d = normalized(desc)
-    ops, c = [], d["conv1_filters"]
-    for b, ((rep, ks, f), res) in enumerate(zip(d["blocks"], d["residual"])):
-        if res:
-            ops.append(("res", b, None, ks, c, f))
-        for r in range(rep):
-            if max(ks) > 1:
-                ops.append(("mix", b, r, ks, c, c))
-            ops.append(("pw_add" if res else "pw", b, r, ks, c, f))
-            c = f
-    return ops
-
-
-def tensor_names(desc: dict) -> List[str]:
-    names = ["input", "conv1"]
-    for kind, b, r, _, _, _ in plan_ops(desc):
-        if kind == "res":
-            names.append("block%d.residual" % b)
-        elif kind == "mix":
-            names.append("block%d.r%d.mixconv" % (b, r))
-        else:
-            names.append("block%d.r%d.pointwise" % (b, r))
-            if kind == "pw_add":
-                names.append("block%d.r%d.add" % (b, r))
-    return names + ["dense"]
 
 
 def add_params(s1, s2, s_out, name="add"):
@@ -136,49 +105,16 @@ def quantize_weights(desc: dict, weights: Sequence[np.ndarray], ranges) -> Quant
     BN; dense kernel [T_f*C, 1] - pooled: [C, 1] - and bias) and the calibrated ranges [n_tensors, 2]."""
     desc = normalized(desc)
     _refuse(desc)
-    names = tensor_names(desc)
-    ranges = checked_ranges(ranges, len(names))
-    scales, zps = activation_table(ranges)
-    it = iter(np.asarray(a, np.float32) for a in weights)
-    k1, c1 = desc["conv1_kernel"], desc["conv1_filters"]
-    wq, ws = weight_params(next(it).reshape(k1 * FEATURE_BINS, c1), 1)                # [k1,1,40,C1]
-    ops = [requant_op(scales, "conv1", wq, ws, np.zeros(c1, np.float32), 0, 1)]
-    t_in, t, t_res = 1, 2, None   # the tensor the next layer reads, the next tensor, the current block's residual
-    for kind, b, r, ks, ci, co in plan_ops(desc):
-        if kind == "res":
-            ops.append(pointwise_op(scales, it, "res", ci, co, t_in, t))
-            t_res = t
-            t += 1
-            continue
-        if kind == "mix":
-            fw, fb = fold_mixconv(it, ks, ci)
-            wq, ws = weight_params(fw, 1)
-            ops.append(requant_op(scales, "mix", wq, ws, fb, t_in, t))
-        else:
-            ops.append(pointwise_op(scales, it, kind, ci, co, t_in, t))
-        if kind == "pw_add":
-            ops[-1]["add_tensors"] = (t, t_res, t + 1)
-            ops[-1]["add"] = add_params(scales[t], scales[t_res], scales[t + 1], names[t + 1])
-            t += 1
-        t_in = t
-        t += 1
-    ops.append(dense_op(scales, it, desc["blocks"][-1][2], t_in, t, td=1 if desc["pool"] else desc["t_final"]))
-    assert t == len(names) - 1
-    if next(it, None) is not None:
-        raise ValueError("more weights than the stream description holds")
-    lut = logistic_table(scales[-1], zps[-1])
-    return QuantizedMixedNetModel(desc, scales, zps, ops, lut, ranges.astype(np.float32))
+    return _plain.quantize_weights(desc, weights, ranges, QuantizedMixedNetModel, 1 if desc["pool"] else desc["t_final"])
 
 
 # ---------------------------------------------------------------------------------------- calibration / public API
 
 def _description(model, stride=None):
     """the stream-mode description of a trained MixedNet ``model``; refuses attention and first_conv_filters = 0"""
-    from .layout import InceptionLayout, _flag
+    from .layout import _flag
     from .streaming import mixednet_stream_description
-    if isinstance(getattr(model, "layout", None), InceptionLayout):
-        raise NotImplementedError("this module's int8 evaluation covers MixedNet only (an Inception model is calibrated and quantized by "
-                                  "quantize_graph.calibrate / quantize_graph.quantize)")
+    refuse_inception(model)
     stride = int(_flag(model.flags, "stride")) if stride is None else int(stride)
     return mixednet_stream_description(model.flags, model.layout.frames, stride, "stream")   # raises for both refusals
 

@@ -12,6 +12,9 @@ reference runs with its ``--test_*`` flags (microwakeword/model_train_eval.py:13
   * ``streaming_model_roc``       test.py:293-403 ``tflite_streaming_model_roc``
   * ``model_accuracy``            test.py:207-290 ``tf_model_accuracy`` (``--test_tf_nonstreaming``)
 
+The MixedNet descriptions (``stream_description``, ``mixednet_stream_description``) read the flag set through
+``layout.block_lists`` / ``layout.MixedNetTopology`` - the one topology walk - and add only their own refusals.
+
 State carry-over, by our reading of test.py:321-324,355-365: the interpreter is created once and never reset, so the rings
 carry over from the ambient tracks (in ``get_data`` order) to the positive tracks of the test set (negatives are skipped
 without being fed).  ``streaming_model_roc`` reproduces exactly that.
@@ -24,23 +27,11 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import native
-from .layout import FEATURE_BINS, InceptionLayout, _flag, parse
+from .layout import FEATURE_BINS, InceptionLayout, MixedNetTopology, _flag, block_lists, parse
 
 SCALE_U16 = np.float32(0.0390625)
 CUTOFFS = np.arange(0, 1.01, 0.01)   # test.py:331
 OP_WINDOWS = tuple(range(1, 11))     # sliding-window sizes of the operating-point grid (the reference evaluates 5 alone)
-
-
-def _block_lists(flags):
-    """the per-block lists of a MixedNet flag set: pointwise filters, repeats, kernel-size tuples, residual flags (as given)"""
-    pf = [int(f) for f in parse(_flag(flags, "pointwise_filters"))]
-    rep = [int(r) for r in parse(_flag(flags, "repeat_in_block"))]
-    ksz = [tuple(int(k) for k in (ks if isinstance(ks, (list, tuple)) else (ks,))) for ks in parse(_flag(flags, "mixconv_kernel_sizes"))]
-    res = list(parse(_flag(flags, "residual_connection")))
-    for lst in (rep, ksz, res):
-        if len(pf) != len(lst):
-            raise ValueError("all input lists have to be the same length")   # mixednet.py:298-305
-    return pf, rep, ksz, res
 
 
 def stream_description(flags, t_final: int, frames: int, stride: int, mode: str) -> dict:
@@ -48,7 +39,7 @@ def stream_description(flags, t_final: int, frames: int, stride: int, mode: str)
     NotImplementedError naming the flag."""
     if mode not in native.STREAM_MODES:
         raise ValueError("mode must be 'stream' or 'non_stream'")
-    pf, rep, ksz, res = _block_lists(flags)
+    pf, rep, ksz, res = block_lists(flags)
     unsupported = []
     if int(_flag(flags, "first_conv_filters")) <= 0:
         unsupported.append("first_conv_filters = 0")
@@ -87,24 +78,19 @@ def mixednet_stream_description(flags, frames: int, stride: int, mode: str) -> d
     itself cannot be built."""
     if mode not in native.STREAM_MODES:
         raise ValueError("mode must be 'stream' or 'non_stream'")
-    pf, rep, ksz, res = _block_lists(flags)
-    res = [int(bool(r)) for r in res]
-    f0, k1 = int(_flag(flags, "first_conv_filters")), int(_flag(flags, "first_conv_kernel_size"))
-    if f0 <= 0:
+    topo = MixedNetTopology(flags, frames)
+    if topo.conv1 is None:
         raise NotImplementedError("streaming evaluation does not cover MixedNet with first_conv_filters = 0")
-    if int(stride) != int(_flag(flags, "stride")):
+    if int(stride) != topo.stride:
         raise ValueError("the streaming stride (%d) must be the model's --stride (%d)" % (stride, _flag(flags, "stride")))
-    t_final = (int(frames) - k1) // int(stride) + 1 - sum(r * (max(ks) - 1) for r, ks in zip(rep, ksz))
-    if int(frames) < k1 or t_final < 1:
+    if topo.t_final < 1:   # the frame counts only fall along the layers
         raise ValueError("spectrogram of %d frames is too short for this network" % int(frames))
-    attention = int(bool(_flag(flags, "spatial_attention"))) if t_final > 1 else 0   # mixednet.py:362
-    pool = (("max" if _flag(flags, "max_pool") else "average") if _flag(flags, "pooled") else 0) if t_final > 1 else 0
-    if attention and t_final < 4:
-        raise ValueError("spatial attention needs at least 4 frames after the last block")
+    attention, pool, _ = topo.head()
     if attention and mode == "stream":
         raise NotImplementedError("streaming evaluation does not cover MixedNet with " + STREAM_ATTENTION_REASON)
-    return dict(conv1_filters=f0, conv1_kernel=k1, stride=int(stride), blocks=list(zip(rep, ksz, pf)), t_final=int(t_final),
-                frames=int(frames), mode=mode, residual=res, attention=attention, pool=pool)
+    return dict(conv1_filters=topo.conv1_filters, conv1_kernel=topo.conv1_kernel, stride=int(stride),
+                blocks=list(zip(topo.repeats, topo.kernels, topo.filters)), t_final=topo.t_final, frames=int(frames), mode=mode,
+                residual=[int(bool(r)) for r in topo.residual], attention=int(attention), pool={0: 0, 1: "average", 2: "max"}[pool])
 
 
 def check_evaluation_topology(flags, frames: int, stride: int, modes: Sequence[str], int8: bool = False, int8_variants: bool = False):

@@ -74,6 +74,33 @@ def test_mixconv_fusion_matches_oracle_right_alignment():
         lay.MixedNetLayout(dict(DEF, mixconv_kernel_sizes="[5],[11,7],[13],[21]"), 194)
 
 
+@pytest.mark.parametrize("name", ["default", "notebook", "synthetic"])
+def test_the_two_mixednet_layouts_map_weights_alike(name):
+    """On a flag set both accept, MixedNetLayout and GraphMixedNetLayout are one weight mapping (layout.NativeWeights over one
+    topology walk): equal native vectors, gradient mask, segment sizes, Keras arrays back and final map.  Only the Keras
+    variable names differ (b0.dw0.kernel / b0.r0.dw0.kernel)."""
+    import engine_checks as ec
+    flags, T = {"default": (ec.DEF, 194), "notebook": (ec.NOTEBOOK, 204), "synthetic": (synthetic.DEFAULT_MIXEDNET_FLAGS, 194)}[name]
+    a, b = lay.MixedNetLayout(flags, T), lay.GraphMixedNetLayout(flags, T)
+    assert [(s, k) for _, s, k in a.keras_vars] == [(s, k) for _, s, k in b.keras_vars]
+    rng = np.random.default_rng(7)
+    ws = [rng.normal(0.0, 0.5, s).astype(np.float32) for _, s, _ in a.keras_vars]
+    (pa, sa), (pb, sb) = a.pack(ws), b.pack(ws)
+    assert pa.size == a.n_params == b.n_params and sa.size == a.n_state == b.n_state
+    np.testing.assert_array_equal(pa, pb)
+    np.testing.assert_array_equal(sa, sb)
+    np.testing.assert_array_equal(a.grad_mask(), b.grad_mask())
+    assert a.grad_mask().sum() == a.keras_param_counts()[1] == b.keras_param_counts()[1]
+    assert [n for _, n in a.segments()] == [n for _, n in b.segments()]
+    back_a, back_b = a.unpack(pa, sa), b.unpack(pa, sa)
+    assert len(back_a) == len(back_b) == len(ws)
+    for w, x, y in zip(ws, back_a, back_b):
+        assert x.shape == y.shape == w.shape
+        np.testing.assert_array_equal(x, y)
+        np.testing.assert_array_equal(x, w)
+    assert (a.t_last, a.c_last) == (b.t_last, b.c_last)
+
+
 def test_initial_weights_follow_keras_defaults():
     L = lay.MixedNetLayout(DEF, 194)
     ws = initial_weights(L, seed=0)

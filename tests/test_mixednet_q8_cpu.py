@@ -75,6 +75,30 @@ def test_tensor_names_with_residuals_on_some_blocks_and_repeats():
     assert qmx.tensor_names(plain) == quantize.tensor_names(plain)
 
 
+@pytest.mark.parametrize("blocks,tf", [([(2, (3,), 8), (1, (3, 5), 7), (1, (1,), 6)], 3), ([(1, (3,), 7)], 1)], ids=["multi-kernel", "t_final=1"])
+def test_both_quantizers_are_one_on_a_plain_description(blocks, tf):
+    """quantize.quantize_weights and quantize_mixednet.quantize_weights are one walk: on a plain description (no residual, no
+    head option) they give the same native arrays and the same summary; only the stored ``desc`` differs (as given / normalised)."""
+    plain = mc.vc.sw.desc_of(6, 5, 2, blocks, tf)
+    general = mc.vc.desc_of(6, 5, 2, blocks, tf)
+    lay = GraphMixedNetLayout(mc.vc.flags_of(general), plain["frames"])
+    assert lay.t_last == tf
+    rng = np.random.default_rng(11)
+    ws = [rng.normal(0.0, 0.5, s).astype(np.float32) for _, s, _ in lay.keras_vars]
+    ws = [np.abs(w) + np.float32(0.25) if n.endswith(("gamma", "moving_variance")) else w for (n, _, _), w in zip(lay.keras_vars, ws)]
+    names = quantize.tensor_names(plain)
+    assert names == qmx.tensor_names(general) and len(names) == 3 + sum(r * (1 + (max(ks) > 1)) for r, ks, _ in blocks)
+    lo = -rng.random(len(names)) * 4.0
+    ranges = np.stack([lo, lo + 0.5 + rng.random(len(names)) * 8.0], 1)
+    models = [q.quantize_weights(d, ws, ranges) for q in (quantize, qmx) for d in (plain, general)]
+    assert [type(m) for m in models] == [quantize.QuantizedModel] * 2 + [qmx.QuantizedMixedNetModel] * 2
+    assert models[0].desc == plain and models[2].desc == models[3].desc == qmx.normalized(general)
+    for m in models[1:]:
+        for a, b in zip(models[0].packed(), m.packed()):
+            assert np.asarray(a).dtype == np.asarray(b).dtype and np.array_equal(a, b)
+        assert m.summary() == models[0].summary()
+
+
 def test_quantized_parameters_follow_the_contract():
     cid = "res-consecutive_cin-eq-f_rep3_nodw_g2_s1-k1eq_avg-tf2"
     b, qm = mc.built(cid), mc.oracle_model(cid)
