@@ -604,6 +604,21 @@ int mww_stream_operating_summary(mww_stream* s, const int64_t* offsets, const in
  * are those of mww_stream_run_host on the same frames, bit for bit. */
 int mww_stream_num_tensors(const mww_stream* s);
 int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_frames, float* ranges);
+/* The same calibration over windows of resident stores (csrc/tu_stream_calibrate.hip): mww_stream_run over
+ * `tracks` with the <REC> form of the float kernel, from the float state the stream has, which it carries on - whether or not
+ * mww_stream_set_quantized has loaded parameters (the float weights stay; the ranges are the same).  Probabilities, logits,
+ * out_offsets and the float rings are those of mww_stream_run on the same tracks on a float stream, bit for bit.
+ *   tracks   every track's pad_rows + copy_rows must be a multiple of the stream's stride (MWW_ERR_INVALID naming the track
+ *            otherwise): then no frame is dropped between tracks and the call is one concatenated stream, which is what a
+ *            converter's calibrator sees.  n_tracks == 0 is MWW_ERR_INVALID.
+ *   ranges   [n_tensors][2].  ranges[0], the input tensor: min / max over every frame fed, the pad_rows zero frames included, a
+ *            u16 store value scaled by 0.0390625 as the kernels read it.  ranges[t], t >= 1: the fold, in workgroup order, of the
+ *            launch's per-workgroup partial rows.  Both reductions run on the device (LDS folds of fixed order, no atomics);
+ *            the host reads n_tensors * 8 bytes and uploads nothing but the call's tables.
+ * `ranges` equals what mww_stream_calibrate_host returns from a stream in the same state on the host rows of the same windows
+ * concatenated (zero rows for the padding).  A stream without the int8 entry points answers as mww_stream_calibrate_host does.
+ * Returns the number of outputs, or an error < 0. */
+int64_t mww_stream_calibrate(mww_stream* s, const mww_window* tracks, int64_t n_tracks, int64_t* out_offsets, float* ranges);
 /* Loads int8 parameters; from then on mww_stream_run / _run_host run the int8 kernel (the float weights stay for
  * calibration) and mww_stream_reset fills every ring with its tensor's zero point.  The plan's ops, in order: conv1, every
  * layer (MixConv: depthwise taps of all groups fused to K = max kernel taps, right-aligned; 1x1), the Dense.

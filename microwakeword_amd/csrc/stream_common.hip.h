@@ -338,6 +338,17 @@ int stream_create(mww_ctx* ctx, SModel* m, int rc_plan, mww_stream** out);
     if (e_ != hipSuccess) return mww::set_error(MWW_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
   } while (0)
 
+// tu_stream_calibrate.hip: the device half of mww_stream_calibrate.  s->rec holds the <REC> launch's partial rows
+// [2 x CU][n_tensors][2], then the input partials [2 x CU][2], then the folded ranges [n_tensors][2].
+struct SCalBuf {
+  float *rec, *in_part, *ranges;
+};
+int calibrate_buffers(mww_stream* s, SCalBuf* b);   // grows s->rec (the device is current)
+// queues the input-range launch over the n_frames virtual frames of a prepared call; *n_in: the partials it writes
+int calibrate_input(mww_stream* s, const SStores& S, const SCall& a, const SCalBuf& b, int64_t n_frames, int* n_in);
+// folds the input partials and the s->grid partial rows of the launch just made on the device, reads n_tensors * 8 bytes back
+int calibrate_fold(mww_stream* s, const SCalBuf& b, int n_in, float* ranges);
+
 inline int unsupported(const std::string& m) { return mww::set_error(MWW_ERR_UNSUPPORTED, m.c_str()); }
 
 template <class T>

@@ -20,8 +20,9 @@
 // state, so no tile reads a ring another tile writes).  Every sum runs in a fixed order: no atomics, runs are bit-identical.
 //
 // Here: the float MixedNet kernel and the float half of the MixedNet model part (Keras-order weight folding, launch), and
-// the host path of EVERY stream - creation, reset, the float and the int8 launch epilogue, calibration,
-// mww_stream_set_quantized - written once against SModel (stream_common.hip.h); the conv/BN graph model part and its two
+// the host path of EVERY stream - creation, reset, the float and the int8 launch epilogue, calibration (over host frames, and
+// over resident windows with the reductions of tu_stream_calibrate.hip), mww_stream_set_quantized - written once against SModel
+// (stream_common.hip.h); the conv/BN graph model part and its two
 // creators are tu_stream_graph.hip / tu_stream_graph_q8.hip.  What is computed FROM the probabilities a stream holds - the
 // detection metrics (mww_stream_metrics), the operating-point grid, detections, mining - is tu_stream_oppoints.hip,
 // tu_stream_detect.hip and tu_stream_mine.hip over stream_post.hip.h.  A MixedNet with residual connections, a pooled head or
@@ -628,6 +629,45 @@ int mww_stream_calibrate_host(mww_stream* s, const float* frames, int64_t n_fram
       ranges[2 * t + 1] = fmaxf(ranges[2 * t + 1], part[((size_t)g * nt + t) * 2 + 1]);
     }
   return MWW_OK;
+}
+
+// The same over windows of resident stores: mww_stream_run with the <REC> form, the input range and the fold of the partial
+// rows on the device (tu_stream_calibrate.hip).  Every track a whole number of strides, so the call is one concatenated stream.
+int64_t mww_stream_calibrate(mww_stream* s, const mww_window* tracks, int64_t n_tracks, int64_t* out_offsets, float* ranges) {
+  if (!s || !ranges || !out_offsets || (n_tracks > 0 && !tracks)) return mww::set_error(MWW_ERR_INVALID, "null argument");
+  if (!s->model->int8) return no_int8(s);
+  if (n_tracks <= 0) return mww::set_error(MWW_ERR_INVALID, "calibration needs at least one track");
+  const int nt = s->model->n_tensors, stride = s->model->g.stride;
+  for (int64_t t = 0; t < n_tracks; ++t) {
+    if (tracks[t].store < 0) return mww::set_error(MWW_ERR_INVALID, "track refers to a store that was not uploaded");
+    const int64_t rows = (int64_t)tracks[t].pad_rows + tracks[t].copy_rows;
+    if (tracks[t].pad_rows >= 0 && tracks[t].copy_rows >= 0 && rows % stride)
+      return mww::set_error(MWW_ERR_INVALID, ("calibration track " + std::to_string(t) + " has " + std::to_string(rows) +
+                                              " rows, not a multiple of the stride " + std::to_string(stride)).c_str());
+  }
+  if (!s->weights_set) return mww::set_error(MWW_ERR_STATE, "calibration runs the float weights: mww_stream_set_weights first");
+  if (s->model->g.mode != MWW_STREAM_MODE_STREAM) return mww::set_error(MWW_ERR_STATE, "calibration runs a stream-mode object");
+  SCHK(hipSetDevice(s->device));
+  SCalBuf b;
+  int rc = calibrate_buffers(s, &b);
+  if (rc) return rc;
+  SStores S;
+  SCall a;
+  int grid = 0, n_in = 0;
+  const int64_t n_out = prepare_call(s, tracks, n_tracks, out_offsets, 0, S, a, &grid);
+  if (n_out < 0) return n_out;
+  if (n_out == 0) {   // no frame fed: empty ranges, as the host form
+    for (int t = 0; t < nt; ++t) {
+      ranges[2 * t] = INFINITY;
+      ranges[2 * t + 1] = -INFINITY;
+    }
+    return 0;
+  }
+  if ((rc = calibrate_input(s, S, a, b, n_out * stride, &n_in))) return rc;
+  const int64_t n = launch_float(s, S, a, grid, b.rec);
+  if (n < 0) return n;
+  if ((rc = calibrate_fold(s, b, n_in, ranges))) return rc;
+  return n;
 }
 
 int mww_stream_read(mww_stream* s, float* probs, float* logits, int64_t n) {

@@ -336,7 +336,12 @@ class FeatureHandler:
                                "there is no CPU batch-assembly path")
 
     def _build_sampler(self):
-        live = [p for p in self.feature_providers if p.get_mode_size("training")]
+        self._sampler = self._sampler_for(self.feature_providers)
+
+    @staticmethod
+    def _sampler_for(providers):
+        """the sampler description (``mww_sampler_desc``, the arrays it points into, the providers it covers) of ``providers``"""
+        live = [p for p in providers if p.get_mode_size("training")]
         if not live:
             raise ValueError("no provider has training spectrograms")
         sw = np.array([p.sampling_weight for p in live], np.float64)
@@ -364,7 +369,7 @@ class FeatureHandler:
         d.set_len = arrs["ln"].ctypes.data_as(C.POINTER(C.c_int32))
         d.cutoff_offsets = arrs["coffs"].ctypes.data_as(C.POINTER(C.c_int32))
         d.cutoffs = arrs["cuts"].ctypes.data_as(C.POINTER(C.c_int32))
-        self._sampler = (d, arrs, live)
+        return d, arrs, live
 
     # ---- RNG plumbing: the sampler continues Python's and numpy's global MT19937 streams
     @staticmethod
@@ -475,6 +480,29 @@ class FeatureHandler:
         return dict(windows=buf["win"][order], masks=buf["masks"][order][:, :nm], labels=labels[order], weights=weights[order],
                     n_time=tc, n_freq=fc, order=order, provider=prov, sample=buf["samp"].copy(),
                     draw_windows=buf["win"].copy(), draw_masks=buf["masks"].copy())
+
+    def draw_seeded_windows(self, batch_size, features_length, seed=0):
+        """The ``windows`` of one ``draw_training_batch`` (default strategy and policy, no masks) drawn from two MT19937
+        states built from ``seed`` - ``random.Random(seed)`` and ``numpy.random.RandomState(seed)`` - over the providers that
+        own rows (mined providers are skipped: their clips come and go with the rounds).  The global generators, the private
+        streams, a running prefetcher and the cached sampler are left exactly as they are."""
+        self._need_engine()
+        d, arrs, _ = self._sampler_for([p for p in self.feature_providers if not isinstance(p, MinedFeatureProvider)])
+        if any(s < 0 or s == native.STRATEGIES["none"] for s in arrs["strat"]):
+            raise ValueError("a provider's truncation strategy cannot form a fixed-length training batch")
+        B = int(batch_size)
+        py = np.array(random.Random(int(seed)).getstate()[1], dtype=np.uint32)
+        ns = np.random.RandomState(int(seed)).get_state()
+        npst = np.empty(625, np.uint32)
+        npst[:624] = ns[1]
+        npst[624] = ns[2]
+        win, masks = np.zeros(B, native.WINDOW_DTYPE), np.zeros((B, 1, 2), np.int32)
+        prov, samp, order = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        lib = self.engine.nl
+        lib.check(lib.lib.mww_sample_training_batch(
+            C.byref(d), py.ctypes.data_as(C.c_void_p), npst.ctypes.data_as(C.c_void_p), B, int(features_length), 0, 0, 0, 0, -1, 0,
+            *[a.ctypes.data_as(C.c_void_p) for a in (win, masks, prov, samp, order)]))
+        return win[order]
 
     def next_training_batch_on_device(self, batch_size, features_length, truncation_strategy="default",
                                       augmentation_policy=None, class_weights=(1.0, 1.0), weight_broadcast=None,

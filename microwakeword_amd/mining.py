@@ -101,12 +101,14 @@ def mining_config(config, world=1):
         return None
     if not isinstance(given, dict):
         raise ValueError("%s must be a mapping (cutoff, every_evals, ...)" % KEY)
-    unknown = sorted(set(given) - set(DEFAULTS) - {"cutoff"})
+    from .quantize import LOOP_DEFAULTS, loop_settings
+    unknown = sorted(set(given) - set(DEFAULTS) - set(LOOP_DEFAULTS) - {"cutoff"}, key=str)
     if unknown:
-        raise ValueError("%s: unknown key(s) %s; known: cutoff, %s" % (KEY, ", ".join(map(str, unknown)), ", ".join(DEFAULTS)))
+        raise ValueError("%s: unknown key(s) %s; known: cutoff, %s" % (KEY, ", ".join(map(str, unknown)),
+                                                                       ", ".join(list(DEFAULTS) + list(LOOP_DEFAULTS))))
     if "cutoff" not in given:
         raise ValueError("%s: cutoff is required" % KEY)
-    m = dict(DEFAULTS, **given)
+    m = loop_settings(KEY, dict(DEFAULTS, **given))
     try:
         m["cutoff"] = float(m["cutoff"])
         for k in ("every_evals", "first_step", "max_new", "sliding_window_length", "ignore_slices_after_accept", "before", "after"):
@@ -150,17 +152,21 @@ def merge_clips(old, old_round, new, new_round, max_total):
 class MiningRounds:
     """What ``train.train`` does with a ``hard_negative_mining`` mapping: at the evaluation boundaries that are due, one
     ``mine_hard_negatives_on_device`` over the label-0 ``"training"`` tracks with the model's current weights, merged into
-    one mined provider of the handler.  A round draws nothing from Python's or numpy's generators."""
+    one mined provider of the handler.  A round draws nothing from Python's or numpy's generators.  With ``quantized`` a round
+    mines with the int8 model of those weights (``quantize.LoopQuantizer``; ``quantizer``: the one a quantized
+    ``streaming_validation`` already made, to be shared), through the same ``mine_hard_negatives_on_device``."""
 
     FILE = "mined_clips.npz"
 
-    def __init__(self, settings, model, data_processor, config, writer=None):
+    def __init__(self, settings, model, data_processor, config, writer=None, quantizer=None):
         from . import native
+        from .quantize import loop_quantizer
         if getattr(data_processor, "engine", None) is not getattr(model, "engine", object()) or not hasattr(data_processor, "add_mined_provider"):
             raise ValueError("%s needs this package's Model and FeatureHandler on one engine: the clips alias rows resident "
                              "in the model's context" % KEY)
         self.m, self.model, self.fh, self.writer = settings, model, data_processor, writer
         self.stride = int(config["stride"])
+        self.quantizer = loop_quantizer(KEY, settings, model, data_processor, config, quantizer)   # its refusals, before any file
         self.path = os.path.join(config["train_dir"], self.FILE) if writer is not None else None
         self.sm = None
         self.provider = None
@@ -208,9 +214,18 @@ class MiningRounds:
     def round(self, step):
         from . import streaming
         m = self.m
-        if self.sm is None:
-            self.sm = streaming.StreamingModel(self.model, self.stride, m["mode"])   # on the model's own context
-        self.sm.set_weights(self.model.get_weights())
+        if self.quantizer is not None:   # the int8 model of the current weights (calibrated once per boundary, whoever asks)
+            try:
+                q = self.quantizer.at(step)
+            except ValueError as e:
+                raise ValueError("%s: quantized: %s" % (KEY, e)) from None
+            if self.sm is not None:
+                self.sm.native.close()
+            self.sm = streaming.QuantizedStreamingModel(q, self.stride, m["mode"], context=self.model)
+        else:
+            if self.sm is None:
+                self.sm = streaming.StreamingModel(self.model, self.stride, m["mode"])   # on the model's own context
+            self.sm.set_weights(self.model.get_weights())
         own = [p for p in self.fh.feature_providers if p is not self.provider]   # the mined clips alias rows that are scanned anyway
         saved, self.fh.feature_providers = self.fh.feature_providers, own
         try:

@@ -294,7 +294,10 @@ def check_mining_config(flags, model_module, config, world):
     from .train import process_group
     m = mining.mining_config(config, max(int(world), process_group()[1]))
     if m is not None and model_module is mixednet:
-        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], [m["mode"]])
+        # quantized: the int8 family must cover the flag set (residual_connection and pooled are covered in the loop)
+        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], [m["mode"]],
+                                            int8=bool(m.get("quantized")), int8_variants=True)
+    return m
 
 
 def check_streaming_validation_config(flags, model_module, config, world):
@@ -304,7 +307,9 @@ def check_streaming_validation_config(flags, model_module, config, world):
     from .train import process_group
     v = streaming.streaming_validation_config(config, max(int(world), process_group()[1]))
     if v is not None and model_module is mixednet:
-        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], [v["mode"]])
+        streaming.check_evaluation_topology(flags.__dict__, config["spectrogram_length"], config["stride"], [v["mode"]],
+                                            int8=bool(v.get("quantized")), int8_variants=True)
+    return v
 
 
 def _evaluate(flags, model_module, config, device, world):
@@ -336,8 +341,9 @@ def _run(flags, model_module, rank, local_rank, world):
     config = load_config(flags, model_module)
     check_evaluation_flags(flags, model_module, config)   # before training and before train_dir is claimed
     if flags.train:
-        check_mining_config(flags, model_module, config, world)   # likewise
-        check_streaming_validation_config(flags, model_module, config, world)
+        from .quantize import check_shared_calibration
+        check_shared_calibration(check_mining_config(flags, model_module, config, world),   # likewise
+                                 check_streaming_validation_config(flags, model_module, config, world))
     device = flags.device if local_rank is None else local_rank
     if flags.train:
         device = flags.device if local_rank is None else local_rank

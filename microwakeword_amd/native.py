@@ -128,7 +128,7 @@ EXPORTS = [
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
     "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections", "mww_stream_operating_points",
-    "mww_stream_mine", "mww_stream_operating_summary",
+    "mww_stream_mine", "mww_stream_operating_summary", "mww_stream_calibrate",
 ]
 
 
@@ -264,6 +264,8 @@ class NativeLib:
                                                    C.c_void_p, C.c_void_p]
         L.mww_stream_num_tensors.argtypes = [C.c_void_p]
         L.mww_stream_calibrate_host.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float)]
+        L.mww_stream_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+        L.mww_stream_calibrate.restype = C.c_int64
         L.mww_stream_set_quantized.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
         L.mww_stream_q8_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.mww_stream_q8_sizes.restype = C.c_int64
@@ -865,6 +867,16 @@ class Stream:
         self.nl.check(self.nl.lib.mww_stream_calibrate_host(self.h, _fptr(x), x.shape[0], _fptr(r)))
         self.n_out = x.shape[0] // self.stride
         return r
+
+    def calibrate(self, windows: np.ndarray):
+        """``mww_stream_calibrate``: the same recording run over windows of the resident stores (WINDOW_DTYPE, each a whole
+        number of strides), the ranges reduced on the device -> (per-window output offsets [n + 1], float32 [n_tensors, 2])"""
+        tr = np.ascontiguousarray(windows, WINDOW_DTYPE).reshape(-1)
+        off = np.zeros(tr.size + 1, np.int64)
+        r = np.zeros((self.num_tensors(), 2), np.float32)
+        n = self.nl.check(self.nl.lib.mww_stream_calibrate(self.h, vp(tr), tr.size, vp(off), _fptr(r)))
+        self.n_out = int(n)
+        return off, r
 
     def q8_sizes(self):
         ni = C.c_int64()

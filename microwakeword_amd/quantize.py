@@ -12,6 +12,10 @@
                     symmetric per-channel weights, int32 biases, ``QuantizeMultiplier`` requantization, a 256-entry
                     logistic table.  BatchNormalization (eps 1e-3) is folded into the 1x1 weights first.
   * ``QuantizedModel``  those parameters, ``save`` / ``load`` as a data-only ``.npz`` and a readable ``summary``.
+  * ``LoopQuantizer``   the int8 model of the CURRENT weights inside the training loop (``quantized: true`` of the
+                    ``streaming_validation`` / ``hard_negative_mining`` mappings): a fixed calibration set of windows of
+                    resident rows (``calibration_windows``, drawn from generators of its own) calibrated on the device
+                    (``mww_stream_calibrate``), then ``quantize_weights`` as above.  The after-training path does not use it.
 
 Nothing here is pinned to TFLite (no TensorFlow on this path); the int8 kernel is pinned to tests/quant_oracle.py.
 ``plan_ops`` / ``tensor_names`` / ``quantize_weights`` are the one walk over a MixedNet description, residual blocks (kinds
@@ -435,3 +439,157 @@ def quantize(model, ranges) -> QuantizedModel:
     lay = model.layout
     desc = stream_description(model.flags, lay.t_last, lay.frames, int(_flag(model.flags, "stride")), "stream")
     return quantize_weights(desc, model.get_weights(), ranges)
+
+
+# ------------------------------------------------------------- the int8 model inside the training loop
+# The keys ``streaming_validation`` and ``hard_negative_mining`` share, with their defaults
+LOOP_DEFAULTS = dict(quantized=False, calibration_samples=CALIBRATION_SAMPLES, calibration_seed=0)
+FORCED_INPUT_RANGE = (0.0, 26.0)   # the two pixels ``calibration_frames`` forces (utils.py:308-309): the preprocessor's min and max
+
+
+def loop_settings(key, settings):
+    """``quantized`` / ``calibration_samples`` / ``calibration_seed`` of a loop option's mapping ``settings``, checked and
+    normalised in place; a ``ValueError`` names ``key`` and the bad key.  A mapping that gives none of the three is returned as it
+    is - the normalised mapping of a configuration from before these keys stays what it was -, so read them with
+    ``settings.get("quantized")``; one that gives any gets the defaults of the others."""
+    if not any(k in settings for k in LOOP_DEFAULTS):
+        return settings
+    for k, default in LOOP_DEFAULTS.items():
+        settings.setdefault(k, default)
+    q, n, seed = settings["quantized"], settings["calibration_samples"], settings["calibration_seed"]
+    integer = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))   # noqa: E731
+    bad = [k for k, ok in (("quantized", isinstance(q, (bool, np.bool_))), ("calibration_samples", integer(n) and n >= 1),
+                           ("calibration_seed", integer(seed) and 0 <= seed < 2 ** 32)) if not ok]
+    if bad:
+        raise ValueError("%s: %s out of range (quantized true or false; calibration_samples an integer >= 1; calibration_seed an "
+                         "integer in 0 .. 2^32 - 1)" % (key, ", ".join(bad)))
+    settings.update(quantized=bool(q), calibration_samples=int(n), calibration_seed=int(seed))
+    return settings
+
+
+def calibration_windows(data_processor, config, samples=CALIBRATION_SAMPLES, seed=0) -> np.ndarray:
+    """The calibration set of the loop quantizer as window descriptors of rows that are already resident: the ``windows`` of
+    one ``"training"`` draw of ``samples`` spectrograms (``FeatureHandler.draw_seeded_windows``: both MT19937 states built from
+    ``seed``, mined providers skipped; no global or private generator moves), each cut to the frames
+    ``representative_dataset_gen`` feeds (utils.py:303-325): its first ``n * stride`` rows, ``n = len(range(0, T - stride,
+    stride))``.  The cut comes off the end: ``pad_rows`` stays, ``copy_rows`` shrinks.  ``T % stride != 0`` is a ValueError (the
+    reference asserts it); an Inception model is fed one frame per step: pass ``dict(config, stride=1)``."""
+    T, s = int(config["spectrogram_length"]), int(config["stride"])
+    if s < 1 or T % s:
+        raise ValueError("spectrogram_length %d is not a multiple of the stride %d" % (T, s))
+    if int(samples) < 1:
+        raise ValueError("calibration_samples must be >= 1")
+    win = data_processor.draw_seeded_windows(int(samples), T, seed)
+    keep = len(range(0, T - s, s)) * s
+    cut = win["pad_rows"].astype(np.int64) + win["copy_rows"] - keep   # rows off the end (a draw holds T rows per window)
+    if np.any(cut < 0):
+        raise ValueError("a drawn window holds fewer than %d rows" % keep)
+    win["pad_rows"] = np.minimum(win["pad_rows"], keep)
+    win["copy_rows"] = keep - win["pad_rows"]
+    return win
+
+
+def window_host_rows(data_processor, windows) -> np.ndarray:
+    """``windows`` (descriptors of resident rows) as the float32 [n, 40] frames the device serves, concatenated: zero rows for
+    ``pad_rows``, u16 stores scaled by 0.0390625 (``MinedFeatureProvider.host_rows``)."""
+    by_id = {int(sid): (p, key) for p in data_processor.feature_providers if getattr(p, "flat", None) for key, sid in p.store_id.items()}
+    parts = [np.zeros((0, FEATURE_BINS), np.float32)]
+    for w in np.asarray(windows).reshape(-1):
+        p, key = by_id[int(w["store"])]
+        rows, elem = int(w["copy_rows"]), int(w["src_elem"])
+        a = p.flat[key][elem:elem + rows * FEATURE_BINS].reshape(rows, FEATURE_BINS)
+        parts.append(np.zeros((int(w["pad_rows"]), FEATURE_BINS), np.float32))
+        parts.append(a.astype(np.float32) * np.float32(0.0390625) if key == "u16" else a.astype(np.float32))
+    return np.concatenate(parts, 0)
+
+
+def widen_input_range(ranges) -> np.ndarray:
+    """The calibrated ranges with the input tensor's widened to include ``FORCED_INPUT_RANGE``: resident rows cannot carry the two
+    pixels ``calibration_frames`` forces, so the loop quantizer states their effect on the range instead."""
+    r = np.array(ranges, np.float32).reshape(-1, 2)
+    r[0, 0] = min(r[0, 0], np.float32(FORCED_INPUT_RANGE[0]))
+    r[0, 1] = max(r[0, 1], np.float32(FORCED_INPUT_RANGE[1]))
+    return r
+
+
+class LoopQuantizer:
+    """The int8 model of ``model``'s CURRENT weights at a training step (``at``), for ``streaming_validation`` and
+    ``hard_negative_mining`` with ``quantized: true``.  The family module is picked as ``model_train_eval`` picks it
+    (``quantize`` for a plain MixedNet, ``quantize_mixednet`` for residual connections / a pooled head, ``quantize_graph`` for
+    Inception); its ``NotImplementedError`` for spatial attention and ``first_conv_filters = 0`` is raised here, before any device
+    work.  The calibration set (``calibration_windows``) is drawn once, here, from generator states of its own; ``at`` draws
+    nothing.  ONE int8-capable stream on the model's context, created at first use, serves every calibration
+    (``native.Stream.calibrate``: the ranges are reduced on the device)."""
+
+    def __init__(self, model, data_processor, config, samples=CALIBRATION_SAMPLES, seed=0):
+        from . import quantize_graph, quantize_mixednet
+        from .layout import InceptionLayout, _flag
+        from .streaming import mixednet_variant_flags, stream_description
+        self.model = model
+        self.samples, self.seed = int(samples), int(seed)
+        self.graph = isinstance(getattr(model, "layout", None), InceptionLayout)
+        if self.graph:
+            self.module, self.int8 = quantize_graph, True
+            self.desc = quantize_graph._description(model)
+            config = dict(config, stride=1)
+        elif mixednet_variant_flags(model.flags):
+            self.module, self.int8 = quantize_mixednet, True
+            self.desc = quantize_mixednet._description(model, config["stride"])   # refuses attention and first_conv_filters = 0
+        else:
+            import sys
+            self.module, self.int8 = sys.modules[__name__], False
+            lay = model.layout
+            self.desc = stream_description(model.flags, lay.t_last, lay.frames, int(_flag(model.flags, "stride")), "stream")
+        self.stride = int(self.desc["stride"])
+        self.windows = calibration_windows(data_processor, config, self.samples, self.seed)
+        self.stream = None
+        self.calibrations = 0
+        self.ranges = None      # of the last calibration, widened
+        self._cached = None     # (step, quantized model)
+
+    def close(self):
+        if self.stream is not None:
+            self.stream.close()
+            self.stream = None
+
+    def calibrate(self) -> np.ndarray:
+        """the widened ranges of the model's current weights: float rings to zeros, one ``calibrate`` over the windows"""
+        from . import native
+        if self.stream is None:
+            self.stream = (native.GraphStream if self.graph else native.Stream)(self.model.engine, self.desc, int8=self.int8)
+        st = self.stream
+        st.set_weights(np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in self.model.get_weights()]))
+        st.reset()
+        _, ranges = st.calibrate(self.windows)
+        self.calibrations += 1
+        self.ranges = widen_input_range(ranges)
+        return self.ranges
+
+    def at(self, step):
+        """the ``Quantized*Model`` of the current weights, calibrated and quantized once per ``step`` however many ask"""
+        if self._cached is None or self._cached[0] != int(step):
+            ranges = self.calibrate()
+            self._cached = (int(step), self.module.quantize_weights(self.desc, self.model.get_weights(), ranges))
+        return self._cached[1]
+
+
+def check_shared_calibration(*mappings):
+    """the loop options' mappings (None: not configured) that say ``quantized`` must name one calibration set: ValueError"""
+    sets = {(m["calibration_samples"], m["calibration_seed"]) for m in mappings if m is not None and m.get("quantized")}
+    if len(sets) > 1:
+        raise ValueError("streaming_validation and hard_negative_mining are both quantized and disagree on calibration_samples / "
+                         "calibration_seed (%s): they share one calibration set" % " against ".join("%d / %d" % s for s in sorted(sets)))
+
+
+def loop_quantizer(owner_key, settings, model, data_processor, config, shared=None):
+    """The ``LoopQuantizer`` of a loop option whose mapping says ``quantized`` (None otherwise): ``shared`` - the other option's,
+    when it has one - is taken when both name the same calibration set, and a disagreement is a ``ValueError``."""
+    if not settings.get("quantized"):
+        return None
+    if shared is not None:
+        if (shared.samples, shared.seed) != (settings["calibration_samples"], settings["calibration_seed"]):
+            raise ValueError("%s: calibration_samples / calibration_seed (%d / %d) differ from the other quantized loop option's (%d / %d): "
+                             "they share one calibration set" % (owner_key, settings["calibration_samples"], settings["calibration_seed"],
+                                                                  shared.samples, shared.seed))
+        return shared
+    return LoopQuantizer(model, data_processor, config, settings["calibration_samples"], settings["calibration_seed"])

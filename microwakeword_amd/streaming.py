@@ -705,12 +705,14 @@ def streaming_validation_config(config, world=1):
         return None
     if not isinstance(given, dict):
         raise ValueError("%s must be a mapping (target_faph, windows, ...)" % key)
-    unknown = sorted(set(given) - set(VALIDATION_DEFAULTS) - {"target_faph"}, key=str)
+    from .quantize import LOOP_DEFAULTS, loop_settings
+    unknown = sorted(set(given) - set(VALIDATION_DEFAULTS) - set(LOOP_DEFAULTS) - {"target_faph"}, key=str)
     if unknown:
-        raise ValueError("%s: unknown key(s) %s; known: target_faph, %s" % (key, ", ".join(map(str, unknown)), ", ".join(VALIDATION_DEFAULTS)))
+        raise ValueError("%s: unknown key(s) %s; known: target_faph, %s" % (key, ", ".join(map(str, unknown)),
+                                                                            ", ".join(list(VALIDATION_DEFAULTS) + list(LOOP_DEFAULTS))))
     if "target_faph" not in given:
         raise ValueError("%s: target_faph is required" % key)
-    v = dict(VALIDATION_DEFAULTS, **given)
+    v = loop_settings(key, dict(VALIDATION_DEFAULTS, **given))
     try:
         v["target_faph"] = float(v["target_faph"])
         v["windows"] = [int(w) for w in (v["windows"] if isinstance(v["windows"], (list, tuple)) else [v["windows"]])]
@@ -757,9 +759,11 @@ def streaming_metrics(summary):
 class StreamingValidation:
     """What ``train.train`` does with a ``streaming_validation`` mapping: at the evaluation boundaries that are due, the
     streaming FAPH / FRR of the model's current weights at the operating point ``target_faph`` selects, added to the
-    validation metrics.  A validation draws nothing from Python's or numpy's generators."""
+    validation metrics.  A validation draws nothing from Python's or numpy's generators.  With ``quantized`` the validation
+    runs the int8 model of those weights (``quantize.LoopQuantizer``; ``quantizer``: the one a quantized ``hard_negative_mining``
+    already made, to be shared); creating the quantizer draws its calibration set from generator states of its own."""
 
-    def __init__(self, settings, model, data_processor, config, writer=None):
+    def __init__(self, settings, model, data_processor, config, writer=None, quantizer=None):
         if getattr(data_processor, "engine", None) is not getattr(model, "engine", object()) or not hasattr(data_processor, "track_windows"):
             raise ValueError("%s needs this package's Model and FeatureHandler on one engine: the tracks are windows of the stores "
                              "resident in the model's context" % VALIDATION_KEY)
@@ -767,7 +771,10 @@ class StreamingValidation:
         if flags is not None and not isinstance(model.layout, InceptionLayout):
             check_evaluation_topology(flags, config["spectrogram_length"], config["stride"], [settings["mode"]])
         self.v, self.model, self.fh, self.config, self.writer = settings, model, data_processor, config, writer
+        from .quantize import loop_quantizer
+        self.quantizer = loop_quantizer(VALIDATION_KEY, settings, model, data_processor, config, quantizer)   # its refusals
         self.sm = None
+        self.step = 0
         self.boundaries = 0
         self.last = None   # the summary of the last validation
 
@@ -777,12 +784,13 @@ class StreamingValidation:
         return is_last or self.boundaries % self.v["every_evals"] == 0
 
     def validate(self, step):
+        self.step = int(step)
         metrics, self.last = validate_streaming(self.config, self.fh, self.model, self)
         if self.writer is not None:
             self.writer.scalars(step, **metrics)
         import logging
         logging.getLogger("microwakeword_amd.train").info(
-            "Step %d (streaming): Validation: recall = %.2f%% at %.3f false accepts per hour (target %g) with window %d and cutoff %.2f; "
+            "Step %d (" + ("streaming, int8" if self.quantizer is not None else "streaming") + "): Validation: recall = %.2f%% at %.3f false accepts per hour (target %g) with window %d and cutoff %.2f; "
             "%.3f ambient hours, %d positives", step, metrics["streaming_recall"] * 100, metrics["streaming_false_accepts_per_hour"],
             self.v["target_faph"], metrics["streaming_window"], metrics["streaming_cutoff"], metrics["streaming_hours"],
             metrics["streaming_positives"])
@@ -794,12 +802,22 @@ def validate_streaming(config, data_processor, model, state):
     and the stream): the ambient tracks of ``ambient_set``, then the label-1 tracks of ``data_set``, through one native run
     from zeroed rings with the state carried from track to track (the order of ``streaming_model_roc``), one
     ``operating_summary`` and the selection at ``target_faph``.  Returns ``(streaming_* metrics, summary)``; raises ValueError
-    without a positive track or a usable window."""
+    without a positive track or a usable window.  With a quantizer (``quantized``) the run is the int8 model of the current
+    weights: ``LoopQuantizer.at(state.step)``, a ``QuantizedStreamingModel`` of it in the configured mode, the same tracks."""
     v = state.v
-    if state.sm is None:
+    if getattr(state, "quantizer", None) is not None:
+        try:
+            q = state.quantizer.at(state.step)
+        except ValueError as e:   # a non-finite calibrated range, an ADD multiplier TFLite would abort on
+            raise ValueError("%s: quantized: %s" % (VALIDATION_KEY, e)) from None
+        if state.sm is not None:
+            state.sm.native.close()
+        state.sm = QuantizedStreamingModel(q, int(config["stride"]), v["mode"], context=model)
+    elif state.sm is None:
         state.sm = StreamingModel(model, int(config["stride"]), v["mode"])   # on the model's own context
     sm = state.sm
-    sm.set_weights(model.get_weights())
+    if getattr(state, "quantizer", None) is None:
+        sm.set_weights(model.get_weights())
     sm.reset()
     amb, _ = data_processor.track_windows(v["ambient_set"], sm.frames)
     pos, _ = data_processor.track_windows(v["data_set"], sm.frames, only_label=1.0)

@@ -196,6 +196,8 @@ def train(model, config, data_processor, verbose=True):
     mining = mining_config(config, world)   # refusals come before the first step
     from .streaming import STREAMING_METRICS, StreamingValidation, streaming_validation_config
     streaming_settings = streaming_validation_config(config, world)   # likewise
+    from .quantize import check_shared_calibration
+    check_shared_calibration(streaming_settings, mining)   # both quantized: one calibration set, one calibration per boundary
     fast = hasattr(data_processor, "next_training_batch_on_device") and hasattr(model, "train_on_device_batch") \
         and getattr(data_processor, "engine", None) is getattr(model, "engine", object())
     prefetch = int(config.get("prefetch_batches", 4))
@@ -213,6 +215,13 @@ def train(model, config, data_processor, verbose=True):
     streamer = None
     if streaming_settings is not None:
         streamer = StreamingValidation(streaming_settings, model, data_processor, config)   # its refusals, before any file is made
+    # `quantized` (quantize.LoopQuantizer): the rounds take the validation's quantizer when it has one, else one made here - its
+    # refusals (a flag set the int8 family does not cover) come before any file is made too
+    from .quantize import loop_quantizer
+    quantizer = streamer.quantizer if streamer is not None else None
+    if mining is not None:
+        quantizer = loop_quantizer("hard_negative_mining", mining, model, data_processor, config, quantizer)
+    if streamer is not None:
         if chief:
             streamer.writer = _JsonSummary(os.path.join(config["summaries_dir"], "validation_streaming"), "scalars")
         streamer.validate(0)
@@ -257,7 +266,8 @@ def train(model, config, data_processor, verbose=True):
     miner = None
     if mining is not None:
         miner = MiningRounds(mining, model, data_processor, config,
-                             _JsonSummary(os.path.join(config["summaries_dir"], "mining"), "scalars") if chief else None)
+                             _JsonSummary(os.path.join(config["summaries_dir"], "mining"), "scalars") if chief else None,
+                             quantizer=quantizer)
 
     warned_weights = False
     steps_max = int(np.sum(ph["training_steps"]))

@@ -27,6 +27,10 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
         # adds, on the probabilities of the ambient tracks followed by the positives: ONE mww_stream_operating_summary call for
         # 10 windows x 101 cutoffs with the selection against the chain it replaces (mww_stream_operating_points + the host's
         # _operating_grid); equality is checked before anything is timed.  --positives 50000: the validation-sized case
+    python tools/stream_eval_throughput.py --hours 1 --calibrate --calibrate_out profiles/int8_in_loop.txt
+        # adds: mww_stream_calibrate over 500 windows of T - 1 rows of the resident ambient store against mww_stream_calibrate_host
+        # on the host rows of the same windows (the calibration of the int8 model inside the training loop); the
+        # ranges are compared first, then medians of --detections_reps calls each, from zeroed rings
 """
 import argparse
 import json
@@ -75,6 +79,9 @@ def main():
                     help="also time one mww_stream_operating_summary call (10 windows x 101 cutoffs) against mww_stream_operating_points + the host grid")
     ap.add_argument("--summary_out", default=None, help="append the summary leg's times, read-back and scratch sizes to this text file")
     ap.add_argument("--summary_target", type=float, default=0.5, help="target FAPH of the summary leg's selection")
+    ap.add_argument("--calibrate", action="store_true",
+                    help="also time mww_stream_calibrate over 500 resident windows against mww_stream_calibrate_host on their host rows")
+    ap.add_argument("--calibrate_out", default=None, help="append the calibration leg's times to this text file")
     a = ap.parse_args()
     if a.model == "inception":
         T = a.frames or 176
@@ -194,7 +201,66 @@ def main():
         if a.summary_out:
             with open(a.summary_out, "at") as fd:
                 fd.write(summary_text(rec))
+    if a.calibrate:
+        rec["calibrate"] = calibrate_leg(model, a.model, amb, T, a.detections_reps)
+        if a.calibrate_out:
+            with open(a.calibrate_out, "at") as fd:
+                fd.write(calibrate_text(rec))
     print(json.dumps(rec), flush=True)
+
+
+def calibrate_leg(model, kind, amb, T, reps, samples=quantize.CALIBRATION_SAMPLES):
+    """``samples`` windows of T - 1 rows (what calibration_windows leaves of a T-row draw at stride 1) at random rows of the
+    resident ambient store, a tenth of them padded in front: ONE mww_stream_calibrate call against ONE mww_stream_calibrate_host
+    call on the host rows of the same windows, each on a stream of its own, from zeroed rings"""
+    rng = np.random.default_rng(7)
+    win = np.zeros(samples, native.WINDOW_DTYPE)
+    pad = np.where(rng.random(samples) < 0.1, rng.integers(1, T - 1, samples), 0)
+    win["store"], win["pad_rows"], win["copy_rows"] = 0, pad, T - 1 - pad
+    win["src_elem"] = rng.integers(0, amb.shape[0] - T, samples).astype(np.int64) * 40
+    rows = np.concatenate([np.concatenate([np.zeros((int(w["pad_rows"]), 40), np.float32),
+                                           amb[int(w["src_elem"]) // 40:int(w["src_elem"]) // 40 + int(w["copy_rows"])].astype(np.float32)
+                                           * streaming.SCALE_U16]) for w in win])
+    flat = np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in model.get_weights()])
+
+    def stream():
+        if kind == "inception":
+            st = native.GraphStream(model.engine, streaming.graph_stream_description(model.flags, T, 1, "stream"), int8=True)
+        elif streaming.mixednet_variant_flags(model.flags):
+            st = native.Stream(model.engine, streaming.mixednet_stream_description(model.flags, T, 1, "stream"), int8=True)
+        else:
+            return streaming.StreamingModel(model, 1, "stream").native
+        st.set_weights(flat)
+        return st
+    dev, host = stream(), stream()
+    _, got = dev.calibrate(win)
+    want = host.calibrate_host(rows)
+    assert np.array_equal(got, want), "mww_stream_calibrate differs from mww_stream_calibrate_host"
+    assert dev.read().tobytes() == host.read().tobytes()
+    out = {"windows": int(samples), "frames": int(rows.shape[0]), "tensors": int(got.shape[0]), "reps": int(reps),
+           "host_bytes_up": int(rows.nbytes), "device_bytes_back": int(got.nbytes)}
+    for name, st, call in (("calibrate_ms", dev, lambda: dev.calibrate(win)), ("calibrate_host_ms", host, lambda: host.calibrate_host(rows))):
+        ts = []
+        for _ in range(reps + 1):   # (the first call is the warm-up)
+            st.reset()
+            t0 = time.perf_counter()
+            call()
+            ts.append(time.perf_counter() - t0)
+        out[name] = round(1e3 * float(np.median(ts[1:])), 3)
+    out["ratio"] = round(out["calibrate_ms"] / out["calibrate_host_ms"], 4)
+    return out
+
+
+def calibrate_text(rec):
+    d = rec["calibrate"]
+    return "\n".join([
+        "mww_stream_calibrate against mww_stream_calibrate_host, one session (tools/stream_eval_throughput.py --calibrate)",
+        "%s, %s" % (rec["model"], rec["library"]),
+        "%d windows, %d frames, %d tensors; ranges and probabilities equal; medians of %d calls after a warm-up, from zeroed rings"
+        % (d["windows"], d["frames"], d["tensors"], d["reps"]),
+        "  mww_stream_calibrate_host (host rows):     %9.3f ms, %9d bytes uploaded" % (d["calibrate_host_ms"], d["host_bytes_up"]),
+        "  mww_stream_calibrate (resident windows):   %9.3f ms, %9d bytes read back" % (d["calibrate_ms"], d["device_bytes_back"]),
+        "  ratio window form / host form:             %9.4f" % d["ratio"], ""]) + "\n"
 
 
 def summary_leg(sm, amb_win, pos_win, reps, target, cooldown=25, step_s=0.02):
