@@ -155,6 +155,25 @@ int mww_set_opt_state(mww_ctx* ctx, const float* m, const float* v, int64_t n, i
 int mww_get_opt_state(mww_ctx* ctx, float* m, float* v, int64_t n, int64_t* step);
 int mww_get_grads(mww_ctx* ctx, float* host, int64_t n);  /* flat gradient of the last step */
 
+/* ---- quantization-aware training of the weights.  The int8 streaming family quantizes every kernel symmetrically, narrow
+ * range, one scale per output channel, ties away from zero: scale_c = max|w_c| / 127 (1 for an all-zero channel),
+ * q = clamp(round(w / scale_c), -127, 127).  That grid is a function of the weights alone, so it can be imposed in the step:
+ * with the option weight_qat = 1 (set through the option call below; default 0) every forward and backward launch reads a
+ * shadow of the parameter vector in which each weight channel holds q * scale_c, refreshed from the master at the start of
+ * every call that runs a forward (train step, forward, window evaluation; one more node of a captured step).  Adam, the
+ * parameter / optimizer-state calls above and checkpoints keep addressing the fp32 master; the flat gradient is the one taken
+ * at the shadow (straight-through estimator).  Activations are not fake-quantized.
+ *
+ * The channel map says which parameters form a channel, in CSR form: channel c owns the parameter indices
+ * chan_elem[chan_start[c] .. chan_start[c + 1]), chan_start[0] = 0, chan_start[n_channels] = n_elems.  Parameters outside every
+ * channel (biases, BN gamma / beta, structurally masked taps) are copied through, as is a channel whose maximum is not
+ * finite.  The map is validated - indices in [0, P), no element in two channels, chan_start ascending - and a refused map
+ * (MWW_ERR_INVALID) leaves the context as it was.  n_channels = 0 removes the map and turns the option off; setting the
+ * option to 1 without a map is MWW_ERR_INVALID. */
+int mww_set_weight_qat(mww_ctx* ctx, const int32_t* chan_start, const int32_t* chan_elem, int32_t n_channels, int64_t n_elems);
+/* the parameter vector the next forward would read: the shadow of the current master, or the master with the option off */
+int mww_get_forward_params(mww_ctx* ctx, float* host, int64_t n);
+
 /* ---- feature stores: replace the RaggedMmap page-cache reads of data.py:255-258.  A store is the
  * flat concatenation of its samples ([T_i][40], uint16 raw micro-frontend values or float32
  * already scaled), uploaded once and kept resident in HBM. */

@@ -176,7 +176,7 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   if (!training && !c->bn_eval_ready) {
     for (int i = 0; i < nb; ++i) {
       Layer& l = L[i];
-      BnEvalPrepareArgs a{c->params + l.o_gamma, c->params + l.o_beta, c->bn_state + l.o_mm, c->bn_state + l.o_mv,
+      BnEvalPrepareArgs a{fwd_params(c) + l.o_gamma, fwd_params(c) + l.o_beta, c->bn_state + l.o_mm, c->bn_state + l.o_mv,
                           bn_slot(l, BN_SCALE), bn_slot(l, BN_SHIFT), l.cout};
       lp.begin("bn_eval_prepare", i);
       hipLaunchKernelGGL(bn_eval_prepare_kernel, dim3(1), dim3(64), 0, c->stream, a);
@@ -192,8 +192,8 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
     f.acc = pl.facc_cur;
     f.inv_n = 1.0f / ((float)B * (float)pl.tout);
     f.update_moving = update_moving ? 1 : 0;
-    f.gamma = c->params + pl.o_gamma;
-    f.beta = c->params + pl.o_beta;
+    f.gamma = fwd_params(c) + pl.o_gamma;
+    f.beta = fwd_params(c) + pl.o_beta;
     f.moving_mean = c->bn_state + pl.o_mm;
     f.moving_var = c->bn_state + pl.o_mv;
     f.scale = bn_slot(pl, BN_SCALE);
@@ -212,7 +212,7 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
       l.facc_cur = sacc.acc;
     }
     if (i == 0) {
-      FwdFirstArgs a{c->x, c->params + o_conv1, c->params + l.o_dw_w, c->params + l.o_dw_b, c->params + l.o_pw_w,
+      FwdFirstArgs a{c->x, fwd_params(c) + o_conv1, fwd_params(c) + l.o_dw_w, fwd_params(c) + l.o_dw_b, fwd_params(c) + l.o_pw_w,
                      l.p, l.stat_part, B, d.frames, l.tout, 0, sacc, x_gather(c), training ? a0 : nullptr};
       lp.begin("fwd_block", i);
       int rc = launch_fwd_first(c, d.conv1_kernel, d.conv1_filters, l.cout, l.k, d.conv1_stride, a, grid);
@@ -220,8 +220,8 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
       if (rc) return rc;
     } else {
       Layer& pl = L[i - 1];
-      FwdBlockArgs a{pl.p, bn_slot(pl, BN_SCALE), bn_slot(pl, BN_SHIFT), c->params + l.o_dw_w, c->params + l.o_dw_b,
-                     c->params + l.o_pw_w, l.p, l.stat_part, B, l.tin, l.tout, ablate, phase_clk + (size_t)(2 * i) * 2048 * kClkSlots,
+      FwdBlockArgs a{pl.p, bn_slot(pl, BN_SCALE), bn_slot(pl, BN_SHIFT), fwd_params(c) + l.o_dw_w, fwd_params(c) + l.o_dw_b,
+                     fwd_params(c) + l.o_pw_w, l.p, l.stat_part, B, l.tin, l.tout, ablate, phase_clk + (size_t)(2 * i) * 2048 * kClkSlots,
                      sacc, fold_of(pl)};
       lp.begin("fwd_block", i);
       int rc = launch_fwd_block(c, l.cin, l.cout, l.k, a, grid);
@@ -232,8 +232,8 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
       StatSource ss;
       int rcs = exchange_stats(c, lp, "bn_stat_exchange", i, l.stat_part, grid, l.cout, 0, 1.0f / ((float)B * (float)l.tout), &ss);
       if (rcs) return rcs;
-      BnFwdFinalizeArgs f{ss.part, ss.G, l.cout, ss.inv_n, c->params + l.o_gamma,
-                          c->params + l.o_beta, c->bn_state + l.o_mm, c->bn_state + l.o_mv, bn_slot(l, BN_SCALE),
+      BnFwdFinalizeArgs f{ss.part, ss.G, l.cout, ss.inv_n, fwd_params(c) + l.o_gamma,
+                          fwd_params(c) + l.o_beta, c->bn_state + l.o_mm, c->bn_state + l.o_mv, bn_slot(l, BN_SCALE),
                           bn_slot(l, BN_SHIFT), bn_slot(l, BN_MEAN), bn_slot(l, BN_RSTD), update_moving ? 1 : 0};
       lp.begin("bn_fwd_finalize", i);
       hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(l.cout), dim3(kThreads), 0, c->stream, f);
@@ -310,7 +310,7 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       if (rcs) return rcs;
     }
     BnBwdFinalizeArgs f{ss.part, ss.G, l.cout, ss.inv_n,
-                        c->params + l.o_gamma, bn_slot(l, BN_RSTD), bn_slot(l, BN_C1), bn_slot(l, BN_MG),
+                        fwd_params(c) + l.o_gamma, bn_slot(l, BN_RSTD), bn_slot(l, BN_C1), bn_slot(l, BN_MG),
                         bn_slot(l, BN_MGX), c->grads + l.o_gamma, c->grads + l.o_beta, ss.dscale};
     BnGradFoldArgs gf;
     memset(&gf, 0, sizeof(gf));
@@ -318,7 +318,7 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       gf.acc = l.gacc_cur;
       gf.inv_n = 1.0f / ((float)B * (float)l.tout);
       gf.dscale = 1.0f;
-      gf.gamma = c->params + l.o_gamma;
+      gf.gamma = fwd_params(c) + l.o_gamma;
       gf.c1 = bn_slot(l, BN_C1);
       gf.mg = bn_slot(l, BN_MG);
       gf.mgx = bn_slot(l, BN_MGX);
@@ -353,11 +353,11 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       a.k_mgx = bn_slot(l, BN_MGX);
       a.k_scale = bn_slot(l, BN_SCALE);
       a.k_shift = bn_slot(l, BN_SHIFT);
-      a.wd = c->params + c->o_dense_w;
+      a.wd = fwd_params(c) + c->o_dense_w;
       a.dz = c->dz;
-      a.dw_w = c->params + l.o_dw_w;
-      a.dw_b = c->params + l.o_dw_b;
-      a.pw_w = c->params + l.o_pw_w;
+      a.dw_w = fwd_params(c) + l.o_dw_w;
+      a.dw_b = fwd_params(c) + l.o_dw_b;
+      a.pw_w = fwd_params(c) + l.o_pw_w;
       a.g_out = pl.g;
       a.gstat_part = pl.gstat_part;
       a.grad_part = l.grad_part;
@@ -386,8 +386,8 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     } else {
       if (last) return fail(MWW_ERR_UNSUPPORTED, "single-block models are not supported");
       BwdFirstArgs a{c->x, a0, l.p, l.g, bn_slot(l, BN_MEAN), bn_slot(l, BN_RSTD), bn_slot(l, BN_C1),
-                     bn_slot(l, BN_MG), bn_slot(l, BN_MGX), c->params + l.o_dw_w, c->params + l.o_dw_b,
-                     c->params + l.o_pw_w, l.grad_part, B, d.frames, l.tout, gf, x_gather(c), ablate,
+                     bn_slot(l, BN_MG), bn_slot(l, BN_MGX), fwd_params(c) + l.o_dw_w, fwd_params(c) + l.o_dw_b,
+                     fwd_params(c) + l.o_pw_w, l.grad_part, B, d.frames, l.tout, gf, x_gather(c), ablate,
                      phase_clk + (size_t)(2 * i + 1) * 2048 * kClkSlots};
       lp.begin("bwd_block", i);
       int rc = launch_bwd_first(c, d.conv1_kernel, d.conv1_filters, l.cout, l.k, d.conv1_stride, a, gbwd);

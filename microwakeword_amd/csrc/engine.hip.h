@@ -159,6 +159,14 @@ struct mww_ctx {
   float* sync_buf = nullptr;        // [layers][fwd 2C | bwd 2C] statistics sums being exchanged
   std::vector<int64_t> sync_off;    // offset of layer i in sync_buf
   float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr, *mask = nullptr;
+  // "weight_qat" option (kernels_qat.hip.h): the forward / backward launches read `shadow`, the master fake-quantized per weight
+  // channel, refreshed at the start of every call that runs a forward; Adam, set / get_params and checkpoints keep the master.
+  // The map (mww_set_weight_qat) is device-resident: CSR channels + the list of parameters outside every channel.
+  bool weight_qat = false;
+  bool shadow_held = false;   // inside mww_evaluate_windows: the shadow was refreshed by the first batch, the master cannot change
+  float* shadow = nullptr;
+  int *qat_start = nullptr, *qat_elem = nullptr, *qat_copy = nullptr;
+  int qat_channels = 0, qat_n_copy = 0;
   unsigned char* direct = nullptr;
   std::vector<unsigned char> direct_host;   // host copy: which parameters' gradients are written directly by a folding kernel
   bool exchange_pending = false;            // a deferred bucket exchange is in flight (data-parallel step)
@@ -249,6 +257,9 @@ struct Launcher {
 };
 
 enum { BN_SCALE = 0, BN_SHIFT, BN_MEAN, BN_RSTD, BN_C1, BN_MG, BN_MGX };
+
+// the parameter vector the forward / backward launches read: the master, or its fake-quantized shadow ("weight_qat")
+inline float* fwd_params(const mww_ctx* c) { return c->weight_qat ? c->shadow : c->params; }
 
 // ---- mww_lib.hip
 template <typename T>

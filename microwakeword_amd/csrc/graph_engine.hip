@@ -246,7 +246,7 @@ GSrc g_make_src(mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
     s.rstd = gbn_slot(pr, BN_RSTD);
   } else {   // a bias (or nothing) instead of a BN: y = p * 1 + bias
     s.scale = gm(c).ones;
-    s.shift = pr.norm == MWW_NORM_BIAS ? c->params + pr.o_beta : gm(c).zeros;
+    s.shift = pr.norm == MWW_NORM_BIAS ? fwd_params(c) + pr.o_beta : gm(c).zeros;
     s.mean = gm(c).zeros;
     s.rstd = gm(c).ones;
   }
@@ -307,7 +307,7 @@ GDwArgs g_make_dw(mww_ctx* c, int oi, int B, bool backward, bool inl = false) {
   GDwArgs a;
   memset(&a, 0, sizeof(a));
   a.src = g_make_src(c, oi, 0, backward, inl);
-  a.w = c->params + o.o_w;
+  a.w = fwd_params(c) + o.o_w;
   a.k = o.k;
   a.C = o.cout;
   a.B = B;
@@ -344,8 +344,8 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
     f.inv_n = 1.0f / ((float)B * (float)pr.tout * (float)(pr.groups > 1 ? pr.cout / pr.groups : 1));
     f.publish = publish ? 1 : 0;
     f.update_moving = update_moving ? 1 : 0;
-    f.gamma = c->params + pr.o_gamma;
-    f.beta = c->params + pr.o_beta;
+    f.gamma = fwd_params(c) + pr.o_gamma;
+    f.beta = fwd_params(c) + pr.o_beta;
     f.moving_mean = c->bn_state + pr.o_mm;
     f.moving_var = c->bn_state + pr.o_mv;
     f.scale = gbn_slot(pr, BN_SCALE);
@@ -357,7 +357,7 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   for (int i = 0; i < n; ++i) {
     GOp& o = m.G[i];
     if (!training && o.norm == MWW_NORM_BN) {
-      GBnEvalArgs e{c->params + o.o_gamma, c->params + o.o_beta, c->bn_state + o.o_mm, c->bn_state + o.o_mv,
+      GBnEvalArgs e{fwd_params(c) + o.o_gamma, fwd_params(c) + o.o_beta, c->bn_state + o.o_mm, c->bn_state + o.o_mv,
                     gbn_slot(o, BN_SCALE), gbn_slot(o, BN_SHIFT), o.cout, o.groups};
       lp.begin("bn_eval_prepare", i);
       hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, c->stream, e);
@@ -380,7 +380,7 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
       memset(&a, 0, sizeof(a));
       a.n_src = q.n_src;
       for (int s = 0; s < q.n_src; ++s) a.src[s] = g_make_src(c, oi, s, false);
-      a.w = c->params + q.o_w;
+      a.w = fwd_params(c) + q.o_w;
       a.k = q.k;
       a.dil = q.dil;
       a.cin = q.cin;
@@ -412,7 +412,7 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
     auto fin_args = [&](int oi, const StatSource& ss) {
       GOp& q = m.G[oi];
       return GBnFwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
-                        c->params + q.o_gamma, c->params + q.o_beta, c->bn_state + q.o_mm, c->bn_state + q.o_mv,
+                        fwd_params(c) + q.o_gamma, fwd_params(c) + q.o_beta, c->bn_state + q.o_mm, c->bn_state + q.o_mv,
                         gbn_slot(q, BN_SCALE), gbn_slot(q, BN_SHIFT), gbn_slot(q, BN_MEAN), gbn_slot(q, BN_RSTD), update_moving ? 1 : 0};
     };
     const bool sync = c->hook && c->sync_bn;
@@ -420,7 +420,7 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
       // twins: one convolution launch and one finalize launch for the pair
       GOp& o2 = m.G[i + 1];
       if (!training) {
-        GBnEvalArgs e{c->params + o2.o_gamma, c->params + o2.o_beta, c->bn_state + o2.o_mm, c->bn_state + o2.o_mv,
+        GBnEvalArgs e{fwd_params(c) + o2.o_gamma, fwd_params(c) + o2.o_beta, c->bn_state + o2.o_mm, c->bn_state + o2.o_mv,
                       gbn_slot(o2, BN_SCALE), gbn_slot(o2, BN_SHIFT), o2.cout, o2.groups};
         hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, c->stream, e);
       }
@@ -494,8 +494,8 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   h.shift = gbn_slot(lo, BN_SHIFT);
   h.mean = gbn_slot(lo, BN_MEAN);
   h.rstd = gbn_slot(lo, BN_RSTD);
-  h.wd = c->params + c->o_dense_w;
-  h.bd = c->params + c->o_dense_b;
+  h.wd = fwd_params(c) + c->o_dense_w;
+  h.bd = fwd_params(c) + c->o_dense_b;
   h.y = (loss || metrics) ? c->y_cur : nullptr;
   h.sw = c->sw_cur;
   h.keep = (drop && !gen_inline) ? m.keep : nullptr;
@@ -536,7 +536,7 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   if (m.head2) {
     GHead2Args h2;
     h2.h = h;
-    h2.watt = m.head_att ? c->params + m.o_att : nullptr;
+    h2.watt = m.head_att ? fwd_params(c) + m.o_att : nullptr;
     h2.pool = m.head_pool;
     h2.hact = m.hact;
     h2.watt_part = m.watt_part;
@@ -580,7 +580,7 @@ int GraphModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     f.inv_n = 1.0f / ((float)B * (float)q.tout * (float)(q.groups > 1 ? q.cout / q.groups : 1));
     f.dscale = 1.0f;
     f.publish = publish ? 1 : 0;
-    f.gamma = c->params + q.o_gamma;
+    f.gamma = fwd_params(c) + q.o_gamma;
     f.c1 = gbn_slot(q, BN_C1);
     f.mg = gbn_slot(q, BN_MG);
     f.mgx = gbn_slot(q, BN_MGX);
@@ -591,7 +591,7 @@ int GraphModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
   auto bwd_fin_args = [&](int oi, const StatSource& ss) {
     GOp& q = m.G[oi];
     return GBnBwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
-                      c->params + q.o_gamma, gbn_slot(q, BN_RSTD), gbn_slot(q, BN_C1), gbn_slot(q, BN_MG), gbn_slot(q, BN_MGX),
+                      fwd_params(c) + q.o_gamma, gbn_slot(q, BN_RSTD), gbn_slot(q, BN_C1), gbn_slot(q, BN_MG), gbn_slot(q, BN_MGX),
                       c->grads + q.o_gamma, c->grads + q.o_beta, ss.dscale, 0};
   };
   auto wgrad_args = [&](int oi) {
@@ -618,7 +618,7 @@ int GraphModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     memset(&a, 0, sizeof(a));
     a.n_src = q.n_src;
     for (int s = 0; s < q.n_src; ++s) a.src[s] = g_make_src(c, oi, s, true, inl);
-    a.w = c->params + q.o_w;   // (the data-gradient kernel reads them transposed / tap-reversed in place)
+    a.w = fwd_params(c) + q.o_w;   // (the data-gradient kernel reads them transposed / tap-reversed in place)
     a.k = q.k;
     a.dil = q.dil;
     a.cin = q.cout;
@@ -697,7 +697,7 @@ int GraphModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
                                1.0f / ((float)B * (float)o.tout * (float)members), &ss);
       if (rcs) return rcs;
       GBnBwdArgs f{ss.part, ss.G, o.cout, o.groups, ss.inv_n,
-                   c->params + o.o_gamma, gbn_slot(o, BN_RSTD), gbn_slot(o, BN_C1), gbn_slot(o, BN_MG), gbn_slot(o, BN_MGX),
+                   fwd_params(c) + o.o_gamma, gbn_slot(o, BN_RSTD), gbn_slot(o, BN_C1), gbn_slot(o, BN_MG), gbn_slot(o, BN_MGX),
                    c->grads + o.o_gamma, c->grads + o.o_beta, ss.dscale, 0};
       lp.begin("bn_bwd_finalize", i);
       hipLaunchKernelGGL(gbn_bwd_finalize_kernel, dim3(o.slots), dim3(kThreads), 0, c->stream, f);
@@ -755,7 +755,7 @@ int GraphModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     if (o.needs_dx) {
       a.n_src = o.n_src;
       for (int s = 0; s < o.n_src; ++s) a.src[s] = g_make_src(c, i, s, true, inl);
-      a.w = c->params + o.o_w;
+      a.w = fwd_params(c) + o.o_w;
       a.k = o.k;
       a.dil = o.dil;
       a.cin = o.cout;

@@ -17,6 +17,7 @@
 #include "engine.hip.h"
 #include "kernels_data.hip.h"
 #include "kernels_head.hip.h"
+#include "kernels_qat.hip.h"
 #include "kernels_tail.hip.h"
 
 using namespace mww;
@@ -60,7 +61,7 @@ int head_frame_limit(int ch) { return (kThreads / (ch / 4)) * kHeadMaxRows; }
 int enqueue_block_head(mww_ctx* c, int B, const Tensor& last, int T, int C, bool bf16, const BnFoldArgs& fold, const StatAcc& gacc, bool loss, bool metrics) {
   float* const bn = last.bn;
   const HeadArgs h{last.p, bn + (size_t)BN_SCALE * C, bn + (size_t)BN_SHIFT * C, bn + (size_t)BN_MEAN * C, bn + (size_t)BN_RSTD * C,
-                   c->params + c->o_dense_w, c->params + c->o_dense_b, (loss || metrics) ? c->y_cur : nullptr, c->sw_cur, c->z, c->prob, c->dz,
+                   fwd_params(c) + c->o_dense_w, fwd_params(c) + c->o_dense_b, (loss || metrics) ? c->y_cur : nullptr, c->sw_cur, c->z, c->prob, c->dz,
                    c->loss_part, last.gstat_part, B, T, 1.0f / (float)B, (loss ? kHeadTraining : 0) | (c->bce_clipped ? kHeadClippedLoss : 0), fold, gacc};
   const int q = C / 4, nrg = kThreads / q;
   Launcher lp{c};
@@ -414,9 +415,36 @@ float adam_alpha(float lr, int64_t t) {
   return lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
 }
 
+// "weight_qat": shadow = fake_quant(master), on the context's stream ahead of the first launch that reads weights (every
+// Adam update and every mww_set_params is ordered on that stream too, or joined to it before the call returns)
+int refresh_shadow(mww_ctx* c) {
+  if (!c->weight_qat || c->shadow_held) return MWW_OK;
+  Launcher lp{c};
+  lp.begin("weight_qat");
+  launch_weight_qat(QatArgs{c->params, c->shadow, c->qat_start, c->qat_elem, c->qat_copy, c->qat_channels, c->qat_n_copy}, c->stream);
+  lp.end();
+  return MWW_OK;
+}
+
+void free_weight_qat(mww_ctx* c) {
+  void* bufs[] = {c->shadow, c->qat_start, c->qat_elem, c->qat_copy};
+  for (void* p : bufs) if (p) (void)hipFree(p);
+  c->shadow = nullptr;
+  c->qat_start = c->qat_elem = c->qat_copy = nullptr;
+  c->qat_channels = c->qat_n_copy = 0;
+  c->weight_qat = false;
+}
+
+void drop_graphs(mww_ctx* c) {
+  for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
+  c->graphs.clear();
+}
+
 int step_sequence(mww_ctx* c, int B, int flags) {
   c->metric_launches = 0;
-  int rc = c->model->enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS));
+  int rc = refresh_shadow(c);   // (under "graphs": one more node of the captured chain)
+  if (rc) return rc;
+  rc = c->model->enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS));
   if (rc) return rc;
   rc = c->model->enqueue_backward(c, B, !(flags & MWW_STEP_NO_APPLY));
   if (rc) return rc;
@@ -752,6 +780,7 @@ void mww_destroy(mww_ctx* c) {
   void* flat[] = {c->params, c->grads, c->adam_m, c->adam_v, c->mask, c->direct, c->bn_state, c->x, c->y, c->sw,
                   c->z, c->prob, c->dz, c->loss_part, c->dwd_part, c->metrics, c->sync_buf};
   for (void* p : flat) if (p) (void)hipFree(p);
+  free_weight_qat(c);
   for (int i = 0; i < MWW_MAX_STORES; ++i) if (c->store[i]) (void)hipFree(c->store[i]);
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
   for (int i = 0; i < kRing; ++i) {
@@ -800,6 +829,56 @@ int mww_set_bn_state(mww_ctx* c, const float* h, int64_t n) {
   if (!c || !h || n != c->S) return fail(MWW_ERR_INVALID, "BN state size mismatch");
   return copy_in(c, c->bn_state, h, (size_t)n * sizeof(float));
 }
+int mww_get_forward_params(mww_ctx* c, float* h, int64_t n) {
+  if (!c || !h || n != c->P) return fail(MWW_ERR_INVALID, "parameter vector size mismatch");
+  HIPCHK(hipSetDevice(c->device));
+  MWW_TRY(refresh_shadow(c));
+  HIPCHK(hipGetLastError());
+  return copy_out(c, h, fwd_params(c), (size_t)n * sizeof(float));
+}
+
+int mww_set_weight_qat(mww_ctx* c, const int32_t* chan_start, const int32_t* chan_elem, int32_t n_channels, int64_t n_elems) {
+  if (!c || n_channels < 0 || n_elems < 0) return fail(MWW_ERR_INVALID, "bad weight_qat map arguments");
+  if (n_channels > 0 && (!chan_start || (n_elems > 0 && !chan_elem))) return fail(MWW_ERR_INVALID, "null weight_qat map");
+  // validated before anything changes: a refused map leaves the context as it was
+  std::vector<int> copy;
+  if (n_channels > 0) {
+    if (n_elems > c->P) return fail(MWW_ERR_INVALID, "weight_qat map lists more elements than the model has parameters");
+    if (chan_start[0] != 0 || chan_start[n_channels] != n_elems) return fail(MWW_ERR_INVALID, "weight_qat map: chan_start must run from 0 to n_elems");
+    for (int32_t i = 0; i < n_channels; ++i)
+      if (chan_start[i + 1] < chan_start[i]) return fail(MWW_ERR_INVALID, "weight_qat map: chan_start must be ascending");
+    std::vector<unsigned char> seen((size_t)c->P, 0);
+    for (int64_t i = 0; i < n_elems; ++i) {
+      const int32_t e = chan_elem[i];
+      if (e < 0 || e >= c->P) return fail(MWW_ERR_INVALID, "weight_qat map: element index outside the parameter vector");
+      if (seen[(size_t)e]) return fail(MWW_ERR_INVALID, "weight_qat map: an element appears in two channels");
+      seen[(size_t)e] = 1;
+    }
+    for (int64_t e = 0; e < c->P; ++e)
+      if (!seen[(size_t)e]) copy.push_back((int)e);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  drop_graphs(c);   // (a capture holds the shadow's and the map's addresses)
+  free_weight_qat(c);
+  if (n_channels == 0) return MWW_OK;
+  auto install = [&]() -> int {
+    MWW_TRY(dev_alloc(&c->shadow, (size_t)c->P));
+    MWW_TRY(dev_alloc(&c->qat_start, (size_t)n_channels + 1));
+    MWW_TRY(dev_alloc(&c->qat_elem, (size_t)n_elems));
+    MWW_TRY(dev_alloc(&c->qat_copy, copy.size()));
+    HIPCHK(hipMemcpy(c->qat_start, chan_start, ((size_t)n_channels + 1) * sizeof(int), hipMemcpyHostToDevice));
+    if (n_elems) HIPCHK(hipMemcpy(c->qat_elem, chan_elem, (size_t)n_elems * sizeof(int), hipMemcpyHostToDevice));
+    if (!copy.empty()) HIPCHK(hipMemcpy(c->qat_copy, copy.data(), copy.size() * sizeof(int), hipMemcpyHostToDevice));
+    return MWW_OK;
+  };
+  const int rc = install();
+  if (rc) { free_weight_qat(c); return rc; }   // (no half-installed map behind a device error)
+  c->qat_channels = n_channels;
+  c->qat_n_copy = (int)copy.size();
+  return MWW_OK;
+}
+
 int mww_get_bn_state(mww_ctx* c, float* h, int64_t n) {
   if (!c || !h || n != c->S) return fail(MWW_ERR_INVALID, "BN state size mismatch");
   return copy_out(c, h, c->bn_state, (size_t)n * sizeof(float));
@@ -1050,6 +1129,8 @@ int mww_forward(mww_ctx* c, int B, int training, int update_metrics) {
     rc = materialise_x(c);
     if (rc) return rc;
   }
+  rc = refresh_shadow(c);
+  if (rc) return rc;
   rc = c->model->enqueue_forward(c, B, training != 0, false, false, update_metrics != 0);
   if (rc) return rc;
   rc = join_side(c);
@@ -1068,8 +1149,10 @@ int mww_evaluate_windows(mww_ctx* c, const mww_window* windows, const float* lab
     if (!rc) rc = mww_assemble_batch(c, windows + s, nullptr, b, 0, 0);
     if (!rc) rc = mww_forward(c, b, 0, 1);
     c->bn_eval_ready = c->model->eval_fold_cached();   // the weights cannot change between the batches of this call
+    c->shadow_held = true;                             // ... so the first batch's shadow serves them all
   }
   c->bn_eval_ready = false;
+  c->shadow_held = false;
   return rc;
 }
 
@@ -1165,6 +1248,7 @@ const OptionRow kOptions[] = {
     {"fused_input", OPT_CORE, 1, 0, 0, nullptr},
     {"assemble_split", OPT_CORE, 1, 8, 0, "assemble_split out of range"},
     {"grid_head", OPT_CORE, 1, 4, 1, "grid_head out of range"},
+    {"weight_qat", OPT_CORE, 0, 1, 0, "weight_qat must be 0 or 1"},
     {"ablate", OPT_BLOCK, 1, 0, 0, nullptr},
     {"pointwise_bf16", OPT_BLOCK, 1, 0, 0, nullptr},
     {"storage_bf16", OPT_BLOCK, 1, 0, 0, nullptr},
@@ -1194,6 +1278,10 @@ int set_core_option(mww_ctx* c, const std::string& name, int64_t v) {
   for (auto& f : flags) if (name == f.first) *f.second = v != 0;
   for (auto& f : ints) if (name == f.first) *f.second = (int)v;
   if (name == "bce_from_logits") c->bce_clipped = v == 0;
+  if (name == "weight_qat") {
+    if (v && !c->shadow) return fail(MWW_ERR_INVALID, "weight_qat needs a channel map: call mww_set_weight_qat first");
+    c->weight_qat = v != 0;
+  }
   if (name == "profile") {   // (the events recorded so far)
     for (auto& e : c->prof) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->prof.clear();
@@ -1210,8 +1298,7 @@ int mww_set_option(mww_ctx* c, const char* name, int64_t v) {
   if (!o) return fail(MWW_ERR_INVALID, std::string("unknown option: ") + name);
   if (o->lo <= o->hi && (v < o->lo || v > (o->hi_cu ? (int64_t)c->n_cu * o->hi : o->hi))) return fail(MWW_ERR_INVALID, o->range_error);
   MWW_TRY(o->owner == OPT_CORE ? set_core_option(c, name, v) : c->model->set_option(c, *o, v));
-  for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
-  c->graphs.clear();
+  drop_graphs(c);
   return MWW_OK;
 }
 

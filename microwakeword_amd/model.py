@@ -178,6 +178,24 @@ class Model:
         self.engine.set_params(p)
         self.engine.set_bn_state(s)
 
+    def set_weight_qat(self, on: bool):
+        """Weight-only quantization-aware training (``qat``; engine option ``weight_qat``): from the next call on, every
+        forward and backward reads the weights snapped per output channel to the int8 grid ``quantize.weight_params``
+        ships, while Adam, ``get_weights`` / ``set_weights`` and checkpoints keep the fp32 master.  The channel map is
+        installed on first use."""
+        if on and not getattr(self, "_qat_map_installed", False):
+            from . import qat
+            self.engine.set_weight_qat_map(*qat.channel_map(self.layout))
+            self._qat_map_installed = True
+        if on or getattr(self, "_qat_map_installed", False):
+            self.engine.set_option("weight_qat", 1 if on else 0)
+        self.weight_qat = bool(on)
+
+    def get_forward_weights(self):
+        """``get_weights()`` as the next forward would read them: the fake-quantized shadow with ``set_weight_qat(True)``,
+        the master otherwise"""
+        return self.layout.unpack(self.engine.get_forward_params(), self.engine.get_bn_state())
+
     def reset_metrics(self):
         self.engine.metrics_reset()
         self._loss_sum, self._loss_n = 0.0, 0
@@ -339,6 +357,8 @@ class Model:
             print_fn("Kernels: %s" % self.kernel_family)
         for line in self.layout.summary_lines():
             print_fn(line)
+        if getattr(self, "weight_qat", False):
+            print_fn("Weights: fake-quantized per output channel to the int8 grid in every forward / backward (fp32 master kept)")
         print_fn("Total params: %d" % total)
         print_fn("Trainable params: %d" % trainable)
         print_fn("Non-trainable params: %d" % (total - trainable))

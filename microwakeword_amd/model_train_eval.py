@@ -344,6 +344,8 @@ def _run(flags, model_module, rank, local_rank, world):
         from .quantize import check_shared_calibration
         check_shared_calibration(check_mining_config(flags, model_module, config, world),   # likewise
                                  check_streaming_validation_config(flags, model_module, config, world))
+        from . import qat
+        qat.parse_config(config)   # weight_quantization_aware: likewise
     device = flags.device if local_rank is None else local_rank
     if flags.train:
         device = flags.device if local_rank is None else local_rank

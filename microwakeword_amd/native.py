@@ -129,6 +129,7 @@ EXPORTS = [
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
     "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections", "mww_stream_operating_points",
     "mww_stream_mine", "mww_stream_operating_summary", "mww_stream_calibrate",
+    "mww_set_weight_qat", "mww_get_forward_params",
 ]
 
 
@@ -187,11 +188,12 @@ class NativeLib:
         L.mww_num_bn_state.argtypes = [C.c_void_p]
         L.mww_num_bn_state.restype = C.c_int64
         for f in (L.mww_set_params, L.mww_get_params, L.mww_set_bn_state, L.mww_get_bn_state, L.mww_set_grad_mask,
-                  L.mww_get_grads):
+                  L.mww_get_grads, L.mww_get_forward_params):
             f.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64]
         L.mww_set_opt_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.c_int64]
         L.mww_get_opt_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64,
                                         C.POINTER(C.c_int64)]
+        L.mww_set_weight_qat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]
         L.mww_upload_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int]
         L.mww_assemble_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.mww_set_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
@@ -494,6 +496,18 @@ class Engine:
 
     def get_grads(self):
         return self._vec_out(self.nl.lib.mww_get_grads, self.n_params)
+
+    def set_weight_qat_map(self, chan_start, chan_elem):
+        """Install (or, with no channels, remove) the channel map of the ``weight_qat`` option: CSR, channel c owns the
+        parameter indices ``chan_elem[chan_start[c]:chan_start[c + 1]]`` (``qat.channel_map``)."""
+        cs = np.ascontiguousarray(chan_start, np.int32).reshape(-1)
+        ce = np.ascontiguousarray(chan_elem, np.int32).reshape(-1)
+        n = max(cs.size - 1, 0)
+        self.nl.check(self.nl.lib.mww_set_weight_qat(self.h, vp(cs) if cs.size else None, vp(ce) if ce.size else None, n, ce.size))
+
+    def get_forward_params(self):
+        """the parameter vector the next forward would read (the fake-quantized shadow with ``weight_qat`` on)"""
+        return self._vec_out(self.nl.lib.mww_get_forward_params, self.n_params)
 
     def set_opt_state(self, m, v, step):
         m = np.ascontiguousarray(m, np.float32).reshape(-1)

@@ -14,6 +14,8 @@ the ambient set accumulated into the same counters, FAPH / recall-at-cutoff / av
 With a ``streaming_validation`` mapping in the configuration every evaluation boundary that is due also measures the streaming
 FAPH / recall at the operating point its ``target_faph`` selects (``streaming.validate_streaming``) and adds the
 ``streaming_*`` metrics to those the best-weights rule may name; without the key nothing changes.
+With a ``weight_quantization_aware`` mapping (``qat``) the steps from ``first_step`` on train for the int8 model:
+the engine's forward / backward read the weights on the int8 grid while Adam keeps the fp32 master.
 
 When both objects come from this package the spectrogram batch never leaves HBM
 (``FeatureHandler.next_training_batch_on_device`` + ``Model.train_on_device_batch``); with any other
@@ -198,6 +200,10 @@ def train(model, config, data_processor, verbose=True):
     streaming_settings = streaming_validation_config(config, world)   # likewise
     from .quantize import check_shared_calibration
     check_shared_calibration(streaming_settings, mining)   # both quantized: one calibration set, one calibration per boundary
+    from . import qat
+    qat_settings = qat.parse_config(config)   # likewise
+    if qat_settings is not None and not hasattr(model, "set_weight_qat"):
+        raise ValueError("%s needs this package's Model (the engine fake-quantizes the weights in the step)" % qat.CONFIG_KEY)
     fast = hasattr(data_processor, "next_training_batch_on_device") and hasattr(model, "train_on_device_batch") \
         and getattr(data_processor, "engine", None) is getattr(model, "engine", object())
     prefetch = int(config.get("prefetch_batches", 4))
@@ -269,6 +275,13 @@ def train(model, config, data_processor, verbose=True):
                              _JsonSummary(os.path.join(config["summaries_dir"], "mining"), "scalars") if chief else None,
                              quantizer=quantizer)
 
+    # weight_quantization_aware: on from optimizer step `first_step` on.  The shadow is a function of the master, so a restored
+    # run needs no state of its own: on / off follows from the restored optimizer step.
+    qat_on = False
+    steps_before = 0
+    if qat_settings is not None and hasattr(model, "engine") and hasattr(model.engine, "get_opt_state"):
+        steps_before = int(model.engine.get_opt_state()[2])
+
     warned_weights = False
     steps_max = int(np.sum(ph["training_steps"]))
     best_min, best_max, best_cutoff = 10000, 0.0, 1.0
@@ -298,6 +311,11 @@ def train(model, config, data_processor, verbose=True):
                   "freq_mask_max_size": ph["freq_mask_max_size"][i], "freq_mask_count": ph["freq_mask_count"][i]}
         cw_neg, cw_pos = ph["negative_class_weight"][i], ph["positive_class_weight"][i]
         mode = config.get("sample_weight_broadcast", DEFAULT_WEIGHT_BROADCAST)
+        if qat_settings is not None and not qat_on and steps_before + step >= qat_settings["first_step"]:
+            model.set_weight_qat(True)   # before this step's forward; every rank derives the same shadow from the same master
+            qat_on = True
+            if chief:
+                log.info("Step #%d: weight quantization-aware training on (forward / backward read the int8 weight grid)", steps_before + step)
         if fast:
             data_processor.next_training_batch_on_device(local_batch, config["spectrogram_length"], "default", policy,
                                                          class_weights=(cw_neg, cw_pos), weight_broadcast=mode)
@@ -333,7 +351,8 @@ def train(model, config, data_processor, verbose=True):
             info = log.info if chief else log.debug
             info("Step #%d: rate %f, accuracy %.2f%%, recall %.2f%%, precision %.2f%%, cross entropy %f",
                  step, lr, result[1] * 100, result[2] * 100, result[3] * 100, result[9])
-            train_writer.scalars(step, loss=result[9], accuracy=result[1], recall=result[2], precision=result[3], auc=result[8])
+            train_writer.scalars(step, loss=result[9], accuracy=result[1], recall=result[2], precision=result[3], auc=result[8],
+                                 **({} if qat_settings is None else {"weight_qat": int(qat_on)}))
             save_weights(os.path.join(config["train_dir"], "last_weights.weights.h5"))
             if private_streams:
                 data_processor.release_private_rng()   # validation shuffles on the global numpy stream (data.py:593-595) ...
