@@ -174,6 +174,29 @@ int mww_set_weight_qat(mww_ctx* ctx, const int32_t* chan_start, const int32_t* c
 /* the parameter vector the next forward would read: the shadow of the current master, or the master with the option off */
 int mww_get_forward_params(mww_ctx* ctx, float* host, int64_t n);
 
+/* ---- weight averaging: an exponential moving average of the trainable parameters, kept on the device next to the master.
+ * State: ema[P] in fp32, laid out and indexed like the vector of mww_get_params, and a count of the updates it has taken.
+ * One update, with om = 1 - decay formed in double:
+ *     updates == 0:  ema[i] = w[i]                                                         (a bit copy of the master)
+ *     otherwise:     ema[i] = (float)((double)ema[i] + om * ((double)w[i] - (double)ema[i]))
+ * three float64 operations and one rounding, uncontracted; a non-finite master propagates.  The update is enqueued on the
+ * context's stream directly behind every Adam update - the one inside mww_train_step or mww_apply_gradients - after which the
+ * optimizer step count is a multiple of every_steps (one more node of a captured step).  A step with MWW_STEP_NO_APPLY
+ * updates nothing; mww_set_params does not touch the average.  The BatchNorm moving statistics are not trainable and are
+ * not averaged.
+ *
+ * mww_set_weight_ema installs the average (updates = 0) with decay in (0, 1) and every_steps >= 1; decay == 0 removes it and
+ * frees the vector.  Other values are MWW_ERR_INVALID and leave the context as it was.
+ *
+ * With the option ema_forward = 1 (the option call below; default 0; MWW_ERR_INVALID without an installed average) and
+ * once updates > 0, every non-training forward - mww_forward(training = 0), mww_evaluate_windows, mww_get_forward_params -
+ * stands on the average instead of the master, with the current moving statistics; with weight_qat it reads
+ * fake_quant(average).  mww_train_step and mww_forward(training = 1) always read the master (or its shadow). */
+int mww_set_weight_ema(mww_ctx* ctx, double decay, int64_t every_steps);
+/* the average and its update count, for checkpoints (host may be NULL to read the count alone); n = mww_num_params */
+int mww_get_ema_state(mww_ctx* ctx, float* host, int64_t n, int64_t* updates);
+int mww_set_ema_state(mww_ctx* ctx, const float* host, int64_t n, int64_t updates);
+
 /* ---- feature stores: replace the RaggedMmap page-cache reads of data.py:255-258.  A store is the
  * flat concatenation of its samples ([T_i][40], uint16 raw micro-frontend values or float32
  * already scaled), uploaded once and kept resident in HBM. */

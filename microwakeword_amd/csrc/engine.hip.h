@@ -163,10 +163,18 @@ struct mww_ctx {
   // channel, refreshed at the start of every call that runs a forward; Adam, set / get_params and checkpoints keep the master.
   // The map (mww_set_weight_qat) is device-resident: CSR channels + the list of parameters outside every channel.
   bool weight_qat = false;
-  bool shadow_held = false;   // inside mww_evaluate_windows: the shadow was refreshed by the first batch, the master cannot change
+  const float* shadow_held = nullptr;   // inside mww_evaluate_windows: the vector the first batch refreshed the shadow from (it cannot
+                                        // change between the batches); a refresh from any other source is not skipped
   float* shadow = nullptr;
   int *qat_start = nullptr, *qat_elem = nullptr, *qat_copy = nullptr;
   int qat_channels = 0, qat_n_copy = 0;
+  // weight averaging (mww_set_weight_ema, kernels_ema.hip.h): `ema` follows the master by one launch behind every
+  // `ema_every`-th Adam update; with the "ema_forward" option a non-training forward reads it (`ema_src`, set for the
+  // duration of such a call) once it holds a first update
+  float* ema = nullptr;
+  double ema_decay = 0.0;
+  int64_t ema_every = 1, ema_updates = 0;
+  bool ema_forward = false, ema_src = false;
   unsigned char* direct = nullptr;
   std::vector<unsigned char> direct_host;   // host copy: which parameters' gradients are written directly by a folding kernel
   bool exchange_pending = false;            // a deferred bucket exchange is in flight (data-parallel step)
@@ -258,8 +266,10 @@ struct Launcher {
 
 enum { BN_SCALE = 0, BN_SHIFT, BN_MEAN, BN_RSTD, BN_C1, BN_MG, BN_MGX };
 
-// the parameter vector the forward / backward launches read: the master, or its fake-quantized shadow ("weight_qat")
-inline float* fwd_params(const mww_ctx* c) { return c->weight_qat ? c->shadow : c->params; }
+// the fp32 vector this call's forward stands on: the master, or the weight average in a non-training call under "ema_forward"
+inline float* fwd_source(const mww_ctx* c) { return c->ema_src ? c->ema : c->params; }
+// the parameter vector the forward / backward launches read: that vector, or its fake-quantized shadow ("weight_qat")
+inline float* fwd_params(const mww_ctx* c) { return c->weight_qat ? c->shadow : fwd_source(c); }
 
 // ---- mww_lib.hip
 template <typename T>

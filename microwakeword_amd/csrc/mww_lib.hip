@@ -16,6 +16,7 @@
 
 #include "engine.hip.h"
 #include "kernels_data.hip.h"
+#include "kernels_ema.hip.h"
 #include "kernels_head.hip.h"
 #include "kernels_qat.hip.h"
 #include "kernels_tail.hip.h"
@@ -416,15 +417,52 @@ float adam_alpha(float lr, int64_t t) {
 }
 
 // "weight_qat": shadow = fake_quant(master), on the context's stream ahead of the first launch that reads weights (every
-// Adam update and every mww_set_params is ordered on that stream too, or joined to it before the call returns)
+// Adam update and every mww_set_params is ordered on that stream too, or joined to it before the call returns).  In a
+// non-training call under "ema_forward" the source is the weight average instead: shadow = fake_quant(ema).  A held shadow
+// (mww_evaluate_windows) is only as good as its source - the next call that reads another vector refreshes.
 int refresh_shadow(mww_ctx* c) {
-  if (!c->weight_qat || c->shadow_held) return MWW_OK;
+  const float* src = fwd_source(c);
+  if (!c->weight_qat || c->shadow_held == src) return MWW_OK;
   Launcher lp{c};
   lp.begin("weight_qat");
-  launch_weight_qat(QatArgs{c->params, c->shadow, c->qat_start, c->qat_elem, c->qat_copy, c->qat_channels, c->qat_n_copy}, c->stream);
+  launch_weight_qat(QatArgs{src, c->shadow, c->qat_start, c->qat_elem, c->qat_copy, c->qat_channels, c->qat_n_copy}, c->stream);
   lp.end();
   return MWW_OK;
 }
+
+// weight averaging: what the Adam update that takes the optimizer to c->step is followed by - nothing, the copy that starts
+// the average, or one blend
+enum { EMA_NONE = 0, EMA_COPY = 1, EMA_BLEND = 2 };
+int ema_due(const mww_ctx* c) {
+  if (!c->ema || c->step % c->ema_every != 0) return EMA_NONE;
+  return c->ema_updates == 0 ? EMA_COPY : EMA_BLEND;
+}
+// ... enqueued on the context's stream directly behind that update (under "graphs": one more node of the captured chain)
+int enqueue_ema(mww_ctx* c, int mode) {
+  if (mode == EMA_NONE) return MWW_OK;
+  Launcher lp{c};
+  lp.begin("weight_ema");
+  launch_weight_ema(EmaArgs{c->params, c->ema, 1.0 - c->ema_decay, (int)c->P, 0, mode == EMA_COPY ? 1 : 0}, c->stream);
+  lp.end();
+  return MWW_OK;
+}
+
+void free_weight_ema(mww_ctx* c) {
+  if (c->ema) (void)hipFree(c->ema);
+  c->ema = nullptr;
+  c->ema_decay = 0.0;
+  c->ema_every = 1;
+  c->ema_updates = 0;
+  c->ema_forward = c->ema_src = false;
+}
+
+// a non-training call under "ema_forward" stands on the weight average once it holds a first update; for this call only
+bool ema_serves(const mww_ctx* c) { return c->ema_forward && c->ema && c->ema_updates > 0; }
+struct EmaSource {
+  mww_ctx* c;
+  EmaSource(mww_ctx* ctx, bool training) : c(ctx) { c->ema_src = !training && ema_serves(c); }
+  ~EmaSource() { c->ema_src = false; }
+};
 
 void free_weight_qat(mww_ctx* c) {
   void* bufs[] = {c->shadow, c->qat_start, c->qat_elem, c->qat_copy};
@@ -440,13 +478,15 @@ void drop_graphs(mww_ctx* c) {
   c->graphs.clear();
 }
 
-int step_sequence(mww_ctx* c, int B, int flags) {
+int step_sequence(mww_ctx* c, int B, int flags, int ema) {
   c->metric_launches = 0;
   int rc = refresh_shadow(c);   // (under "graphs": one more node of the captured chain)
   if (rc) return rc;
   rc = c->model->enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS));
   if (rc) return rc;
   rc = c->model->enqueue_backward(c, B, !(flags & MWW_STEP_NO_APPLY));
+  if (rc) return rc;
+  rc = enqueue_ema(c, ema);   // behind the last Adam launch of the step (stream order, also with two gradient buckets)
   if (rc) return rc;
   // the metric state has one writer per step (kernels_head.hip.h MetricState): a second launch with the role would lose counts
   if (c->metric_launches > 1) return fail(MWW_ERR_STATE, "internal: more than one launch of this step carries the metric update");
@@ -781,6 +821,7 @@ void mww_destroy(mww_ctx* c) {
                   c->z, c->prob, c->dz, c->loss_part, c->dwd_part, c->metrics, c->sync_buf};
   for (void* p : flat) if (p) (void)hipFree(p);
   free_weight_qat(c);
+  free_weight_ema(c);
   for (int i = 0; i < MWW_MAX_STORES; ++i) if (c->store[i]) (void)hipFree(c->store[i]);
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
   for (int i = 0; i < kRing; ++i) {
@@ -832,9 +873,45 @@ int mww_set_bn_state(mww_ctx* c, const float* h, int64_t n) {
 int mww_get_forward_params(mww_ctx* c, float* h, int64_t n) {
   if (!c || !h || n != c->P) return fail(MWW_ERR_INVALID, "parameter vector size mismatch");
   HIPCHK(hipSetDevice(c->device));
+  EmaSource source(c, false);
   MWW_TRY(refresh_shadow(c));
   HIPCHK(hipGetLastError());
   return copy_out(c, h, fwd_params(c), (size_t)n * sizeof(float));
+}
+
+int mww_set_weight_ema(mww_ctx* c, double decay, int64_t every_steps) {
+  if (!c) return fail(MWW_ERR_INVALID, "null context");
+  // validated before anything changes: a refused call leaves the context as it was
+  if (decay != 0.0) {
+    if (!(decay > 0.0 && decay < 1.0)) return fail(MWW_ERR_INVALID, "weight_ema: decay must lie in (0, 1), or be 0 to remove the average");
+    if (every_steps < 1) return fail(MWW_ERR_INVALID, "weight_ema: every_steps must be at least 1");
+  }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  drop_graphs(c);   // (a capture holds the average's address, the decay and whether its node copies or blends)
+  if (decay == 0.0) {
+    free_weight_ema(c);
+    return MWW_OK;
+  }
+  if (!c->ema) MWW_TRY(dev_alloc(&c->ema, (size_t)c->P));
+  c->ema_decay = decay;
+  c->ema_every = every_steps;
+  c->ema_updates = 0;
+  return MWW_OK;
+}
+int mww_get_ema_state(mww_ctx* c, float* h, int64_t n, int64_t* updates) {
+  if (!c || !c->ema) return fail(MWW_ERR_INVALID, "no weight average installed: call mww_set_weight_ema first");
+  if (n != c->P) return fail(MWW_ERR_INVALID, "weight average size mismatch");
+  if (updates) *updates = c->ema_updates;
+  return h ? copy_out(c, h, c->ema, (size_t)n * sizeof(float)) : MWW_OK;
+}
+int mww_set_ema_state(mww_ctx* c, const float* h, int64_t n, int64_t updates) {
+  if (!c || !c->ema) return fail(MWW_ERR_INVALID, "no weight average installed: call mww_set_weight_ema first");
+  if (!h || n != c->P || updates < 0) return fail(MWW_ERR_INVALID, "weight average size mismatch");
+  MWW_TRY(copy_in(c, c->ema, h, (size_t)n * sizeof(float)));
+  if ((c->ema_updates == 0) != (updates == 0)) drop_graphs(c);   // (a captured step's node copies or blends)
+  c->ema_updates = updates;
+  return MWW_OK;
 }
 
 int mww_set_weight_qat(mww_ctx* c, const int32_t* chan_start, const int32_t* chan_elem, int32_t n_channels, int64_t n_elems) {
@@ -1061,6 +1138,7 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
     rc = push_hyper(c, adam_alpha(lr, c->step), (c->hook && c->reduce_grads) ? 1.0f / (float)c->world : 1.0f);
     if (rc) return rc;
   }
+  const int ema = apply ? ema_due(c) : EMA_NONE;
   unsigned long long counter = 0;
   const bool gen_dropout = c->model->step_counter(&counter);
   if (gen_dropout) {
@@ -1078,7 +1156,7 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
     bool handover = false;
     const unsigned mkey = c->model->replay_key(&handover);
     const bool flips = c->bn_inline && handover;
-    const unsigned ckey = (flips ? (4 | c->fpar | (c->gpar << 1)) : 0) | (c->x_lazy ? 8 : 0) | (c->y_cur != c->y ? 16 : 0) | (c->tail_roles ? 32 : 0);
+    const unsigned ckey = (flips ? (4 | c->fpar | (c->gpar << 1)) : 0) | (c->x_lazy ? 8 : 0) | (c->y_cur != c->y ? 16 : 0) | (c->tail_roles ? 32 : 0) | ((unsigned)ema << 6);
     hipGraphExec_t exec = nullptr;
     for (auto& g : c->graphs)
       if (g.B == B && g.flags == flags && g.mail == mail && g.core == ckey && g.model == mkey) exec = g.exec;
@@ -1089,7 +1167,7 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
     if (!exec) {
       hipGraph_t graph;
       HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-      rc = step_sequence(c, B, flags);
+      rc = step_sequence(c, B, flags, ema);
       hipError_t e = hipStreamEndCapture(c->stream, &graph);
       if (rc) return rc;
       if (e != hipSuccess) return fail(MWW_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1098,11 +1176,13 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
       c->graphs.push_back({B, flags, mail, ckey, mkey, exec});
     }
     HIPCHK(hipGraphLaunch(exec, c->stream));
+    if (ema) c->ema_updates += 1;
     return mail_commit(c);
   }
-  rc = step_sequence(c, B, flags);
+  rc = step_sequence(c, B, flags, ema);
   if (rc) return rc;
   HIPCHK(hipGetLastError());
+  if (ema) c->ema_updates += 1;
   return mail_commit(c);
 }
 
@@ -1114,7 +1194,11 @@ int mww_apply_gradients(mww_ctx* c, float lr, float gscale) {
   if (rc) return rc;
   rc = enqueue_adam(c);
   if (rc) return rc;
+  const int ema = ema_due(c);
+  rc = enqueue_ema(c, ema);
+  if (rc) return rc;
   HIPCHK(hipGetLastError());
+  if (ema) c->ema_updates += 1;
   return mail_commit(c);
 }
 
@@ -1129,6 +1213,7 @@ int mww_forward(mww_ctx* c, int B, int training, int update_metrics) {
     rc = materialise_x(c);
     if (rc) return rc;
   }
+  EmaSource source(c, training != 0);
   rc = refresh_shadow(c);
   if (rc) return rc;
   rc = c->model->enqueue_forward(c, B, training != 0, false, false, update_metrics != 0);
@@ -1149,10 +1234,11 @@ int mww_evaluate_windows(mww_ctx* c, const mww_window* windows, const float* lab
     if (!rc) rc = mww_assemble_batch(c, windows + s, nullptr, b, 0, 0);
     if (!rc) rc = mww_forward(c, b, 0, 1);
     c->bn_eval_ready = c->model->eval_fold_cached();   // the weights cannot change between the batches of this call
-    c->shadow_held = true;                             // ... so the first batch's shadow serves them all
+    // ... so the first batch's shadow serves them all (the source mww_forward chose: the master, or the weight average)
+    c->shadow_held = ema_serves(c) ? c->ema : c->params;
   }
   c->bn_eval_ready = false;
-  c->shadow_held = false;
+  c->shadow_held = nullptr;
   return rc;
 }
 
@@ -1249,6 +1335,7 @@ const OptionRow kOptions[] = {
     {"assemble_split", OPT_CORE, 1, 8, 0, "assemble_split out of range"},
     {"grid_head", OPT_CORE, 1, 4, 1, "grid_head out of range"},
     {"weight_qat", OPT_CORE, 0, 1, 0, "weight_qat must be 0 or 1"},
+    {"ema_forward", OPT_CORE, 0, 1, 0, "ema_forward must be 0 or 1"},
     {"ablate", OPT_BLOCK, 1, 0, 0, nullptr},
     {"pointwise_bf16", OPT_BLOCK, 1, 0, 0, nullptr},
     {"storage_bf16", OPT_BLOCK, 1, 0, 0, nullptr},
@@ -1281,6 +1368,10 @@ int set_core_option(mww_ctx* c, const std::string& name, int64_t v) {
   if (name == "weight_qat") {
     if (v && !c->shadow) return fail(MWW_ERR_INVALID, "weight_qat needs a channel map: call mww_set_weight_qat first");
     c->weight_qat = v != 0;
+  }
+  if (name == "ema_forward") {
+    if (v && !c->ema) return fail(MWW_ERR_INVALID, "ema_forward needs the weight average: call mww_set_weight_ema first");
+    c->ema_forward = v != 0;
   }
   if (name == "profile") {   // (the events recorded so far)
     for (auto& e : c->prof) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }

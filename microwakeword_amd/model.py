@@ -17,6 +17,7 @@ INTEGRATION.md) and reads either the twin or — if h5py is importable — a rea
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import List, Optional, Sequence
@@ -171,7 +172,14 @@ class Model:
         return self.layout.keras_param_counts()[0]
 
     def get_weights(self):
-        return self.layout.unpack(self.engine.get_params(), self.engine.get_bn_state())
+        params = self.engine.get_params()
+        if getattr(self, "_averaged", False):
+            # inside averaged_weights(): the trainable variables from the average; the BN moving statistics and the masked
+            # MixConv taps (no Keras variable reaches them, the layout packs them) from the master model
+            ema, _ = self.engine.get_ema_state()
+            trainable = self.layout.grad_mask() != 0
+            params[trainable] = ema[trainable]
+        return self.layout.unpack(params, self.engine.get_bn_state())
 
     def set_weights(self, weights: Sequence[np.ndarray]):
         p, s = self.layout.pack(weights)
@@ -195,6 +203,43 @@ class Model:
         """``get_weights()`` as the next forward would read them: the fake-quantized shadow with ``set_weight_qat(True)``,
         the master otherwise"""
         return self.layout.unpack(self.engine.get_forward_params(), self.engine.get_bn_state())
+
+    def set_weight_averaging(self, decay, every_steps=1):
+        """Weight averaging (``averaging``; ``mww_set_weight_ema``): from the next Adam update on the engine keeps an
+        exponential moving average of the trainable parameters on the device, updated behind every ``every_steps``-th
+        update (the first update copies the master).  ``decay`` 0 removes it.  Training is not affected; evaluate and save
+        on the average inside ``averaged_weights()``."""
+        self.engine.set_weight_ema(decay, every_steps)
+        self.weight_averaging = dict(decay=float(decay), every_steps=int(every_steps)) if decay else None
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside: every inference-mode forward (``predict_on_batch``, ``evaluate``, window evaluation) reads the weight
+        average (engine option ``ema_forward``), and ``get_weights()`` / ``save_weights()`` return the averaged trainable
+        variables with the master model's BN moving statistics.  Training steps keep reading the master.  A no-op while no
+        average is installed or it has not taken its first update."""
+        on = bool(getattr(self, "weight_averaging", None)) and not getattr(self, "_averaged", False) \
+            and self.engine.ema_updates() > 0
+        if not on:
+            yield self
+            return
+        self.engine.set_option("ema_forward", 1)
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._averaged = False
+            self.engine.set_option("ema_forward", 0)
+
+    @contextlib.contextmanager
+    def master_weights(self):
+        """Inside: ``get_weights()`` / ``save_weights()`` return the master also within ``averaged_weights()`` (the restore
+        checkpoint)."""
+        was, self._averaged = getattr(self, "_averaged", False), False
+        try:
+            yield self
+        finally:
+            self._averaged = was
 
     def reset_metrics(self):
         self.engine.metrics_reset()
@@ -344,11 +389,19 @@ class Model:
 
     def save_optimizer_state(self, path):
         m, v, step = self.engine.get_opt_state()
-        np.savez(path, m=m, v=v, step=np.int64(step), lr=np.float64(self.optimizer.learning_rate.value))
+        extra = {}
+        avg = getattr(self, "weight_averaging", None)
+        if avg:   # the weight average travels with the optimizer state: a restored run continues the same average
+            ema, updates = self.engine.get_ema_state()
+            extra = dict(ema=ema, ema_updates=np.int64(updates), ema_decay=np.float64(avg["decay"]), ema_every_steps=np.int64(avg["every_steps"]))
+        np.savez(path, m=m, v=v, step=np.int64(step), lr=np.float64(self.optimizer.learning_rate.value), **extra)
 
     def load_optimizer_state(self, path):
         z = np.load(path)
         self.engine.set_opt_state(z["m"], z["v"], int(z["step"]))
+        if "ema" in z.files:   # (a file written without weight averaging has none of the four: it loads as before)
+            self.set_weight_averaging(float(z["ema_decay"]), int(z["ema_every_steps"]))
+            self.engine.set_ema_state(z["ema"], int(z["ema_updates"]))
 
     def summary(self, print_fn=print):
         total, trainable = self.layout.keras_param_counts()
@@ -357,6 +410,9 @@ class Model:
             print_fn("Kernels: %s" % self.kernel_family)
         for line in self.layout.summary_lines():
             print_fn(line)
+        if getattr(self, "weight_averaging", None):
+            print_fn("Weight averaging: exponential moving average of the trainable variables, decay %g, every %d step(s)"
+                     % (self.weight_averaging["decay"], self.weight_averaging["every_steps"]))
         if getattr(self, "weight_qat", False):
             print_fn("Weights: fake-quantized per output channel to the int8 grid in every forward / backward (fp32 master kept)")
         print_fn("Total params: %d" % total)

@@ -346,6 +346,8 @@ def _run(flags, model_module, rank, local_rank, world):
                                  check_streaming_validation_config(flags, model_module, config, world))
         from . import qat
         qat.parse_config(config)   # weight_quantization_aware: likewise
+        from . import averaging
+        averaging.parse_config(config)   # weight_averaging: likewise
     device = flags.device if local_rank is None else local_rank
     if flags.train:
         device = flags.device if local_rank is None else local_rank

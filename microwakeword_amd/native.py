@@ -129,7 +129,7 @@ EXPORTS = [
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
     "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections", "mww_stream_operating_points",
     "mww_stream_mine", "mww_stream_operating_summary", "mww_stream_calibrate",
-    "mww_set_weight_qat", "mww_get_forward_params",
+    "mww_set_weight_qat", "mww_get_forward_params", "mww_set_weight_ema", "mww_get_ema_state", "mww_set_ema_state",
 ]
 
 
@@ -194,6 +194,9 @@ class NativeLib:
         L.mww_get_opt_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64,
                                         C.POINTER(C.c_int64)]
         L.mww_set_weight_qat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]
+        L.mww_set_weight_ema.argtypes = [C.c_void_p, C.c_double, C.c_int64]
+        L.mww_get_ema_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]
+        L.mww_set_ema_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int64]
         L.mww_upload_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int]
         L.mww_assemble_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.mww_set_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
@@ -508,6 +511,28 @@ class Engine:
     def get_forward_params(self):
         """the parameter vector the next forward would read (the fake-quantized shadow with ``weight_qat`` on)"""
         return self._vec_out(self.nl.lib.mww_get_forward_params, self.n_params)
+
+    def set_weight_ema(self, decay, every_steps=1):
+        """Install the on-device exponential moving average of the parameters (``averaging``; ``mww_set_weight_ema``): updated
+        behind every ``every_steps``-th Adam update, the first update a copy of the master.  ``decay`` 0 removes it."""
+        self.nl.check(self.nl.lib.mww_set_weight_ema(self.h, float(decay), int(every_steps)))
+
+    def get_ema_state(self):
+        """(ema [P] float32, updates) of the installed average"""
+        a = np.empty(self.n_params, np.float32)
+        updates = C.c_int64()
+        self.nl.check(self.nl.lib.mww_get_ema_state(self.h, _fptr(a), self.n_params, C.byref(updates)))
+        return a, int(updates.value)
+
+    def ema_updates(self):
+        """the number of updates the installed average has taken (no copy of the vector)"""
+        updates = C.c_int64()
+        self.nl.check(self.nl.lib.mww_get_ema_state(self.h, None, self.n_params, C.byref(updates)))
+        return int(updates.value)
+
+    def set_ema_state(self, ema, updates):
+        a = np.ascontiguousarray(ema, np.float32).reshape(-1)
+        self.nl.check(self.nl.lib.mww_set_ema_state(self.h, _fptr(a), a.size, int(updates)))
 
     def set_opt_state(self, m, v, step):
         m = np.ascontiguousarray(m, np.float32).reshape(-1)

@@ -16,6 +16,9 @@ FAPH / recall at the operating point its ``target_faph`` selects (``streaming.va
 ``streaming_*`` metrics to those the best-weights rule may name; without the key nothing changes.
 With a ``weight_quantization_aware`` mapping (``qat``) the steps from ``first_step`` on train for the int8 model:
 the engine's forward / backward read the weights on the int8 grid while Adam keeps the fp32 master.
+With a ``weight_averaging`` mapping (``averaging``) the engine keeps an exponential moving average of the trainable
+weights from ``first_step`` on, and every evaluation boundary - the weight files, both validations, the best-weights rule, a
+mining round - stands on the averaged model; the steps themselves and the restore checkpoint keep the raw iterate.
 
 When both objects come from this package the spectrogram batch never leaves HBM
 (``FeatureHandler.next_training_batch_on_device`` + ``Model.train_on_device_batch``); with any other
@@ -204,6 +207,10 @@ def train(model, config, data_processor, verbose=True):
     qat_settings = qat.parse_config(config)   # likewise
     if qat_settings is not None and not hasattr(model, "set_weight_qat"):
         raise ValueError("%s needs this package's Model (the engine fake-quantizes the weights in the step)" % qat.CONFIG_KEY)
+    from . import averaging
+    avg_settings = averaging.parse_config(config)   # likewise
+    if avg_settings is not None and not hasattr(model, "set_weight_averaging"):
+        raise ValueError("%s needs this package's Model (the engine keeps the average on the device)" % averaging.CONFIG_KEY)
     fast = hasattr(data_processor, "next_training_batch_on_device") and hasattr(model, "train_on_device_batch") \
         and getattr(data_processor, "engine", None) is getattr(model, "engine", object())
     prefetch = int(config.get("prefetch_batches", 4))
@@ -249,6 +256,16 @@ def train(model, config, data_processor, verbose=True):
         resumed_step = int(model.engine.get_opt_state()[2]) if hasattr(model.engine, "get_opt_state") else 0
         seed = config.get("data_parallel_seed")
         shard_feature_handler(data_processor, rank, world, seed=None if seed is None else int(seed), prefetch=prefetch, epoch=resumed_step)
+        if avg_settings is not None and world > 1:
+            # a weight average rank 0 restored goes to every rank like the Adam state; from then on nothing is exchanged (the
+            # update is a deterministic function of identical masters)
+            held = model.engine.get_ema_state() if chief and getattr(model, "weight_averaging", None) else None
+            head = dp.broadcast_host(np.array([-1.0 if held is None else float(held[1])], np.float64))
+            if head[0] >= 0:
+                ema = dp.broadcast_host(held[0] if chief else np.zeros(model.engine.n_params, np.float32))
+                if not chief:
+                    model.set_weight_averaging(avg_settings["decay"], avg_settings["every_steps"])
+                    model.engine.set_ema_state(ema, int(head[0]))
         log.info("data-parallel: rank %d of %d, %d windows per rank and step (global batch %d), %s BatchNorm", rank, world,
                  config["batch_size"] // world, config["batch_size"], "synchronised" if dp.sync_bn else "rank-local")
     elif fast and hasattr(data_processor, "use_private_rng") and prefetch > 0:
@@ -279,8 +296,23 @@ def train(model, config, data_processor, verbose=True):
     # run needs no state of its own: on / off follows from the restored optimizer step.
     qat_on = False
     steps_before = 0
-    if qat_settings is not None and hasattr(model, "engine") and hasattr(model.engine, "get_opt_state"):
+    if (qat_settings is not None or avg_settings is not None) and hasattr(model, "engine") and hasattr(model.engine, "get_opt_state"):
         steps_before = int(model.engine.get_opt_state()[2])
+    # weight_averaging: installed before optimizer step `first_step`, whose update copies the master.  The average and its
+    # update count travel in the checkpoint's optimizer state, so a restored run continues the same average.
+    avg_on = False
+    if avg_settings is not None and getattr(model, "weight_averaging", None):
+        avg_on = True
+        if model.weight_averaging != {k: avg_settings[k] for k in ("decay", "every_steps")}:   # the configuration decides
+            ema, updates = model.engine.get_ema_state()
+            model.set_weight_averaging(avg_settings["decay"], avg_settings["every_steps"])
+            model.engine.set_ema_state(ema, updates)
+        if chief:
+            log.info("weight averaging continues from the checkpoint (%d updates, decay %g)", model.engine.ema_updates(), avg_settings["decay"])
+
+    def averaged():
+        # what is validated, selected, mined with and written at a boundary is the averaged model (a no-op before its first update)
+        return model.averaged_weights() if avg_on else contextlib.nullcontext()
 
     warned_weights = False
     steps_max = int(np.sum(ph["training_steps"]))
@@ -294,9 +326,10 @@ def train(model, config, data_processor, verbose=True):
         if not chief:
             return
         os.makedirs(ckpt_dir, exist_ok=True)
-        model.save_weights(ckpt + ".weights")
+        with (model.master_weights() if avg_on else contextlib.nullcontext()):   # the checkpoint holds the master, also inside averaged()
+            model.save_weights(ckpt + ".weights")
         if hasattr(model, "save_optimizer_state"):
-            model.save_optimizer_state(ckpt + ".opt.npz")
+            model.save_optimizer_state(ckpt + ".opt.npz")   # (with the weight average, when one is installed)
 
     for step in range(1, steps_max + 1):
         acc = 0
@@ -316,6 +349,12 @@ def train(model, config, data_processor, verbose=True):
             qat_on = True
             if chief:
                 log.info("Step #%d: weight quantization-aware training on (forward / backward read the int8 weight grid)", steps_before + step)
+        if avg_settings is not None and not avg_on and steps_before + step >= avg_settings["first_step"]:
+            model.set_weight_averaging(avg_settings["decay"], avg_settings["every_steps"])   # every rank: the same average of the same masters
+            avg_on = True
+            if chief:
+                log.info("Step #%d: weight averaging on (decay %g, every %d step(s)); evaluation boundaries stand on the average",
+                         steps_before + step, avg_settings["decay"], avg_settings["every_steps"])
         if fast:
             data_processor.next_training_batch_on_device(local_batch, config["spectrogram_length"], "default", policy,
                                                          class_weights=(cw_neg, cw_pos), weight_broadcast=mode)
@@ -352,46 +391,49 @@ def train(model, config, data_processor, verbose=True):
             info("Step #%d: rate %f, accuracy %.2f%%, recall %.2f%%, precision %.2f%%, cross entropy %f",
                  step, lr, result[1] * 100, result[2] * 100, result[3] * 100, result[9])
             train_writer.scalars(step, loss=result[9], accuracy=result[1], recall=result[2], precision=result[3], auc=result[8],
-                                 **({} if qat_settings is None else {"weight_qat": int(qat_on)}))
-            save_weights(os.path.join(config["train_dir"], "last_weights.weights.h5"))
-            if private_streams:
-                data_processor.release_private_rng()   # validation shuffles on the global numpy stream (data.py:593-595) ...
-            nm = validate_nonstreaming(config, data_processor, model, "validation")
-            streamed = streamer is not None and streamer.due(is_last)
-            if streamed:
-                nm.update(streamer.validate(step))   # while the private streams are released; it draws nothing
-            if private_streams and miner is None:
-                data_processor.use_private_rng(prefetch=prefetch)   # ... and the training draws continue behind them
-            model.reset_metrics()
-            info("Step %d (nonstreaming): Validation: recall at no faph = %.3f with cutoff %.2f, accuracy = %.2f%%, recall = %.2f%%, "
-                     "precision = %.2f%%, ambient false positives = %d, estimated false positives per hour = %.5f, loss = %.5f, "
-                     "auc = %.5f, average viable recall = %.9f", step, nm["recall_at_no_faph"] * 100, nm["cutoff_for_no_faph"],
-                 nm["accuracy"] * 100, nm["recall"] * 100, nm["precision"] * 100, nm["ambient_false_positives"],
-                 nm["ambient_false_positives_per_hour"], nm["loss"], nm["auc"], nm["average_viable_recall"])
-            val_writer.scalars(step, loss=nm["loss"], accuracy=nm["accuracy"], recall=nm["recall"], precision=nm["precision"],
-                               recall_at_no_faph=nm["recall_at_no_faph"], auc=nm["auc"], average_viable_recall=nm["average_viable_recall"])
-            if chief:
-                os.makedirs(os.path.join(config["train_dir"], "train"), exist_ok=True)
-            save_weights(os.path.join(config["train_dir"], "train", f"{int(best_min * 10000)}_weights_{step}.weights.h5"))
-            # a boundary without a streaming validation (every_evals > 1) has no value for a streaming metric: the rule waits
-            judged = streamed or not streaming_named
-            cur_min = 0.0 if config["minimization_metric"] is None or not judged else nm[config["minimization_metric"]]
-            cur_max = nm[config["maximization_metric"]] if judged else 0.0
-            if judged and _is_better(cur_min, cur_max, best_min, best_max, config["target_minimization"]):
-                best_min, best_max, best_cutoff = cur_min, cur_max, nm["cutoff_for_no_faph"]
-                save_weights(os.path.join(config["train_dir"], "best_weights.weights.h5"))
-                save_ckpt()
-            info("So far the best minimization quantity is %.3f with best maximization quantity of %.5f%%; no faph cutoff is %.2f",
-                 best_min, best_max * 100, best_cutoff)
-            if miner is not None:
-                # after validation, the best-weights rule and the checkpoint, and before the private streams are taken up again: a
-                # round draws nothing, so the draws continue where they would without it
-                if miner.due(step, is_last):
-                    miner.round(step)
+                                 **({} if qat_settings is None else {"weight_qat": int(qat_on)}),
+                                 **({} if avg_settings is None else {"weight_averaging": int(avg_on)}))
+            with averaged():
+                save_weights(os.path.join(config["train_dir"], "last_weights.weights.h5"))
                 if private_streams:
-                    data_processor.use_private_rng(prefetch=prefetch)
+                    data_processor.release_private_rng()   # validation shuffles on the global numpy stream (data.py:593-595) ...
+                nm = validate_nonstreaming(config, data_processor, model, "validation")
+                streamed = streamer is not None and streamer.due(is_last)
+                if streamed:
+                    nm.update(streamer.validate(step))   # while the private streams are released; it draws nothing
+                if private_streams and miner is None:
+                    data_processor.use_private_rng(prefetch=prefetch)   # ... and the training draws continue behind them
+                model.reset_metrics()
+                info("Step %d (nonstreaming): Validation: recall at no faph = %.3f with cutoff %.2f, accuracy = %.2f%%, recall = %.2f%%, "
+                         "precision = %.2f%%, ambient false positives = %d, estimated false positives per hour = %.5f, loss = %.5f, "
+                         "auc = %.5f, average viable recall = %.9f", step, nm["recall_at_no_faph"] * 100, nm["cutoff_for_no_faph"],
+                     nm["accuracy"] * 100, nm["recall"] * 100, nm["precision"] * 100, nm["ambient_false_positives"],
+                     nm["ambient_false_positives_per_hour"], nm["loss"], nm["auc"], nm["average_viable_recall"])
+                val_writer.scalars(step, loss=nm["loss"], accuracy=nm["accuracy"], recall=nm["recall"], precision=nm["precision"],
+                                   recall_at_no_faph=nm["recall_at_no_faph"], auc=nm["auc"], average_viable_recall=nm["average_viable_recall"])
+                if chief:
+                    os.makedirs(os.path.join(config["train_dir"], "train"), exist_ok=True)
+                save_weights(os.path.join(config["train_dir"], "train", f"{int(best_min * 10000)}_weights_{step}.weights.h5"))
+                # a boundary without a streaming validation (every_evals > 1) has no value for a streaming metric: the rule waits
+                judged = streamed or not streaming_named
+                cur_min = 0.0 if config["minimization_metric"] is None or not judged else nm[config["minimization_metric"]]
+                cur_max = nm[config["maximization_metric"]] if judged else 0.0
+                if judged and _is_better(cur_min, cur_max, best_min, best_max, config["target_minimization"]):
+                    best_min, best_max, best_cutoff = cur_min, cur_max, nm["cutoff_for_no_faph"]
+                    save_weights(os.path.join(config["train_dir"], "best_weights.weights.h5"))
+                    save_ckpt()
+                info("So far the best minimization quantity is %.3f with best maximization quantity of %.5f%%; no faph cutoff is %.2f",
+                     best_min, best_max * 100, best_cutoff)
+                if miner is not None:
+                    # after validation, the best-weights rule and the checkpoint, and before the private streams are taken up again: a
+                    # round draws nothing, so the draws continue where they would without it
+                    if miner.due(step, is_last):
+                        miner.round(step)
+                    if private_streams:
+                        data_processor.use_private_rng(prefetch=prefetch)
     save_ckpt()
-    save_weights(os.path.join(config["train_dir"], "last_weights.weights.h5"))
+    with averaged():
+        save_weights(os.path.join(config["train_dir"], "last_weights.weights.h5"))
     if dp is not None:
         dp.barrier()   # rank 0's files are complete before any rank returns (and tears the process group down)
     return dict(best_minimization=best_min, best_maximization=best_max, best_no_faph_cutoff=best_cutoff)
