@@ -183,19 +183,53 @@ int mww_get_forward_params(mww_ctx* ctx, float* host, int64_t n);
  * context's stream directly behind every Adam update - the one inside mww_train_step or mww_apply_gradients - after which the
  * optimizer step count is a multiple of every_steps (one more node of a captured step).  A step with MWW_STEP_NO_APPLY
  * updates nothing; mww_set_params does not touch the average.  The BatchNorm moving statistics are not trainable and are
- * not averaged.
+ * not averaged: they are re-estimated for the average by the calls of the next block.
  *
  * mww_set_weight_ema installs the average (updates = 0) with decay in (0, 1) and every_steps >= 1; decay == 0 removes it and
  * frees the vector.  Other values are MWW_ERR_INVALID and leave the context as it was.
  *
  * With the option ema_forward = 1 (the option call below; default 0; MWW_ERR_INVALID without an installed average) and
  * once updates > 0, every non-training forward - mww_forward(training = 0), mww_evaluate_windows, mww_get_forward_params -
- * stands on the average instead of the master, with the current moving statistics; with weight_qat it reads
- * fake_quant(average).  mww_train_step and mww_forward(training = 1) always read the master (or its shadow). */
+ * stands on the average instead of the master, with the master's current moving statistics - or, while they are valid, with
+ * the average's own re-estimated ones (next block); with weight_qat it reads fake_quant(average).  mww_train_step and
+ * mww_forward(training = 1) always read the master (or its shadow). */
 int mww_set_weight_ema(mww_ctx* ctx, double decay, int64_t every_steps);
 /* the average and its update count, for checkpoints (host may be NULL to read the count alone); n = mww_num_params */
 int mww_get_ema_state(mww_ctx* ctx, float* host, int64_t n, int64_t* updates);
 int mww_set_ema_state(mww_ctx* ctx, const float* host, int64_t n, int64_t updates);
+
+/* ---- BatchNorm statistics for the average.  The moving statistics were accumulated under the raw iterates; the averaged
+ * model wants the statistics of its own activations.  State: ema_bn[S] in fp32, laid out and indexed like the vector of
+ * mww_get_bn_state, and a validity flag.  A pass over K >= 1 batches:
+ *     batch k:  the forward of mww_forward(training = 1, update_metrics = 0) on the current batch - batch statistics, moving
+ *               statistics untouched, no loss, no metrics, no dropout - reading the AVERAGE (with weight_qat:
+ *               fake_quant(average)), whatever the ema_forward option says; directly behind it one collect launch adds, for
+ *               every statistic slot s (a BN channel, a (channel, sub-band) slot of a SubSpectralNormalization), the fp32
+ *               batch mean and biased batch variance that forward normalised with to float64 sums:
+ *               M[s] += (double)mean_k[s], V[s] += (double)var_k[s], in batch order
+ *     commit:   ema_bn[o_mm + s] = (float)(M[s] / (double)K), ema_bn[o_mv + s] = (float)(V[s] / (double)K); valid = 1
+ * mean_k / var_k are re-derived from the sums the forward's own statistics fold consumed, with its expressions and summation
+ * order: they are that fold's floats bit for bit.  No atomics: two passes over the same batches write the same bytes.  The
+ * master's bn_state is never written, nothing random is drawn, and a pass is never captured under "graphs" (captured steps
+ * stay replayable behind it).  While valid, every non-training forward that stands on the average (ema_forward = 1, updates
+ * > 0) folds ema_bn instead of the master's moving statistics.  Whatever changes what such a forward reads clears the flag -
+ * an update of the average, mww_set_ema_state, mww_set_weight_ema, the weight_qat option or map - and closes a pass in
+ * progress; evaluations then read the master's moving statistics again.
+ *
+ * mww_bn_reestimate_begin zeroes the sums (MWW_ERR_INVALID unless an average is installed and has taken an update);
+ * mww_bn_reestimate_batch runs the forward + collect on the current batch's first B rows (MWW_ERR_STATE without an open pass
+ * or a batch); mww_bn_reestimate_commit writes ema_bn (MWW_ERR_STATE with no batch collected).  mww_bn_reestimate_windows is
+ * the three over a window list, gathered from the resident stores like mww_evaluate_windows: n must be a positive multiple
+ * of batch (MWW_ERR_INVALID otherwise), so that every batch weighs the same.  A refused call leaves the context as it was. */
+int mww_bn_reestimate_begin(mww_ctx* ctx);
+int mww_bn_reestimate_batch(mww_ctx* ctx, int B);
+int mww_bn_reestimate_commit(mww_ctx* ctx);
+/* (mww_bn_reestimate_windows: declared behind mww_evaluate_windows, where mww_window is known) */
+/* the statistics a forward at the average folds: ema_bn with *valid = 1, or the master's moving statistics with *valid = 0
+ * (host / valid may be NULL); the setter installs ema_bn and marks it valid (data-parallel: the mean of the ranks' passes).
+ * n = mww_num_bn_state; MWW_ERR_INVALID without an installed average. */
+int mww_get_ema_bn_state(mww_ctx* ctx, float* host, int64_t n, int* valid);
+int mww_set_ema_bn_state(mww_ctx* ctx, const float* host, int64_t n);
 
 /* ---- feature stores: replace the RaggedMmap page-cache reads of data.py:255-258.  A store is the
  * flat concatenation of its samples ([T_i][40], uint16 raw micro-frontend values or float32
@@ -295,6 +329,8 @@ int mww_forward(mww_ctx* ctx, int B, int training, int update_metrics);
  * call), threshold / AUC / loss counters accumulated on the device (read them with mww_metrics_read).  One call per
  * evaluation instead of three per batch. */
 int mww_evaluate_windows(mww_ctx* ctx, const mww_window* windows, const float* labels, int64_t n, int batch);
+/* a BatchNorm re-estimation pass over a window list (see "BatchNorm statistics for the average" above) */
+int mww_bn_reestimate_windows(mww_ctx* ctx, const mww_window* windows, int64_t n, int batch);
 
 /* outputs of the last train step / forward (waits for the stream). Any pointer may be NULL. */
 int mww_read_outputs(mww_ctx* ctx, int B, float* probs, float* logits, float* loss);

@@ -6,6 +6,7 @@
 
 #include "engine.hip.h"
 #include "block_launch.hip.h"
+#include "kernels_bnre.hip.h"
 
 // the fp32 block backward runs as the wide-workgroup form (option "bwd_wide"; kernels_bwdw.hip.h) unless told otherwise
 // options "conv1_x6" (the conv1 weight gradient in the first block's backward kernel) and "conv1_x6_fwd" (the first convolution
@@ -78,6 +79,7 @@ struct BlockModel : Model {
   int alloc(mww_ctx* c, std::vector<BnSlots>* bn) override;
   int enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) override;
   int enqueue_backward(mww_ctx* c, int B, bool fuse_adam) override;
+  int enqueue_bn_collect(mww_ctx* c, int B) override;
   std::vector<int> stat_widths() const override {
     std::vector<int> w;
     for (const Layer& l : L) w.push_back(l.cout);
@@ -176,7 +178,7 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   if (!training && !c->bn_eval_ready) {
     for (int i = 0; i < nb; ++i) {
       Layer& l = L[i];
-      BnEvalPrepareArgs a{fwd_params(c) + l.o_gamma, fwd_params(c) + l.o_beta, c->bn_state + l.o_mm, c->bn_state + l.o_mv,
+      BnEvalPrepareArgs a{fwd_params(c) + l.o_gamma, fwd_params(c) + l.o_beta, eval_bn_state(c) + l.o_mm, eval_bn_state(c) + l.o_mv,
                           bn_slot(l, BN_SCALE), bn_slot(l, BN_SHIFT), l.cout};
       lp.begin("bn_eval_prepare", i);
       hipLaunchKernelGGL(bn_eval_prepare_kernel, dim3(1), dim3(64), 0, c->stream, a);
@@ -268,6 +270,38 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
     return MWW_OK;
   }
   return enqueue_side_work(c, B, metrics, loss, c->tail_src);
+}
+
+// BN re-estimation: where the training forward of B windows just enqueued left every block's sums - the accumulator rows its
+// first consumer folded, or the partial rows (behind a sync-BN exchange: the row of global sums) bn_fwd_finalize_kernel read -
+// with the inv_n of that fold
+int BlockModel::enqueue_bn_collect(mww_ctx* c, int B) {
+  const bool inl = c->bn_inline && !(c->hook && c->sync_bn);
+  std::vector<BnreRow> rows(L.size());
+  memset(rows.data(), 0, rows.size() * sizeof(BnreRow));
+  for (size_t i = 0; i < L.size(); ++i) {
+    Layer& l = L[i];
+    BnreRow& r = rows[i];
+    const float inv_n = 1.0f / ((float)B * (float)l.tout);
+    r.C = l.cout;
+    r.groups = 1;
+    r.o_mm = (int)l.o_mm;
+    r.o_mv = (int)l.o_mv;
+    if (inl) {
+      r.form = BNRE_ROWS;
+      r.acc[0] = l.facc[0];
+      r.acc[1] = l.facc[1];
+      r.inv_n = inv_n;
+    } else {
+      const int grid = i == 0 ? std::min(B, grid_fwd) : fwd_block_grid(c, l, B);
+      const StatSource ss = forward_stat_source(c, (int)i, l.stat_part, grid, l.cout, inv_n);
+      r.form = BNRE_PART_BLOCK;
+      r.part = ss.part;
+      r.G = ss.G;
+      r.inv_n = ss.inv_n;
+    }
+  }
+  return enqueue_bnre_collect(c, rows);
 }
 
 // the weight-gradient partial rows of blocks [b0, b1)

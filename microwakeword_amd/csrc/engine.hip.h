@@ -16,6 +16,7 @@
 namespace mww {
 
 struct MetricState;   // kernels_head.hip.h
+struct BnreRow;       // kernels_bnre.hip.h
 
 int fail(int code, const std::string& msg);   // sets mww_last_error(), returns code
 
@@ -124,6 +125,9 @@ struct Model {
   virtual int alloc(mww_ctx* c, std::vector<BnSlots>* bn) = 0;
   virtual int enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) = 0;
   virtual int enqueue_backward(mww_ctx* c, int B, bool fuse_adam) = 0;
+  // BN re-estimation (kernels_bnre.hip.h): enqueue the collect for the training-mode forward of B windows just enqueued - one
+  // table row per BN'd tensor, saying where that forward left the tensor's sums (enqueue_bnre_collect launches them)
+  virtual int enqueue_bn_collect(mww_ctx* c, int B) = 0;
   virtual std::vector<int> stat_widths() const = 0;   // channels of every BN'd tensor, in sync-BN order
   virtual bool lazy_ok(const mww_ctx* c, int B) const = 0;   // may this batch stay descriptor-only ("fused_input")?
   virtual bool step_counter(unsigned long long* n) { return false; }   // the counter this step's dropout mask is drawn from, if one is
@@ -175,6 +179,16 @@ struct mww_ctx {
   double ema_decay = 0.0;
   int64_t ema_every = 1, ema_updates = 0;
   bool ema_forward = false, ema_src = false;
+  // BatchNorm re-estimation for the average (mww_bn_reestimate_*, kernels_bnre.hip.h): `ema_bn` = the batch statistics of
+  // training-mode forwards at the average, averaged over a pass; while `ema_bn_valid`, a non-training forward that stands on the
+  // average folds them instead of the master's moving statistics (eval_bn_state).  Allocated by the first pass.
+  float* ema_bn = nullptr;
+  bool ema_bn_valid = false;
+  double* bnre_acc = nullptr;             // [S] float64 sums of the pass in progress
+  int64_t bnre_batches = -1;              // batches collected by the pass in progress; -1: none is open
+  mww::BnreRow* bnre_table = nullptr;     // device-resident table of the collect launch
+  int bnre_table_rows = 0;
+  std::vector<char> bnre_table_host;      // what it holds (uploaded again only when a row changes)
   unsigned char* direct = nullptr;
   std::vector<unsigned char> direct_host;   // host copy: which parameters' gradients are written directly by a folding kernel
   bool exchange_pending = false;            // a deferred bucket exchange is in flight (data-parallel step)
@@ -270,6 +284,9 @@ enum { BN_SCALE = 0, BN_SHIFT, BN_MEAN, BN_RSTD, BN_C1, BN_MG, BN_MGX };
 inline float* fwd_source(const mww_ctx* c) { return c->ema_src ? c->ema : c->params; }
 // the parameter vector the forward / backward launches read: that vector, or its fake-quantized shadow ("weight_qat")
 inline float* fwd_params(const mww_ctx* c) { return c->weight_qat ? c->shadow : fwd_source(c); }
+// the moving statistics an eval-mode fold reads: the master's, or - in a call that stands on the average - the average's own
+// re-estimated ones while they are valid
+inline float* eval_bn_state(const mww_ctx* c) { return (c->ema_src && c->ema_bn_valid) ? c->ema_bn : c->bn_state; }
 
 // ---- mww_lib.hip
 template <typename T>
@@ -286,6 +303,10 @@ int enqueue_side_work(mww_ctx* c, int B, bool metrics, bool loss, const DenseSou
 // sync-BN: the partial rows (or their sum over the ranks) the finalize kernel should read
 struct StatSource { const float* part; int G; float inv_n; float dscale; };
 int exchange_stats(mww_ctx* c, Launcher& lp, const char* what, int layer, const float* part, int G, int C, int bwd, float local_inv_n, StatSource* out);
+// what exchange_stats handed the forward finalize of `layer` in the forward just enqueued (nothing is launched or exchanged)
+StatSource forward_stat_source(const mww_ctx* c, int layer, const float* part, int G, int C, float local_inv_n);
+// BN re-estimation: block0 / nblocks of the rows are filled in, the device table is brought up to date, the collect is launched
+int enqueue_bnre_collect(mww_ctx* c, std::vector<BnreRow>& rows);
 int enqueue_grad_assembly(mww_ctx* c, int B, GradReduceArgs& ga, bool fuse_adam, int64_t lo = 0, int64_t hi = -1, bool last_range = true);
 // the block engine's classifier head and the launch that opens its backward pass (BN_L's backward finalize + dense gradient +
 // metrics): their kernels share kernels_head.hip.h / kernels_tail.hip.h with the core's own, which one unit alone can include

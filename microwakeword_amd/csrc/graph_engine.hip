@@ -9,6 +9,7 @@
 
 #include "engine.hip.h"
 #include "graph_launch.hip.h"
+#include "kernels_bnre.hip.h"
 
 namespace mww {
 
@@ -60,6 +61,7 @@ struct GraphModel : Model {
   int alloc(mww_ctx* c, std::vector<BnSlots>* bn) override;
   int enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) override;
   int enqueue_backward(mww_ctx* c, int B, bool fuse_adam) override;
+  int enqueue_bn_collect(mww_ctx* c, int B) override;
   std::vector<int> stat_widths() const override {
     std::vector<int> w;
     for (const GOp& o : G) w.push_back(o.cout);
@@ -357,7 +359,7 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   for (int i = 0; i < n; ++i) {
     GOp& o = m.G[i];
     if (!training && o.norm == MWW_NORM_BN) {
-      GBnEvalArgs e{fwd_params(c) + o.o_gamma, fwd_params(c) + o.o_beta, c->bn_state + o.o_mm, c->bn_state + o.o_mv,
+      GBnEvalArgs e{fwd_params(c) + o.o_gamma, fwd_params(c) + o.o_beta, eval_bn_state(c) + o.o_mm, eval_bn_state(c) + o.o_mv,
                     gbn_slot(o, BN_SCALE), gbn_slot(o, BN_SHIFT), o.cout, o.groups};
       lp.begin("bn_eval_prepare", i);
       hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, c->stream, e);
@@ -420,7 +422,7 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
       // twins: one convolution launch and one finalize launch for the pair
       GOp& o2 = m.G[i + 1];
       if (!training) {
-        GBnEvalArgs e{fwd_params(c) + o2.o_gamma, fwd_params(c) + o2.o_beta, c->bn_state + o2.o_mm, c->bn_state + o2.o_mv,
+        GBnEvalArgs e{fwd_params(c) + o2.o_gamma, fwd_params(c) + o2.o_beta, eval_bn_state(c) + o2.o_mm, eval_bn_state(c) + o2.o_mv,
                       gbn_slot(o2, BN_SCALE), gbn_slot(o2, BN_SHIFT), o2.cout, o2.groups};
         hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, c->stream, e);
       }
@@ -558,6 +560,42 @@ int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   lp.end();
   const DenseSource ds{lo.p, h.scale, h.shift, drop ? m.keep : nullptr, h.rp, h.rscale, h.rshift, h.rT, h.rdrop, 0};
   return enqueue_side_work(c, B, metrics, loss, ds);
+}
+
+// BN re-estimation: where the training forward of B windows just enqueued left the sums of every op with a BatchNorm - the
+// accumulator rows its first consumer folded (gfold_forward_finish), or the partial rows (behind a sync-BN exchange: the row of
+// global sums) gbn_fwd_finalize_body read - with the inv_n of that fold
+int GraphModel::enqueue_bn_collect(mww_ctx* c, int B) {
+  GraphModel& m = *this;
+  const bool inl = c->bn_inline && m.g_inline_ok && !(c->hook && c->sync_bn) && !m.profile_split;
+  const int gg = std::min(B, m.grid_g);
+  std::vector<BnreRow> rows;
+  for (size_t i = 0; i < m.G.size(); ++i) {
+    GOp& o = m.G[i];
+    if (o.norm != MWW_NORM_BN) continue;
+    BnreRow r;
+    memset(&r, 0, sizeof(r));
+    const float inv_n = 1.0f / ((float)B * (float)o.tout * (float)(o.groups > 1 ? o.cout / o.groups : 1));
+    r.C = o.cout;
+    r.groups = o.groups;
+    r.o_mm = (int)o.o_mm;
+    r.o_mv = (int)o.o_mv;
+    if (inl) {
+      if (o.groups > 1 && o.cout > kGFoldC) return fail(MWW_ERR_UNSUPPORTED, "bn_reestimate: a SubSpectralNormalization wider than a wave");
+      r.form = BNRE_ROWS;
+      r.acc[0] = o.facc[0];
+      r.acc[1] = o.facc[1];
+      r.inv_n = inv_n;
+    } else {
+      const StatSource ss = forward_stat_source(c, (int)i, o.stat_part, gg, o.cout, inv_n);
+      r.form = BNRE_PART_GRAPH;
+      r.part = ss.part;
+      r.G = ss.G;
+      r.inv_n = ss.inv_n;
+    }
+    rows.push_back(r);
+  }
+  return enqueue_bnre_collect(c, rows);
 }
 
 int GraphModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "engine.hip.h"
+#include "kernels_bnre.hip.h"
 #include "kernels_data.hip.h"
 #include "kernels_ema.hip.h"
 #include "kernels_head.hip.h"
@@ -207,6 +208,44 @@ int exchange_stats(mww_ctx* c, Launcher& lp, const char* what, int layer, const 
   out->G = 1;
   out->inv_n = local_inv_n / (float)c->world;
   out->dscale = 1.0f / (float)c->world;
+  return MWW_OK;
+}
+
+StatSource forward_stat_source(const mww_ctx* c, int layer, const float* part, int G, int C, float local_inv_n) {
+  if (!(c->hook && c->sync_bn)) return StatSource{part, G, local_inv_n, 1.0f};
+  // (every layer has its own place in sync_buf: the sums of the whole forward are still there)
+  return StatSource{c->sync_buf + c->sync_off[layer], 1, local_inv_n / (float)c->world, 1.0f / (float)c->world};
+}
+
+int enqueue_bnre_collect(mww_ctx* c, std::vector<BnreRow>& rows) {
+  if (rows.empty()) return MWW_OK;
+  int blocks = 0;
+  for (BnreRow& r : rows) {
+    r.nblocks = r.form == BNRE_ROWS ? 1 : (r.groups > 1 ? r.groups : r.C);
+    r.block0 = blocks;
+    blocks += r.nblocks;
+  }
+  const size_t bytes = rows.size() * sizeof(BnreRow);
+  if (c->bnre_table_host.size() != bytes || memcmp(c->bnre_table_host.data(), rows.data(), bytes) != 0) {
+    // a row changes with the batch size, the statistics path ("bn_inline", sync-BN) or a grid option - not from batch to
+    // batch of a pass (the accumulator parity travels as a launch argument) - so this wait is paid once per configuration
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the launches that read the old table are done)
+    if (c->bnre_table_rows < (int)rows.size()) {
+      if (c->bnre_table) HIPCHK(hipFree(c->bnre_table));
+      c->bnre_table = nullptr;
+      c->bnre_table_rows = 0;
+      MWW_TRY(dev_alloc(&c->bnre_table, rows.size()));
+      c->bnre_table_rows = (int)rows.size();
+    }
+    c->bnre_table_host.clear();
+    HIPCHK(hipMemcpy(c->bnre_table, rows.data(), bytes, hipMemcpyHostToDevice));
+    c->bnre_table_host.assign(reinterpret_cast<const char*>(rows.data()), reinterpret_cast<const char*>(rows.data()) + bytes);
+  }
+  Launcher lp{c};
+  lp.begin("bn_reestimate_collect");
+  // the forward flipped the parity behind its last launch: its rows are the other one's
+  launch_bnre_collect(BnreCollectArgs{c->bnre_table, (int)rows.size(), c->fpar ^ 1, c->bnre_acc}, blocks, c->stream);
+  lp.end();
   return MWW_OK;
 }
 
@@ -447,7 +486,23 @@ int enqueue_ema(mww_ctx* c, int mode) {
   return MWW_OK;
 }
 
+// BN re-estimation: whatever changes what a forward at the average reads - an update of the average, mww_set_ema_state,
+// installing / removing the average, the "weight_qat" option or map - leaves the re-estimated statistics describing another
+// model: evaluations read the master's moving statistics again, and a pass in progress is closed
+void invalidate_ema_bn(mww_ctx* c) {
+  c->ema_bn_valid = false;
+  c->bnre_batches = -1;
+}
+
 void free_weight_ema(mww_ctx* c) {
+  invalidate_ema_bn(c);
+  void* bnre[] = {c->ema_bn, c->bnre_acc, c->bnre_table};
+  for (void* p : bnre) if (p) (void)hipFree(p);
+  c->ema_bn = nullptr;
+  c->bnre_acc = nullptr;
+  c->bnre_table = nullptr;
+  c->bnre_table_rows = 0;
+  c->bnre_table_host.clear();
   if (c->ema) (void)hipFree(c->ema);
   c->ema = nullptr;
   c->ema_decay = 0.0;
@@ -897,6 +952,7 @@ int mww_set_weight_ema(mww_ctx* c, double decay, int64_t every_steps) {
   c->ema_decay = decay;
   c->ema_every = every_steps;
   c->ema_updates = 0;
+  invalidate_ema_bn(c);
   return MWW_OK;
 }
 int mww_get_ema_state(mww_ctx* c, float* h, int64_t n, int64_t* updates) {
@@ -911,6 +967,7 @@ int mww_set_ema_state(mww_ctx* c, const float* h, int64_t n, int64_t updates) {
   MWW_TRY(copy_in(c, c->ema, h, (size_t)n * sizeof(float)));
   if ((c->ema_updates == 0) != (updates == 0)) drop_graphs(c);   // (a captured step's node copies or blends)
   c->ema_updates = updates;
+  invalidate_ema_bn(c);
   return MWW_OK;
 }
 
@@ -938,6 +995,7 @@ int mww_set_weight_qat(mww_ctx* c, const int32_t* chan_start, const int32_t* cha
   HIPCHK(hipStreamSynchronize(c->stream));
   drop_graphs(c);   // (a capture holds the shadow's and the map's addresses)
   free_weight_qat(c);
+  invalidate_ema_bn(c);
   if (n_channels == 0) return MWW_OK;
   auto install = [&]() -> int {
     MWW_TRY(dev_alloc(&c->shadow, (size_t)c->P));
@@ -1176,13 +1234,13 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
       c->graphs.push_back({B, flags, mail, ckey, mkey, exec});
     }
     HIPCHK(hipGraphLaunch(exec, c->stream));
-    if (ema) c->ema_updates += 1;
+    if (ema) { c->ema_updates += 1; invalidate_ema_bn(c); }
     return mail_commit(c);
   }
   rc = step_sequence(c, B, flags, ema);
   if (rc) return rc;
   HIPCHK(hipGetLastError());
-  if (ema) c->ema_updates += 1;
+  if (ema) { c->ema_updates += 1; invalidate_ema_bn(c); }
   return mail_commit(c);
 }
 
@@ -1198,7 +1256,7 @@ int mww_apply_gradients(mww_ctx* c, float lr, float gscale) {
   rc = enqueue_ema(c, ema);
   if (rc) return rc;
   HIPCHK(hipGetLastError());
-  if (ema) c->ema_updates += 1;
+  if (ema) { c->ema_updates += 1; invalidate_ema_bn(c); }
   return mail_commit(c);
 }
 
@@ -1222,6 +1280,94 @@ int mww_forward(mww_ctx* c, int B, int training, int update_metrics) {
   if (rc) return rc;
   HIPCHK(hipGetLastError());
   return mail_commit(c);
+}
+
+// ---- BatchNorm re-estimation for the weight average (kernels_bnre.hip.h)
+int mww_bn_reestimate_begin(mww_ctx* c) {
+  if (!c) return fail(MWW_ERR_INVALID, "null context");
+  if (!c->ema || c->ema_updates == 0) return fail(MWW_ERR_INVALID, "bn_reestimate needs a weight average that has taken an update");
+  HIPCHK(hipSetDevice(c->device));
+  if (!c->ema_bn) MWW_TRY(dev_alloc(&c->ema_bn, (size_t)c->S));
+  if (!c->bnre_acc) MWW_TRY(dev_alloc(&c->bnre_acc, (size_t)c->S));
+  HIPCHK(hipMemsetAsync(c->bnre_acc, 0, (size_t)c->S * sizeof(double), c->stream));
+  c->bnre_batches = 0;
+  return MWW_OK;
+}
+
+int mww_bn_reestimate_batch(mww_ctx* c, int B) {
+  if (!c || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
+  if (c->bnre_batches < 0) return fail(MWW_ERR_STATE, "bn_reestimate: no pass is open (call mww_bn_reestimate_begin; an update of the average closes a pass)");
+  if (c->have_batch < B) return fail(MWW_ERR_STATE, "forward needs a batch of at least B rows");
+  HIPCHK(hipSetDevice(c->device));
+  int rc = flush_targets(c);
+  if (rc) return rc;
+  if (c->lazy_slot != c->mail_cur) {
+    rc = materialise_x(c);
+    if (rc) return rc;
+  }
+  // the forward of mww_forward(training = 1, update_metrics = 0) - batch statistics, moving statistics untouched, no loss, no
+  // metrics, no dropout - standing on the average (with "weight_qat": on its shadow); never captured
+  EmaSource source(c, true);
+  c->ema_src = true;
+  rc = refresh_shadow(c);
+  if (rc) return rc;
+  rc = c->model->enqueue_forward(c, B, true, false, false, false);
+  if (rc) return rc;
+  rc = join_side(c);
+  if (rc) return rc;
+  rc = c->model->enqueue_bn_collect(c, B);   // directly behind the forward: its accumulator parity is still the current one
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  c->bnre_batches += 1;
+  return mail_commit(c);
+}
+
+int mww_bn_reestimate_commit(mww_ctx* c) {
+  if (!c) return fail(MWW_ERR_INVALID, "null context");
+  if (c->bnre_batches <= 0) return fail(MWW_ERR_STATE, "bn_reestimate: commit without a collected batch");
+  HIPCHK(hipSetDevice(c->device));
+  Launcher lp{c};
+  lp.begin("bn_reestimate_commit");
+  launch_bnre_commit(BnreCommitArgs{c->bnre_acc, c->ema_bn, (double)c->bnre_batches, (int)c->S}, c->stream);
+  lp.end();
+  HIPCHK(hipGetLastError());
+  c->bnre_batches = -1;
+  c->ema_bn_valid = true;
+  return MWW_OK;
+}
+
+int mww_bn_reestimate_windows(mww_ctx* c, const mww_window* windows, int64_t n, int batch) {
+  if (!c || !windows || batch <= 0 || batch > c->max_batch) return fail(MWW_ERR_INVALID, "bad re-estimation arguments");
+  if (n <= 0 || n % batch != 0) return fail(MWW_ERR_INVALID, "bn_reestimate: the window count must be a positive multiple of the batch size (every batch weighs the same)");
+  if (!c->ema || c->ema_updates == 0) return fail(MWW_ERR_INVALID, "bn_reestimate needs a weight average that has taken an update");
+  // the first batch is assembled before the pass opens: windows the stores refuse leave the context as it was
+  int rc = mww_assemble_batch(c, windows, nullptr, batch, 0, 0);
+  if (!rc) rc = mww_bn_reestimate_begin(c);
+  for (int64_t s = 0; s < n && !rc; s += batch) {
+    if (s) rc = mww_assemble_batch(c, windows + s, nullptr, batch, 0, 0);
+    if (!rc) rc = mww_bn_reestimate_batch(c, batch);
+    c->shadow_held = c->ema;   // the average cannot change between the batches: the first batch's shadow serves them all
+  }
+  c->shadow_held = nullptr;
+  if (rc) { c->bnre_batches = -1; return rc; }
+  return mww_bn_reestimate_commit(c);
+}
+
+int mww_get_ema_bn_state(mww_ctx* c, float* h, int64_t n, int* valid) {
+  if (!c || !c->ema) return fail(MWW_ERR_INVALID, "no weight average installed: call mww_set_weight_ema first");
+  if (n != c->S) return fail(MWW_ERR_INVALID, "BN state size mismatch");
+  if (valid) *valid = c->ema_bn_valid ? 1 : 0;
+  return h ? copy_out(c, h, c->ema_bn_valid ? c->ema_bn : c->bn_state, (size_t)n * sizeof(float)) : MWW_OK;
+}
+int mww_set_ema_bn_state(mww_ctx* c, const float* h, int64_t n) {
+  if (!c || !c->ema) return fail(MWW_ERR_INVALID, "no weight average installed: call mww_set_weight_ema first");
+  if (!h || n != c->S) return fail(MWW_ERR_INVALID, "BN state size mismatch");
+  HIPCHK(hipSetDevice(c->device));
+  if (!c->ema_bn) MWW_TRY(dev_alloc(&c->ema_bn, (size_t)c->S));
+  MWW_TRY(copy_in(c, c->ema_bn, h, (size_t)n * sizeof(float)));
+  c->bnre_batches = -1;
+  c->ema_bn_valid = true;
+  return MWW_OK;
 }
 
 int mww_evaluate_windows(mww_ctx* c, const mww_window* windows, const float* labels, int64_t n, int batch) {
@@ -1367,6 +1513,7 @@ int set_core_option(mww_ctx* c, const std::string& name, int64_t v) {
   if (name == "bce_from_logits") c->bce_clipped = v == 0;
   if (name == "weight_qat") {
     if (v && !c->shadow) return fail(MWW_ERR_INVALID, "weight_qat needs a channel map: call mww_set_weight_qat first");
+    if (c->weight_qat != (v != 0)) invalidate_ema_bn(c);
     c->weight_qat = v != 0;
   }
   if (name == "ema_forward") {

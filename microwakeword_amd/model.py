@@ -174,11 +174,13 @@ class Model:
     def get_weights(self):
         params = self.engine.get_params()
         if getattr(self, "_averaged", False):
-            # inside averaged_weights(): the trainable variables from the average; the BN moving statistics and the masked
-            # MixConv taps (no Keras variable reaches them, the layout packs them) from the master model
+            # inside averaged_weights(): the trainable variables from the average; the masked MixConv taps (no Keras variable
+            # reaches them, the layout packs them) from the master model; the BN moving statistics the average's own
+            # re-estimated ones while they are valid (reestimate_bn), else the master's
             ema, _ = self.engine.get_ema_state()
             trainable = self.layout.grad_mask() != 0
             params[trainable] = ema[trainable]
+            return self.layout.unpack(params, self.engine.get_ema_bn_state()[0])
         return self.layout.unpack(params, self.engine.get_bn_state())
 
     def set_weights(self, weights: Sequence[np.ndarray]):
@@ -212,11 +214,22 @@ class Model:
         self.engine.set_weight_ema(decay, every_steps)
         self.weight_averaging = dict(decay=float(decay), every_steps=int(every_steps)) if decay else None
 
+    def reestimate_bn(self, windows, batch):
+        """Re-estimate the BatchNorm statistics for the weight average (``averaging``; ``mww_bn_reestimate_windows``): one pass
+        of training-mode forwards at the average over ``windows`` (descriptors of resident rows, a positive multiple of
+        ``batch``).  Until the average's next update, evaluations and ``get_weights()`` / ``save_weights()`` inside
+        ``averaged_weights()`` use the result.  Data-parallel with rank-local BatchNorm: every rank passes over windows of its
+        own shard and the ranks install the mean of their results; with sync-BN the batch statistics are global already."""
+        self.engine.bn_reestimate_windows(windows, batch)
+        if self.data_parallel is not None:
+            self.data_parallel.average_ema_bn_state()
+
     @contextlib.contextmanager
     def averaged_weights(self):
         """Inside: every inference-mode forward (``predict_on_batch``, ``evaluate``, window evaluation) reads the weight
         average (engine option ``ema_forward``), and ``get_weights()`` / ``save_weights()`` return the averaged trainable
-        variables with the master model's BN moving statistics.  Training steps keep reading the master.  A no-op while no
+        variables with the master model's BN moving statistics - or, after ``reestimate_bn`` and until the average's next update,
+        with the statistics re-estimated for the average.  Training steps keep reading the master.  A no-op while no
         average is installed or it has not taken its first update."""
         on = bool(getattr(self, "weight_averaging", None)) and not getattr(self, "_averaged", False) \
             and self.engine.ema_updates() > 0

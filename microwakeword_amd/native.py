@@ -130,6 +130,8 @@ EXPORTS = [
     "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections", "mww_stream_operating_points",
     "mww_stream_mine", "mww_stream_operating_summary", "mww_stream_calibrate",
     "mww_set_weight_qat", "mww_get_forward_params", "mww_set_weight_ema", "mww_get_ema_state", "mww_set_ema_state",
+    "mww_bn_reestimate_begin", "mww_bn_reestimate_batch", "mww_bn_reestimate_commit", "mww_bn_reestimate_windows",
+    "mww_get_ema_bn_state", "mww_set_ema_bn_state",
 ]
 
 
@@ -197,6 +199,12 @@ class NativeLib:
         L.mww_set_weight_ema.argtypes = [C.c_void_p, C.c_double, C.c_int64]
         L.mww_get_ema_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]
         L.mww_set_ema_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int64]
+        L.mww_bn_reestimate_begin.argtypes = [C.c_void_p]
+        L.mww_bn_reestimate_batch.argtypes = [C.c_void_p, C.c_int]
+        L.mww_bn_reestimate_commit.argtypes = [C.c_void_p]
+        L.mww_bn_reestimate_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+        L.mww_get_ema_bn_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int)]
+        L.mww_set_ema_bn_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64]
         L.mww_upload_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int]
         L.mww_assemble_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.mww_set_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
@@ -533,6 +541,42 @@ class Engine:
     def set_ema_state(self, ema, updates):
         a = np.ascontiguousarray(ema, np.float32).reshape(-1)
         self.nl.check(self.nl.lib.mww_set_ema_state(self.h, _fptr(a), a.size, int(updates)))
+
+    # ---- BatchNorm statistics re-estimated for the average (``averaging``; include/mww.h)
+    def bn_reestimate_begin(self):
+        """open a re-estimation pass: zero its float64 sums (needs an installed average that has taken an update)"""
+        self.nl.check(self.nl.lib.mww_bn_reestimate_begin(self.h))
+
+    def bn_reestimate_batch(self, B):
+        """training-mode forward at the average on the current batch's first ``B`` rows + the collect launch behind it"""
+        self.nl.check(self.nl.lib.mww_bn_reestimate_batch(self.h, int(B)))
+
+    def bn_reestimate_commit(self):
+        """write the pass's means into ``ema_bn`` and mark it valid"""
+        self.nl.check(self.nl.lib.mww_bn_reestimate_commit(self.h))
+
+    def bn_reestimate_windows(self, windows: np.ndarray, batch: int):
+        """one pass over a window list gathered from the resident stores, in batches of exactly ``batch`` (one native call)"""
+        windows = np.ascontiguousarray(windows, WINDOW_DTYPE)
+        self.nl.check(self.nl.lib.mww_bn_reestimate_windows(self.h, windows.ctypes.data_as(C.c_void_p), windows.shape[0], int(batch)))
+
+    def get_ema_bn_state(self):
+        """(statistics [S] float32 a forward at the average folds, valid): the re-estimated ``ema_bn`` when valid, else the
+        master's moving statistics"""
+        a = np.empty(self.n_state, np.float32)
+        valid = C.c_int()
+        self.nl.check(self.nl.lib.mww_get_ema_bn_state(self.h, _fptr(a), self.n_state, C.byref(valid)))
+        return a, bool(valid.value)
+
+    def ema_bn_valid(self):
+        valid = C.c_int()
+        self.nl.check(self.nl.lib.mww_get_ema_bn_state(self.h, None, self.n_state, C.byref(valid)))
+        return bool(valid.value)
+
+    def set_ema_bn_state(self, a):
+        """install ``ema_bn`` and mark it valid"""
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        self.nl.check(self.nl.lib.mww_set_ema_bn_state(self.h, _fptr(a), a.size))
 
     def set_opt_state(self, m, v, step):
         m = np.ascontiguousarray(m, np.float32).reshape(-1)

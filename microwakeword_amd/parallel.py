@@ -285,6 +285,18 @@ class DataParallel:
         if self.grad_view.is_cuda:
             torch.cuda.synchronize(self.grad_view.device)
 
+    def average_ema_bn_state(self):
+        """The same for the statistics re-estimated for the weight average (``Model.reestimate_bn``): every rank passed over
+        windows of its own shard; the ranks install ``averaging.bn_rank_mean`` of their results.  A no-op with sync-BN (the
+        batch statistics were global) and on one rank."""
+        if self.sync_bn or not dist.is_initialized() or self.world == 1:
+            return
+        mine, valid = self.engine.get_ema_bn_state()
+        if not self.agree(valid):
+            raise RuntimeError("a rank holds no re-estimated BatchNorm statistics")
+        total = self.allreduce_host(mine.astype(np.float64))
+        self.engine.set_ema_bn_state((total / np.float64(self.world)).astype(np.float32))
+
     def train_step(self, B, lr, flags=0, prefetch=None):
         """Local forward/backward, gradient all-reduce, Adam on the averaged gradient.  ``prefetch`` (optional
         callable, e.g. the draw of the next batch) runs after the step has been enqueued."""

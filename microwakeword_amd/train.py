@@ -18,7 +18,9 @@ With a ``weight_quantization_aware`` mapping (``qat``) the steps fro
 the engine's forward / backward read the weights on the int8 grid while Adam keeps the fp32 master.
 With a ``weight_averaging`` mapping (``averaging``) the engine keeps an exponential moving average of the trainable
 weights from ``first_step`` on, and every evaluation boundary - the weight files, both validations, the best-weights rule, a
-mining round - stands on the averaged model; the steps themselves and the restore checkpoint keep the raw iterate.
+mining round - stands on the averaged model; the steps themselves and the restore checkpoint keep the raw iterate.  With
+``bn_reestimate: {samples, seed}`` in that mapping every boundary starts with one pass of training-mode forwards at the average
+over seeded resident windows, and the averaged model is evaluated, quantized and written with the BatchNorm statistics of that pass.
 
 When both objects come from this package the spectrogram batch never leaves HBM
 (``FeatureHandler.next_training_batch_on_device`` + ``Model.train_on_device_batch``); with any other
@@ -310,9 +312,18 @@ def train(model, config, data_processor, verbose=True):
         if chief:
             log.info("weight averaging continues from the checkpoint (%d updates, decay %g)", model.engine.ema_updates(), avg_settings["decay"])
 
+    # weight_averaging.bn_reestimate: the windows of the passes, drawn once (resident training rows of this rank's shard, no RNG
+    # stream moves, no SpecAugment: the statistics describe the clean windows an evaluation sees), whole batches of the rank's batch
+    bn_windows = averaging.bn_reestimate_windows(avg_settings, data_processor, config["spectrogram_length"], local_batch)
+
+    @contextlib.contextmanager
     def averaged():
         # what is validated, selected, mined with and written at a boundary is the averaged model (a no-op before its first update)
-        return model.averaged_weights() if avg_on else contextlib.nullcontext()
+        with (model.averaged_weights() if avg_on else contextlib.nullcontext()):
+            if bn_windows is not None and getattr(model, "_averaged", False) and not model.engine.ema_bn_valid():
+                # first thing at the boundary: the averaged model's own BatchNorm statistics (valid until the average's next update)
+                model.reestimate_bn(bn_windows, local_batch)
+            yield
 
     warned_weights = False
     steps_max = int(np.sum(ph["training_steps"]))
