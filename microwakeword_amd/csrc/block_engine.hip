@@ -49,6 +49,10 @@ __global__ void bn_bwd_finalize_kernel(BnBwdFinalizeArgs a);
 namespace {
 
 float* bn_slot(Layer& l, int i) { return l.bn + (size_t)i * l.cout; }
+// 1 / (the elements behind one channel's statistics in a batch of B windows)
+float b_inv_n(const Layer& l, int B) { return 1.0f / ((float)B * (float)l.tout); }
+// statistics hand-over instead of finalize launches ("bn_inline"; sync-BN exchanges the sums in between)
+bool b_handover(const mww_ctx* c) { return c->bn_inline && !(c->hook && c->sync_bn); }
 
 struct BlockModel : Model {
   mww_mixednet_desc d;
@@ -186,13 +190,13 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
     }
   }
   // statistics of BN_i: accumulator rows folded by the next kernel, or partial rows + a finalize launch
-  const bool inl = training && c->bn_inline && !(c->hook && c->sync_bn);
+  const bool inl = training && b_handover(c);
   auto fold_of = [&](Layer& pl) {
     BnFoldArgs f;
     memset(&f, 0, sizeof(f));
     if (!inl) return f;
-    f.acc = pl.facc_cur;
-    f.inv_n = 1.0f / ((float)B * (float)pl.tout);
+    f.acc = fwd_rows(c, pl).acc;
+    f.inv_n = b_inv_n(pl, B);
     f.update_moving = update_moving ? 1 : 0;
     f.gamma = fwd_params(c) + pl.o_gamma;
     f.beta = fwd_params(c) + pl.o_beta;
@@ -207,12 +211,7 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   for (int i = 0; i < nb; ++i) {
     Layer& l = L[i];
     const int grid = i == 0 ? std::min(B, grid_fwd) : fwd_block_grid(c, l, B);
-    StatAcc sacc{nullptr, nullptr};
-    if (inl) {
-      sacc.acc = l.facc[c->fpar];
-      sacc.clear = l.facc[c->fpar ^ 1];
-      l.facc_cur = sacc.acc;
-    }
+    const StatAcc sacc = inl ? fwd_rows(c, l) : StatAcc{nullptr, nullptr};
     if (i == 0) {
       FwdFirstArgs a{c->x, fwd_params(c) + o_conv1, fwd_params(c) + l.o_dw_w, fwd_params(c) + l.o_dw_b, fwd_params(c) + l.o_pw_w,
                      l.p, l.stat_part, B, d.frames, l.tout, 0, sacc, x_gather(c), training ? a0 : nullptr};
@@ -232,7 +231,7 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
     }
     if (training && !inl) {
       StatSource ss;
-      int rcs = exchange_stats(c, lp, "bn_stat_exchange", i, l.stat_part, grid, l.cout, 0, 1.0f / ((float)B * (float)l.tout), &ss);
+      int rcs = exchange_stats(c, lp, "bn_stat_exchange", i, l.stat_part, grid, l.cout, 0, b_inv_n(l, B), &ss);
       if (rcs) return rcs;
       BnFwdFinalizeArgs f{ss.part, ss.G, l.cout, ss.inv_n, fwd_params(c) + l.o_gamma,
                           fwd_params(c) + l.o_beta, c->bn_state + l.o_mm, c->bn_state + l.o_mv, bn_slot(l, BN_SCALE),
@@ -244,16 +243,11 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
   }
   Layer& ll = L[nb - 1];
   const BnFoldArgs hfold = fold_of(ll);
-  if (inl) c->fpar ^= 1;
+  if (inl) c->fpar ^= 1;   // (behind the last reader of this walk's forward rows)
   // train step with the statistics hand-over: BN_L's backward sums go to accumulator rows (folded by the last block's
   // backward kernel) and the dense-weight gradient / metric update ride in the gradient-reduction launch
   const bool tail_late = loss && inl && c->tail_roles;
-  StatAcc hgacc{nullptr, nullptr};
-  if (tail_late) {
-    hgacc.acc = ll.gacc[c->gpar];
-    hgacc.clear = ll.gacc[c->gpar ^ 1];
-    ll.gacc_cur = hgacc.acc;
-  }
+  const StatAcc hgacc = tail_late ? bwd_rows(c, ll) : StatAcc{nullptr, nullptr};
   int rc = enqueue_block_head(c, B, ll, ll.tout, ll.cout, st_bf16, hfold, hgacc, loss, metrics);
   if (rc) return rc;
   c->tail_src = DenseSource{ll.p, bn_slot(ll, BN_SCALE), bn_slot(ll, BN_SHIFT), nullptr, nullptr, nullptr, nullptr, 0, 0, st_bf16 ? 1 : 0};
@@ -276,13 +270,13 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
 // first consumer folded, or the partial rows (behind a sync-BN exchange: the row of global sums) bn_fwd_finalize_kernel read -
 // with the inv_n of that fold
 int BlockModel::enqueue_bn_collect(mww_ctx* c, int B) {
-  const bool inl = c->bn_inline && !(c->hook && c->sync_bn);
+  const bool inl = b_handover(c);
   std::vector<BnreRow> rows(L.size());
   memset(rows.data(), 0, rows.size() * sizeof(BnreRow));
   for (size_t i = 0; i < L.size(); ++i) {
     Layer& l = L[i];
     BnreRow& r = rows[i];
-    const float inv_n = 1.0f / ((float)B * (float)l.tout);
+    const float inv_n = b_inv_n(l, B);
     r.C = l.cout;
     r.groups = 1;
     r.o_mm = (int)l.o_mm;
@@ -324,7 +318,7 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
   const int nb = d.n_blocks;
   const int gbwd = std::min(B, grid_bwd);
   const int ghead = std::min(B, c->grid_head);
-  const bool inl = c->bn_inline && !(c->hook && c->sync_bn);
+  const bool inl = b_handover(c);
   // data-parallel step: the gradient of [blocks >= split, dense] (a contiguous tail of the flat vector) is final once
   // block `split`'s backward kernel is enqueued; it is assembled and handed to the exchange hook there, so that the
   // all-reduce runs next to the remaining backward kernels.  Needs the statistics hand-over (the BN
@@ -339,8 +333,7 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     const bool fold_here = inl && (!last || c->tail_in_reduce);
     StatSource ss{nullptr, 0, 0.f, 1.0f};
     if (!fold_here) {
-      int rcs = exchange_stats(c, lp, "bn_gstat_exchange", i, l.gstat_part, last ? ghead : gbwd, l.cout, 1,
-                               1.0f / ((float)B * (float)l.tout), &ss);
+      int rcs = exchange_stats(c, lp, "bn_gstat_exchange", i, l.gstat_part, last ? ghead : gbwd, l.cout, 1, b_inv_n(l, B), &ss);
       if (rcs) return rcs;
     }
     BnBwdFinalizeArgs f{ss.part, ss.G, l.cout, ss.inv_n,
@@ -349,8 +342,8 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
     BnGradFoldArgs gf;
     memset(&gf, 0, sizeof(gf));
     if (fold_here) {
-      gf.acc = l.gacc_cur;
-      gf.inv_n = 1.0f / ((float)B * (float)l.tout);
+      gf.acc = bwd_rows(c, l).acc;
+      gf.inv_n = b_inv_n(l, B);
       gf.dscale = 1.0f;
       gf.gamma = fwd_params(c) + l.o_gamma;
       gf.c1 = bn_slot(l, BN_C1);
@@ -400,12 +393,7 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
       a.Tout = l.tout;
       a.ablate = ablate;
       a.phase_clk = phase_clk + (size_t)(2 * i + 1) * 2048 * kClkSlots;
-      a.gacc = StatAcc{nullptr, nullptr};
-      if (inl) {
-        a.gacc.acc = pl.gacc[c->gpar];
-        a.gacc.clear = pl.gacc[c->gpar ^ 1];
-        pl.gacc_cur = a.gacc.acc;
-      }
+      a.gacc = inl ? bwd_rows(c, pl) : StatAcc{nullptr, nullptr};
       a.gfold = gf;
       lp.begin("bwd_block", i);
       int rc = launch_bwd_block(c, l.cin, l.cout, l.k, last, a, gbwd);

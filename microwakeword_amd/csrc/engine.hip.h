@@ -41,11 +41,9 @@ struct Tensor {
   float* grad_part = nullptr;  // [rows][the weights this tensor's backward launch produces]
   float* bn = nullptr;         // 9 x cout: scale, shift, mean, rstd, c1, mg, mgx, (spare x2)
   // statistics hand-over without finalize launches (common.hip.h): [parity][kStatRows][2][cout] for the forward
-  // sums (x, x^2) and the backward sums (g, g*xhat); *_cur = rows the latest producer launch added to
+  // sums (x, x^2) and the backward sums (g, g*xhat); which parity a launch adds to: fwd_rows / bwd_rows below
   double* facc[2] = {nullptr, nullptr};
   double* gacc[2] = {nullptr, nullptr};
-  double* facc_cur = nullptr;
-  double* gacc_cur = nullptr;
 };
 // everything but p and g (whose sizes and owners are the engine's business) / every buffer that is set
 int tensor_alloc(Tensor* t, int cout, size_t rows_fwd, size_t rows_bwd, size_t grad_part);
@@ -276,9 +274,27 @@ struct Launcher {
     if (!c->profile || idx >= c->prof.size()) return;
     (void)hipEventRecord(c->prof[idx].b, c->stream);
   }
+  // the bracket just opened and closed held no launch: drop its entry
+  void cancel() {
+    if (!c->profile) return;
+    (void)hipEventDestroy(c->prof.back().a);
+    (void)hipEventDestroy(c->prof.back().b);
+    c->prof.pop_back();
+  }
 };
 
 enum { BN_SCALE = 0, BN_SHIFT, BN_MEAN, BN_RSTD, BN_C1, BN_MG, BN_MGX };
+
+// The accumulator rows of tensor t in the walk being enqueued: .acc = the rows this walk's producer launches add to and its
+// folding launches read, .clear = the other parity's rows, which the producers zero for the next walk.  One expression serves
+// the writers and the readers because c->fpar (c->gpar) is constant from the first launch that adds to a tensor's rows to the
+// last launch that folds them: the forward sums of a tensor are produced and folded inside one forward walk, the backward sums
+// are produced by the head of a step's forward walk or by an op's consumers in its backward walk and folded in that same
+// backward walk, and each walk flips its own parity exactly once, as the last thing it does about parity (the forward walk
+// after the head's fold is built).  A graph replay (mww_train_step) flips both parities without running a walk: there is
+// no per-tensor state for that to leave behind.
+inline StatAcc fwd_rows(const mww_ctx* c, const Tensor& t) { return StatAcc{t.facc[c->fpar], t.facc[c->fpar ^ 1]}; }
+inline StatAcc bwd_rows(const mww_ctx* c, const Tensor& t) { return StatAcc{t.gacc[c->gpar], t.gacc[c->gpar ^ 1]}; }
 
 // the fp32 vector this call's forward stands on: the master, or the weight average in a non-training call under "ema_forward"
 inline float* fwd_source(const mww_ctx* c) { return c->ema_src ? c->ema : c->params; }

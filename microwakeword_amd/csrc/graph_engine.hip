@@ -74,8 +74,12 @@ struct GraphModel : Model {
     *n = dropout_counter++;
     return true;
   }
+  // the statistics hand-over instead of finalize launches (kernels_graph.hip.h): the graph and its options allow it / this
+  // context runs it (sync-BN has to exchange the sums in between)
+  bool handover_possible() const { return g_inline_ok && !profile_split; }
+  bool handover(const mww_ctx* c) const { return c->bn_inline && !(c->hook && c->sync_bn) && handover_possible(); }
   unsigned replay_key(bool* handover) const override {
-    *handover = g_inline_ok && !profile_split;
+    *handover = handover_possible();
     return (g_role_split ? 1 : 0) | (grid_g_auto ? 2 : 0) | (frame_chunks << 2) | (g_cap_fwd << 5) | (g_cap_bwd << 9) | (g_dgrad_share << 13);
   }
   int debug_tensor(mww_ctx* c, const char* name, int B, DebugTensor* t) override;
@@ -224,13 +228,58 @@ int launch_gwgrad(mww_ctx* c, bool ch, int nc, const GWgradArgs& a, const GridPi
   return g_rc(k_launch_gwgrad(g_launch_ctx(c), ch, nc, a, pk, lds, shape));
 }
 
-float* gbn_slot(GOp& o, int i) { return o.bn + (size_t)i * o.cout; }
+float* gbn_slot(const GOp& o, int i) { return o.bn + (size_t)i * o.cout; }
+
+// an argument struct with every field 0: the builders below name what their launch reads
+template <typename T>
+T g_zero() {
+  T t;
+  memset(&t, 0, sizeof(t));
+  return t;
+}
+
+// the folded BN of op o as a consumer reads it / the residual branch added before o's activation (a: GSrc, GFoldFwd, GHeadArgs)
+template <class A>
+void g_bn_arrays(A& a, const GOp& o) {
+  a.scale = gbn_slot(o, BN_SCALE); a.shift = gbn_slot(o, BN_SHIFT); a.mean = gbn_slot(o, BN_MEAN); a.rstd = gbn_slot(o, BN_RSTD);
+}
+template <class A>
+void g_residual(A& a, const std::vector<GOp>& G, const GOp& o) {
+  if (o.res_src < 0) return;
+  const GOp& rr = G[o.res_src];
+  a.rp = rr.p; a.rscale = gbn_slot(rr, BN_SCALE); a.rshift = gbn_slot(rr, BN_SHIFT); a.rT = rr.tout; a.rdrop = o.res_drop;
+}
+
+// 1 / (the elements behind one statistic of op o - a channel's, or a sub-spectral group's - in a batch of B windows)
+float g_inv_n(const GOp& o, int B) { return 1.0f / ((float)B * (float)o.tout * (float)(o.groups > 1 ? o.cout / o.groups : 1)); }
+
+// What the steps of one walk over the ops share.  The argument builders (g_make_*, g_*_args, g_fold_*) read it, the model and
+// the context and write nothing: each returns what one role of one launch is handed, whatever was built before it.  The steps
+// (g_fwd_*, g_bwd_*) launch; the backward ones list the weight-gradient partial rows they leave behind in `ga`.
+struct GWalk {
+  mww_ctx* c;
+  const GraphModel& m;
+  int B;
+  bool inl;     // statistics hand-over instead of finalize launches (kernels_graph.hip.h)
+  bool pick;    // per-launch grids (g_role_grid)
+  bool split;   // a launch that holds several roles divides its workgroups between them
+  bool pair;    // twin ops share their launches
+  int gg;       // workgroups of a launch whose grid is fixed
+  Launcher lp;
+  bool training = false, update_moving = false;   // (forward walk)
+  int ghead = 0;                                  // (backward walk) workgroups of the head launch
+  GradReduceArgs ga;
+  GWalk(mww_ctx* c_, const GraphModel& m_, int B_, bool inl_)
+      : c(c_), m(m_), B(B_), inl(inl_), pick(inl_ && m_.grid_g_auto), split(inl_ && m_.g_role_split),
+        pair(!(c_->hook && c_->sync_bn) && !m_.profile_split), gg(std::min(B_, m_.grid_g)), lp{c_} {
+    ga.nseg = 0;
+  }
+};
 
 // source i of op `oi` as the kernels see it; `backward` adds the gradient routing flags
-GSrc g_make_src(mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
-  GOp& o = gm(c).G[oi];
-  GSrc s;
-  memset(&s, 0, sizeof(s));
+GSrc g_make_src(const mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
+  const GOp& o = gm(c).G[oi];
+  GSrc s = g_zero<GSrc>();
   s.toff = o.toff[i];
   if (o.src[i] < 0) {
     s.p = c->x;
@@ -239,13 +288,10 @@ GSrc g_make_src(mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
     s.flags = GSRC_IDENTITY;
     return s;
   }
-  GOp& pr = gm(c).G[o.src[i]];
+  const GOp& pr = gm(c).G[o.src[i]];
   s.p = pr.p;
   if (pr.norm == MWW_NORM_BN) {
-    s.scale = gbn_slot(pr, BN_SCALE);
-    s.shift = gbn_slot(pr, BN_SHIFT);
-    s.mean = gbn_slot(pr, BN_MEAN);
-    s.rstd = gbn_slot(pr, BN_RSTD);
+    g_bn_arrays(s, pr);
   } else {   // a bias (or nothing) instead of a BN: y = p * 1 + bias
     s.scale = gm(c).ones;
     s.shift = pr.norm == MWW_NORM_BIAS ? fwd_params(c) + pr.o_beta : gm(c).zeros;
@@ -271,26 +317,14 @@ GSrc g_make_src(mww_ctx* c, int oi, int i, bool backward, bool inl = false) {
     s.c0 = 0;
   }
   if (pr.act == MWW_ACT_LINEAR) s.flags |= GSRC_LINEAR;
-  if (pr.res_src >= 0) {
-    GOp& rr = gm(c).G[pr.res_src];
-    s.rp = rr.p;
-    s.rscale = gbn_slot(rr, BN_SCALE);
-    s.rshift = gbn_slot(rr, BN_SHIFT);
-    s.rT = rr.tout;
-    s.rdrop = pr.res_drop;
-  }
+  g_residual(s, gm(c).G, pr);
   if (backward) s.flags |= GSRC_GRAD | (o.src_first[i] ? 0 : GSRC_ACCUM) | (o.src_last[i] ? GSRC_STATS : 0);
-  if (backward && inl && o.src_last[i]) {   // the slice's backward sums go to the producer's accumulator rows
-    s.gacc.acc = pr.gacc[c->gpar];
-    s.gacc.clear = pr.gacc[c->gpar ^ 1];
-    pr.gacc_cur = s.gacc.acc;
-  }
+  if (backward && inl && o.src_last[i]) s.gacc = bwd_rows(c, pr);   // the slice's backward sums go to the producer's accumulator rows
   return s;
 }
 
-GBnBwd g_make_bnbwd(mww_ctx* c, GOp& o) {
-  GBnBwd y;
-  memset(&y, 0, sizeof(y));
+GBnBwd g_make_bnbwd(const mww_ctx* c, const GOp& o) {
+  GBnBwd y = g_zero<GBnBwd>();
   y.g = o.g;
   y.p = o.p;
   if (o.norm != MWW_NORM_BN) {   // dp = g
@@ -304,278 +338,477 @@ GBnBwd g_make_bnbwd(mww_ctx* c, GOp& o) {
   return y;
 }
 
-GDwArgs g_make_dw(mww_ctx* c, int oi, int B, bool backward, bool inl = false) {
-  GOp& o = gm(c).G[oi];
-  GDwArgs a;
-  memset(&a, 0, sizeof(a));
+GDwArgs g_make_dw(const mww_ctx* c, int oi, int B, bool backward, bool inl = false) {
+  const GOp& o = gm(c).G[oi];
+  GDwArgs a = g_zero<GDwArgs>();
   a.src = g_make_src(c, oi, 0, backward, inl);
   a.w = fwd_params(c) + o.o_w;
-  a.k = o.k;
-  a.C = o.cout;
-  a.B = B;
-  a.Tin = o.tin;
-  a.Tout = o.tout;
+  a.k = o.k; a.C = o.cout; a.B = B; a.Tin = o.tin; a.Tout = o.tout;
   a.out = o.p;
   a.y = g_make_bnbwd(c, o);
   a.grad_part = o.grad_part;
   return a;
 }
 
-}  // namespace
+// ---- forward roles
+// the fold of op pi's forward sums inside a consumer's launch (publish: that consumer also writes the BN arrays out)
+GFoldFwd g_fold_fwd(const GWalk& w, int pi, bool publish) {
+  const mww_ctx* c = w.c;
+  const GOp& pr = w.m.G[pi];
+  GFoldFwd f = g_zero<GFoldFwd>();
+  f.acc = fwd_rows(c, pr).acc;
+  f.C = pr.cout;
+  f.groups = pr.groups;
+  f.inv_n = g_inv_n(pr, w.B);
+  f.publish = publish ? 1 : 0;
+  f.update_moving = w.update_moving ? 1 : 0;
+  f.gamma = fwd_params(c) + pr.o_gamma; f.beta = fwd_params(c) + pr.o_beta;
+  f.moving_mean = c->bn_state + pr.o_mm; f.moving_var = c->bn_state + pr.o_mv;
+  g_bn_arrays(f, pr);
+  return f;
+}
 
-int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) {
-  GraphModel& m = *this;
-  if (c->x_lazy && !g_stem_gathers(c)) {   // (an option changed since the batch was assembled)
-    int rcx = materialise_x(c);
-    if (rcx) return rcx;
+// what the three roles of a convolution share: its sources (grad: with the gradient routing), taps and batch (a: GConvArgs, GWgradArgs)
+template <class A>
+void g_conv_common(A& a, const GWalk& w, int oi, bool grad) {
+  const GOp& q = w.m.G[oi];
+  a.n_src = q.n_src;
+  for (int s = 0; s < q.n_src; ++s) a.src[s] = g_make_src(w.c, oi, s, grad, w.inl);
+  a.k = q.k; a.dil = q.dil; a.B = w.B;
+}
+
+int g_leader(const GraphModel& m, int oi) { return (oi > 0 && m.G[oi - 1].twin_next) ? oi - 1 : oi; }   // first op of the launch op oi rides in
+
+GConvArgs g_fwd_args(const GWalk& w, int oi) {
+  const mww_ctx* c = w.c;
+  const GraphModel& m = w.m;
+  const GOp& q = m.G[oi];
+  GConvArgs a = g_zero<GConvArgs>();
+  g_conv_common(a, w, oi, false);
+  a.w = fwd_params(c) + q.o_w;
+  a.cin = q.cin; a.stride = q.stride; a.Tin = q.tin; a.Tout = q.tout;
+  a.out = q.p; a.out_planes = g_planes(c, q); a.out_pc = q.pc; a.out_pstride = g_pstride(c, q);
+  a.stat_part = (w.training && q.norm == MWW_NORM_BN) ? q.stat_part : nullptr;
+  if (!w.inl) return a;
+  a.sacc = fwd_rows(c, q);
+  for (int s = 0; s < q.n_src; ++s) {
+    const int pi = q.src[s];
+    if (pi < 0 || m.G[pi].norm != MWW_NORM_BN) continue;   // (no statistics to fold)
+    const int fc = m.G[pi].first_consumer;
+    if (g_leader(m, oi) != g_leader(m, fc)) continue;   // a later launch: the arrays were published by the first one
+    bool first_ref = true;
+    for (int s2 = 0; s2 < s; ++s2) first_ref = first_ref && q.src[s2] != pi;
+    a.fold[s] = g_fold_fwd(w, pi, oi == fc && first_ref);
   }
-  Launcher lp{c};
-  const int n = (int)m.G.size();
-  const int gg = std::min(B, m.grid_g);
-  // statistics hand-over instead of finalize launches (kernels_graph.hip.h)
-  const bool inl = training && c->bn_inline && m.g_inline_ok && !(c->hook && c->sync_bn) && !m.profile_split;
-  const bool pick = inl && m.grid_g_auto;   // per-launch grids (g_role_grid)
-  auto leader = [&](int oi) { return (oi > 0 && m.G[oi - 1].twin_next) ? oi - 1 : oi; };   // first op of the launch op oi rides in
-  auto fold_of = [&](int pi, bool publish) {
-    GOp& pr = m.G[pi];
-    GFoldFwd f;
-    memset(&f, 0, sizeof(f));
-    f.acc = pr.facc_cur;
-    f.C = pr.cout;
-    f.groups = pr.groups;
-    f.inv_n = 1.0f / ((float)B * (float)pr.tout * (float)(pr.groups > 1 ? pr.cout / pr.groups : 1));
-    f.publish = publish ? 1 : 0;
-    f.update_moving = update_moving ? 1 : 0;
-    f.gamma = fwd_params(c) + pr.o_gamma;
-    f.beta = fwd_params(c) + pr.o_beta;
-    f.moving_mean = c->bn_state + pr.o_mm;
-    f.moving_var = c->bn_state + pr.o_mv;
-    f.scale = gbn_slot(pr, BN_SCALE);
-    f.shift = gbn_slot(pr, BN_SHIFT);
-    f.mean = gbn_slot(pr, BN_MEAN);
-    f.rstd = gbn_slot(pr, BN_RSTD);
-    return f;
-  };
-  for (int i = 0; i < n; ++i) {
-    GOp& o = m.G[i];
-    if (!training && o.norm == MWW_NORM_BN) {
-      GBnEvalArgs e{fwd_params(c) + o.o_gamma, fwd_params(c) + o.o_beta, eval_bn_state(c) + o.o_mm, eval_bn_state(c) + o.o_mv,
-                    gbn_slot(o, BN_SCALE), gbn_slot(o, BN_SHIFT), o.cout, o.groups};
-      lp.begin("bn_eval_prepare", i);
-      hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, c->stream, e);
-      lp.end();
-    }
-    if (o.kind == MWW_OP_DEPTHWISE) {
-      GDwArgs dw = g_make_dw(c, i, B, false);
-      if (inl && o.src[0] >= 0 && m.G[o.src[0]].norm == MWW_NORM_BN && m.G[o.src[0]].first_consumer == i)
-        dw.fold = fold_of(o.src[0], true);
-      lp.begin("dw_fwd", i);
-      // (no statistics leave this launch: its grid is free to follow its occupancy even without the hand-over)
-      const int rc = g_rc(k_launch_gdw(g_launch_ctx(c), 0, dw, GridPick{m.grid_g_auto ? 0 : gg, B, 1, m.g_cap_fwd, nullptr}, o.lds_fwd));
-      lp.end();
-      if (rc) return rc;
-      continue;
-    }
-    auto fwd_args = [&](int oi) {
-      GOp& q = m.G[oi];
-      GConvArgs a;
-      memset(&a, 0, sizeof(a));
-      a.n_src = q.n_src;
-      for (int s = 0; s < q.n_src; ++s) a.src[s] = g_make_src(c, oi, s, false);
-      a.w = fwd_params(c) + q.o_w;
-      a.k = q.k;
-      a.dil = q.dil;
-      a.cin = q.cin;
-      a.stride = q.stride;
-      a.B = B;
-      a.Tin = q.tin;
-      a.Tout = q.tout;
-      a.out = q.p;
-      a.out_planes = g_planes(c, q);
-      a.out_pc = q.pc;
-      a.out_pstride = g_pstride(c, q);
-      a.stat_part = (training && q.norm == MWW_NORM_BN) ? q.stat_part : nullptr;
-      if (inl) {
-        a.sacc.acc = q.facc[c->fpar];
-        a.sacc.clear = q.facc[c->fpar ^ 1];
-        q.facc_cur = a.sacc.acc;
-        for (int s = 0; s < q.n_src; ++s) {
-          const int pi = q.src[s];
-          if (pi < 0 || m.G[pi].norm != MWW_NORM_BN) continue;   // (no statistics to fold)
-          const int fc = m.G[pi].first_consumer;
-          if (leader(oi) != leader(fc)) continue;   // a later launch: the arrays were published by the first one
-          bool first_ref = true;
-          for (int s2 = 0; s2 < s; ++s2) first_ref = first_ref && q.src[s2] != pi;
-          a.fold[s] = fold_of(pi, oi == fc && first_ref);
-        }
-      }
-      return a;
-    };
-    auto fin_args = [&](int oi, const StatSource& ss) {
-      GOp& q = m.G[oi];
-      return GBnFwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
-                        fwd_params(c) + q.o_gamma, fwd_params(c) + q.o_beta, c->bn_state + q.o_mm, c->bn_state + q.o_mv,
-                        gbn_slot(q, BN_SCALE), gbn_slot(q, BN_SHIFT), gbn_slot(q, BN_MEAN), gbn_slot(q, BN_RSTD), update_moving ? 1 : 0};
-    };
-    const bool sync = c->hook && c->sync_bn;
-    if (o.twin_next && !sync && !m.profile_split) {
-      // twins: one convolution launch and one finalize launch for the pair
-      GOp& o2 = m.G[i + 1];
-      if (!training) {
-        GBnEvalArgs e{fwd_params(c) + o2.o_gamma, fwd_params(c) + o2.o_beta, eval_bn_state(c) + o2.o_mm, eval_bn_state(c) + o2.o_mv,
-                      gbn_slot(o2, BN_SCALE), gbn_slot(o2, BN_SHIFT), o2.cout, o2.groups};
-        hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, c->stream, e);
-      }
-      const GConvArgs fa0 = fwd_args(i), fa1 = fwd_args(i + 1);
-      lp.begin("conv_fwd2_", i);
-      const bool split2 = inl && m.g_role_split;
-      const int r2 = k_launch_gfwd2(g_launch_ctx(c), o.cout, fa0, fa1, GridPick{pick ? 0 : (split2 ? std::max(1, gg / 2) : gg), B, split2 ? 2 : 1, m.g_cap_fwd, nullptr},
-                                    std::max(o.lds_fwd, o2.lds_fwd), g_shape_id(c, o) == g_shape_id(c, o2) ? g_shape_id(c, o) : 0);
-      lp.end();
-      if (r2 != kGNoKernel) {
-        if (r2) return g_rc(r2);
-        if (training && !inl) {
-          const float inv_n = 1.0f / ((float)B * (float)o.tout * (float)(o.groups > 1 ? o.cout / o.groups : 1));
-          StatSource s0{o.stat_part, gg, inv_n, 1.0f}, s1{o2.stat_part, gg, inv_n, 1.0f};
-          const GBnFwdArgs f0 = fin_args(i, s0), f1 = fin_args(i + 1, s1);
-          const int n0 = o.slots;
-          lp.begin("bn_fwd_finalize2_", i);
-          hipLaunchKernelGGL(gbn_fwd_finalize2_kernel, dim3(o.slots + o2.slots), dim3(kThreads), 0, c->stream, f0, f1, n0);
-          lp.end();
-        }
-        ++i;   // the twin is done
-        continue;
-      }
-      if (c->profile) {   // width not instantiated: nothing was launched, fall through to the single-op route
-        (void)hipEventDestroy(c->prof.back().a);
-        (void)hipEventDestroy(c->prof.back().b);
-        c->prof.pop_back();
-      }
-    }
-    GConvArgs fa = fwd_args(i);
-    int Tc = 0;
-    const int S = g_chunks(c, o, inl, false, &Tc);
-    lp.begin("conv_fwd", i);
-    int rc;
-    if (S > 1) {
-      fa.S = S;
-      fa.Tc = Tc;
-      rc = launch_gconv(c, true, o.cout, fa, GridPick{pick ? 0 : gg, B * S, 1, m.g_cap_fwd, nullptr}, g_lds_fwd(o, g_chunk_in(o, Tc), Tc));
-    } else {
-      rc = launch_gconv(c, false, o.cout, fa, GridPick{pick ? 0 : gg, B, 1, m.g_cap_fwd, nullptr}, o.lds_fwd, g_shape_id(c, o));
-    }
-    lp.end();
-    if (rc) return rc;
-    if (training && o.norm == MWW_NORM_BN && !inl) {
-      const int members = o.groups > 1 ? o.cout / o.groups : 1;
-      StatSource ss;
-      int rcs = exchange_stats(c, lp, "bn_stat_exchange", i, o.stat_part, gg, o.cout, 0,
-                               1.0f / ((float)B * (float)o.tout * (float)members), &ss);
-      if (rcs) return rcs;
-      const GBnFwdArgs f = fin_args(i, ss);
-      lp.begin("bn_fwd_finalize", i);
-      hipLaunchKernelGGL(gbn_fwd_finalize_kernel, dim3(o.slots), dim3(kThreads), 0, c->stream, f);
-      lp.end();
-    }
-  }
-  GOp& lo = m.G[n - 1];
-  const bool drop = loss && m.dropout > 0.f;   // Dropout is active in the train step only (Keras training=True)
-  const bool gen_inline = drop && !m.keep_explicit && !m.head2;   // ghead_kernel draws the mask itself
-  if (drop && !m.keep_explicit && !gen_inline) {
-    const long long ne = (long long)B * c->t_last * c->c_last;
-    DropoutMaskArgs dm{m.keep, ne, m.dropout_seed, reinterpret_cast<const unsigned*>(mail_hyper(c)) + 2, m.dropout};
-    lp.begin("dropout_mask");
-    hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, dm);
-    lp.end();
-  }
-  const int ghead = std::min(B, c->grid_head);
-  GHeadArgs h;
-  memset(&h, 0, sizeof(h));
+  return a;
+}
+
+GBnEvalArgs g_bn_eval_args(const mww_ctx* c, const GOp& o) {
+  return GBnEvalArgs{fwd_params(c) + o.o_gamma, fwd_params(c) + o.o_beta, eval_bn_state(c) + o.o_mm, eval_bn_state(c) + o.o_mv,
+                     gbn_slot(o, BN_SCALE), gbn_slot(o, BN_SHIFT), o.cout, o.groups};
+}
+
+GBnFwdArgs g_bn_fwd_args(const GWalk& w, const GOp& q, const StatSource& ss) {
+  const mww_ctx* c = w.c;
+  return GBnFwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
+                    fwd_params(c) + q.o_gamma, fwd_params(c) + q.o_beta, c->bn_state + q.o_mm, c->bn_state + q.o_mv,
+                    gbn_slot(q, BN_SCALE), gbn_slot(q, BN_SHIFT), gbn_slot(q, BN_MEAN), gbn_slot(q, BN_RSTD), w.update_moving ? 1 : 0};
+}
+
+// drop: Dropout is active (the train step only: Keras training=True); gen_inline: ghead_kernel draws the mask itself
+GHeadArgs g_head_args(const GWalk& w, bool loss, bool metrics, bool drop, bool gen_inline) {
+  const mww_ctx* c = w.c;
+  const GraphModel& m = w.m;
+  const int last = (int)m.G.size() - 1;
+  const GOp& lo = m.G[last];
+  GHeadArgs h = g_zero<GHeadArgs>();
   h.p = lo.p;
-  h.scale = gbn_slot(lo, BN_SCALE);
-  h.shift = gbn_slot(lo, BN_SHIFT);
-  h.mean = gbn_slot(lo, BN_MEAN);
-  h.rstd = gbn_slot(lo, BN_RSTD);
+  g_bn_arrays(h, lo);
   h.wd = fwd_params(c) + c->o_dense_w;
   h.bd = fwd_params(c) + c->o_dense_b;
   h.y = (loss || metrics) ? c->y_cur : nullptr;
   h.sw = c->sw_cur;
   h.keep = (drop && !gen_inline) ? m.keep : nullptr;
   if (gen_inline) {
-    h.keep_gen = m.keep;
-    h.seed = m.dropout_seed;
-    h.counter = reinterpret_cast<const unsigned*>(mail_hyper(c)) + 2;
-    h.rate = m.dropout;
+    h.keep_gen = m.keep; h.seed = m.dropout_seed; h.rate = m.dropout;
+    h.counter = reinterpret_cast<const unsigned*>(mail_hyper(w.c)) + 2;
   }
-  h.z = c->z;
-  h.prob = c->prob;
-  h.dz = c->dz;
-  h.loss_part = c->loss_part;
-  h.g = lo.g;
-  h.gstat_part = lo.gstat_part;
-  h.B = B;
-  h.T = lo.tout;
-  h.C = lo.cout;
-  h.inv_b = 1.0f / (float)B;
+  h.z = c->z; h.prob = c->prob; h.dz = c->dz; h.loss_part = c->loss_part;
+  h.g = lo.g; h.gstat_part = lo.gstat_part;
+  h.B = w.B; h.T = lo.tout; h.C = lo.cout;
+  h.inv_b = 1.0f / (float)w.B;
   h.training = (loss ? kHeadTraining : 0) | (c->bce_clipped ? kHeadClippedLoss : 0);
-  if (inl) {
-    h.fold = fold_of(n - 1, true);   // the head is the first (and only) consumer of the last op
-    c->fpar ^= 1;
-    if (loss) {
-      h.gacc.acc = lo.gacc[c->gpar];
-      h.gacc.clear = lo.gacc[c->gpar ^ 1];
-      lo.gacc_cur = h.gacc.acc;
-    }
+  if (w.inl) {
+    h.fold = g_fold_fwd(w, last, true);   // the head is the first (and only) consumer of the last op
+    if (loss) h.gacc = bwd_rows(c, lo);
   }
-  if (lo.res_src >= 0) {
-    GOp& rr = m.G[lo.res_src];
-    h.rp = rr.p;
-    h.rscale = gbn_slot(rr, BN_SCALE);
-    h.rshift = gbn_slot(rr, BN_SHIFT);
-    h.rT = rr.tout;
-    h.rdrop = lo.res_drop;
+  g_residual(h, m.G, lo);
+  return h;
+}
+
+GHead2Args g_head2_args(const GWalk& w, const GHeadArgs& h) {
+  GHead2Args h2;
+  h2.h = h;
+  h2.watt = w.m.head_att ? fwd_params(w.c) + w.m.o_att : nullptr;
+  h2.pool = w.m.head_pool;
+  h2.hact = w.m.hact;
+  h2.watt_part = w.m.watt_part;
+  return h2;
+}
+
+// ---- backward roles
+// the fold of op q's backward sums inside its own backward launch (publish: the weight-gradient role writes c1 / mg / mgx /
+// dgamma / dbeta out)
+GFoldBwd g_fold_bwd(const GWalk& w, const GOp& q, bool publish) {
+  const mww_ctx* c = w.c;
+  GFoldBwd f = g_zero<GFoldBwd>();
+  if (!w.inl || q.norm != MWW_NORM_BN) return f;
+  f.acc = bwd_rows(c, q).acc;
+  f.groups = q.groups;
+  f.inv_n = g_inv_n(q, w.B);
+  f.dscale = 1.0f;
+  f.publish = publish ? 1 : 0;
+  f.gamma = fwd_params(c) + q.o_gamma;
+  f.c1 = gbn_slot(q, BN_C1); f.mg = gbn_slot(q, BN_MG); f.mgx = gbn_slot(q, BN_MGX);
+  f.dgamma = c->grads + q.o_gamma; f.dbeta = c->grads + q.o_beta;
+  return f;
+}
+
+GBnBwdArgs g_bn_bwd_args(const mww_ctx* c, const GOp& q, const StatSource& ss) {
+  return GBnBwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
+                    fwd_params(c) + q.o_gamma, gbn_slot(q, BN_RSTD), gbn_slot(q, BN_C1), gbn_slot(q, BN_MG), gbn_slot(q, BN_MGX),
+                    c->grads + q.o_gamma, c->grads + q.o_beta, ss.dscale, 0};
+}
+// d bias = sum of the output gradient = the first statistic the consumers already accumulated
+GBnBwdArgs g_bias_grad_args(const mww_ctx* c, const GOp& q, int rows) {
+  return GBnBwdArgs{q.gstat_part, rows, q.cout, 1, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->grads + q.o_beta, 1.0f, 1};
+}
+
+GWgradArgs g_wgrad_args(const GWalk& w, int oi) {
+  const GOp& q = w.m.G[oi];
+  GWgradArgs a = g_zero<GWgradArgs>();
+  g_conv_common(a, w, oi, false);
+  a.y = g_make_bnbwd(w.c, q);
+  a.y.fold = g_fold_bwd(w, q, true);
+  a.cin = q.cin; a.stride = q.stride; a.Tin = q.tin; a.Tout = q.tout;
+  a.grad_part = q.grad_part;
+  return a;
+}
+
+GConvArgs g_dgrad_args(const GWalk& w, int oi) {
+  const GOp& q = w.m.G[oi];
+  GConvArgs a = g_zero<GConvArgs>();
+  g_conv_common(a, w, oi, true);
+  a.w = fwd_params(w.c) + q.o_w;   // (the data-gradient kernel reads them transposed / tap-reversed in place)
+  a.cin = q.cout; a.stride = 1; a.Tin = q.tout; a.Tout = q.tin;
+  a.y = g_make_bnbwd(w.c, q);
+  a.y.fold = g_fold_bwd(w, q, false);
+  return a;
+}
+
+// the gradient of a residual op, gathered from the ops that add it
+GResGatherArgs g_res_gather_args(const GraphModel& m, const GOp& o, int B) {
+  GResGatherArgs ra = g_zero<GResGatherArgs>();
+  ra.n = (int)o.adders.size();
+  for (int q = 0; q < ra.n; ++q) {
+    const GOp& x = m.G[o.adders[q]];
+    ra.gx[q] = x.g; ra.Tx[q] = x.tout; ra.drop[q] = x.res_drop;
   }
+  ra.p = o.p; ra.mean = gbn_slot(o, BN_MEAN); ra.rstd = gbn_slot(o, BN_RSTD);
+  ra.g = o.g; ra.gstat_part = o.gstat_part;
+  ra.B = B; ra.T = o.tout; ra.C = o.cout;
+  return ra;
+}
+
+// `rows` partial rows of the n weights at dst of the flat gradient
+void g_add_segment(GradReduceArgs& ga, const float* part, int rows, int n, int64_t dst) {
+  ga.seg[ga.nseg++] = GradSegment{part, rows, n, n, (int)dst};
+}
+
+// ---- the steps of the forward walk
+void g_fwd_bn_eval(GWalk& w, int i, bool bracket) {
+  const GBnEvalArgs e = g_bn_eval_args(w.c, w.m.G[i]);
+  if (bracket) w.lp.begin("bn_eval_prepare", i);
+  hipLaunchKernelGGL(gbn_eval_prepare_kernel, dim3(1), dim3(kThreads), 0, w.c->stream, e);
+  if (bracket) w.lp.end();
+}
+
+int g_fwd_depthwise(GWalk& w, int i) {
+  const GraphModel& m = w.m;
+  const GOp& o = m.G[i];
+  GDwArgs dw = g_make_dw(w.c, i, w.B, false);
+  if (w.inl && o.src[0] >= 0 && m.G[o.src[0]].norm == MWW_NORM_BN && m.G[o.src[0]].first_consumer == i)
+    dw.fold = g_fold_fwd(w, o.src[0], true);
+  w.lp.begin("dw_fwd", i);
+  // (no statistics leave this launch: its grid is free to follow its occupancy even without the hand-over)
+  const int rc = g_rc(k_launch_gdw(g_launch_ctx(w.c), 0, dw, GridPick{m.grid_g_auto ? 0 : w.gg, w.B, 1, m.g_cap_fwd, nullptr}, o.lds_fwd));
+  w.lp.end();
+  return rc;
+}
+
+// twins (i, i + 1): one convolution launch and one finalize launch for the pair.  *launched stays false where the width has
+// no twin instantiation: no convolution went out and both ops take the single-op route
+int g_fwd_twins(GWalk& w, int i, bool* launched) {
+  mww_ctx* c = w.c;
+  const GraphModel& m = w.m;
+  const GOp &o = m.G[i], &o2 = m.G[i + 1];
+  if (!w.training) g_fwd_bn_eval(w, i + 1, false);
+  const GConvArgs fa0 = g_fwd_args(w, i), fa1 = g_fwd_args(w, i + 1);
+  w.lp.begin("conv_fwd2_", i);
+  const int r2 = k_launch_gfwd2(g_launch_ctx(c), o.cout, fa0, fa1, GridPick{w.pick ? 0 : (w.split ? std::max(1, w.gg / 2) : w.gg), w.B, w.split ? 2 : 1, m.g_cap_fwd, nullptr},
+                                std::max(o.lds_fwd, o2.lds_fwd), g_shape_id(c, o) == g_shape_id(c, o2) ? g_shape_id(c, o) : 0);
+  w.lp.end();
+  if (r2 == kGNoKernel) {
+    w.lp.cancel();
+    return MWW_OK;
+  }
+  if (r2) return g_rc(r2);
+  *launched = true;
+  if (w.training && !w.inl) {
+    const float inv_n = g_inv_n(o, w.B);
+    const StatSource s0{o.stat_part, w.gg, inv_n, 1.0f}, s1{o2.stat_part, w.gg, inv_n, 1.0f};
+    const GBnFwdArgs f0 = g_bn_fwd_args(w, o, s0), f1 = g_bn_fwd_args(w, o2, s1);
+    const int n0 = o.slots;
+    w.lp.begin("bn_fwd_finalize2_", i);
+    hipLaunchKernelGGL(gbn_fwd_finalize2_kernel, dim3(o.slots + o2.slots), dim3(kThreads), 0, c->stream, f0, f1, n0);
+    w.lp.end();
+  }
+  return MWW_OK;
+}
+
+int g_fwd_conv(GWalk& w, int i) {
+  mww_ctx* c = w.c;
+  const GOp& o = w.m.G[i];
+  GConvArgs fa = g_fwd_args(w, i);
+  int Tc = 0;
+  const int S = g_chunks(c, o, w.inl, false, &Tc);
+  const bool ch = S > 1;   // frame chunks: S work items per window, no static shape
+  if (ch) { fa.S = S; fa.Tc = Tc; }
+  w.lp.begin("conv_fwd", i);
+  const int rc = launch_gconv(c, ch, o.cout, fa, GridPick{w.pick ? 0 : w.gg, w.B * S, 1, w.m.g_cap_fwd, nullptr},
+                              ch ? g_lds_fwd(o, g_chunk_in(o, Tc), Tc) : o.lds_fwd, ch ? 0 : g_shape_id(c, o));
+  w.lp.end();
+  return rc;
+}
+
+// without the hand-over: the partial rows (behind a sync-BN exchange: the row of global sums) -> the BN arrays of op i
+int g_fwd_bn_finalize(GWalk& w, int i) {
+  const GOp& o = w.m.G[i];
+  StatSource ss;
+  MWW_TRY(exchange_stats(w.c, w.lp, "bn_stat_exchange", i, o.stat_part, w.gg, o.cout, 0, g_inv_n(o, w.B), &ss));
+  const GBnFwdArgs f = g_bn_fwd_args(w, o, ss);
+  w.lp.begin("bn_fwd_finalize", i);
+  hipLaunchKernelGGL(gbn_fwd_finalize_kernel, dim3(o.slots), dim3(kThreads), 0, w.c->stream, f);
+  w.lp.end();
+  return MWW_OK;
+}
+
+// the dropout mask where the head does not draw it itself, the head, and what rides behind it
+int g_fwd_head(GWalk& w, bool loss, bool metrics) {
+  mww_ctx* c = w.c;
+  const GraphModel& m = w.m;
+  const GOp& lo = m.G.back();
+  const bool drop = loss && m.dropout > 0.f;   // Dropout is active in the train step only (Keras training=True)
+  const bool gen_inline = drop && !m.keep_explicit && !m.head2;   // ghead_kernel draws the mask itself
+  if (drop && !m.keep_explicit && !gen_inline) {
+    const long long ne = (long long)w.B * c->t_last * c->c_last;
+    DropoutMaskArgs dm{m.keep, ne, m.dropout_seed, reinterpret_cast<const unsigned*>(mail_hyper(c)) + 2, m.dropout};
+    w.lp.begin("dropout_mask");
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, dm);
+    w.lp.end();
+  }
+  const int ghead = std::min(w.B, c->grid_head);
+  const GHeadArgs h = g_head_args(w, loss, metrics, drop, gen_inline);
+  // the head's fold was the last reader of this walk's forward rows: the walk's last word on parity (fwd_rows)
+  if (w.inl) c->fpar ^= 1;
   if (m.head2) {
-    GHead2Args h2;
-    h2.h = h;
-    h2.watt = m.head_att ? fwd_params(c) + m.o_att : nullptr;
-    h2.pool = m.head_pool;
-    h2.hact = m.hact;
-    h2.watt_part = m.watt_part;
+    const GHead2Args h2 = g_head2_args(w, h);
     const size_t lds = m.lds_head2;
     if (lds > 64 * 1024)
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ghead_att_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    lp.begin("head");
+    w.lp.begin("head");
     hipLaunchKernelGGL(ghead_att_kernel, dim3(ghead), dim3(kThreads), lds, c->stream, h2);
-    lp.end();
+    w.lp.end();
     // the dense layer sees hact (already activated): identity "BN" for the dense-weight gradient
     DenseSource ds;
     ds.p = m.hact;
     ds.scale = m.ones;
     ds.shift = m.zeros;
-    return enqueue_side_work(c, B, metrics, loss, ds);
+    return enqueue_side_work(c, w.B, metrics, loss, ds);
   }
-  lp.begin("head");
+  w.lp.begin("head");
   hipLaunchKernelGGL(ghead_kernel, dim3(ghead), dim3(kThreads), 0, c->stream, h);
-  lp.end();
+  w.lp.end();
   const DenseSource ds{lo.p, h.scale, h.shift, drop ? m.keep : nullptr, h.rp, h.rscale, h.rshift, h.rT, h.rdrop, 0};
-  return enqueue_side_work(c, B, metrics, loss, ds);
+  return enqueue_side_work(c, w.B, metrics, loss, ds);
+}
+
+// ---- the steps of the backward walk
+// twins (i - 1, i): one finalize launch and one four-role backward launch for the pair
+int g_bwd_twins(GWalk& w, int i) {
+  mww_ctx* c = w.c;
+  const GraphModel& m = w.m;
+  const GOp &o = m.G[i], &o1 = m.G[i - 1];
+  const float inv_n = g_inv_n(o, w.B);
+  const StatSource s0{o.gstat_part, w.gg, inv_n, 1.0f}, s1{o1.gstat_part, w.gg, inv_n, 1.0f};
+  const GBnBwdArgs bf0 = g_bn_bwd_args(c, o, s0), bf1 = g_bn_bwd_args(c, o1, s1);
+  const GWgradArgs w0 = g_wgrad_args(w, i), w1 = g_wgrad_args(w, i - 1);
+  const GConvArgs d0 = g_dgrad_args(w, i), d1 = g_dgrad_args(w, i - 1);
+  const int n0 = o.slots, gg4 = w.split ? std::max(1, w.gg / 4) : w.gg;
+  w.lp.begin("conv_bwd2_", i);
+  if (!w.inl) hipLaunchKernelGGL(gbn_bwd_finalize2_kernel, dim3(o.slots + o1.slots), dim3(kThreads), 0, c->stream, bf0, bf1, n0);
+  int rows = gg4;
+  const int r2 = k_launch_gbwd2(g_launch_ctx(c), o.cout, w0, d0, w1, d1, GridPick{w.pick ? 0 : gg4, w.B, w.split ? 4 : 1, m.g_cap_bwd, &rows},
+                               std::max(std::max(o.lds_wg, o.lds_dx), std::max(o1.lds_wg, o1.lds_dx)),
+                               g_shape_id(c, o) == g_shape_id(c, o1) ? g_shape_id(c, o) : 0);
+  w.lp.end();
+  if (r2) return g_rc(r2, "twin ops without a fused backward instantiation");
+  g_add_segment(w.ga, o.grad_part, rows, o.k * o.cin * o.cout, o.o_w);
+  g_add_segment(w.ga, o1.grad_part, rows, o1.k * o1.cin * o1.cout, o1.o_w);
+  return MWW_OK;
+}
+
+void g_bwd_res_gather(GWalk& w, int i) {
+  const GResGatherArgs ra = g_res_gather_args(w.m, w.m.G[i], w.B);
+  w.lp.begin("residual_gather", i);
+  hipLaunchKernelGGL(gres_gather_kernel, dim3(w.gg), dim3(kThreads), 0, w.c->stream, ra);
+  w.lp.end();
+}
+
+// without the hand-over: op i's backward sums (behind a sync-BN exchange) -> c1 / mg / mgx and the gradients of gamma and beta,
+// or of a bias
+int g_bwd_finalize(GWalk& w, int i) {
+  mww_ctx* c = w.c;
+  const GOp& o = w.m.G[i];
+  if (o.norm == MWW_NORM_BN) {
+    StatSource ss;
+    MWW_TRY(exchange_stats(c, w.lp, "bn_gstat_exchange", i, o.gstat_part, i == (int)w.m.G.size() - 1 ? w.ghead : w.gg, o.cout, 1, g_inv_n(o, w.B), &ss));
+    const GBnBwdArgs f = g_bn_bwd_args(c, o, ss);
+    w.lp.begin("bn_bwd_finalize", i);
+    hipLaunchKernelGGL(gbn_bwd_finalize_kernel, dim3(o.slots), dim3(kThreads), 0, c->stream, f);
+    w.lp.end();
+  } else if (o.norm == MWW_NORM_BIAS) {
+    const GBnBwdArgs f = g_bias_grad_args(c, o, w.gg);
+    w.lp.begin("bias_grad", i);
+    hipLaunchKernelGGL(gbn_bwd_finalize_kernel, dim3(o.cout), dim3(kThreads), 0, c->stream, f);
+    w.lp.end();
+  }
+  return MWW_OK;
+}
+
+int g_bwd_depthwise(GWalk& w, int i) {
+  mww_ctx* c = w.c;
+  const GraphModel& m = w.m;
+  const GOp& o = m.G[i];
+  GDwArgs dw = g_make_dw(c, i, w.B, true, w.inl);
+  if (w.inl && o.norm == MWW_NORM_BIAS) {   // the rows this op's consumer added (sum g, ..) to: folded by the weight-gradient launch
+    dw.bias_acc = bwd_rows(c, o).acc;
+    dw.dbeta = c->grads + o.o_beta;
+  }
+  w.lp.begin("dw_wgrad", i);
+  int gwg = 0;   // (its partial rows are its own)
+  int rc = g_rc(k_launch_gdw_wgrad(g_launch_ctx(c), dw, GridPick{m.grid_g_auto ? 0 : w.gg, w.B, 1, m.g_cap_bwd, &gwg}, o.lds_wg));
+  w.lp.end();
+  if (rc) return rc;
+  if (o.needs_dx) {
+    w.lp.begin("dw_dgrad", i);
+    // (partial statistics rows are shared without the hand-over)
+    rc = g_rc(k_launch_gdw(g_launch_ctx(c), 1, dw, GridPick{w.pick ? 0 : w.gg, w.B, 1, m.g_cap_bwd, nullptr}, o.lds_dx));
+    w.lp.end();
+    if (rc) return rc;
+  }
+  g_add_segment(w.ga, o.grad_part, gwg, o.k * o.cout, o.o_w);
+  return MWW_OK;
+}
+
+// weight and data gradient of op i: one launch with both roles, or - no such instantiation, no data gradient, or
+// "profile_split" - a launch each
+int g_bwd_conv(GWalk& w, int i) {
+  mww_ctx* c = w.c;
+  const GraphModel& m = w.m;
+  const GOp& o = m.G[i];
+  GWgradArgs wa = g_wgrad_args(w, i);
+  GConvArgs da = o.needs_dx ? g_dgrad_args(w, i) : g_zero<GConvArgs>();
+  int rows = w.gg, Tc = 0;
+  const int S = g_chunks(c, o, w.inl, true, &Tc);   // frame chunks (1x1 ops): S work items per window for both roles
+  size_t lds_wg = o.lds_wg, lds_dx = o.lds_dx;
+  if (S > 1) {
+    wa.S = da.S = S;
+    wa.Tc = da.Tc = Tc;
+    lds_wg = g_lds_wg(o, g_chunk_in(o, Tc), Tc);
+    lds_dx = o.needs_dx ? g_lds_dx(o, Tc, Tc) : 0;
+  }
+  const int items = w.B * S;
+  bool fused = false;
+  if (o.needs_dx && !m.profile_split) {
+    w.lp.begin("conv_bwd", i);
+    const GridPick pkf{w.pick ? 0 : (w.split ? std::max(1, w.gg / 2) : w.gg), items, w.split ? 2 : 1, m.g_cap_bwd, &rows};
+    const int rf = k_launch_gbwd(g_launch_ctx(c), S > 1, o.cout, o.cin, wa, da, pkf, std::max(lds_wg, lds_dx), g_shape_id(c, o));
+    w.lp.end();
+    if (rf > 0) return g_rc(rf);
+    fused = rf == 0;
+    if (!fused) w.lp.cancel();
+  }
+  if (!fused) {
+    w.lp.begin("conv_wgrad", i);
+    const GridPick pkw{w.pick ? 0 : w.gg, items, 1, m.g_cap_bwd, &rows};
+    int rc = launch_gwgrad(c, S > 1, o.cout, wa, pkw, lds_wg, g_shape_id(c, o));
+    w.lp.end();
+    if (rc) return rc;
+    if (o.needs_dx) {
+      w.lp.begin("conv_dgrad", i);
+      const GridPick pkd{w.pick ? 0 : w.gg, items, 1, m.g_cap_bwd, nullptr};
+      rc = g_rc(k_launch_gdgrad(g_launch_ctx(c), S > 1, o.cin, da, pkd, lds_dx));
+      w.lp.end();
+      if (rc) return rc;
+    }
+  }
+  g_add_segment(w.ga, o.grad_part, rows, o.k * o.cin * o.cout, o.o_w);
+  return MWW_OK;
+}
+
+}  // namespace
+
+// The forward plan: per op its eval-mode BN fold, then its launch - a depthwise op's, a twin pair's, or a convolution's with,
+// outside the hand-over, its BN finalize - and the head behind the last op.
+int GraphModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_moving, bool loss, bool metrics) {
+  if (c->x_lazy && !g_stem_gathers(c)) MWW_TRY(materialise_x(c));   // (an option changed since the batch was assembled)
+  GWalk w(c, *this, B, training && handover(c));
+  w.training = training;
+  w.update_moving = update_moving;
+  const int n = (int)G.size();
+  for (int i = 0; i < n; ++i) {
+    const GOp& o = G[i];
+    if (!training && o.norm == MWW_NORM_BN) g_fwd_bn_eval(w, i, true);
+    if (o.kind == MWW_OP_DEPTHWISE) {
+      MWW_TRY(g_fwd_depthwise(w, i));
+      continue;
+    }
+    if (o.twin_next && w.pair) {
+      bool launched = false;
+      MWW_TRY(g_fwd_twins(w, i, &launched));
+      if (launched) {
+        ++i;   // the twin is done
+        continue;
+      }
+    }
+    MWW_TRY(g_fwd_conv(w, i));
+    if (training && o.norm == MWW_NORM_BN && !w.inl) MWW_TRY(g_fwd_bn_finalize(w, i));
+  }
+  return g_fwd_head(w, loss, metrics);
 }
 
 // BN re-estimation: where the training forward of B windows just enqueued left the sums of every op with a BatchNorm - the
 // accumulator rows its first consumer folded (gfold_forward_finish), or the partial rows (behind a sync-BN exchange: the row of
 // global sums) gbn_fwd_finalize_body read - with the inv_n of that fold
 int GraphModel::enqueue_bn_collect(mww_ctx* c, int B) {
-  GraphModel& m = *this;
-  const bool inl = c->bn_inline && m.g_inline_ok && !(c->hook && c->sync_bn) && !m.profile_split;
-  const int gg = std::min(B, m.grid_g);
+  const bool inl = handover(c);
+  const int gg = std::min(B, grid_g);
   std::vector<BnreRow> rows;
-  for (size_t i = 0; i < m.G.size(); ++i) {
-    GOp& o = m.G[i];
+  for (size_t i = 0; i < G.size(); ++i) {
+    const GOp& o = G[i];
     if (o.norm != MWW_NORM_BN) continue;
-    BnreRow r;
-    memset(&r, 0, sizeof(r));
-    const float inv_n = 1.0f / ((float)B * (float)o.tout * (float)(o.groups > 1 ? o.cout / o.groups : 1));
+    BnreRow r = g_zero<BnreRow>();
     r.C = o.cout;
     r.groups = o.groups;
     r.o_mm = (int)o.o_mm;
@@ -585,9 +818,9 @@ int GraphModel::enqueue_bn_collect(mww_ctx* c, int B) {
       r.form = BNRE_ROWS;
       r.acc[0] = o.facc[0];
       r.acc[1] = o.facc[1];
-      r.inv_n = inv_n;
+      r.inv_n = g_inv_n(o, B);
     } else {
-      const StatSource ss = forward_stat_source(c, (int)i, o.stat_part, gg, o.cout, inv_n);
+      const StatSource ss = forward_stat_source(c, (int)i, o.stat_part, gg, o.cout, g_inv_n(o, B));
       r.form = BNRE_PART_GRAPH;
       r.part = ss.part;
       r.G = ss.G;
@@ -598,270 +831,27 @@ int GraphModel::enqueue_bn_collect(mww_ctx* c, int B) {
   return enqueue_bnre_collect(c, rows);
 }
 
+// The backward plan, from the last op down: a twin pair's launch; or the gradient gathered for a residual op, outside the
+// hand-over the BN / bias finalize, and the op's own launches.  With the hand-over every op folds the sums its consumers (or
+// the head) added to its accumulator rows inside its own launch.
 int GraphModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
-  GraphModel& m = *this;
-  Launcher lp{c};
-  const int n = (int)m.G.size();
-  const int gg = std::min(B, m.grid_g);
-  const int ghead = std::min(B, c->grid_head);
-  GradReduceArgs ga;
-  memset(&ga, 0, sizeof(ga));
-  // statistics hand-over: the op's own backward launch folds (sum g, sum g*xhat) from the accumulator rows its consumers
-  // (or the head) added to; the weight-gradient role publishes c1 / mg / mgx / dgamma / dbeta
-  const bool inl = c->bn_inline && m.g_inline_ok && !(c->hook && c->sync_bn) && !m.profile_split;
-  auto bfold = [&](GOp& q, bool publish) {
-    GFoldBwd f;
-    memset(&f, 0, sizeof(f));
-    if (!inl || q.norm != MWW_NORM_BN) return f;
-    f.acc = q.gacc_cur;
-    f.groups = q.groups;
-    f.inv_n = 1.0f / ((float)B * (float)q.tout * (float)(q.groups > 1 ? q.cout / q.groups : 1));
-    f.dscale = 1.0f;
-    f.publish = publish ? 1 : 0;
-    f.gamma = fwd_params(c) + q.o_gamma;
-    f.c1 = gbn_slot(q, BN_C1);
-    f.mg = gbn_slot(q, BN_MG);
-    f.mgx = gbn_slot(q, BN_MGX);
-    f.dgamma = c->grads + q.o_gamma;
-    f.dbeta = c->grads + q.o_beta;
-    return f;
-  };
-  auto bwd_fin_args = [&](int oi, const StatSource& ss) {
-    GOp& q = m.G[oi];
-    return GBnBwdArgs{ss.part, ss.G, q.cout, q.groups, ss.inv_n,
-                      fwd_params(c) + q.o_gamma, gbn_slot(q, BN_RSTD), gbn_slot(q, BN_C1), gbn_slot(q, BN_MG), gbn_slot(q, BN_MGX),
-                      c->grads + q.o_gamma, c->grads + q.o_beta, ss.dscale, 0};
-  };
-  auto wgrad_args = [&](int oi) {
-    GOp& q = m.G[oi];
-    GWgradArgs w;
-    memset(&w, 0, sizeof(w));
-    w.n_src = q.n_src;
-    for (int s = 0; s < q.n_src; ++s) w.src[s] = g_make_src(c, oi, s, false);
-    w.y = g_make_bnbwd(c, q);
-    w.y.fold = bfold(q, true);
-    w.k = q.k;
-    w.dil = q.dil;
-    w.cin = q.cin;
-    w.stride = q.stride;
-    w.B = B;
-    w.Tin = q.tin;
-    w.Tout = q.tout;
-    w.grad_part = q.grad_part;
-    return w;
-  };
-  auto dgrad_args = [&](int oi) {
-    GOp& q = m.G[oi];
-    GConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_src = q.n_src;
-    for (int s = 0; s < q.n_src; ++s) a.src[s] = g_make_src(c, oi, s, true, inl);
-    a.w = fwd_params(c) + q.o_w;   // (the data-gradient kernel reads them transposed / tap-reversed in place)
-    a.k = q.k;
-    a.dil = q.dil;
-    a.cin = q.cout;
-    a.stride = 1;
-    a.B = B;
-    a.Tin = q.tout;
-    a.Tout = q.tin;
-    a.y = g_make_bnbwd(c, q);
-    a.y.fold = bfold(q, false);
-    return a;
-  };
-  const bool split = inl && m.g_role_split;
-  const bool pick = inl && m.grid_g_auto;   // per-launch grids (g_role_grid)
-  const int gg2 = split ? std::max(1, gg / 2) : gg, gg4 = split ? std::max(1, gg / 4) : gg;
-  auto add_segment = [&](int oi, int rows) {
-    GOp& q = m.G[oi];
-    GradSegment s;
-    s.part = q.grad_part;
-    s.G = rows;
-    s.stride = q.k * q.cin * q.cout;
-    s.n = s.stride;
-    s.dst = (int)q.o_w;
-    ga.seg[ga.nseg++] = s;
-  };
-  const bool sync = c->hook && c->sync_bn;
-  for (int i = n - 1; i >= 0; --i) {
-    GOp& o = m.G[i];
-    const int members = o.groups > 1 ? o.cout / o.groups : 1;
-    if (i > 0 && m.G[i - 1].twin_next && !sync && !m.profile_split) {
-      // twins (i-1, i): one finalize launch and one four-role backward launch for the pair
-      GOp& o1 = m.G[i - 1];
-      const float inv_n = 1.0f / ((float)B * (float)o.tout * (float)members);
-      StatSource s0{o.gstat_part, gg, inv_n, 1.0f}, s1{o1.gstat_part, gg, inv_n, 1.0f};
-      const GBnBwdArgs bf0 = bwd_fin_args(i, s0), bf1 = bwd_fin_args(i - 1, s1);
-      const GWgradArgs w0 = wgrad_args(i), w1 = wgrad_args(i - 1);
-      const GConvArgs d0 = dgrad_args(i), d1 = dgrad_args(i - 1);
-      const int n0 = o.slots;
-      lp.begin("conv_bwd2_", i);
-      if (!inl) hipLaunchKernelGGL(gbn_bwd_finalize2_kernel, dim3(o.slots + o1.slots), dim3(kThreads), 0, c->stream, bf0, bf1, n0);
-      int rows = gg4;
-      const int r2 = k_launch_gbwd2(g_launch_ctx(c), o.cout, w0, d0, w1, d1, GridPick{pick ? 0 : gg4, B, split ? 4 : 1, m.g_cap_bwd, &rows},
-                                   std::max(std::max(o.lds_wg, o.lds_dx), std::max(o1.lds_wg, o1.lds_dx)),
-                                   g_shape_id(c, o) == g_shape_id(c, o1) ? g_shape_id(c, o) : 0);
-      lp.end();
-      if (r2) return g_rc(r2, "twin ops without a fused backward instantiation");
-      add_segment(i, rows);
-      add_segment(i - 1, rows);
+  GWalk w(c, *this, B, handover(c));
+  w.ghead = std::min(B, c->grid_head);
+  for (int i = (int)G.size() - 1; i >= 0; --i) {
+    const GOp& o = G[i];
+    if (i > 0 && G[i - 1].twin_next && w.pair) {
+      MWW_TRY(g_bwd_twins(w, i));
       --i;
       continue;
     }
-    if (!o.adders.empty()) {
-      GResGatherArgs ra;
-      memset(&ra, 0, sizeof(ra));
-      ra.n = (int)o.adders.size();
-      for (int q = 0; q < ra.n; ++q) {
-        GOp& x = m.G[o.adders[q]];
-        ra.gx[q] = x.g;
-        ra.Tx[q] = x.tout;
-        ra.drop[q] = x.res_drop;
-      }
-      ra.p = o.p;
-      ra.mean = gbn_slot(o, BN_MEAN);
-      ra.rstd = gbn_slot(o, BN_RSTD);
-      ra.g = o.g;
-      ra.gstat_part = o.gstat_part;
-      ra.B = B;
-      ra.T = o.tout;
-      ra.C = o.cout;
-      lp.begin("residual_gather", i);
-      hipLaunchKernelGGL(gres_gather_kernel, dim3(gg), dim3(kThreads), 0, c->stream, ra);
-      lp.end();
-    }
-    if (o.norm == MWW_NORM_BN && !inl) {
-      StatSource ss;
-      int rcs = exchange_stats(c, lp, "bn_gstat_exchange", i, o.gstat_part, i == n - 1 ? ghead : gg, o.cout, 1,
-                               1.0f / ((float)B * (float)o.tout * (float)members), &ss);
-      if (rcs) return rcs;
-      GBnBwdArgs f{ss.part, ss.G, o.cout, o.groups, ss.inv_n,
-                   fwd_params(c) + o.o_gamma, gbn_slot(o, BN_RSTD), gbn_slot(o, BN_C1), gbn_slot(o, BN_MG), gbn_slot(o, BN_MGX),
-                   c->grads + o.o_gamma, c->grads + o.o_beta, ss.dscale, 0};
-      lp.begin("bn_bwd_finalize", i);
-      hipLaunchKernelGGL(gbn_bwd_finalize_kernel, dim3(o.slots), dim3(kThreads), 0, c->stream, f);
-      lp.end();
-    } else if (o.norm == MWW_NORM_BIAS && !inl) {
-      // d bias = sum of the output gradient = the first statistic the consumers already accumulated
-      GBnBwdArgs f{o.gstat_part, gg, o.cout, 1, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->grads + o.o_beta, 1.0f, 1};
-      lp.begin("bias_grad", i);
-      hipLaunchKernelGGL(gbn_bwd_finalize_kernel, dim3(o.cout), dim3(kThreads), 0, c->stream, f);
-      lp.end();
-    }
-    if (o.kind == MWW_OP_DEPTHWISE) {
-      GDwArgs dw = g_make_dw(c, i, B, true, inl);
-      if (inl && o.norm == MWW_NORM_BIAS) {   // the rows this op's consumer added (sum g, ..) to: folded by the weight-gradient launch
-        dw.bias_acc = o.gacc_cur;
-        dw.dbeta = c->grads + o.o_beta;
-      }
-      lp.begin("dw_wgrad", i);
-      int gwg = 0;   // (its partial rows are its own)
-      int rc = g_rc(k_launch_gdw_wgrad(g_launch_ctx(c), dw, GridPick{m.grid_g_auto ? 0 : gg, B, 1, m.g_cap_bwd, &gwg}, o.lds_wg));
-      lp.end();
-      if (rc) return rc;
-      if (o.needs_dx) {
-        lp.begin("dw_dgrad", i);
-        // (partial statistics rows are shared without the hand-over)
-        rc = g_rc(k_launch_gdw(g_launch_ctx(c), 1, dw, GridPick{pick ? 0 : gg, B, 1, m.g_cap_bwd, nullptr}, o.lds_dx));
-        lp.end();
-        if (rc) return rc;
-      }
-      GradSegment s;
-      s.part = o.grad_part;
-      s.G = gwg;
-      s.stride = o.k * o.cout;
-      s.n = s.stride;
-      s.dst = (int)o.o_w;
-      ga.seg[ga.nseg++] = s;
-      continue;
-    }
-    GWgradArgs w;
-    memset(&w, 0, sizeof(w));
-    w.n_src = o.n_src;
-    for (int s = 0; s < o.n_src; ++s) w.src[s] = g_make_src(c, i, s, false);
-    w.y = g_make_bnbwd(c, o);
-    w.y.fold = bfold(o, true);
-    w.k = o.k;
-    w.dil = o.dil;
-    w.cin = o.cin;
-    w.stride = o.stride;
-    w.B = B;
-    w.Tin = o.tin;
-    w.Tout = o.tout;
-    w.grad_part = o.grad_part;
-    GConvArgs a;
-    memset(&a, 0, sizeof(a));
-    if (o.needs_dx) {
-      a.n_src = o.n_src;
-      for (int s = 0; s < o.n_src; ++s) a.src[s] = g_make_src(c, i, s, true, inl);
-      a.w = fwd_params(c) + o.o_w;
-      a.k = o.k;
-      a.dil = o.dil;
-      a.cin = o.cout;
-      a.stride = 1;
-      a.B = B;
-      a.Tin = o.tout;
-      a.Tout = o.tin;
-      a.y = g_make_bnbwd(c, o);
-      a.y.fold = bfold(o, false);
-    }
-    bool fused = false;
-    int rows = gg;
-    int Tc = 0;
-    const int S = g_chunks(c, o, inl, true, &Tc);   // frame chunks (1x1 ops): S work items per window for both roles
-    size_t lds_wg = o.lds_wg, lds_dx = o.lds_dx;
-    if (S > 1) {
-      w.S = a.S = S;
-      w.Tc = a.Tc = Tc;
-      lds_wg = g_lds_wg(o, g_chunk_in(o, Tc), Tc);
-      lds_dx = o.needs_dx ? g_lds_dx(o, Tc, Tc) : 0;
-    }
-    const int items = B * S;
-    if (o.needs_dx && !m.profile_split) {
-      lp.begin("conv_bwd", i);
-      const GridPick pkf{pick ? 0 : gg2, items, split ? 2 : 1, m.g_cap_bwd, &rows};
-      const int rf = k_launch_gbwd(g_launch_ctx(c), S > 1, o.cout, o.cin, w, a, pkf, std::max(lds_wg, lds_dx), g_shape_id(c, o));
-      lp.end();
-      if (rf > 0) return g_rc(rf);
-      fused = rf == 0;
-      if (!fused && c->profile) {   // nothing was launched: drop the empty profile entry
-        (void)hipEventDestroy(c->prof.back().a);
-        (void)hipEventDestroy(c->prof.back().b);
-        c->prof.pop_back();
-      }
-    }
-    if (!fused) {
-      lp.begin("conv_wgrad", i);
-      const GridPick pkw{pick ? 0 : gg, items, 1, m.g_cap_bwd, &rows};
-      int rc = launch_gwgrad(c, S > 1, o.cout, w, pkw, lds_wg, g_shape_id(c, o));
-      lp.end();
-      if (rc) return rc;
-      if (o.needs_dx) {
-        lp.begin("conv_dgrad", i);
-        const GridPick pkd{pick ? 0 : gg, items, 1, m.g_cap_bwd, nullptr};
-        rc = g_rc(k_launch_gdgrad(g_launch_ctx(c), S > 1, o.cin, a, pkd, lds_dx));
-        lp.end();
-        if (rc) return rc;
-      }
-    }
-    GradSegment s;
-    s.part = o.grad_part;
-    s.G = rows;
-    s.stride = o.k * o.cin * o.cout;
-    s.n = s.stride;
-    s.dst = (int)o.o_w;
-    ga.seg[ga.nseg++] = s;
+    if (!o.adders.empty()) g_bwd_res_gather(w, i);
+    if (!w.inl) MWW_TRY(g_bwd_finalize(w, i));
+    if (o.kind == MWW_OP_DEPTHWISE) MWW_TRY(g_bwd_depthwise(w, i));
+    else MWW_TRY(g_bwd_conv(w, i));
   }
-  if (m.head2 && m.head_att) {
-    GradSegment s;
-    s.part = m.watt_part;
-    s.G = ghead;
-    s.stride = 8;
-    s.n = 8;
-    s.dst = (int)m.o_att;
-    ga.seg[ga.nseg++] = s;
-  }
-  if (inl) c->gpar ^= 1;
-  return enqueue_grad_assembly(c, B, ga, fuse_adam);
+  if (head2 && head_att) g_add_segment(w.ga, watt_part, w.ghead, 8, o_att);
+  if (w.inl) c->gpar ^= 1;   // behind the last reader of this step's backward rows: the walk's last word on parity (bwd_rows)
+  return enqueue_grad_assembly(c, B, w.ga, fuse_adam);
 }
 
 namespace {

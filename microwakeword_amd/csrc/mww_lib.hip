@@ -435,8 +435,10 @@ int push_hyper(mww_ctx* c, float alpha, float gscale) {
   h[1] = gscale;
   return MWW_OK;
 }
-// labels / weights written by mww_set_targets that no assembly kernel carried to the device
-int flush_targets(mww_ctx* c) {
+// What every call that runs a forward opens with: the labels / weights written by mww_set_targets that no assembly kernel
+// carried to the device, and x written out where the batch is descriptor-only but its mailbox slot is no longer the current
+// one (only until then is it gathered in place)
+int batch_ready(mww_ctx* c) {
   if (c->targets_in_mail > 0) {
     const char* m = c->mail_host[c->mail_cur];
     const size_t n = (size_t)c->targets_in_mail * sizeof(float);
@@ -446,7 +448,7 @@ int flush_targets(mww_ctx* c) {
     c->y_cur = c->y;
     c->sw_cur = c->sw;
   }
-  return MWW_OK;
+  return c->lazy_slot != c->mail_cur ? materialise_x(c) : MWW_OK;
 }
 
 float adam_alpha(float lr, int64_t t) {
@@ -1184,12 +1186,8 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
   if (!c || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
   if (c->have_batch < B || c->have_targets < B) return fail(MWW_ERR_STATE, "train step needs a batch and targets of at least B rows");
   HIPCHK(hipSetDevice(c->device));
-  int rc = flush_targets(c);
+  int rc = batch_ready(c);
   if (rc) return rc;
-  if (c->lazy_slot != c->mail_cur) {   // a descriptor-only batch is gathered in place only while its mailbox slot is current
-    rc = materialise_x(c);
-    if (rc) return rc;
-  }
   const bool apply = !(flags & MWW_STEP_NO_APPLY);
   if (apply) {
     c->step += 1;
@@ -1265,12 +1263,8 @@ int mww_forward(mww_ctx* c, int B, int training, int update_metrics) {
   if (c->have_batch < B) return fail(MWW_ERR_STATE, "forward needs a batch of at least B rows");
   if (update_metrics && c->have_targets < B) return fail(MWW_ERR_STATE, "metric update needs targets");
   HIPCHK(hipSetDevice(c->device));
-  int rc = flush_targets(c);
+  int rc = batch_ready(c);
   if (rc) return rc;
-  if (c->lazy_slot != c->mail_cur) {
-    rc = materialise_x(c);
-    if (rc) return rc;
-  }
   EmaSource source(c, training != 0);
   rc = refresh_shadow(c);
   if (rc) return rc;
@@ -1299,12 +1293,8 @@ int mww_bn_reestimate_batch(mww_ctx* c, int B) {
   if (c->bnre_batches < 0) return fail(MWW_ERR_STATE, "bn_reestimate: no pass is open (call mww_bn_reestimate_begin; an update of the average closes a pass)");
   if (c->have_batch < B) return fail(MWW_ERR_STATE, "forward needs a batch of at least B rows");
   HIPCHK(hipSetDevice(c->device));
-  int rc = flush_targets(c);
+  int rc = batch_ready(c);
   if (rc) return rc;
-  if (c->lazy_slot != c->mail_cur) {
-    rc = materialise_x(c);
-    if (rc) return rc;
-  }
   // the forward of mww_forward(training = 1, update_metrics = 0) - batch statistics, moving statistics untouched, no loss, no
   // metrics, no dropout - standing on the average (with "weight_qat": on its shadow); never captured
   EmaSource source(c, true);

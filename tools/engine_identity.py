@@ -1,7 +1,10 @@
 """Bit identity of the training engines between two builds of the library: a fixed, seeded list of cases, one JSON line per
 case with the sha256 of what a context hands back - parameters, Adam state, BN state and gradients after three train steps,
 the probabilities / logits / loss / metric counters of those steps and of one inference forward, the counters of
-mww_evaluate_windows, and the p1 / g1 / bn1 tensors of mww_debug_read.  The kernels sum in a fixed order, so a change that
+mww_evaluate_windows, the p1 / g1 / bn1 tensors of mww_debug_read, and (`sequence`) the outputs and parameters of a
+training-mode forward followed by further train steps, which leaves the accumulator parities of the statistics hand-over out of
+step with each other and, under "graphs", ends on a replayed graph.  For the cases that ask for it, `profile` is the sha256 of
+the launch NAMES one more step records under option "profile" (no times).  The kernels sum in a fixed order, so a change that
 moves no arithmetic leaves every hash as it was.
 
     python tools/engine_identity.py --lib A.so > a.jsonl      # every case
@@ -10,10 +13,11 @@ moves no arithmetic leaves every hash as it was.
     python tools/engine_identity.py --lib tests/hipemu/libmww_emu.so --emulator   # the same list at emulator sizes
 
 The cases: the default MixedNet under every schedule option of either owner, the notebook topology, the default Inception
-under the graph engine's options, a MixedNet flag set on the graph engine with generated dropout, both engines behind a
-world-1 pass-through exchange hook (sync-BN + gradient exchange), and the two-bucket gradient exchange.  Batches come from
-a feature store through mww_assemble_batch (descriptor-only where the model gathers).  No oracle is consulted: this
-compares builds.
+under the graph engine's options, the Inception variant (two stem layers, dilation, sub-spectral groups, dropout), MixedNet
+flag sets on the graph engine - generated dropout, residual branches, the attention / pooled heads, no first convolution,
+captured graphs - both engines behind a world-1 pass-through exchange hook (sync-BN + gradient exchange), and the two-bucket
+gradient exchange.  Batches come from a feature store through mww_assemble_batch (descriptor-only where the model gathers).
+No oracle is consulted: this compares builds.
 """
 import argparse
 import hashlib
@@ -25,8 +29,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-FIELDS = ("params", "adam", "bn_state", "grads", "outputs", "metrics", "forward", "evaluate", "debug")
+FIELDS = ("params", "adam", "bn_state", "grads", "outputs", "metrics", "forward", "evaluate", "debug", "sequence", "profile")
 STEPS = 3
+# train steps of `sequence`: one - or, under "graphs", one more than the mailbox ring has slots (kRing = 8), since a captured step
+# is replayed only when mailbox slot and accumulator parities recur
+SEQUENCE_STEPS, SEQUENCE_STEPS_GRAPHS = 1, 9
 MIXEDNET_OPTIONS = ({}, {"bn_inline": 0}, {"tail_roles": 0}, {"side_stream": 1}, {"graphs": 1}, {"fused_input": 0}, {"bwd_wide": 0},
                     {"conv1_x6": 0}, {"conv1_x6_fwd": 1}, {"bwd_first_wide": 1}, {"dp_commit_late": 0}, {"dp_commit_late": 1},
                     {"pointwise_bf16": 1}, {"storage_bf16": 1})
@@ -35,7 +42,7 @@ INCEPTION_OPTIONS = ({}, {"graph_planar": 0}, {"graph_static_shapes": 0}, {"grap
 
 
 def cases(emulator):
-    """(name, kind, flags, B, T, options, hook) - hook: None or (sync_bn, reduce_grads)"""
+    """(name, kind, flags, B, T, options, hook[, profile]) - hook: None or (sync_bn, reduce_grads); profile: hash the launch names"""
     import engine_checks as ec
     mix = (4, 60) if emulator else (6, 194)
     note = (3, 204) if emulator else (6, 204)   # (first-conv stride 3: the shortest length the emulator tests run)
@@ -47,14 +54,22 @@ def cases(emulator):
         if emulator and "grid_graph" in o:
             o = {"grid_graph": 8}   # (the emulated device has 4 CUs: at most 16 workgroups)
         out.append(("inception/" + tag(o), "inception", ec.INC, inc[0], inc[1], o, None))
+    out.append(("inception/graphs=1", "inception", ec.INC, inc[0], inc[1], {"graphs": 1}, None))
+    out.append(("inception/profile", "inception", ec.INC, inc[0], inc[1], {}, None, True))
+    out.append(("inception/variant", "inception", ec.INC_VARIANT, inc[0], inc[1], {"dropout_seed": 77}, None))
     out.append(("graph_mixednet/dropout", "graph_mixednet", dict(ec.GRAPH_MIXEDNET, dropout=0.25), 3, 100, {"dropout_seed": 1234}, None))
+    gmix = (3, 100) if emulator else (6, 150)
+    for name, flags, o, prof in (("graphs=1", ec.GRAPH_MIXEDNET, {"graphs": 1}, False), ("profile", ec.GRAPH_MIXEDNET, {}, True),
+                                 ("residual", ec.GRAPH_MIXEDNET_RESIDUAL, {}, False), ("full", ec.GRAPH_MIXEDNET_FULL, {}, False),
+                                 ("attention", ec.GRAPH_MIXEDNET_HEADS[0], {}, False), ("noconv1", ec.GRAPH_MIXEDNET_NOCONV1, {}, False)):
+        out.append(("graph_mixednet/" + name, "graph_mixednet", flags, gmix[0], gmix[1], o, None, prof))
     out.append(("mixednet/hook", "mixednet", ec.DEF, mix[0], mix[1], {}, (True, True)))
     out.append(("inception/hook", "inception", ec.INC, inc[0], inc[1], {}, (True, True)))
     out.append(("mixednet/grad_buckets=2", "mixednet", ec.DEF, mix[0], mix[1], {"grad_buckets": 2}, (False, True)))
     return out
 
 
-def run_case(lib, name, kind, flags, B, T, options, hook):
+def run_case(lib, name, kind, flags, B, T, options, hook, profile=False):
     from microwakeword_amd import native
     from microwakeword_amd.layout import GraphMixedNetLayout, InceptionLayout, MixedNetLayout
     rng = np.random.default_rng(int(hashlib.sha256(name.encode()).hexdigest()[:8], 16))
@@ -108,8 +123,28 @@ def run_case(lib, name, kind, flags, B, T, options, hook):
     ev = win[(STEPS + 1) * B:]
     eng.evaluate_windows(ev, (rng.random(ev.shape[0]) < 0.5).astype(np.float32), B)
     h["evaluate"].update(metrics())
+
+    def step(s):
+        w = slice(s * B, (s + 1) * B)
+        eng.set_targets((rng.random(B) < 0.5).astype(np.float32), rng.choice([0.5, 1.0, 2.0], size=B).astype(np.float32))
+        eng.assemble(win[w], masks[w], 2, 2)
+        eng.train_step(B, 1e-2)
+
+    eng.assemble(win[:B], None, 0, 0)
+    eng.forward(B, training=True)
+    add("sequence", *eng.read_outputs(B, want_loss=False)[:2])
+    for s in range(SEQUENCE_STEPS_GRAPHS if options.get("graphs") else SEQUENCE_STEPS):
+        step(s % STEPS)
+        p, z, loss = eng.read_outputs(B)
+        add("sequence", p, z, np.float32(loss))
+    add("sequence", eng.get_params())
+    if profile:
+        eng.set_option("profile", 1)
+        eng.profile_read()   # (nothing of the calls above)
+        step(0)
+        h["profile"].update("\n".join(n for n, _ in eng.profile_read()).encode())
     eng.close()
-    return json.dumps(dict(case=name, **{f: h[f].hexdigest()[:32] for f in FIELDS}))
+    return json.dumps(dict(case=name, **{f: h[f].hexdigest()[:32] if f != "profile" or profile else "-" for f in FIELDS}))
 
 
 def compare(path_a, path_b):
