@@ -169,7 +169,10 @@ def non_stream(qm, frames, T, want_logits=False):
     for i in range(q.n):
         tensors.append(q.conv(i, q.gather(i, tensors)))
     logit = q.head(tensors[-1])
-    assert logit.size == L - T + 1, (logit.size, L, T)   # the description's receptive field is the window
+    # the description's receptive field is the window - or shorter, where a drop removes more leading frames than aligning
+    # the sources needs: the ops run right-aligned, so the windows ending at T, T + 1, ... are the last L - T + 1 positions
+    assert logit.size >= L - T + 1, (logit.size, L, T)
+    logit = logit[logit.size - (L - T + 1):]
     u8 = q.output(logit)[0]
     return (u8, logit.astype(np.int8)) if want_logits else u8
 
