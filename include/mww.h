@@ -231,6 +231,41 @@ int mww_bn_reestimate_commit(mww_ctx* ctx);
 int mww_get_ema_bn_state(mww_ctx* ctx, float* host, int64_t n, int* valid);
 int mww_set_ema_bn_state(mww_ctx* ctx, const float* host, int64_t n);
 
+/* ---- sharpness-aware steps (SAM) and global-norm gradient clipping.  Both stand on one quantity, the sum of squares of the
+ * whole flat gradient g (indexed like mww_get_grads) between the backward pass and Adam:
+ *     S = sumsq(g): 1024 lanes; lane j = the float64 sum of (double)g[i] * (double)g[i] over i = j, j + 1024, ... ascending,
+ *                   multiply and add uncontracted; S = ((s_0 + s_1) + s_2) + ... in lane order.  No atomics.
+ * Sharpness-aware step, radius rho:  scale = rho / (sqrt(S) + 1e-12) in float64; w'[i] = w[i] + (float)(scale * (double)g[i]).
+ * Clipping, threshold c:             k = c / max(sqrt(S), c) in float64 (max(r, c) = r > c ? r : c, so k is exactly 1.0 at or
+ *                                    below the threshold and for a NaN S); g[i] = (float)(k * (double)g[i]) in place.
+ * Nothing is screened: a non-finite gradient gives a non-finite w', and the call still returns MWW_OK.
+ *
+ * With a radius installed, mww_train_step without MWW_STEP_NO_APPLY enqueues:
+ *   1. shadow refresh (weight_qat); forward in training mode - moving statistics updated, loss, metrics as the flags say -
+ *      and backward without Adam: g(w);
+ *   2. S of g(w) and the perturbation: the master becomes w', a bit copy of w is kept;
+ *   3. shadow refresh again (weight_qat: the second pass reads fake_quant(w')); forward on the same batch with the same dropout
+ *      mask, batch statistics of its own, moving statistics NOT updated, loss, no metrics; backward without Adam: g(w');
+ *   4. the master restored from the bit copy (never by subtracting); S of g(w'); the clip if installed; Adam at w with g(w'),
+ *      the hyper-parameters pushed once and the optimizer step count up by one; the weight-average update when one is due.
+ * So: the BatchNorm moving statistics and the metric counters are those of the first pass; the dropout counter advances once
+ * per step (a run's mask sequence is that of a plain run); mww_get_grads returns what Adam consumed; mww_read_outputs
+ * returns the last forward's values, i.e. the second pass's.  With clipping alone the step is forward, backward without Adam,
+ * S, clip, Adam - at or below the threshold the bytes of the plain step.  Clipping also stands in front of Adam in
+ * mww_apply_gradients (it sees the gradient buffer as it is; grad_scale multiplies behind it).  A MWW_STEP_NO_APPLY step is
+ * never sharpened or clipped.  Under "graphs" such a step is enqueued eagerly (the same bytes); installing or removing either
+ * feature drops the captured steps.  A context that installs neither launches exactly what it launched before.
+ *
+ * mww_set_sharpness_aware: rho > 0 installs, 0 removes; mww_set_grad_clip likewise.  Any other value (negative, NaN, infinite)
+ * is MWW_ERR_INVALID.  Both are single-device: installing either next to an exchange hook, or a hook (mww_set_allreduce_hook,
+ * mww_allreduce_init) next to either, is MWW_ERR_UNSUPPORTED.  A refused call leaves the context as it was.
+ * mww_get_grad_norms returns S of the last such step's first-pass gradient and of the gradient Adam consumed, before
+ * clipping (clipping alone: the same number twice); it waits for the stream; either pointer may be NULL; MWW_ERR_STATE before
+ * the first such step. */
+int mww_set_sharpness_aware(mww_ctx* ctx, double rho);
+int mww_set_grad_clip(mww_ctx* ctx, double global_norm);
+int mww_get_grad_norms(mww_ctx* ctx, double* first_sumsq, double* final_sumsq);
+
 /* ---- feature stores: replace the RaggedMmap page-cache reads of data.py:255-258.  A store is the
  * flat concatenation of its samples ([T_i][40], uint16 raw micro-frontend values or float32
  * already scaled), uploaded once and kept resident in HBM. */

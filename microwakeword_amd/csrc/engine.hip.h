@@ -187,6 +187,14 @@ struct mww_ctx {
   mww::BnreRow* bnre_table = nullptr;     // device-resident table of the collect launch
   int bnre_table_rows = 0;
   std::vector<char> bnre_table_host;      // what it holds (uploaded again only when a row changes)
+  // sharpness-aware steps and global-norm clipping (mww_set_sharpness_aware / mww_set_grad_clip, kernels_sam.hip.h): an
+  // applying train step of a context that has either takes its gradient with a separate Adam launch; `sam_w` = the bit copy of
+  // the master a sharpness-aware step restores from, `norm_scalars` = {S of the first pass's gradient, its perturbation scale,
+  // S of the gradient Adam consumes, its clipping factor}
+  double sam_rho = 0.0, clip_norm = 0.0;
+  float* sam_w = nullptr;
+  double* norm_scalars = nullptr;
+  bool norms_valid = false;   // a step has written norm_scalars (mww_get_grad_norms)
   unsigned char* direct = nullptr;
   std::vector<unsigned char> direct_host;   // host copy: which parameters' gradients are written directly by a folding kernel
   bool exchange_pending = false;            // a deferred bucket exchange is in flight (data-parallel step)

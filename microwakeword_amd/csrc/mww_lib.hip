@@ -20,6 +20,7 @@
 #include "kernels_ema.hip.h"
 #include "kernels_head.hip.h"
 #include "kernels_qat.hip.h"
+#include "kernels_sam.hip.h"
 #include "kernels_tail.hip.h"
 
 using namespace mww;
@@ -535,16 +536,87 @@ void drop_graphs(mww_ctx* c) {
   c->graphs.clear();
 }
 
+// ---- sharpness-aware steps and global-norm clipping (kernels_sam.hip.h; include/mww.h states the sequence)
+enum { NORM_FIRST = 0, NORM_SCALE = 1, NORM_FINAL = 2, NORM_CLIP = 3, NORM_SCALARS = 4 };
+
+void free_sharpness(mww_ctx* c) {
+  if (c->sam_w) (void)hipFree(c->sam_w);
+  if (c->norm_scalars) (void)hipFree(c->norm_scalars);
+  c->sam_w = nullptr;
+  c->norm_scalars = nullptr;
+  c->sam_rho = c->clip_norm = 0.0;
+  c->norms_valid = false;
+}
+
+// S of the gradient as it stands -> norm_scalars[slot] (and [also], if >= 0), with the scalar of `mode` behind it
+int enqueue_grad_sumsq(mww_ctx* c, int slot, int also, int mode, double value) {
+  Launcher lp{c};
+  lp.begin("grad_sumsq");
+  launch_grad_sumsq(SumsqArgs{c->grads, (int)c->P, mode, value, c->norm_scalars + slot, also >= 0 ? c->norm_scalars + also : nullptr,
+                              c->norm_scalars + slot + 1}, c->stream);
+  lp.end();
+  return MWW_OK;
+}
+
+// what stands between the gradient Adam is about to consume and Adam: its S (first: this is also the step's first-pass
+// gradient) and, with clipping installed, the scaling
+int enqueue_final_norm(mww_ctx* c, bool first) {
+  const bool clip = c->clip_norm > 0.0;
+  MWW_TRY(enqueue_grad_sumsq(c, NORM_FINAL, first ? NORM_FIRST : -1, clip ? kSumsqClip : kSumsqOnly, c->clip_norm));
+  if (clip) {
+    Launcher lp{c};
+    lp.begin("grad_clip");
+    launch_grad_scale(GradScaleArgs{c->grads, c->norm_scalars + NORM_CLIP, (int)c->P, 0}, c->stream);
+    lp.end();
+  }
+  c->norms_valid = true;
+  return MWW_OK;
+}
+
+// the applying step of a context with a sharpness-aware radius or a clipping threshold: the gradient is assembled without
+// Adam, Adam is a launch of its own
+int sharp_sequence(mww_ctx* c, int B, int flags, int ema) {
+  const bool sam = c->sam_rho > 0.0;
+  MWW_TRY(refresh_shadow(c));
+  MWW_TRY(c->model->enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS)));
+  MWW_TRY(c->model->enqueue_backward(c, B, false));   // g(w)
+  if (sam) {
+    MWW_TRY(enqueue_grad_sumsq(c, NORM_FIRST, -1, kSumsqPerturb, c->sam_rho));
+    Launcher lp{c};
+    lp.begin("sam_perturb");
+    launch_sam_perturb(SamPerturbArgs{c->grads, c->params, c->sam_w, c->norm_scalars + NORM_SCALE, (int)c->P, 0}, c->stream);
+    lp.end();
+    // the second pass: the same batch (a descriptor-only one is gathered through the same mailbox slot, committed behind this
+    // call), the same dropout mask (the step's counter, or the pinned mask), batch statistics of its own that leave the moving
+    // statistics alone, no metrics; the accumulator parities flip as in a second gradient-only step
+    MWW_TRY(refresh_shadow(c));   // "weight_qat": fake_quant(w')
+    MWW_TRY(c->model->enqueue_forward(c, B, true, false, true, false));
+    MWW_TRY(c->model->enqueue_backward(c, B, false));   // g(w')
+    lp.begin("sam_restore");
+    HIPCHK(hipMemcpyAsync(c->params, c->sam_w, (size_t)c->P * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    lp.end();
+  }
+  MWW_TRY(enqueue_final_norm(c, !sam));
+  MWW_TRY(enqueue_adam(c));
+  return enqueue_ema(c, ema);
+}
+
 int step_sequence(mww_ctx* c, int B, int flags, int ema) {
   c->metric_launches = 0;
-  int rc = refresh_shadow(c);   // (under "graphs": one more node of the captured chain)
-  if (rc) return rc;
-  rc = c->model->enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS));
-  if (rc) return rc;
-  rc = c->model->enqueue_backward(c, B, !(flags & MWW_STEP_NO_APPLY));
-  if (rc) return rc;
-  rc = enqueue_ema(c, ema);   // behind the last Adam launch of the step (stream order, also with two gradient buckets)
-  if (rc) return rc;
+  int rc;
+  if (!(flags & MWW_STEP_NO_APPLY) && (c->sam_rho > 0.0 || c->clip_norm > 0.0)) {
+    rc = sharp_sequence(c, B, flags, ema);
+    if (rc) return rc;
+  } else {
+    rc = refresh_shadow(c);   // (under "graphs": one more node of the captured chain)
+    if (rc) return rc;
+    rc = c->model->enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS));
+    if (rc) return rc;
+    rc = c->model->enqueue_backward(c, B, !(flags & MWW_STEP_NO_APPLY));
+    if (rc) return rc;
+    rc = enqueue_ema(c, ema);   // behind the last Adam launch of the step (stream order, also with two gradient buckets)
+    if (rc) return rc;
+  }
   // the metric state has one writer per step (kernels_head.hip.h MetricState): a second launch with the role would lose counts
   if (c->metric_launches > 1) return fail(MWW_ERR_STATE, "internal: more than one launch of this step carries the metric update");
   return MWW_OK;
@@ -712,6 +784,8 @@ int mww_create_convnet(const mww_convnet_desc* desc, int device, void* stream, m
 int mww_set_allreduce_hook(mww_ctx* c, mww_allreduce_fn fn, void* user, int world_size, int sync_bn, int reduce_grads) {
   if (!c) return fail(MWW_ERR_INVALID, "null context");
   if (fn && world_size < 1) return fail(MWW_ERR_INVALID, "world size must be positive");
+  if (fn && (c->sam_rho > 0.0 || c->clip_norm > 0.0))
+    return fail(MWW_ERR_UNSUPPORTED, "sharpness-aware steps and gradient clipping are single-device: remove them before installing an exchange hook");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   c->hook = fn;
@@ -840,6 +914,8 @@ int mww_allreduce_world(mww_ctx* c) {
 
 int mww_allreduce_init(mww_ctx* c, int rank, int world, const void* unique_id, int sync_bn) {
   if (!c || !unique_id || world < 1 || rank < 0 || rank >= world) return fail(MWW_ERR_INVALID, "bad rank / world size");
+  if (c->sam_rho > 0.0 || c->clip_norm > 0.0)   // (before the communicator is touched: a refused call leaves the context as it was)
+    return fail(MWW_ERR_UNSUPPORTED, "sharpness-aware steps and gradient clipping are single-device: remove them before installing an exchange hook");
   int rc = mww_allreduce_destroy(c);
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
@@ -879,6 +955,7 @@ void mww_destroy(mww_ctx* c) {
   for (void* p : flat) if (p) (void)hipFree(p);
   free_weight_qat(c);
   free_weight_ema(c);
+  free_sharpness(c);
   for (int i = 0; i < MWW_MAX_STORES; ++i) if (c->store[i]) (void)hipFree(c->store[i]);
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
   for (int i = 0; i < kRing; ++i) {
@@ -970,6 +1047,47 @@ int mww_set_ema_state(mww_ctx* c, const float* h, int64_t n, int64_t updates) {
   if ((c->ema_updates == 0) != (updates == 0)) drop_graphs(c);   // (a captured step's node copies or blends)
   c->ema_updates = updates;
   invalidate_ema_bn(c);
+  return MWW_OK;
+}
+
+namespace {
+// installs (value > 0) or removes (0) one of the two features; the buffers live while either is installed
+int set_sharpness(mww_ctx* c, double value, bool sam, const char* what) {
+  if (!c) return fail(MWW_ERR_INVALID, "null context");
+  // validated before anything changes: a refused call leaves the context as it was
+  if (!(value >= 0.0) || std::isinf(value)) return fail(MWW_ERR_INVALID, std::string(what) + " must be a finite number > 0, or 0 to remove it");
+  if (value > 0.0 && c->hook)
+    return fail(MWW_ERR_UNSUPPORTED, std::string(what) + " is single-device: it cannot be installed next to an exchange hook");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  drop_graphs(c);   // (a step with either feature is not the captured sequence)
+  const double rho = sam ? value : c->sam_rho, clip = sam ? c->clip_norm : value;
+  if (rho == 0.0 && clip == 0.0) {
+    free_sharpness(c);
+    return MWW_OK;
+  }
+  if (!c->norm_scalars) MWW_TRY(dev_alloc(&c->norm_scalars, (size_t)NORM_SCALARS));
+  if (rho > 0.0 && !c->sam_w) MWW_TRY(dev_alloc(&c->sam_w, (size_t)c->P));
+  if (rho == 0.0 && c->sam_w) {
+    (void)hipFree(c->sam_w);
+    c->sam_w = nullptr;
+  }
+  c->sam_rho = rho;
+  c->clip_norm = clip;
+  return MWW_OK;
+}
+}  // namespace
+
+int mww_set_sharpness_aware(mww_ctx* c, double rho) { return set_sharpness(c, rho, true, "sharpness_aware: rho"); }
+int mww_set_grad_clip(mww_ctx* c, double global_norm) { return set_sharpness(c, global_norm, false, "grad_clip: global_norm"); }
+
+int mww_get_grad_norms(mww_ctx* c, double* first_sumsq, double* final_sumsq) {
+  if (!c) return fail(MWW_ERR_INVALID, "null context");
+  if (!c->norms_valid) return fail(MWW_ERR_STATE, "grad_norms: no sharpness-aware or clipped step has run yet");
+  double h[NORM_SCALARS];
+  MWW_TRY(copy_out(c, h, c->norm_scalars, sizeof(h)));
+  if (first_sumsq) *first_sumsq = h[NORM_FIRST];
+  if (final_sumsq) *final_sumsq = h[NORM_FINAL];
   return MWW_OK;
 }
 
@@ -1205,7 +1323,9 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
     h[2] = (unsigned)(counter & 0xFFFFFFFFull);
     h[3] = (unsigned)(counter >> 32);
   }
-  if (c->use_graphs && !c->profile && !c->hook) {   // the exchange hook enqueues foreign work: no capture
+  // a sharpness-aware or clipped step is enqueued eagerly also under "graphs" (two walks flip the parities twice; same bytes)
+  const bool sharp = apply && (c->sam_rho > 0.0 || c->clip_norm > 0.0);
+  if (c->use_graphs && !c->profile && !c->hook && !sharp) {   // the exchange hook enqueues foreign work: no capture
     // only the Adam / dropout nodes and the gather of a descriptor-only batch read the mailbox
     const int mail = (apply || gen_dropout || c->x_lazy) ? c->mail_cur : -1;
     // the accumulator parities of the statistics hand-over are baked into the captured kernel arguments
@@ -1248,6 +1368,10 @@ int mww_apply_gradients(mww_ctx* c, float lr, float gscale) {
   c->step += 1;
   int rc = push_hyper(c, adam_alpha(lr, c->step), gscale);
   if (rc) return rc;
+  if (c->clip_norm > 0.0) {   // the gradient as it stands in the buffer is clipped; grad_scale multiplies behind it, inside Adam
+    rc = enqueue_final_norm(c, true);
+    if (rc) return rc;
+  }
   rc = enqueue_adam(c);
   if (rc) return rc;
   const int ema = ema_due(c);

@@ -214,6 +214,25 @@ class Model:
         self.engine.set_weight_ema(decay, every_steps)
         self.weight_averaging = dict(decay=float(decay), every_steps=int(every_steps)) if decay else None
 
+    def set_sharpness_aware(self, rho):
+        """Sharpness-aware training (``sharpness``; ``mww_set_sharpness_aware``): from the next step on every train step takes
+        the gradient at ``w``, moves to ``w + rho g / |g|``, takes the gradient there and applies Adam at ``w`` with that second
+        gradient - two forward / backward passes per step.  ``rho`` 0 removes it.  Single-device."""
+        self.engine.set_sharpness_aware(rho)
+        self.sharpness_aware = float(rho) if rho else None
+
+    def set_gradient_clipping(self, global_norm):
+        """Global-norm gradient clipping (Keras ``global_clipnorm``; ``sharpness.clip``; ``mww_set_grad_clip``): the gradient
+        Adam consumes is scaled down to the norm ``global_norm`` when it is longer.  0 removes it.  Single-device."""
+        self.engine.set_grad_clip(global_norm)
+        self.gradient_clipping = float(global_norm) if global_norm else None
+
+    def gradient_norms(self):
+        """(first, final): the L2 norms of the last sharpness-aware or clipped step's first-pass gradient and of the gradient
+        Adam consumed, before clipping (``sqrt`` of the engine's float64 sums of squares).  Waits for the device."""
+        first, final = self.engine.get_grad_norms()
+        return float(np.sqrt(first)), float(np.sqrt(final))
+
     def reestimate_bn(self, windows, batch):
         """Re-estimate the BatchNorm statistics for the weight average (``averaging``; ``mww_bn_reestimate_windows``): one pass
         of training-mode forwards at the average over ``windows`` (descriptors of resident rows, a positive multiple of
@@ -426,6 +445,10 @@ class Model:
         if getattr(self, "weight_averaging", None):
             print_fn("Weight averaging: exponential moving average of the trainable variables, decay %g, every %d step(s)"
                      % (self.weight_averaging["decay"], self.weight_averaging["every_steps"]))
+        if getattr(self, "sharpness_aware", None):
+            print_fn("Train step: sharpness-aware, rho %g (second gradient at w + rho g / |g|; two passes per step)" % self.sharpness_aware)
+        if getattr(self, "gradient_clipping", None):
+            print_fn("Gradient clipping: global norm %g" % self.gradient_clipping)
         if getattr(self, "weight_qat", False):
             print_fn("Weights: fake-quantized per output channel to the int8 grid in every forward / backward (fp32 master kept)")
         print_fn("Total params: %d" % total)

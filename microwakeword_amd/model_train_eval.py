@@ -348,6 +348,9 @@ def _run(flags, model_module, rank, local_rank, world):
         qat.parse_config(config)   # weight_quantization_aware: likewise
         from . import averaging
         averaging.parse_config(config)   # weight_averaging: likewise
+        from . import sharpness
+        from .train import process_group
+        sharpness.parse_config(config, max(int(world), process_group()[1]))   # sharpness_aware, gradient_clipping: likewise (single-device)
     device = flags.device if local_rank is None else local_rank
     if flags.train:
         device = flags.device if local_rank is None else local_rank

@@ -132,6 +132,7 @@ EXPORTS = [
     "mww_set_weight_qat", "mww_get_forward_params", "mww_set_weight_ema", "mww_get_ema_state", "mww_set_ema_state",
     "mww_bn_reestimate_begin", "mww_bn_reestimate_batch", "mww_bn_reestimate_commit", "mww_bn_reestimate_windows",
     "mww_get_ema_bn_state", "mww_set_ema_bn_state",
+    "mww_set_sharpness_aware", "mww_set_grad_clip", "mww_get_grad_norms",
 ]
 
 
@@ -205,6 +206,9 @@ class NativeLib:
         L.mww_bn_reestimate_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         L.mww_get_ema_bn_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int)]
         L.mww_set_ema_bn_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64]
+        L.mww_set_sharpness_aware.argtypes = [C.c_void_p, C.c_double]
+        L.mww_set_grad_clip.argtypes = [C.c_void_p, C.c_double]
+        L.mww_get_grad_norms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.mww_upload_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int]
         L.mww_assemble_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.mww_set_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
@@ -541,6 +545,23 @@ class Engine:
     def set_ema_state(self, ema, updates):
         a = np.ascontiguousarray(ema, np.float32).reshape(-1)
         self.nl.check(self.nl.lib.mww_set_ema_state(self.h, _fptr(a), a.size, int(updates)))
+
+    def set_sharpness_aware(self, rho):
+        """Make every applying train step a sharpness-aware one of radius ``rho`` (``sharpness``; ``mww_set_sharpness_aware``):
+        gradient at ``w``, step to ``w + rho g / |g|``, gradient there, Adam at ``w`` with the second gradient.  0 removes it."""
+        self.nl.check(self.nl.lib.mww_set_sharpness_aware(self.h, float(rho)))
+
+    def set_grad_clip(self, global_norm):
+        """Scale the gradient Adam consumes to a global norm of at most ``global_norm`` (``sharpness.clip``;
+        ``mww_set_grad_clip``).  0 removes it."""
+        self.nl.check(self.nl.lib.mww_set_grad_clip(self.h, float(global_norm)))
+
+    def get_grad_norms(self):
+        """(first_sumsq, final_sumsq) of the last sharpness-aware or clipped step: the float64 sums of squares of the first
+        pass's gradient and of the gradient Adam consumed, before clipping.  Waits for the stream."""
+        first, final = C.c_double(), C.c_double()
+        self.nl.check(self.nl.lib.mww_get_grad_norms(self.h, C.byref(first), C.byref(final)))
+        return float(first.value), float(final.value)
 
     # ---- BatchNorm statistics re-estimated for the average (``averaging``; include/mww.h)
     def bn_reestimate_begin(self):

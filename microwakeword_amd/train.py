@@ -21,6 +21,9 @@ weights from ``first_step`` on, and every evaluation boundary - the weight files
 mining round - stands on the averaged model; the steps themselves and the restore checkpoint keep the raw iterate.  With
 ``bn_reestimate: {samples, seed}`` in that mapping every boundary starts with one pass of training-mode forwards at the average
 over seeded resident windows, and the averaged model is evaluated, quantized and written with the BatchNorm statistics of that pass.
+With a ``sharpness_aware`` mapping (``sharpness``) the steps from ``first_step`` on are sharpness-aware ones (a second
+gradient at ``w + rho g / |g|``), with a ``gradient_clipping`` mapping the gradient Adam consumes is clipped to a global norm; the
+first-pass gradient norm joins the progress line and the train scalars where the loop reads the device back anyway.  Single-device.
 
 When both objects come from this package the spectrogram batch never leaves HBM
 (``FeatureHandler.next_training_batch_on_device`` + ``Model.train_on_device_batch``); with any other
@@ -213,6 +216,14 @@ def train(model, config, data_processor, verbose=True):
     avg_settings = averaging.parse_config(config)   # likewise
     if avg_settings is not None and not hasattr(model, "set_weight_averaging"):
         raise ValueError("%s needs this package's Model (the engine keeps the average on the device)" % averaging.CONFIG_KEY)
+    from . import sharpness
+    sam_settings, clip_settings = sharpness.parse_config(config, world)   # likewise; both are single-device
+    if (sam_settings is not None or clip_settings is not None) and config.get("data_parallel"):
+        raise ValueError("%s / %s are single-device for now: they cannot run with data_parallel (the engine refuses them next to an exchange hook)"
+                         % (sharpness.SAM_KEY, sharpness.CLIP_KEY))
+    for key, got, method in ((sharpness.SAM_KEY, sam_settings, "set_sharpness_aware"), (sharpness.CLIP_KEY, clip_settings, "set_gradient_clipping")):
+        if got is not None and not hasattr(model, method):
+            raise ValueError("%s needs this package's Model (the engine takes the gradient norm between the backward pass and Adam)" % key)
     fast = hasattr(data_processor, "next_training_batch_on_device") and hasattr(model, "train_on_device_batch") \
         and getattr(data_processor, "engine", None) is getattr(model, "engine", object())
     prefetch = int(config.get("prefetch_batches", 4))
@@ -298,7 +309,7 @@ def train(model, config, data_processor, verbose=True):
     # run needs no state of its own: on / off follows from the restored optimizer step.
     qat_on = False
     steps_before = 0
-    if (qat_settings is not None or avg_settings is not None) and hasattr(model, "engine") and hasattr(model.engine, "get_opt_state"):
+    if (qat_settings is not None or avg_settings is not None or sam_settings is not None) and hasattr(model, "engine") and hasattr(model.engine, "get_opt_state"):
         steps_before = int(model.engine.get_opt_state()[2])
     # weight_averaging: installed before optimizer step `first_step`, whose update copies the master.  The average and its
     # update count travel in the checkpoint's optimizer state, so a restored run continues the same average.
@@ -311,6 +322,18 @@ def train(model, config, data_processor, verbose=True):
             model.engine.set_ema_state(ema, updates)
         if chief:
             log.info("weight averaging continues from the checkpoint (%d updates, decay %g)", model.engine.ema_updates(), avg_settings["decay"])
+
+    # sharpness_aware: on from optimizer step `first_step` on, re-derived from the restored step like weight_quantization_aware (it
+    # has no state of its own); gradient_clipping: on for the whole run
+    sam_on = False
+    if clip_settings is not None:
+        model.set_gradient_clipping(clip_settings["global_norm"])
+        if chief:
+            log.info("gradient clipping on (global norm %g)", clip_settings["global_norm"])
+
+    def grad_norm_record():
+        # the first-pass gradient norm of the step just taken; only called where the loop reads the device back anyway
+        return {"grad_norm": model.gradient_norms()[0]} if (sam_on or clip_settings is not None) else {}
 
     # weight_averaging.bn_reestimate: the windows of the passes, drawn once (resident training rows of this rank's shard, no RNG
     # stream moves, no SpecAugment: the statistics describe the clean windows an evaluation sees), whole batches of the rank's batch
@@ -366,6 +389,11 @@ def train(model, config, data_processor, verbose=True):
             if chief:
                 log.info("Step #%d: weight averaging on (decay %g, every %d step(s)); evaluation boundaries stand on the average",
                          steps_before + step, avg_settings["decay"], avg_settings["every_steps"])
+        if sam_settings is not None and not sam_on and steps_before + step >= sam_settings["first_step"]:
+            model.set_sharpness_aware(sam_settings["rho"])   # before this step's forward
+            sam_on = True
+            if chief:
+                log.info("Step #%d: sharpness-aware steps on (rho %g; two forward / backward passes per step)", steps_before + step, sam_settings["rho"])
         if fast:
             data_processor.next_training_batch_on_device(local_batch, config["spectrogram_length"], "default", policy,
                                                          class_weights=(cw_neg, cw_pos), weight_broadcast=mode)
@@ -387,9 +415,10 @@ def train(model, config, data_processor, verbose=True):
                         "the batch loss; per_sample = the evident intent, mean_i(penalty_i x class_weight(y_i) x bce_i).  INTEGRATION.md "
                         "section 2.", cw_neg, cw_pos, "the reference's arithmetic" if mode == "keras_last_axis" else "this reading", mode)
         if verbose and chief and result is not None:
+            norm = grad_norm_record()
             print("Validation Batch #{:d}: Accuracy = {:.3f}; Recall = {:.3f}; Precision = {:.3f}; Loss = {:.4f}; Mini-Batch #{:d}".format(
                 (step // config["eval_step_interval"] + 1), result[1], result[2], result[3], result[9],
-                (step % config["eval_step_interval"])), end="\r")
+                (step % config["eval_step_interval"])) + ("; Gradient norm = {:.4g}".format(norm["grad_norm"]) if norm else ""), end="\r")
 
         is_last = step == steps_max
         if (step % config["eval_step_interval"]) == 0 or is_last:
@@ -403,7 +432,8 @@ def train(model, config, data_processor, verbose=True):
                  step, lr, result[1] * 100, result[2] * 100, result[3] * 100, result[9])
             train_writer.scalars(step, loss=result[9], accuracy=result[1], recall=result[2], precision=result[3], auc=result[8],
                                  **({} if qat_settings is None else {"weight_qat": int(qat_on)}),
-                                 **({} if avg_settings is None else {"weight_averaging": int(avg_on)}))
+                                 **({} if avg_settings is None else {"weight_averaging": int(avg_on)}),
+                                 **({} if sam_settings is None else {"sharpness_aware": int(sam_on)}), **grad_norm_record())
             with averaged():
                 save_weights(os.path.join(config["train_dir"], "last_weights.weights.h5"))
                 if private_streams:
