@@ -707,6 +707,49 @@ int mww_stream_operating_points(mww_stream* s, const int64_t* offsets, const int
 int mww_stream_operating_summary(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, const int32_t* windows,
                                  int n_windows, int skip, int cooldown, const double* cutoffs, int n_cutoffs, int stride, double step_s,
                                  uint64_t* counts, uint64_t* accepts, double* hours, int64_t* short_tracks, int64_t* n_kind);
+/* The grid of mww_stream_operating_summary resampled on the device (csrc/tu_stream_bootstrap.hip): `replicates`
+ * bootstrap replicates over the evaluation units, one record each read back - replicates * sizeof(mww_boot_record) bytes,
+ * whatever the tracks, windows and cutoffs.  Inputs and limits are those of mww_stream_operating_summary; here `cutoffs` must
+ * ascend strictly (MWW_ERR_INVALID otherwise: the selection rule assumes it, and a positive is then stored as one level).
+ * Everything below is integer arithmetic or single IEEE float64 operations (no contraction): streaming.operating_bootstrap_host
+ * restates it, byte for byte.
+ *   units      a positive unit is a kind-1 track (n_pos of them).  An ambient unit is a block of a kind-0 track: with block = 0
+ *              every kind-0 track is one block, an empty one too; with block = L > 0, a positive multiple of
+ *              MWW_BOOT_BLOCK_UNIT, a track of n probabilities has ceil(n / L) blocks, whatever the window, and at window k
+ *              block b owns the moving-average indices [b L, min((b + 1) L, m_k)), possibly none.  A block's count at (k, c)
+ *              is the number of the track's detections whose index it owns - detections of the whole-track cooldown walk of
+ *              mww_stream_metrics, so the cooldown carries across block borders and a track's blocks sum to its count -, its
+ *              length at k the size of its index range.  NB is the number of blocks, in (track, block) order.
+ *   draws      draw(seed, kind, r, i, n): ctr = kind << 56 | r << 32 | i; z = seed + ctr * 0x9E3779B97F4A7C15 (mod 2^64);
+ *              z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (the splitmix64
+ *              finaliser); the result is ((z >> 32) * n) >> 32: a multiply-shift without rejection, its bias below n / 2^32.
+ *              Replicate r draws the NB blocks draw(seed, 0, r, i, NB), i < NB, and the n_pos positives draw(seed, 1, r, i,
+ *              n_pos), i < n_pos; one set of draws serves all windows.
+ *   grid       counts_r[k][c] = the sum of the drawn blocks' counts, slices_r[k] = the sum of their lengths (int64),
+ *              accepts_r[k][c] = the drawn positives with (double)score[k][t] > cutoffs[c] (strict; -inf never);
+ *              hours_r[k] = ((double)(slices_r[k] * stride) * step_s) / 3600.0, faph_r = (double)counts_r / hours_r,
+ *              frr_r = 1 - (double)accepts_r / n_pos.  A window is usable in a replicate when it is usable on the full data
+ *              (a kind-0 and a kind-1 track exist, none is without a moving-average value) and slices_r[k] > 0.
+ *   record     sel_row, sel_cutoff: streaming.select_operating_points(faph_r, frr_r, usable_r, target_faph, windows) - per
+ *              usable window the smallest cutoff with faph_r <= target_faph there and at every larger cutoff, then the window
+ *              of the smallest (frr_r, faph_r, window, row) -, (-1, -1) when no window meets the target; sel_counts,
+ *              sel_slices, sel_accepts: counts_r, slices_r, accepts_r there (0 without a point).  fixed_*: the same three at
+ *              (fixed_row, fixed_cutoff), a point of the grid, or 0 with fixed_row = fixed_cutoff = -1.
+ * The re-selected point gives the uncertainty of the metric a selection rests on, the fixed point that of a cutoff that ships.
+ * max_scratch_bytes caps the device scratch of the block tables, 4 W NB C + 8 W NB + W n_pos bytes (0: 256 MiB); beyond it the
+ * call is MWW_ERR_UNSUPPORTED and asks for a larger block.  A refused call leaves the probabilities held as they are.  On the
+ * probabilities held, so on a stream of any creator, float or int8.  Two calls on the same probabilities write the same bytes. */
+#define MWW_BOOT_BLOCK_UNIT 1024
+#define MWW_BOOT_MAX_REPLICATES 65536
+typedef struct {
+  int32_t sel_row, sel_cutoff;
+  uint64_t sel_counts; int64_t sel_slices; uint64_t sel_accepts;
+  uint64_t fixed_counts; int64_t fixed_slices; uint64_t fixed_accepts;
+} mww_boot_record;
+int mww_stream_operating_bootstrap(mww_stream* s, const int64_t* offsets, const int32_t* kind, int64_t n_tracks, const int32_t* windows,
+                                   int n_windows, int skip, int cooldown, const double* cutoffs, int n_cutoffs, int stride, double step_s,
+                                   int replicates, uint64_t seed, int64_t block, double target_faph, int fixed_row, int fixed_cutoff,
+                                   int64_t max_scratch_bytes, mww_boot_record* records);
 
 /* ---- int8 quantized streaming model (the reference's --test_tflite_streaming_quantized; microwakeword_amd/quantize.py
  * derives the parameters, INTEGRATION.md states the contract).

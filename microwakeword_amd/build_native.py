@@ -25,7 +25,7 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(ROOT, "microwakeword_amd", "libmww_hip.so")
 OBJDIR = os.path.join(ROOT, "build", "obj")
 UNITS = ("version.cpp", "mww_lib.hip", "block_engine.hip", "tu_bwd_first.hip", "tu_bwd64.hip", "tu_bwd48.hip", "tu_bwd32.hip", "tu_fwd.hip", "tu_bwdw.hip", "tu_bwd.hip",
-         "tu_graph.hip", "graph_engine.hip", "tu_qat.hip", "tu_ema.hip", "tu_bnre.hip", "tu_sam.hip", "sampler.cpp", "tu_stream.hip", "tu_stream_q8.hip", "tu_stream_graph.hip", "tu_stream_graph_q8.hip", "tu_stream_detect.hip", "tu_stream_mine.hip", "tu_stream_oppoints.hip", "tu_stream_calibrate.hip")   # version.cpp first: the one unit that carries the stamp
+         "tu_graph.hip", "graph_engine.hip", "tu_qat.hip", "tu_ema.hip", "tu_bnre.hip", "tu_sam.hip", "sampler.cpp", "tu_stream.hip", "tu_stream_q8.hip", "tu_stream_graph.hip", "tu_stream_graph_q8.hip", "tu_stream_detect.hip", "tu_stream_mine.hip", "tu_stream_oppoints.hip", "tu_stream_bootstrap.hip", "tu_stream_calibrate.hip")   # version.cpp first: the one unit that carries the stamp
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-pthread")
 EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
 EMU_CLANG = "/opt/rocm/lib/llvm/bin/clang++"

@@ -1,5 +1,6 @@
 // What the entry points on the probabilities a stream holds have in common (mww_stream_metrics, _operating_points,
-// _operating_summary: tu_stream_oppoints.hip; mww_stream_detections, mww_stream_mine: stream_detect.hip.h), each written here and
+// _operating_summary: tu_stream_oppoints.hip; _operating_bootstrap: tu_stream_bootstrap.hip; mww_stream_detections, mww_stream_mine:
+// stream_detect.hip.h), each written here and
 // nowhere else: the moving average (every test of the family rests on all its users forming the same bits), the values of a
 // track, the segment search, the shared sizes, the track-table check, the segment plan and the packing of a call's tables.
 // No two entry points run at once and each synchronises before it returns, so they share two scratch buffers of the stream:

@@ -147,6 +147,16 @@ def build_parser():
                              "and the window and cutoff with the fewest false rejections at no more than this many false accepts per hour")
     parser.add_argument("--operating_point_windows", type=str, default=",".join(str(w) for w in range(1, 11)),
                         help="the sliding-window sizes of --operating_point_faph (comma separated, each 1..256, at most 32)")
+    parser.add_argument("--operating_point_bootstrap", type=int, default=None,
+                        help="with --operating_point_faph: also bootstrap the operating point on the device with this many replicates "
+                             "(1..65536) and write operating_point_bootstrap.json (settings, percentile intervals of recall and FAPH at the "
+                             "recommended point and of the recall re-selected per replicate) / operating_point_bootstrap.npz (one record per "
+                             "replicate) next to operating_point.json")
+    parser.add_argument("--operating_point_bootstrap_seed", type=int, default=0, help="seed of the bootstrap's counter hash (0 .. 2^64 - 1)")
+    parser.add_argument("--operating_point_bootstrap_block", type=int, default=0,
+                        help="ambient resampling unit in moving-average values: 0 resamples whole ambient tracks, a positive multiple of 1024 "
+                             "blocks of that length")
+    parser.add_argument("--operating_point_bootstrap_confidence", type=float, default=0.95, help="confidence of the percentile intervals (0 .. 1)")
     parser.add_argument("--restore_checkpoint", type=int, default=0)
     parser.add_argument("--use_weights", type=str, default="best_weights")
     parser.add_argument("--verbosity", type=str, default="INFO")
@@ -249,8 +259,28 @@ def operating_point_windows(flags):
     return windows
 
 
+def operating_point_bootstrap_settings(flags):
+    """The ``bootstrap`` settings of ``--operating_point_bootstrap`` (None without the flag), checked from the flags alone:
+    ValueError naming the flag for a value out of range, or without ``--operating_point_faph`` (any of the four flags)."""
+    from . import streaming
+    given = {name: getattr(flags, "operating_point_bootstrap" + ("_" + name if name != "replicates" else ""), default)
+             for name, default in (("replicates", None),) + tuple((k, v) for k, v in streaming.BOOTSTRAP_DEFAULTS.items() if k != "replicates")}
+    if given["replicates"] is None:
+        if any(given[k] != v for k, v in streaming.BOOTSTRAP_DEFAULTS.items() if k != "replicates"):
+            raise ValueError("--operating_point_bootstrap_seed / _block / _confidence need --operating_point_bootstrap")
+        return None
+    if getattr(flags, "operating_point_faph", None) is None:
+        raise ValueError("--operating_point_bootstrap needs --operating_point_faph")
+    try:
+        return streaming.bootstrap_settings("--operating_point_bootstrap", given)
+    except ValueError as e:
+        raise ValueError(str(e).replace("--operating_point_bootstrap: bootstrap", "--operating_point_bootstrap (replicates) and its _seed / _block / "
+                                        "_confidence flags")) from None
+
+
 def _operating_points(flags, config, folder, sm, data_processor):
-    """``--operating_point_faph``: the grid of the evaluation ``folder`` just ran, on the same tracks from the same start"""
+    """``--operating_point_faph``: the grid of the evaluation ``folder`` just ran, on the same tracks from the same start; with
+    ``--operating_point_bootstrap`` also the bootstrap of its operating point, from the same start again"""
     windows = operating_point_windows(flags)
     if windows is None:
         return
@@ -259,6 +289,12 @@ def _operating_points(flags, config, folder, sm, data_processor):
     grid = streaming.operating_point_grid(config, folder, sm, data_processor, flags.operating_point_faph, windows, data_set="testing",
                                           ambient_set="testing_ambient")
     logging.info("%s: %s", folder, streaming.operating_point_text(grid).splitlines()[-1])
+    boot = operating_point_bootstrap_settings(flags)
+    if boot is not None:
+        sm.reset()
+        out = streaming.operating_point_bootstrap(config, folder, sm, data_processor, flags.operating_point_faph, windows, boot,
+                                                  data_set="testing", ambient_set="testing_ambient")
+        logging.info("%s: bootstrap intervals %s", folder, out["bootstrap"]["intervals"])
 
 
 def quantization_module(model, backend="native"):
@@ -338,6 +374,7 @@ def _run(flags, model_module, rank, local_rank, world):
                     "well-defined calibration to restate")
         raise NotImplementedError(msg)
     operating_point_windows(flags)
+    operating_point_bootstrap_settings(flags)
     config = load_config(flags, model_module)
     check_evaluation_flags(flags, model_module, config)   # before training and before train_dir is claimed
     if flags.train:

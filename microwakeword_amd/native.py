@@ -86,6 +86,12 @@ STREAM_MAX_KERNELS = 8
 STREAM_MAX_REPEAT = 8
 STREAM_MODES = {"stream": 0, "non_stream": 1}
 OP_MAX_WINDOWS, OP_MAX_WINDOW = 32, 256   # MWW_OP_MAX_WINDOWS, MWW_OP_MAX_WINDOW (include/mww.h)
+BOOT_BLOCK_UNIT, BOOT_MAX_REPLICATES = 1024, 65536   # MWW_BOOT_BLOCK_UNIT, MWW_BOOT_MAX_REPLICATES
+# mww_boot_record: one bootstrap replicate's re-selected point and its numbers, then the numbers at the fixed point
+BOOT_RECORD_DTYPE = np.dtype([("sel_row", np.int32), ("sel_cutoff", np.int32), ("sel_counts", np.uint64), ("sel_slices", np.int64),
+                              ("sel_accepts", np.uint64), ("fixed_counts", np.uint64), ("fixed_slices", np.int64),
+                              ("fixed_accepts", np.uint64)])
+assert BOOT_RECORD_DTYPE.itemsize == 56
 
 
 class StreamDesc(C.Structure):
@@ -128,7 +134,7 @@ EXPORTS = [
     "mww_stream_metrics", "mww_stream_num_tensors", "mww_stream_calibrate_host", "mww_stream_set_quantized", "mww_stream_q8_sizes",
     "mww_stream_read_q8", "mww_stream_get_state_q8", "mww_stream_create_convnet", "mww_stream_create_convnet_q8",
     "mww_stream_create_mixednet", "mww_stream_create_mixednet_q8", "mww_stream_detections", "mww_stream_operating_points",
-    "mww_stream_mine", "mww_stream_operating_summary", "mww_stream_calibrate",
+    "mww_stream_mine", "mww_stream_operating_summary", "mww_stream_operating_bootstrap", "mww_stream_calibrate",
     "mww_set_weight_qat", "mww_get_forward_params", "mww_set_weight_ema", "mww_get_ema_state", "mww_set_ema_state",
     "mww_bn_reestimate_begin", "mww_bn_reestimate_batch", "mww_bn_reestimate_commit", "mww_bn_reestimate_windows",
     "mww_get_ema_bn_state", "mww_set_ema_bn_state",
@@ -279,6 +285,9 @@ class NativeLib:
         L.mww_stream_operating_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                    C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p]
+        L.mww_stream_operating_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_int64, C.c_double,
+                                                     C.c_int, C.c_int, C.c_int64, C.c_void_p]
         L.mww_stream_num_tensors.argtypes = [C.c_void_p]
         L.mww_stream_calibrate_host.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float)]
         L.mww_stream_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
@@ -959,6 +968,26 @@ class Stream:
             self.h, vp(off), vp(kd), n, vp(win), win.size, int(skip), int(cooldown), vp(cut), cut.size,
             int(self.stride if stride is None else stride), float(step_s), vp(counts), vp(accepts), vp(hours), vp(short), vp(n_kind)))
         return counts, accepts, hours, short, n_kind
+
+    def operating_bootstrap(self, offsets, kind, windows, cutoffs, skip=25, cooldown=25, stride=None, step_s=0.02, target_faph=0.5,
+                            replicates=1000, seed=0, block=0, fixed=None, max_scratch_bytes=0):
+        """``mww_stream_operating_bootstrap`` on the probabilities held: ``replicates`` bootstrap replicates of the grid of
+        ``operating_summary`` (ambient blocks of ``block`` moving-average values - 0: whole tracks - and positive tracks
+        resampled by the counter hash of ``seed``), each reduced on the device to one record.  ``fixed``: a (row, cutoff) of the
+        grid whose numbers every record also carries, or None.  ``max_scratch_bytes``: the cap on the block tables (0: the
+        default).  -> records BOOT_RECORD_DTYPE [replicates]; ``stride`` defaults to the stream's own."""
+        off, kd, n = _track_table(offsets, kind)
+        win = np.ascontiguousarray(windows, np.int32).reshape(-1)
+        cut = np.ascontiguousarray(cutoffs, np.float64).reshape(-1)
+        row, col = (-1, -1) if fixed is None else (int(fixed[0]), int(fixed[1]))
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed must be an unsigned 64-bit integer")
+        rec = np.zeros(max(int(replicates), 0), BOOT_RECORD_DTYPE)
+        self.nl.check(self.nl.lib.mww_stream_operating_bootstrap(
+            self.h, vp(off), vp(kd), n, vp(win), win.size, int(skip), int(cooldown), vp(cut), cut.size,
+            int(self.stride if stride is None else stride), float(step_s), int(replicates), int(seed), int(block), float(target_faph),
+            row, col, int(max_scratch_bytes), vp(rec) if rec.size else None))
+        return rec
 
     # ---- int8 form (include/mww.h, mww_stream_set_quantized)
     def num_tensors(self) -> int:

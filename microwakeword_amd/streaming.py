@@ -219,6 +219,24 @@ class StreamingModel:
             offsets, kind, windows, cutoffs, ignore_slices_after_accept, ignore_slices_after_accept, stride, step_s)
         return _operating_summary(counts, accepts, hours, short, n_kind, windows, cutoffs, target_faph)
 
+    def operating_bootstrap(self, offsets, kind, windows=OP_WINDOWS, cutoffs=CUTOFFS, ignore_slices_after_accept=25, stride=None, step_s=0.02,
+                            target_faph=0.5, replicates=1000, seed=0, block=0, confidence=0.95, fixed=None, max_scratch_bytes=0):
+        """``operating_summary`` with ``target_faph`` plus the bootstrap of its operating point on the device
+        (mww_stream_operating_bootstrap; ``operating_bootstrap_host`` is the host restatement, the definitions stand above it):
+        the summary's dict with ``bootstrap`` = dict(records, replicates, seed, block, confidence, fixed_row, fixed_cutoff,
+        intervals).  ``records`` (native.BOOT_RECORD_DTYPE [replicates]) is all that is read back; ``intervals``
+        (``bootstrap_intervals``) come from it on the host.  ``fixed``: a (row, cutoff index) of the grid, default the full
+        data's recommended point (none when no window meets the target); ``block``: 0 or a multiple of
+        native.BOOT_BLOCK_UNIT moving-average values."""
+        stride = self.stride if stride is None else int(stride)
+        if not 0 < float(confidence) < 1:
+            raise ValueError("confidence must lie strictly between 0 and 1")
+        summary = self.operating_summary(offsets, kind, windows, cutoffs, ignore_slices_after_accept, stride, step_s, target_faph)
+        fixed = _bootstrap_fixed(summary, fixed)
+        records = self.native.operating_bootstrap(offsets, kind, windows, cutoffs, ignore_slices_after_accept, ignore_slices_after_accept,
+                                                  stride, step_s, target_faph, replicates, seed, block, fixed, max_scratch_bytes)
+        return _bootstrap_result(summary, records, fixed, stride, step_s, replicates, seed, block, confidence)
+
 
 def load_quantized(path):
     """the ``QuantizedModel`` (MixedNet), ``QuantizedMixedNetModel`` (MixedNet with residuals / a pooled head) or
@@ -617,6 +635,188 @@ def operating_summary_host(ambient_probabilities, positive_probabilities, window
     return out
 
 
+# ---- bootstrap of the operating point (mww_stream_operating_bootstrap).  The definitions, once:
+#   units    a positive unit is a positive track.  An ambient unit is a block of an ambient track: with block = 0 every track
+#            is one block, an empty one too; with block = L > 0 (a multiple of native.BOOT_BLOCK_UNIT) a track of n
+#            probabilities has ceil(n / L) blocks, whatever the window, and at window k block b owns the moving-average indices
+#            [b L, min((b + 1) L, m_k)), possibly none.  A block's count at (k, c) is the number of the track's detections -
+#            those of the whole-track cooldown walk, so the cooldown carries across block borders and the blocks of a track
+#            sum to its count - whose index it owns; its length at k is the size of its index range.  NB blocks in all, in
+#            (track, block) order.
+#   draws    ``bootstrap_draw``; replicate r draws the NB blocks draw(seed, 0, r, i, NB) and the n_pos positives
+#            draw(seed, 1, r, i, n_pos); one set of draws serves all windows.
+#   grid     counts_r[k, c]: the sum of the drawn blocks' counts; slices_r[k]: the sum of their lengths; accepts_r[k, c]: the
+#            drawn positives with float64(score[k, t]) > cutoffs[c]; hours_r = ((slices_r * stride) * step_s) / 3600.0,
+#            faph_r = float64(counts_r) / hours_r, frr_r = 1 - float64(accepts_r) / n_pos; a window is usable in a replicate
+#            when it is usable on the full data and slices_r[k] > 0.
+#   records  per replicate the point ``select_operating_points(faph_r, frr_r, usable_r, target_faph, windows)`` re-selects
+#            ((-1, -1) when no window meets the target) with counts_r, slices_r, accepts_r there, and the same three at a fixed
+#            point of the grid.  The re-selected point gives the uncertainty of the metric a selection rests on, the fixed
+#            point that of the cutoff that ships.
+#   intervals  ``bootstrap_intervals``: percentiles of the sorted replicate values.
+# What the intervals are not: blocks of one recording are not independent (a block bootstrap only keeps the dependence inside
+# a block); with few ambient tracks and block = 0 the FAPH interval is coarse (it takes few distinct values); percentile
+# intervals are not bias-corrected.
+
+def bootstrap_draw(seed, kind, r, i, n):
+    """Draw ``i`` (an integer or an array of them, < 2^32) of replicate ``r`` (< 2^16 here, < 2^24 by the layout) for
+    ``kind`` (0: ambient blocks, 1: positives) out of ``n`` (< 2^32) units, int64 in 0 .. n - 1: the counter
+    ``kind << 56 | r << 32 | i`` times 0x9E3779B97F4A7C15 plus ``seed`` (mod 2^64) through the splitmix64 finaliser, then
+    ``((z >> 32) * n) >> 32``.  A multiply-shift without rejection: the bias is below n / 2^32."""
+    u = np.uint64
+    idx = np.atleast_1d(np.asarray(i)).astype(np.uint64)
+    ctr = np.full(idx.shape, (int(kind) << 56) | (int(r) << 32), np.uint64) | idx
+    z = np.full(idx.shape, int(seed) & (2 ** 64 - 1), np.uint64) + ctr * u(0x9E3779B97F4A7C15)   # arrays wrap mod 2^64
+    z ^= z >> u(30)
+    z *= u(0xBF58476D1CE4E5B9)
+    z ^= z >> u(27)
+    z *= u(0x94D049BB133111EB)
+    z ^= z >> u(31)
+    out = (((z >> u(32)) * u(int(n))) >> u(32)).astype(np.int64)
+    return out.reshape(np.shape(i)) if np.ndim(i) else int(out[0])
+
+
+def bootstrap_block_counts(moving_average_values, cutoffs, ignore_slices_after_accept, block, n_blocks):
+    """One ambient track's detections per block, uint32 [n_blocks, C]: ``detection_positions`` at every cutoff at once (the loop
+    of test.py:119-135 on a vector of cooldowns, as ``false_accept_counts`` runs it), each detection counted in block
+    ``index // block`` (``block`` 0: the one block)."""
+    cutoffs = np.asarray(cutoffs, np.float64)
+    out = np.zeros((n_blocks, cutoffs.shape[0]), np.uint32)
+    cooldown = np.full(cutoffs.shape[0], ignore_slices_after_accept, np.int64)
+    for i, value in enumerate(np.asarray(moving_average_values, np.float32)):
+        cooldown = np.maximum(cooldown - 1, 0)
+        hit = (cooldown == 0) & (np.float64(value) > cutoffs)
+        out[i // block if block else 0] += hit.astype(np.uint32)
+        cooldown[hit] = ignore_slices_after_accept
+    return out
+
+
+def bootstrap_units_host(ambient_probabilities, positive_probabilities, windows, cutoffs, ignore_slices_after_accept=25, block=0, skip=None):
+    """The units of the bootstrap on given per-track probabilities: ``(blk_cnt uint32 [W, NB, C], blk_len int64 [W, NB],
+    score float32 [W, n_pos])`` from ``moving_average_in_order`` and the detections binned by ``index // block``."""
+    block = int(block)
+    if block < 0 or block % native.BOOT_BLOCK_UNIT:
+        raise ValueError("block must be 0 or a positive multiple of %d" % native.BOOT_BLOCK_UNIT)
+    skip = ignore_slices_after_accept if skip is None else skip
+    windows = [int(w) for w in windows]
+    n_blocks = [(-(-len(p) // block) if block else 1) for p in ambient_probabilities]
+    first = np.concatenate([[0], np.cumsum(n_blocks)]).astype(np.int64)
+    blk_cnt = np.zeros((len(windows), int(first[-1]), len(cutoffs)), np.uint32)
+    blk_len = np.zeros((len(windows), int(first[-1])), np.int64)
+    score = np.zeros((len(windows), len(positive_probabilities)), np.float32)
+    done = {}
+    for k, w in enumerate(windows):
+        if w in done:   # a window may repeat
+            blk_cnt[k], blk_len[k], score[k] = blk_cnt[done[w]], blk_len[done[w]], score[done[w]]
+            continue
+        done[w] = k
+        for j, p in enumerate(ambient_probabilities):
+            ma = moving_average_in_order(p, w)
+            blk_cnt[k, first[j]:first[j + 1]] = bootstrap_block_counts(ma, cutoffs, ignore_slices_after_accept, block, n_blocks[j])
+            for b in range(n_blocks[j]):
+                blk_len[k, first[j] + b] = max(min((b + 1) * block, ma.size) - b * block, 0) if block else ma.size
+        pos = [moving_average_in_order(np.asarray(p, np.float32)[skip:], w) for p in positive_probabilities]
+        score[k] = [np.max(a) if a.size else np.float32(-np.inf) for a in pos]
+    return blk_cnt, blk_len, score
+
+
+def bootstrap_records_host(units, usable, windows, cutoffs, stride, step_s, target_faph, replicates, seed, fixed=None,
+                           select=select_operating_points):
+    """The records of ``replicates`` replicates on the units of ``bootstrap_units_host`` (``usable``: the windows usable on the
+    full data): native.BOOT_RECORD_DTYPE [replicates], what mww_stream_operating_bootstrap writes.  ``select``: the selection
+    rule (a test compares another)."""
+    blk_cnt, blk_len, score = units
+    cutoffs = np.asarray(cutoffs, np.float64).reshape(-1)
+    if np.any(~(np.diff(cutoffs) > 0)):
+        raise ValueError("the cutoffs of a bootstrap must ascend strictly")
+    if not 1 <= int(replicates) <= native.BOOT_MAX_REPLICATES:
+        raise ValueError("replicates must lie in 1..%d" % native.BOOT_MAX_REPLICATES)
+    W, NB, C = blk_cnt.shape
+    n_pos = score.shape[1]
+    score64 = score.astype(np.float64)
+    rec = np.zeros(int(replicates), native.BOOT_RECORD_DTYPE)
+    for r in range(int(replicates)):
+        d = bootstrap_draw(seed, 0, r, np.arange(NB), NB)
+        counts = blk_cnt[:, d, :].astype(np.uint64).sum(axis=1, dtype=np.uint64)
+        slices = blk_len[:, d].sum(axis=1, dtype=np.int64)
+        t = bootstrap_draw(seed, 1, r, np.arange(n_pos), n_pos)
+        accepts = np.array([np.count_nonzero(score64[k, t][:, None] > cutoffs[None, :], axis=0) for k in range(W)], np.uint64).reshape(W, C)
+        usable_r = np.asarray(usable, bool) & (slices > 0)
+        faph, frr = np.full((W, C), np.nan), np.full((W, C), np.nan)
+        for k in np.nonzero(usable_r)[0]:
+            faph[k] = counts[k].astype(np.float64) / (int(slices[k]) * stride * step_s / 3600.0)
+            frr[k] = 1 - accepts[k].astype(np.float64) / n_pos
+        row = col = -1
+        if usable_r.any():
+            chosen, row = select(faph, frr, usable_r, target_faph, windows)
+            col = int(chosen[row]) if row >= 0 else -1
+        rec[r]["sel_row"], rec[r]["sel_cutoff"] = row, col
+        if row >= 0:
+            rec[r]["sel_counts"], rec[r]["sel_slices"], rec[r]["sel_accepts"] = counts[row, col], slices[row], accepts[row, col]
+        if fixed is not None:
+            rec[r]["fixed_counts"], rec[r]["fixed_slices"], rec[r]["fixed_accepts"] = counts[tuple(fixed)], slices[fixed[0]], accepts[tuple(fixed)]
+    return rec
+
+
+def bootstrap_intervals(records, n_positive, stride, step_s, confidence=0.95, fixed=True):
+    """Percentile intervals from the records: for confidence q and the sorted replicate values v[0 .. R - 1],
+    ``lower = v[floor((1 - q) / 2 * R)]``, ``upper = v[ceil((1 + q) / 2 * R) - 1]``.  At the fixed point: ``recall`` (1 - frr)
+    and ``false_accepts_per_hour`` (+inf in a replicate that drew no ambient time); re-selected per replicate:
+    ``recall_at_target`` and ``false_accepts_per_hour_at_target``, a replicate without a point counting as recall 0 and FAPH
+    +inf.  -> dict name -> (lower, upper); the fixed-point entries are None without a fixed point.  These are plain percentile
+    intervals, not bias-corrected."""
+    q = float(confidence)
+    if not 0 < q < 1:
+        raise ValueError("confidence must lie strictly between 0 and 1")
+    R = records.shape[0]
+    # the two products up to 1e-9: in float64 (1 - 0.9) / 2 * 40 falls just short of 2
+    lo = min(max(int(np.floor((1 - q) / 2 * R + 1e-9)), 0), R - 1)
+    hi = min(max(int(np.ceil((1 + q) / 2 * R - 1e-9)) - 1, 0), R - 1)
+
+    def series(prefix, has_point):
+        hours = records[prefix + "_slices"].astype(np.int64) * stride * step_s / 3600.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            faph = np.where(has_point & (hours > 0), records[prefix + "_counts"].astype(np.float64) / hours, np.inf)
+        recall = np.where(has_point, 1 - (1 - records[prefix + "_accepts"].astype(np.float64) / n_positive), 0.0)
+        return [(float(np.sort(v)[lo]), float(np.sort(v)[hi])) for v in (recall, faph)]
+
+    at_target = series("sel", records["sel_row"] >= 0)
+    at_fixed = series("fixed", np.ones(R, bool)) if fixed else [None, None]
+    return dict(recall=at_fixed[0], false_accepts_per_hour=at_fixed[1], recall_at_target=at_target[0],
+                false_accepts_per_hour_at_target=at_target[1])
+
+
+def _bootstrap_fixed(summary, fixed):
+    """the fixed point of a bootstrap: the given (row, cutoff index), else the full data's recommended point, else None"""
+    if fixed is not None:
+        return int(fixed[0]), int(fixed[1])
+    r = summary["recommended"]
+    return (int(r), int(summary["chosen"][r])) if r >= 0 else None
+
+
+def _bootstrap_result(summary, records, fixed, stride, step_s, replicates, seed, block, confidence):
+    out = dict(summary)
+    out["bootstrap"] = dict(records=records, replicates=int(replicates), seed=int(seed), block=int(block), confidence=float(confidence),
+                            fixed_row=fixed[0] if fixed else -1, fixed_cutoff=fixed[1] if fixed else -1,
+                            intervals=bootstrap_intervals(records, summary["n_positive"], stride, step_s, confidence, fixed is not None))
+    return out
+
+
+def operating_bootstrap_host(ambient_probabilities, positive_probabilities, windows=OP_WINDOWS, cutoffs=CUTOFFS, stride=1, step_s=0.02,
+                             ignore_slices_after_accept=25, target_faph=0.5, replicates=1000, seed=0, block=0, confidence=0.95,
+                             fixed=None, skip=None, units=None):
+    """Host restatement of ``StreamingModel.operating_bootstrap`` on given per-track probabilities, by the definitions above:
+    ``operating_summary_host`` plus ``bootstrap`` (records, settings, intervals).  ``units``: those of ``bootstrap_units_host``
+    on the same inputs, when the caller has them already."""
+    summary = operating_summary_host(ambient_probabilities, positive_probabilities, windows, cutoffs, stride, step_s,
+                                     ignore_slices_after_accept, target_faph, skip)
+    if units is None:
+        units = bootstrap_units_host(ambient_probabilities, positive_probabilities, windows, cutoffs, ignore_slices_after_accept, block, skip)
+    fixed = _bootstrap_fixed(summary, fixed)
+    records = bootstrap_records_host(units, summary["usable"], summary["windows"], cutoffs, stride, step_s, target_faph, replicates, seed, fixed)
+    return _bootstrap_result(summary, records, fixed, stride, step_s, replicates, seed, block, confidence)
+
+
 def operating_point_text(grid):
     """``operating_points.txt``: one line per window, then the recommendation"""
     lines = []
@@ -684,32 +884,100 @@ def operating_point_grid(config, folder, sm, data_processor, target_faph, window
     return grid
 
 
+def operating_point_bootstrap(config, folder, sm, data_processor, target_faph, windows=OP_WINDOWS, bootstrap=None, data_set="testing",
+                              ambient_set="testing_ambient", ignore_slices_after_accept=25):
+    """The bootstrap of the operating point of ``operating_point_grid`` (``--operating_point_bootstrap``): the ambient tracks,
+    then the positive tracks of ``data_set``, through ONE native run from the state the stream has - the order and the carried
+    state of the grid's two runs, so the same probabilities -, then ``StreamingModel.operating_bootstrap`` with the settings
+    ``bootstrap`` (``bootstrap_settings``; default ``BOOTSTRAP_DEFAULTS``).  Writes ``operating_point_bootstrap.json`` (settings,
+    the fixed point, the intervals) and ``operating_point_bootstrap.npz`` (the records, field by field) into
+    ``<train_dir>/<folder>`` and returns the dict of ``operating_bootstrap``; the grid's files are not touched."""
+    import json
+    b = dict(BOOTSTRAP_DEFAULTS, **(bootstrap or {}))
+    windows = [int(w) for w in windows]
+    amb, _ = data_processor.track_windows(ambient_set, sm.frames)
+    pos, _ = data_processor.track_windows(data_set, sm.frames, only_label=1.0)
+    offsets = sm.native.run(np.concatenate([amb, pos]))
+    kind = np.concatenate([np.zeros(amb.size, np.int32), np.ones(pos.size, np.int32)])
+    out = sm.operating_bootstrap(offsets, kind, windows, CUTOFFS, ignore_slices_after_accept, int(config["stride"]), config["window_step_ms"] / 1000,
+                                 target_faph, b["replicates"], b["seed"], b["block"], b["confidence"])
+    boot = out[BOOTSTRAP_KEY]
+    r, c = boot["fixed_row"], boot["fixed_cutoff"]
+    path = os.path.join(config["train_dir"], folder)
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, "operating_point_bootstrap.json"), "wt") as fd:
+        json.dump({"replicates": boot["replicates"], "seed": boot["seed"], "block": boot["block"], "confidence": boot["confidence"],
+                   "target_false_accepts_per_hour": float(target_faph),
+                   "probability_cutoff": float(out["cutoffs"][c]) if r >= 0 else None,
+                   "sliding_window_size": int(out["windows"][r]) if r >= 0 else None,
+                   "intervals": {k: (list(v) if v is not None else None) for k, v in boot["intervals"].items()},
+                   "replicates_without_operating_point": int(np.count_nonzero(boot["records"]["sel_row"] < 0)),
+                   "mode": sm.mode, "quantized": isinstance(sm, QuantizedStreamingModel)}, fd, indent=2)
+        fd.write("\n")
+    np.savez(os.path.join(path, "operating_point_bootstrap.npz"), windows=out["windows"], cutoffs=out["cutoffs"],
+             fixed=np.array([r, c], np.int64), **{name: boot["records"][name].copy() for name in native.BOOT_RECORD_DTYPE.names})
+    return out
+
+
 # ---- the training-loop option (train.train; DESIGN 10f)
 VALIDATION_KEY = "streaming_validation"
 VALIDATION_DEFAULTS = dict(windows=[5], mode="stream", ignore_slices_after_accept=25, data_set="validation", ambient_set="validation_ambient",
                            every_evals=1)
 STREAMING_METRICS = ("streaming_recall", "streaming_false_rejection_rate", "streaming_false_accepts_per_hour", "streaming_cutoff",
                      "streaming_window", "streaming_hours", "streaming_positives")
+# ... and, with a ``bootstrap`` sub-mapping, the percentile bounds of ``bootstrap_intervals``: recall and FAPH at the full data's
+# operating point (the cutoff that would ship), recall at the point each replicate re-selects (the metric the loop selects on)
+BOOTSTRAP_KEY = "bootstrap"
+BOOTSTRAP_DEFAULTS = dict(replicates=1000, seed=0, confidence=0.95, block=0)
+STREAMING_BOOTSTRAP_METRICS = ("streaming_recall_lower", "streaming_recall_upper", "streaming_false_accepts_per_hour_lower",
+                               "streaming_false_accepts_per_hour_upper", "streaming_recall_at_target_lower",
+                               "streaming_recall_at_target_upper")
+STREAMING_METRIC_NAMES = STREAMING_METRICS + STREAMING_BOOTSTRAP_METRICS   # what the best-weights rule may name
+
+
+def bootstrap_settings(key, given):
+    """The ``bootstrap`` sub-mapping of ``streaming_validation`` (``replicates``, ``seed``, ``confidence``, ``block``) with its
+    defaults filled in; a ValueError names ``key``, the sub-mapping and the bad key."""
+    name = "%s: %s" % (key, BOOTSTRAP_KEY)
+    if not isinstance(given, dict):
+        raise ValueError("%s must be a mapping (%s)" % (name, ", ".join(BOOTSTRAP_DEFAULTS)))
+    unknown = sorted(set(given) - set(BOOTSTRAP_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError("%s: unknown key(s) %s; known: %s" % (name, ", ".join(map(str, unknown)), ", ".join(BOOTSTRAP_DEFAULTS)))
+    b = dict(BOOTSTRAP_DEFAULTS, **given)
+    integer = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))   # noqa: E731
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))   # noqa: E731
+    bad = [k for k, ok in (("replicates", integer(b["replicates"]) and 1 <= b["replicates"] <= native.BOOT_MAX_REPLICATES),
+                           ("seed", integer(b["seed"]) and 0 <= b["seed"] < 2 ** 64),
+                           ("confidence", number(b["confidence"]) and 0 < b["confidence"] < 1),
+                           ("block", integer(b["block"]) and b["block"] >= 0 and b["block"] % native.BOOT_BLOCK_UNIT == 0)) if not ok]
+    if bad:
+        raise ValueError("%s: %s out of range (replicates an integer in 1..%d; seed an integer in 0 .. 2^64 - 1; confidence strictly "
+                         "between 0 and 1; block 0 or a positive multiple of %d moving-average values)"
+                         % (name, ", ".join(bad), native.BOOT_MAX_REPLICATES, native.BOOT_BLOCK_UNIT))
+    return dict(replicates=int(b["replicates"]), seed=int(b["seed"]), confidence=float(b["confidence"]), block=int(b["block"]))
 
 
 def streaming_validation_config(config, world=1):
     """The ``streaming_validation`` mapping of a training configuration with its defaults filled in, or None without the key.
     Unknown keys, out-of-range values and a world size above 1 are ``ValueError``s that name the key; so is a
-    ``minimization_metric`` / ``maximization_metric`` that names a streaming metric without the key."""
+    ``minimization_metric`` / ``maximization_metric`` that names a streaming metric without the key, or one of
+    ``STREAMING_BOOTSTRAP_METRICS`` without the ``bootstrap`` sub-mapping.  The normalised mapping has a ``bootstrap`` entry
+    (``bootstrap_settings``) only when the configuration gives one."""
     key = VALIDATION_KEY
     given = config.get(key)
     if given is None:
-        named = [config.get(k) for k in ("minimization_metric", "maximization_metric") if config.get(k) in STREAMING_METRICS]
+        named = [config.get(k) for k in ("minimization_metric", "maximization_metric") if config.get(k) in STREAMING_METRIC_NAMES]
         if named:
             raise ValueError("%s: the metric %s needs the %s mapping (target_faph, ...)" % (key, ", ".join(named), key))
         return None
     if not isinstance(given, dict):
         raise ValueError("%s must be a mapping (target_faph, windows, ...)" % key)
     from .quantize import LOOP_DEFAULTS, loop_settings
-    unknown = sorted(set(given) - set(VALIDATION_DEFAULTS) - set(LOOP_DEFAULTS) - {"target_faph"}, key=str)
+    unknown = sorted(set(given) - set(VALIDATION_DEFAULTS) - set(LOOP_DEFAULTS) - {"target_faph", BOOTSTRAP_KEY}, key=str)
     if unknown:
         raise ValueError("%s: unknown key(s) %s; known: target_faph, %s" % (key, ", ".join(map(str, unknown)),
-                                                                            ", ".join(list(VALIDATION_DEFAULTS) + list(LOOP_DEFAULTS))))
+                                                                            ", ".join(list(VALIDATION_DEFAULTS) + list(LOOP_DEFAULTS) + [BOOTSTRAP_KEY])))
     if "target_faph" not in given:
         raise ValueError("%s: target_faph is required" % key)
     v = loop_settings(key, dict(VALIDATION_DEFAULTS, **given))
@@ -731,6 +999,12 @@ def streaming_validation_config(config, world=1):
         raise ValueError("%s: %s out of range (target_faph a number; ignore_slices_after_accept >= 0; 1..%d windows of 1..%d; every_evals >= 1; "
                          "mode stream or non_stream; data_set, ambient_set names of modes)"
                          % (key, ", ".join(bad), native.OP_MAX_WINDOWS, native.OP_MAX_WINDOW))
+    if BOOTSTRAP_KEY in given:
+        v[BOOTSTRAP_KEY] = bootstrap_settings(key, given[BOOTSTRAP_KEY])
+    else:
+        named = [config.get(k) for k in ("minimization_metric", "maximization_metric") if config.get(k) in STREAMING_BOOTSTRAP_METRICS]
+        if named:
+            raise ValueError("%s: the metric %s needs the %s sub-mapping (replicates, seed, confidence, block)" % (key, ", ".join(named), BOOTSTRAP_KEY))
     if int(world) > 1:
         raise ValueError("%s is not available under data parallelism (world size %d): a rank holds its shard of the validation "
                          "stores only" % (key, int(world)))
@@ -753,6 +1027,12 @@ def streaming_metrics(summary):
                    streaming_false_accepts_per_hour=float(min(summary["faph"][k, -1] for k in usable)),
                    streaming_cutoff=float("nan"), streaming_window=-1)
     out.update(streaming_hours=float(summary["hours"][r if r >= 0 else usable[0]]), streaming_positives=int(summary["n_positive"]))
+    if BOOTSTRAP_KEY in summary:   # ``operating_bootstrap``: the bounds.  Without a recommended point there is no fixed point: the
+        # bounds at it are the point values above (recall 0, the fallback FAPH), an interval without width
+        iv = summary[BOOTSTRAP_KEY]["intervals"]
+        recall = iv["recall"] or (out["streaming_recall"],) * 2
+        faph = iv["false_accepts_per_hour"] or (out["streaming_false_accepts_per_hour"],) * 2
+        out.update(zip(STREAMING_BOOTSTRAP_METRICS, (*recall, *faph, *iv["recall_at_target"])))
     return out
 
 
@@ -794,6 +1074,14 @@ class StreamingValidation:
             "%.3f ambient hours, %d positives", step, metrics["streaming_recall"] * 100, metrics["streaming_false_accepts_per_hour"],
             self.v["target_faph"], metrics["streaming_window"], metrics["streaming_cutoff"], metrics["streaming_hours"],
             metrics["streaming_positives"])
+        if self.v.get(BOOTSTRAP_KEY):
+            b = self.v[BOOTSTRAP_KEY]
+            logging.getLogger("microwakeword_amd.train").info(
+                "Step %d (streaming, bootstrap): %g%% percentile intervals of %d replicates (block %d): recall [%.2f%%, %.2f%%] and [%.3f, %.3f] "
+                "false accepts per hour at that cutoff; recall at the target, re-selected per replicate, [%.2f%%, %.2f%%]", step,
+                b["confidence"] * 100, b["replicates"], b["block"], metrics["streaming_recall_lower"] * 100, metrics["streaming_recall_upper"] * 100,
+                metrics["streaming_false_accepts_per_hour_lower"], metrics["streaming_false_accepts_per_hour_upper"],
+                metrics["streaming_recall_at_target_lower"] * 100, metrics["streaming_recall_at_target_upper"] * 100)
         return metrics
 
 
@@ -826,8 +1114,14 @@ def validate_streaming(config, data_processor, model, state):
     offsets = sm.native.run(np.concatenate([amb, pos]))
     kind = np.concatenate([np.zeros(amb.size, np.int32), np.ones(pos.size, np.int32)])
     try:
-        summary = sm.operating_summary(offsets, kind, v["windows"], CUTOFFS, v["ignore_slices_after_accept"], sm.stride,
-                                       config["window_step_ms"] / 1000, v["target_faph"])
+        if v.get(BOOTSTRAP_KEY):   # the summary plus the bootstrap of its operating point: the draws are a counter hash of the seed
+            b = v[BOOTSTRAP_KEY]
+            summary = sm.operating_bootstrap(offsets, kind, v["windows"], CUTOFFS, v["ignore_slices_after_accept"], sm.stride,
+                                             config["window_step_ms"] / 1000, v["target_faph"], b["replicates"], b["seed"], b["block"],
+                                             b["confidence"])
+        else:
+            summary = sm.operating_summary(offsets, kind, v["windows"], CUTOFFS, v["ignore_slices_after_accept"], sm.stride,
+                                           config["window_step_ms"] / 1000, v["target_faph"])
     except ValueError as e:
         raise ValueError("%s: %s" % (VALIDATION_KEY, e)) from None
     return streaming_metrics(summary), summary

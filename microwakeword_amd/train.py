@@ -204,7 +204,7 @@ def train(model, config, data_processor, verbose=True):
     chief = rank == 0
     from .mining import MiningRounds, mining_config
     mining = mining_config(config, world)   # refusals come before the first step
-    from .streaming import STREAMING_METRICS, StreamingValidation, streaming_validation_config
+    from .streaming import STREAMING_METRIC_NAMES, StreamingValidation, streaming_validation_config
     streaming_settings = streaming_validation_config(config, world)   # likewise
     from .quantize import check_shared_calibration
     check_shared_calibration(streaming_settings, mining)   # both quantized: one calibration set, one calibration per boundary
@@ -251,7 +251,7 @@ def train(model, config, data_processor, verbose=True):
         if chief:
             streamer.writer = _JsonSummary(os.path.join(config["summaries_dir"], "validation_streaming"), "scalars")
         streamer.validate(0)
-    streaming_named = [k for k in ("minimization_metric", "maximization_metric") if config.get(k) in STREAMING_METRICS]
+    streaming_named = [k for k in ("minimization_metric", "maximization_metric") if config.get(k) in STREAMING_METRIC_NAMES]
 
     dp = None
     if world > 1 or config.get("data_parallel"):

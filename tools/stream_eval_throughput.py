@@ -31,6 +31,11 @@ positives through ``StreamingModel.predict_tracks`` + the metrics kernel, agains
         # adds: mww_stream_calibrate over 500 windows of T - 1 rows of the resident ambient store against mww_stream_calibrate_host
         # on the host rows of the same windows (the calibration of the int8 model inside the training loop); the
         # ranges are compared first, then medians of --detections_reps calls each, from zeroed rings
+    python tools/stream_eval_throughput.py --hours 20 --bootstrap 1000 --bootstrap_out profiles/stream_operating_bootstrap_throughput.txt
+        # adds, on the probabilities of the ambient tracks followed by the positives: ONE StreamingModel.operating_bootstrap call
+        # (the summary, mww_stream_operating_bootstrap with R replicates, the intervals) at block 0 and block 30720 against
+        # operating_summary alone; the records are first compared with streaming.operating_bootstrap_host on a reduced set
+        # (the restatement walks every moving-average value in Python), which is also where the restatement is timed
 """
 import argparse
 import json
@@ -79,6 +84,9 @@ def main():
                     help="also time one mww_stream_operating_summary call (10 windows x 101 cutoffs) against mww_stream_operating_points + the host grid")
     ap.add_argument("--summary_out", default=None, help="append the summary leg's times, read-back and scratch sizes to this text file")
     ap.add_argument("--summary_target", type=float, default=0.5, help="target FAPH of the summary leg's selection")
+    ap.add_argument("--bootstrap", type=int, default=None, metavar="R",
+                    help="also time one StreamingModel.operating_bootstrap call with R replicates (block 0 and 30720) against operating_summary alone")
+    ap.add_argument("--bootstrap_out", default=None, help="append the bootstrap leg's times and read-back sizes to this text file")
     ap.add_argument("--calibrate", action="store_true",
                     help="also time mww_stream_calibrate over 500 resident windows against mww_stream_calibrate_host on their host rows")
     ap.add_argument("--calibrate_out", default=None, help="append the calibration leg's times to this text file")
@@ -201,6 +209,11 @@ def main():
         if a.summary_out:
             with open(a.summary_out, "at") as fd:
                 fd.write(summary_text(rec))
+    if a.bootstrap is not None:
+        rec["bootstrap"] = bootstrap_leg(sm, amb_win, pos_win, a.bootstrap, a.detections_reps, a.summary_target)
+        if a.bootstrap_out:
+            with open(a.bootstrap_out, "at") as fd:
+                fd.write(bootstrap_text(rec))
     if a.calibrate:
         rec["calibrate"] = calibrate_leg(model, a.model, amb, T, a.detections_reps)
         if a.calibrate_out:
@@ -310,6 +323,96 @@ def summary_leg(sm, amb_win, pos_win, reps, target, cooldown=25, step_s=0.02):
             "chain_table_bytes": tables, "summary_table_bytes": tables_ambient,
             "chain_scratch_bytes": W * C * 8 + W * n * 12 + W * n * C * 8 + W * n_seg * 4,
             "summary_scratch_bytes": W * C * 16 + W * 24 + 16 + W * n_amb * C * 8 + W * n_blk * (C + 1) * 4 + W * n_seg * 4}
+
+
+def bootstrap_leg(sm, amb_win, pos_win, replicates, reps, target, cooldown=25, step_s=0.02, blocks=(0, 30720), check=(2, 40000, 200, 64)):
+    """One session.  First the check, on a reduced set - `check` = (ambient tracks, rows kept of each, positives, replicates):
+    the restatement walks every moving-average value in Python, some 10 us per value and window -: the dict of
+    StreamingModel.operating_bootstrap against streaming.operating_bootstrap_host on the probabilities read back, records and
+    intervals byte for byte, at each block; the restatement's wall time there is recorded next to the device call's.  Then, on
+    the probabilities of all ambient tracks followed by the positives (one native run): the median wall time of `reps` calls
+    (after one warm-up call each) of operating_summary alone and of operating_bootstrap with `replicates` replicates at each
+    block - the summary, mww_stream_operating_bootstrap, the intervals; host work included."""
+    windows, cut = streaming.OP_WINDOWS, streaming.CUTOFFS
+
+    def median_ms(fn):
+        fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return round(float(np.median(ts)) * 1e3, 3)
+
+    c_amb, c_rows, c_pos, c_rep = check
+    small = amb_win[:c_amb].copy()
+    small["copy_rows"] = np.minimum(small["copy_rows"], c_rows)
+    sm.reset()
+    off = sm.native.run(np.concatenate([small, pos_win[:c_pos]]))
+    kind = np.concatenate([np.zeros(small.size, np.int32), np.ones(min(c_pos, pos_win.size), np.int32)])
+    p = sm.read_probabilities()
+    tracks = [p[off[t]:off[t + 1]] for t in range(off.size - 1)]
+    out = {"replicates": int(replicates), "reps": reps, "windows": list(windows), "cooldown": cooldown, "target_faph": target,
+           "record_bytes": native.BOOT_RECORD_DTYPE.itemsize,
+           "check": {"ambient_tracks": int(small.size), "positives": int(kind.sum()), "probabilities": int(off[-1]), "replicates": c_rep}}
+    for block in blocks:
+        t0 = time.perf_counter()
+        want = streaming.operating_bootstrap_host(tracks[:small.size], tracks[small.size:], windows, cut, sm.stride, step_s, cooldown, target,
+                                                  c_rep, 1, block)
+        host_s = time.perf_counter() - t0
+        got = sm.operating_bootstrap(off, kind, windows, cut, cooldown, sm.stride, step_s, target, c_rep, 1, block)
+        assert got["bootstrap"]["records"].tobytes() == want["bootstrap"]["records"].tobytes(), block
+        assert got["bootstrap"]["intervals"] == want["bootstrap"]["intervals"] and got["recommended"] == want["recommended"], block
+        for k in ("counts", "accepts", "hours", "faph", "frr", "chosen"):
+            assert np.asarray(got[k]).tobytes() == np.asarray(want[k]).tobytes(), (block, k)
+        out["check"]["block_%d" % block] = {"host_restatement_s": round(host_s, 3),
+                                            "device_ms": median_ms(lambda: sm.operating_bootstrap(off, kind, windows, cut, cooldown, sm.stride, step_s,
+                                                                                                  target, c_rep, 1, block))}
+    n_amb, n_pos = int(amb_win.size), int(pos_win.size)
+    sm.reset()
+    off = sm.native.run(np.concatenate([amb_win, pos_win]))
+    kind = np.concatenate([np.zeros(n_amb, np.int32), np.ones(n_pos, np.int32)])
+    W, C = len(windows), cut.size
+    out.update(probabilities=int(off[-1]), ambient_tracks=n_amb, positives=n_pos, read_back_bytes=replicates * native.BOOT_RECORD_DTYPE.itemsize,
+               summary_ms=median_ms(lambda: sm.operating_summary(off, kind, windows, cut, cooldown, sm.stride, step_s, target)),
+               summary_bytes=W * C * 16 + W * 24 + 16)
+    for block in blocks:
+        g = sm.operating_bootstrap(off, kind, windows, cut, cooldown, sm.stride, step_s, target, replicates, 1, block)
+        again = sm.operating_bootstrap(off, kind, windows, cut, cooldown, sm.stride, step_s, target, replicates, 1, block)
+        assert g["bootstrap"]["records"].tobytes() == again["bootstrap"]["records"].tobytes()
+        n_blk = int(sum(-(-int(n) // block) if block else 1 for n in np.diff(off)[:n_amb]))
+        out["block_%d" % block] = {
+            "blocks": n_blk, "scratch_bytes": W * n_blk * C * 4 + W * n_blk * 8 + W * n_pos,
+            "bootstrap_ms": median_ms(lambda: sm.operating_bootstrap(off, kind, windows, cut, cooldown, sm.stride, step_s, target, replicates, 1, block)),
+            "native_call_ms": median_ms(lambda: sm.native.operating_bootstrap(off, kind, windows, cut, cooldown, cooldown, sm.stride, step_s, target,
+                                                                              replicates, 1, block, None)),
+            "intervals": g["bootstrap"]["intervals"], "replicates_without_point": int(np.count_nonzero(g["bootstrap"]["records"]["sel_row"] < 0))}
+    return out
+
+
+def bootstrap_text(rec):
+    d = rec["bootstrap"]
+    c = d["check"]
+    lines = ["StreamingModel.operating_bootstrap against operating_summary alone, one session (tools/stream_eval_throughput.py --bootstrap %d --positives %d)"
+             % (d["replicates"], d["positives"]),
+             "library: %s" % rec["library"], "model: %s%s" % (rec["model"], ", int8" if rec.get("quantized") else ""),
+             "check first, on %d probabilities (%d ambient tracks + %d positives), %d replicates: records, intervals, summary byte-identical to "
+             "streaming.operating_bootstrap_host" % (c["probabilities"], c["ambient_tracks"], c["positives"], c["replicates"])]
+    for name in sorted(k for k in c if k.startswith("block_")):
+        lines.append("  %-12s the restatement %9.3f s (one run), the device call %9.3f ms" % (name.replace("_", " ") + ":", c[name]["host_restatement_s"], c[name]["device_ms"]))
+    lines += ["%d probabilities: %d ambient tracks + %d positives, windows %s x 101 cutoffs, cooldown %d, target %g FAPH, %d replicates; median wall "
+              "time of %d calls each after a warm-up call, host work included"
+              % (d["probabilities"], d["ambient_tracks"], d["positives"], ",".join(str(w) for w in d["windows"]), d["cooldown"], d["target_faph"],
+                 d["replicates"], d["reps"]),
+              "  operating_summary alone:                          %10.3f ms, %9d bytes read back" % (d["summary_ms"], d["summary_bytes"])]
+    for name in sorted((k for k in d if k.startswith("block_")), key=lambda k: int(k.split("_")[1])):
+        b = d[name]
+        lines.append("  operating_bootstrap, %-12s %5d blocks:   %10.3f ms (mww_stream_operating_bootstrap alone %.3f ms), %9d + %d bytes read back, "
+                     "%d bytes of block tables" % (name.replace("_", " ") + ",", b["blocks"], b["bootstrap_ms"], b["native_call_ms"], d["summary_bytes"],
+                                                   d["read_back_bytes"], b["scratch_bytes"]))
+        lines.append("      intervals %s; %d replicates without a point" % (json.dumps(b["intervals"]), b["replicates_without_point"]))
+    lines.append("")
+    return "".join(line + "\n" for line in lines)
 
 
 def summary_text(rec):

@@ -1,12 +1,13 @@
 """Throughput of the PRODUCT train loop (microwakeword_amd.train.train on the package's own Model / FeatureHandler) on the
 synthetic benchmark stores, next to bench.py's figure for the same step: what a user of the CLI gets.
-usage: python tools/train_loop_throughput.py [steps] [batch] [mixednet|inception] [streaming_validation] [quantized]
+usage: python tools/train_loop_throughput.py [steps] [batch] [mixednet|inception] [streaming_validation] [quantized] [bootstrap]
 With the fourth argument the configuration carries ``streaming_validation: {target_faph: 0.5}`` and the wall time of
 the evaluation boundary is printed in its parts: validate_nonstreaming and each streaming validation (the dry one first).
 With the fifth the session runs the loop twice, five boundaries each: with the float mapping, then with ``quantized: true``, whose
 validation is printed in ITS parts too: LoopQuantizer.calibrate (mww_stream_calibrate over the 500 windows), quantize_weights (the
 host quantization), QuantizedStreamingModel (the upload of the int8 parameters); the rest of validate_streaming is the run and
-the summary."""
+the summary.  With ``bootstrap`` as the last argument the mapping also carries ``bootstrap: {replicates: 1000}``: the
+summary becomes ``operating_bootstrap``, inside validate_streaming."""
 import random
 import sys
 import tempfile
@@ -24,6 +25,7 @@ B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 kind = sys.argv[3] if len(sys.argv) > 3 else "mixednet"
 with_streaming = len(sys.argv) > 4 and sys.argv[4] == "streaming_validation"
 with_quantized = with_streaming and len(sys.argv) > 5 and sys.argv[5] == "quantized"
+with_bootstrap = with_streaming and sys.argv[-1] == "bootstrap"
 T = 194
 timed = {}
 
@@ -54,7 +56,7 @@ for verbose in ((False, False) if with_quantized else (False, True)):
                negative_class_weight=[1.0], eval_step_interval=steps, target_minimization=0.9, minimization_metric=None,
                maximization_metric="accuracy")
     if with_streaming:
-        cfg["streaming_validation"] = dict(target_faph=0.5)
+        cfg["streaming_validation"] = dict(target_faph=0.5, **(dict(bootstrap=dict(replicates=1000)) if with_bootstrap else {}))
     if with_quantized:
         cfg["eval_step_interval"] = max(1, steps // 5)
         cfg["streaming_validation"]["quantized"] = bool(timed)   # the second run of the session
