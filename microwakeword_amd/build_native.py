@@ -3,7 +3,9 @@
 The library is the translation units of ``UNITS`` (``mww_lib.hip``: the C ABI and the core of a context; ``block_engine.hip`` and
 ``graph_engine.hip``: the host side of the two engines; the
 block-kernel families of ``block_launch.hip.h``, the largest split by width; the conv/BN graph kernels of
-``graph_launch.hip.h``; the weight fake-quantization, weight-averaging, BatchNorm re-estimation and gradient-norm (sharpness-aware step, clipping) kernels; the streaming units; the sampler) compiled in parallel and linked once.  Objects are cached under ``build/obj`` keyed by the sha256 of the flags and of
+``graph_launch.hip.h``; one unit per step feature, kernels and host code together - weight fake-quantization (``tu_qat.hip``), weight
+averaging (``tu_ema.hip``), BatchNorm re-estimation (``tu_bnre.hip``), sharpness-aware steps and clipping (``tu_sam.hip``); the host-only
+exchange binding ``tu_exchange.hip``; the streaming units; the sampler) compiled in parallel and linked once.  Objects are cached under ``build/obj`` keyed by the sha256 of the flags and of
 every file the unit includes, so editing one kernel header recompiles only the units that see it.
 
 The sha256 of the whole source set (``csrc/*`` + ``include/mww.h``) is compiled into the library
@@ -25,7 +27,7 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(ROOT, "microwakeword_amd", "libmww_hip.so")
 OBJDIR = os.path.join(ROOT, "build", "obj")
 UNITS = ("version.cpp", "mww_lib.hip", "block_engine.hip", "tu_bwd_first.hip", "tu_bwd64.hip", "tu_bwd48.hip", "tu_bwd32.hip", "tu_fwd.hip", "tu_bwdw.hip", "tu_bwd.hip",
-         "tu_graph.hip", "graph_engine.hip", "tu_qat.hip", "tu_ema.hip", "tu_bnre.hip", "tu_sam.hip", "sampler.cpp", "tu_stream.hip", "tu_stream_q8.hip", "tu_stream_graph.hip", "tu_stream_graph_q8.hip", "tu_stream_detect.hip", "tu_stream_mine.hip", "tu_stream_oppoints.hip", "tu_stream_bootstrap.hip", "tu_stream_calibrate.hip")   # version.cpp first: the one unit that carries the stamp
+         "tu_graph.hip", "graph_engine.hip", "tu_qat.hip", "tu_ema.hip", "tu_bnre.hip", "tu_sam.hip", "tu_exchange.hip", "sampler.cpp", "tu_stream.hip", "tu_stream_q8.hip", "tu_stream_graph.hip", "tu_stream_graph_q8.hip", "tu_stream_detect.hip", "tu_stream_mine.hip", "tu_stream_oppoints.hip", "tu_stream_bootstrap.hip", "tu_stream_calibrate.hip")   # version.cpp first: the one unit that carries the stamp
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-pthread")
 EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
 EMU_CLANG = "/opt/rocm/lib/llvm/bin/clang++"

@@ -52,7 +52,7 @@ float* bn_slot(Layer& l, int i) { return l.bn + (size_t)i * l.cout; }
 // 1 / (the elements behind one channel's statistics in a batch of B windows)
 float b_inv_n(const Layer& l, int B) { return 1.0f / ((float)B * (float)l.tout); }
 // statistics hand-over instead of finalize launches ("bn_inline"; sync-BN exchanges the sums in between)
-bool b_handover(const mww_ctx* c) { return c->bn_inline && !(c->hook && c->sync_bn); }
+bool b_handover(const mww_ctx* c) { return c->bn_inline && !(c->xch.hook && c->xch.sync_bn); }
 
 struct BlockModel : Model {
   mww_mixednet_desc d;
@@ -256,7 +256,7 @@ int BlockModel::enqueue_forward(mww_ctx* c, int B, bool training, bool update_mo
     c->tail_metrics = metrics;
     return MWW_OK;
   }
-  if (loss && !(c->hook && c->sync_bn)) {
+  if (loss && !(c->xch.hook && c->xch.sync_bn)) {
     // train step: the dense-weight gradient and the metric update share the launch of the last block's
     // BN-backward finalize (head_tail_kernel, first thing in enqueue_backward)
     c->tail_pending = true;
@@ -324,7 +324,7 @@ int BlockModel::enqueue_backward(mww_ctx* c, int B, bool fuse_adam) {
   // all-reduce runs next to the remaining backward kernels.  Needs the statistics hand-over (the BN
   // gamma / beta gradients of a block are then written by that block's own backward kernel).
   const int split = nb >= 3 ? nb - 2 : 0;
-  const bool bucketed = fuse_adam && c->hook && c->reduce_grads && !c->sync_bn && inl && c->tail_in_reduce && c->grad_buckets == 2 && split > 0;
+  const bool bucketed = fuse_adam && c->xch.hook && c->xch.reduce_grads && !c->xch.sync_bn && inl && c->tail_in_reduce && c->xch.buckets == 2 && split > 0;
   for (int i = nb - 1; i >= 0; --i) {
     Layer& l = L[i];
     const bool last = (i == nb - 1);

@@ -1,6 +1,7 @@
 // What the units of libmww_hip.so's training side share: the core of a context (mww_ctx), the interface of its model part (Model:
 // block_engine.hip, graph_engine.hip), the tensor record of both, error reporting, profiling brackets and the helpers of mww_lib.hip
-// that the engines call.  Internal: the ABI is include/mww.h.
+// that the engines and the step features call.  A step feature's state and interface are declared in its own header
+// (kernels_qat / ema / bnre / sam.hip.h) and its host code sits with its kernels (tu_*.hip).  Internal: the ABI is include/mww.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,11 +13,15 @@
 #include "../../include/mww.h"
 #include "kernels_bwd.hip.h"    // GradReduceArgs, XGather
 #include "kernels_data.hip.h"   // AssembleArgs
+#include "kernels_bnre.hip.h"   // the step features: BnreState,
+#include "kernels_ema.hip.h"    // EmaState,
+#include "kernels_qat.hip.h"    // QatState,
+#include "kernels_sam.hip.h"    // SharpState
 
 namespace mww {
 
 struct MetricState;   // kernels_head.hip.h
-struct BnreRow;       // kernels_bnre.hip.h
+struct RcclState;     // tu_exchange.hip
 
 int fail(int code, const std::string& msg);   // sets mww_last_error(), returns code
 
@@ -79,17 +84,19 @@ struct ProfileEntry {
   hipEvent_t a, b;
 };
 
-// RCCL bound at run time (dlopen: the library loads on hosts without RCCL and shares the copy a framework in the same
-// process has already loaded); only the five entry points the gradient / statistics exchange needs
-struct RcclApi {
-  void* so = nullptr;
-  struct UniqueId { char internal[128]; };
-  int (*GetUniqueId)(UniqueId*) = nullptr;
-  int (*CommInitRank)(void**, int, UniqueId, int) = nullptr;
-  int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*CommDestroy)(void*) = nullptr;
-  int (*CommCount)(void*, int*) = nullptr;   // optional: mww_allreduce_world
-  const char* (*GetErrorString)(int) = nullptr;
+// data-parallel exchange (tu_exchange.hip installs it: mww_set_allreduce_hook, mww_allreduce_init; the step of mww_lib.hip and
+// the engines read it)
+struct Exchange {
+  mww_allreduce_fn hook = nullptr;
+  void* user = nullptr;
+  int world = 1;
+  bool sync_bn = false, reduce_grads = false;
+  RcclState* rccl = nullptr;        // mww_allreduce_init: the library's own communicator + side stream (the hook then points at it)
+  float* sync_buf = nullptr;        // [layers][fwd 2C | bwd 2C] statistics sums being exchanged
+  std::vector<int64_t> sync_off;    // offset of layer i in sync_buf
+  bool pending = false;             // a deferred bucket exchange is in flight (data-parallel step)
+  int buckets = 1;                  // data-parallel step: gradient exchanged in this many buckets ("grad_buckets" option; 2 = first
+                                    // bucket overlapped with the backward tail - slower at W = 1, unmeasured at W > 1, so not the default)
 };
 
 constexpr int kRing = 8;
@@ -152,54 +159,15 @@ struct mww_ctx {
   int64_t o_dense_w = 0, o_dense_b = 0;
   int t_last = 0, c_last = 0, dwd_stride = 0;
   int metric_launches = 0;   // launches of the step being enqueued that carry the metric role (kernels_head.hip.h MetricState: one writer)
-  // data-parallel exchange hook (mww_set_allreduce_hook)
-  mww_allreduce_fn hook = nullptr;
-  void* hook_user = nullptr;
-  int world = 1;
-  bool sync_bn = false, reduce_grads = false;
-  struct RcclState* rccl = nullptr;  // mww_allreduce_init: the library's own communicator + side stream (the hook then points at it)
-  float* sync_buf = nullptr;        // [layers][fwd 2C | bwd 2C] statistics sums being exchanged
-  std::vector<int64_t> sync_off;    // offset of layer i in sync_buf
   float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr, *mask = nullptr;
-  // "weight_qat" option (kernels_qat.hip.h): the forward / backward launches read `shadow`, the master fake-quantized per weight
-  // channel, refreshed at the start of every call that runs a forward; Adam, set / get_params and checkpoints keep the master.
-  // The map (mww_set_weight_qat) is device-resident: CSR channels + the list of parameters outside every channel.
-  bool weight_qat = false;
-  const float* shadow_held = nullptr;   // inside mww_evaluate_windows: the vector the first batch refreshed the shadow from (it cannot
-                                        // change between the batches); a refresh from any other source is not skipped
-  float* shadow = nullptr;
-  int *qat_start = nullptr, *qat_elem = nullptr, *qat_copy = nullptr;
-  int qat_channels = 0, qat_n_copy = 0;
-  // weight averaging (mww_set_weight_ema, kernels_ema.hip.h): `ema` follows the master by one launch behind every
-  // `ema_every`-th Adam update; with the "ema_forward" option a non-training forward reads it (`ema_src`, set for the
-  // duration of such a call) once it holds a first update
-  float* ema = nullptr;
-  double ema_decay = 0.0;
-  int64_t ema_every = 1, ema_updates = 0;
-  bool ema_forward = false, ema_src = false;
-  // BatchNorm re-estimation for the average (mww_bn_reestimate_*, kernels_bnre.hip.h): `ema_bn` = the batch statistics of
-  // training-mode forwards at the average, averaged over a pass; while `ema_bn_valid`, a non-training forward that stands on the
-  // average folds them instead of the master's moving statistics (eval_bn_state).  Allocated by the first pass.
-  float* ema_bn = nullptr;
-  bool ema_bn_valid = false;
-  double* bnre_acc = nullptr;             // [S] float64 sums of the pass in progress
-  int64_t bnre_batches = -1;              // batches collected by the pass in progress; -1: none is open
-  mww::BnreRow* bnre_table = nullptr;     // device-resident table of the collect launch
-  int bnre_table_rows = 0;
-  std::vector<char> bnre_table_host;      // what it holds (uploaded again only when a row changes)
-  // sharpness-aware steps and global-norm clipping (mww_set_sharpness_aware / mww_set_grad_clip, kernels_sam.hip.h): an
-  // applying train step of a context that has either takes its gradient with a separate Adam launch; `sam_w` = the bit copy of
-  // the master a sharpness-aware step restores from, `norm_scalars` = {S of the first pass's gradient, its perturbation scale,
-  // S of the gradient Adam consumes, its clipping factor}
-  double sam_rho = 0.0, clip_norm = 0.0;
-  float* sam_w = nullptr;
-  double* norm_scalars = nullptr;
-  bool norms_valid = false;   // a step has written norm_scalars (mww_get_grad_norms)
+  // the step features, each with its state (the header named), host code and kernels in a unit of its own
+  mww::QatState qat;       // kernels_qat.hip.h
+  mww::EmaState ema;       // kernels_ema.hip.h
+  mww::BnreState bnre;     // kernels_bnre.hip.h
+  mww::SharpState sharp;   // kernels_sam.hip.h
+  mww::Exchange xch;
   unsigned char* direct = nullptr;
   std::vector<unsigned char> direct_host;   // host copy: which parameters' gradients are written directly by a folding kernel
-  bool exchange_pending = false;            // a deferred bucket exchange is in flight (data-parallel step)
-  int grad_buckets = 1;                     // data-parallel step: gradient exchanged in this many buckets ("grad_buckets" option; 2 = first
-                                            // bucket overlapped with the backward tail - slower at W = 1, unmeasured at W > 1, so not the default)
   float* bn_state = nullptr;
   float *x = nullptr, *y = nullptr, *sw = nullptr, *z = nullptr, *prob = nullptr, *dz = nullptr, *loss_part = nullptr;
   float* dwd_part = nullptr;
@@ -305,12 +273,12 @@ inline StatAcc fwd_rows(const mww_ctx* c, const Tensor& t) { return StatAcc{t.fa
 inline StatAcc bwd_rows(const mww_ctx* c, const Tensor& t) { return StatAcc{t.gacc[c->gpar], t.gacc[c->gpar ^ 1]}; }
 
 // the fp32 vector this call's forward stands on: the master, or the weight average in a non-training call under "ema_forward"
-inline float* fwd_source(const mww_ctx* c) { return c->ema_src ? c->ema : c->params; }
+inline float* fwd_source(const mww_ctx* c) { return c->ema.src ? c->ema.vec : c->params; }
 // the parameter vector the forward / backward launches read: that vector, or its fake-quantized shadow ("weight_qat")
-inline float* fwd_params(const mww_ctx* c) { return c->weight_qat ? c->shadow : fwd_source(c); }
+inline float* fwd_params(const mww_ctx* c) { return c->qat.enabled ? c->qat.shadow : fwd_source(c); }
 // the moving statistics an eval-mode fold reads: the master's, or - in a call that stands on the average - the average's own
 // re-estimated ones while they are valid
-inline float* eval_bn_state(const mww_ctx* c) { return (c->ema_src && c->ema_bn_valid) ? c->ema_bn : c->bn_state; }
+inline float* eval_bn_state(const mww_ctx* c) { return (c->ema.src && c->bnre.valid) ? c->bnre.ema_bn : c->bn_state; }
 
 // ---- mww_lib.hip
 template <typename T>
@@ -320,6 +288,15 @@ int dev_alloc(T** p, size_t n) {
   return MWW_OK;
 }
 int create_context(Model* m, int frames, int max_batch, int device, void* stream, mww_ctx** out);   // takes the model over, also when it fails
+// what the step features' units need of the core: the Adam launch, the hipGraph cache, synchronous copies on the context's
+// stream, and the opening (batch_ready) and closing (join_side, mail_commit) of a call that runs a forward
+int enqueue_adam(mww_ctx* c);
+void drop_graphs(mww_ctx* c);
+int copy_in(mww_ctx* c, void* dst, const void* src, size_t bytes);
+int copy_out(mww_ctx* c, void* dst, const void* src, size_t bytes);
+int batch_ready(mww_ctx* c);
+int join_side(mww_ctx* c);
+int mail_commit(mww_ctx* c);
 const float* mail_hyper(mww_ctx* c);
 int materialise_x(mww_ctx* c);   // descriptor-only batch -> x, for readers outside the first block's kernels
 XGather x_gather(mww_ctx* c);
@@ -329,8 +306,6 @@ struct StatSource { const float* part; int G; float inv_n; float dscale; };
 int exchange_stats(mww_ctx* c, Launcher& lp, const char* what, int layer, const float* part, int G, int C, int bwd, float local_inv_n, StatSource* out);
 // what exchange_stats handed the forward finalize of `layer` in the forward just enqueued (nothing is launched or exchanged)
 StatSource forward_stat_source(const mww_ctx* c, int layer, const float* part, int G, int C, float local_inv_n);
-// BN re-estimation: block0 / nblocks of the rows are filled in, the device table is brought up to date, the collect is launched
-int enqueue_bnre_collect(mww_ctx* c, std::vector<BnreRow>& rows);
 int enqueue_grad_assembly(mww_ctx* c, int B, GradReduceArgs& ga, bool fuse_adam, int64_t lo = 0, int64_t hi = -1, bool last_range = true);
 // the block engine's classifier head and the launch that opens its backward pass (BN_L's backward finalize + dense gradient +
 // metrics): their kernels share kernels_head.hip.h / kernels_tail.hip.h with the core's own, which one unit alone can include

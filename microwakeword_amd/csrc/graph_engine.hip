@@ -77,7 +77,7 @@ struct GraphModel : Model {
   // the statistics hand-over instead of finalize launches (kernels_graph.hip.h): the graph and its options allow it / this
   // context runs it (sync-BN has to exchange the sums in between)
   bool handover_possible() const { return g_inline_ok && !profile_split; }
-  bool handover(const mww_ctx* c) const { return c->bn_inline && !(c->hook && c->sync_bn) && handover_possible(); }
+  bool handover(const mww_ctx* c) const { return c->bn_inline && !(c->xch.hook && c->xch.sync_bn) && handover_possible(); }
   unsigned replay_key(bool* handover) const override {
     *handover = handover_possible();
     return (g_role_split ? 1 : 0) | (grid_g_auto ? 2 : 0) | (frame_chunks << 2) | (g_cap_fwd << 5) | (g_cap_bwd << 9) | (g_dgrad_share << 13);
@@ -271,7 +271,7 @@ struct GWalk {
   GradReduceArgs ga;
   GWalk(mww_ctx* c_, const GraphModel& m_, int B_, bool inl_)
       : c(c_), m(m_), B(B_), inl(inl_), pick(inl_ && m_.grid_g_auto), split(inl_ && m_.g_role_split),
-        pair(!(c_->hook && c_->sync_bn) && !m_.profile_split), gg(std::min(B_, m_.grid_g)), lp{c_} {
+        pair(!(c_->xch.hook && c_->xch.sync_bn) && !m_.profile_split), gg(std::min(B_, m_.grid_g)), lp{c_} {
     ga.nseg = 0;
   }
 };

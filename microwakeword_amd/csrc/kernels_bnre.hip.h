@@ -22,7 +22,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+#include <vector>
+
 #include "common.hip.h"
+
+struct mww_ctx;
 
 namespace mww {
 
@@ -53,8 +58,29 @@ struct BnreCommitArgs {
   int n;                  // S
 };
 
-int launch_bnre_collect(const BnreCollectArgs& a, int blocks, hipStream_t stream);   // tu_bnre.hip
+// BatchNorm re-estimation for the average (mww_bn_reestimate_*): `ema_bn` = the batch statistics of training-mode forwards at
+// the average, averaged over a pass; while `valid`, a non-training forward that stands on the average folds them instead of the
+// master's moving statistics (eval_bn_state).  Allocated by the first pass.
+struct BnreState {
+  float* ema_bn = nullptr;
+  bool valid = false;
+  double* acc = nullptr;          // [S] float64 sums of the pass in progress
+  int64_t batches = -1;           // batches collected by the pass in progress; -1: none is open
+  BnreRow* table = nullptr;       // device-resident table of the collect launch
+  int table_rows = 0;
+  std::vector<char> table_host;   // what it holds (uploaded again only when a row changes)
+};
+
+// ---- tu_bnre.hip (also mww_bn_reestimate_*, mww_get_ema_bn_state, mww_set_ema_bn_state)
+int launch_bnre_collect(const BnreCollectArgs& a, int blocks, hipStream_t stream);
 int launch_bnre_commit(const BnreCommitArgs& a, hipStream_t stream);
+// Whatever changes what a forward at the average reads - an update of the average, mww_set_ema_state, installing / removing the
+// average, the "weight_qat" option or map - leaves the re-estimated statistics describing another model: evaluations read the
+// master's moving statistics again, and a pass in progress is closed
+void invalidate_ema_bn(mww_ctx* c);
+void free_bn_reestimate(mww_ctx* c);
+// (Model::enqueue_bn_collect) block0 / nblocks of the rows are filled in, the device table is brought up to date, the collect is launched
+int enqueue_bnre_collect(mww_ctx* c, std::vector<BnreRow>& rows);
 
 #ifdef MWW_BNRE_TU
 // sums -> the fp32 batch mean and biased batch variance; the expressions of bn_fold_channel / bn_fwd_finalize_kernel /

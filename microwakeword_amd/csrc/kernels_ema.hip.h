@@ -11,6 +11,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
+struct mww_ctx;
+
 namespace mww {
 
 constexpr int kEmaThreads = 256;
@@ -23,7 +27,33 @@ struct EmaArgs {
   int first;             // the first update: copy
 };
 
-int launch_weight_ema(const EmaArgs& a, hipStream_t stream);   // tu_ema.hip
+// weight averaging (mww_set_weight_ema): `vec` follows the master by one launch behind every `every`-th Adam update; with the
+// "ema_forward" option a non-training forward reads it (`src`, set for the duration of such a call) once it holds a first update
+struct EmaState {
+  float* vec = nullptr;
+  double decay = 0.0;
+  int64_t every = 1, updates = 0;
+  bool forward = false, src = false;
+};
+
+// ---- tu_ema.hip (also mww_set_weight_ema, mww_get_ema_state, mww_set_ema_state)
+int launch_weight_ema(const EmaArgs& a, hipStream_t stream);
+// what the Adam update that takes the optimizer to c->step is followed by - nothing, the copy that starts the average, or one
+// blend; enqueued on the context's stream directly behind that update; counted once the call that enqueued it cannot fail
+enum { EMA_NONE = 0, EMA_COPY = 1, EMA_BLEND = 2 };
+int ema_due(const mww_ctx* c);
+int enqueue_ema(mww_ctx* c, int mode);
+void ema_enqueued(mww_ctx* c, int mode);
+// a non-training call under "ema_forward" stands on the weight average once it holds a first update; for this call only
+bool ema_serves(const mww_ctx* c);
+const float* eval_source(const mww_ctx* c);   // the vector such a call stands on: the average where it serves, else the master
+struct EmaSource {
+  mww_ctx* c;
+  EmaSource(mww_ctx* ctx, bool training);
+  ~EmaSource();
+};
+int set_ema_forward(mww_ctx* c, bool on);     // the "ema_forward" option
+void free_weight_ema(mww_ctx* c);             // (with the statistics re-estimated for it)
 
 #ifdef MWW_EMA_TU
 __device__ __forceinline__ float ema_blend(float e, float w, double om) {

@@ -14,6 +14,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+struct mww_ctx;
+
 namespace mww {
 
 constexpr int kQatThreads = 1024;   // the longest channel (the dense kernel, thousands of elements) is the launch's critical path
@@ -27,7 +29,24 @@ struct QatArgs {
   int n_channels, n_copy;
 };
 
-int launch_weight_qat(const QatArgs& a, hipStream_t stream);   // tu_qat.hip
+// "weight_qat" option: the forward / backward launches read `shadow`, the master fake-quantized per weight channel, refreshed
+// at the start of every call that runs a forward; Adam, set / get_params and checkpoints keep the master.
+// The map (mww_set_weight_qat) is device-resident: CSR channels + the list of parameters outside every channel.
+struct QatState {
+  bool enabled = false;
+  const float* held = nullptr;   // inside mww_evaluate_windows: the vector the first batch refreshed the shadow from (it cannot
+                                 // change between the batches); a refresh from any other source is not skipped
+  float* shadow = nullptr;
+  int *start = nullptr, *elem = nullptr, *copy = nullptr;
+  int channels = 0, n_copy = 0;
+};
+
+// ---- tu_qat.hip (also mww_set_weight_qat, mww_get_forward_params)
+int launch_weight_qat(const QatArgs& a, hipStream_t stream);
+int refresh_shadow(mww_ctx* c);                       // shadow = fake_quant(the vector this call's forward stands on), where it is due
+void hold_shadow(mww_ctx* c, const float* source);    // the shadow serves every further call that stands on `source` (null: no longer)
+int set_weight_qat_enabled(mww_ctx* c, bool on);      // the "weight_qat" option
+void free_weight_qat(mww_ctx* c);
 
 #ifdef MWW_QAT_TU
 __global__ __launch_bounds__(kQatThreads) void weight_qat_kernel(QatArgs a) {

@@ -17,6 +17,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+struct mww_ctx;
+
 namespace mww {
 
 constexpr int kSumsqLanes = 1024;
@@ -48,10 +50,27 @@ struct GradScaleArgs {
   int n, n4;
 };
 
-// tu_sam.hip
+// An applying train step of a context that has either feature takes its gradient with a separate Adam launch; `saved` = the bit
+// copy of the master a sharpness-aware step restores from, `scalars` = {S of the first pass's gradient, its perturbation scale,
+// S of the gradient Adam consumes, its clipping factor}
+struct SharpState {
+  double rho = 0.0, clip_norm = 0.0;
+  float* saved = nullptr;
+  double* scalars = nullptr;
+  bool valid = false;   // a step has written scalars (mww_get_grad_norms)
+};
+
+// ---- tu_sam.hip (also mww_set_sharpness_aware, mww_set_grad_clip, mww_get_grad_norms)
 int launch_grad_sumsq(const SumsqArgs& a, hipStream_t stream);
 int launch_sam_perturb(const SamPerturbArgs& a, hipStream_t stream);
 int launch_grad_scale(const GradScaleArgs& a, hipStream_t stream);
+bool sharp_step(const mww_ctx* c);   // an applying train step is sharp_sequence (a radius or a threshold is installed)
+int sharp_sequence(mww_ctx* c, int B, int flags, int ema);
+int enqueue_clip(mww_ctx* c);        // mww_apply_gradients: the gradient as it stands in the buffer is clipped, where a threshold is installed
+// Both features are single-device: neither stands next to an exchange hook.  `installing` names the feature being installed
+// (null: the hook is); MWW_OK where the other side is absent
+int single_device_only(const mww_ctx* c, const char* installing);
+void free_sharpness(mww_ctx* c);
 
 #ifdef MWW_SAM_TU
 __global__ __launch_bounds__(kSumsqLanes) void grad_sumsq_kernel(SumsqArgs a) {

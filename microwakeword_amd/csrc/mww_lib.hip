@@ -1,10 +1,10 @@
 // libmww_hip.so — the C ABI of include/mww.h and the core of a context: device memory, mailboxes, batch assembly, gradient
-// assembly / exchange / Adam, side work, RCCL and the step driver.  The model part of a context is one of the two engines
-// (block_engine.hip, graph_engine.hip); engine.hip.h holds what the three share.
+// assembly / exchange / Adam, side work, the step driver and the option table.  The model part of a context is one of the two
+// engines (block_engine.hip, graph_engine.hip); the step features (weight QAT, weight averaging, BN re-estimation, sharpness /
+// clipping) and the exchange binding have units of their own (tu_qat / ema / bnre / sam / exchange.hip), reached through the
+// interfaces of their headers; engine.hip.h holds what all of them share.
 // One context = one device + one HIP stream + one model; every call enqueues on that stream.
 #include <hip/hip_runtime.h>
-
-#include <dlfcn.h>
 
 #include <cmath>
 #include <cstdio>
@@ -15,12 +15,8 @@
 #include <vector>
 
 #include "engine.hip.h"
-#include "kernels_bnre.hip.h"
 #include "kernels_data.hip.h"
-#include "kernels_ema.hip.h"
 #include "kernels_head.hip.h"
-#include "kernels_qat.hip.h"
-#include "kernels_sam.hip.h"
 #include "kernels_tail.hip.h"
 
 using namespace mww;
@@ -126,7 +122,7 @@ XGather x_gather(mww_ctx* c) {
   return g;
 }
 
-static int join_side(mww_ctx* c) {
+int join_side(mww_ctx* c) {
   if (c->side_pending) {
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
     c->side_pending = false;
@@ -198,56 +194,24 @@ int exchange_stats(mww_ctx* c, Launcher& lp, const char* what, int layer, const 
   out->G = G;
   out->inv_n = local_inv_n;
   out->dscale = 1.0f;
-  if (!(c->hook && c->sync_bn)) return MWW_OK;
-  float* buf = c->sync_buf + c->sync_off[layer] + (bwd ? 2 * C : 0);
+  if (!(c->xch.hook && c->xch.sync_bn)) return MWW_OK;
+  float* buf = c->xch.sync_buf + c->xch.sync_off[layer] + (bwd ? 2 * C : 0);
   StatCollapseArgs a{part, G, C, buf};
   lp.begin(what, layer);
   hipLaunchKernelGGL(stat_collapse_kernel, dim3(C), dim3(kThreads), 0, c->stream, a);
   lp.end();
-  if (c->hook(c->hook_user, buf, 2 * C, MWW_EXCHANGE_IN_ORDER) != 0) return fail(MWW_ERR_STATE, "all-reduce hook failed");
+  if (c->xch.hook(c->xch.user, buf, 2 * C, MWW_EXCHANGE_IN_ORDER) != 0) return fail(MWW_ERR_STATE, "all-reduce hook failed");
   out->part = buf;
   out->G = 1;
-  out->inv_n = local_inv_n / (float)c->world;
-  out->dscale = 1.0f / (float)c->world;
+  out->inv_n = local_inv_n / (float)c->xch.world;
+  out->dscale = 1.0f / (float)c->xch.world;
   return MWW_OK;
 }
 
 StatSource forward_stat_source(const mww_ctx* c, int layer, const float* part, int G, int C, float local_inv_n) {
-  if (!(c->hook && c->sync_bn)) return StatSource{part, G, local_inv_n, 1.0f};
+  if (!(c->xch.hook && c->xch.sync_bn)) return StatSource{part, G, local_inv_n, 1.0f};
   // (every layer has its own place in sync_buf: the sums of the whole forward are still there)
-  return StatSource{c->sync_buf + c->sync_off[layer], 1, local_inv_n / (float)c->world, 1.0f / (float)c->world};
-}
-
-int enqueue_bnre_collect(mww_ctx* c, std::vector<BnreRow>& rows) {
-  if (rows.empty()) return MWW_OK;
-  int blocks = 0;
-  for (BnreRow& r : rows) {
-    r.nblocks = r.form == BNRE_ROWS ? 1 : (r.groups > 1 ? r.groups : r.C);
-    r.block0 = blocks;
-    blocks += r.nblocks;
-  }
-  const size_t bytes = rows.size() * sizeof(BnreRow);
-  if (c->bnre_table_host.size() != bytes || memcmp(c->bnre_table_host.data(), rows.data(), bytes) != 0) {
-    // a row changes with the batch size, the statistics path ("bn_inline", sync-BN) or a grid option - not from batch to
-    // batch of a pass (the accumulator parity travels as a launch argument) - so this wait is paid once per configuration
-    HIPCHK(hipStreamSynchronize(c->stream));   // (the launches that read the old table are done)
-    if (c->bnre_table_rows < (int)rows.size()) {
-      if (c->bnre_table) HIPCHK(hipFree(c->bnre_table));
-      c->bnre_table = nullptr;
-      c->bnre_table_rows = 0;
-      MWW_TRY(dev_alloc(&c->bnre_table, rows.size()));
-      c->bnre_table_rows = (int)rows.size();
-    }
-    c->bnre_table_host.clear();
-    HIPCHK(hipMemcpy(c->bnre_table, rows.data(), bytes, hipMemcpyHostToDevice));
-    c->bnre_table_host.assign(reinterpret_cast<const char*>(rows.data()), reinterpret_cast<const char*>(rows.data()) + bytes);
-  }
-  Launcher lp{c};
-  lp.begin("bn_reestimate_collect");
-  // the forward flipped the parity behind its last launch: its rows are the other one's
-  launch_bnre_collect(BnreCollectArgs{c->bnre_table, (int)rows.size(), c->fpar ^ 1, c->bnre_acc}, blocks, c->stream);
-  lp.end();
-  return MWW_OK;
+  return StatSource{c->xch.sync_buf + c->xch.sync_off[layer], 1, local_inv_n / (float)c->xch.world, 1.0f / (float)c->xch.world};
 }
 
 }  // namespace mww
@@ -255,7 +219,6 @@ namespace {
 
 // gradient assembly: fixed-order sum of the per-workgroup partials (+ the dense layer's, which come
 // from the side stream), structural mask, optionally fused with the Adam update
-int enqueue_adam(mww_ctx* c);
 
 // Gradient assembly of the parameter range [lo, hi): one grad_final_kernel launch (kernels_tail.hip.h) finishes every
 // parameter of the range - fixed-order sums of the partial rows listed in `ga` (and of the rows the dense / metric
@@ -333,7 +296,7 @@ int assemble_range(mww_ctx* c, int B, const GradReduceArgs& ga, int64_t lo, int6
 
 // gradient exchange of a finished range through the caller's hook (data-parallel step)
 int exchange_range(mww_ctx* c, int64_t lo, int64_t hi, int flags) {
-  if (c->hook(c->hook_user, flags == MWW_EXCHANGE_FLUSH ? nullptr : c->grads + lo, flags == MWW_EXCHANGE_FLUSH ? 0 : hi - lo, flags) != 0)
+  if (c->xch.hook(c->xch.user, flags == MWW_EXCHANGE_FLUSH ? nullptr : c->grads + lo, flags == MWW_EXCHANGE_FLUSH ? 0 : hi - lo, flags) != 0)
     return fail(MWW_ERR_STATE, "all-reduce hook failed");
   return MWW_OK;
 }
@@ -359,25 +322,21 @@ int enqueue_grad_assembly(mww_ctx* c, int B, GradReduceArgs& ga, bool fuse_adam,
     s.dst = (int)c->o_dense_w;
     ga.seg[ga.nseg++] = s;
   }
-  const bool exchange = fuse_adam && c->hook && c->reduce_grads;
+  const bool exchange = fuse_adam && c->xch.hook && c->xch.reduce_grads;
   // single device: Adam rides in the assembly launch; data-parallel: local gradient -> sum over the ranks (the 1/W
   // factor travels as the gradient scale next to the step size, see mww_train_step) -> Adam on the average
   int rc = assemble_range(c, B, ga, lo, hi, tail_here, tail_here && c->tail_metrics, fuse_adam && !exchange);
   if (rc || !exchange) return rc;
   rc = exchange_range(c, lo, hi, last_range ? MWW_EXCHANGE_IN_ORDER : MWW_EXCHANGE_DEFERRED);
-  if (!last_range) c->exchange_pending = true;
+  if (!last_range) c->xch.pending = true;
   if (rc || !last_range) return rc;
-  if (c->exchange_pending) {
+  if (c->xch.pending) {
     rc = exchange_range(c, 0, 0, MWW_EXCHANGE_FLUSH);
-    c->exchange_pending = false;
+    c->xch.pending = false;
     if (rc) return rc;
   }
   return enqueue_adam(c);
 }
-
-}  // namespace mww
-
-namespace mww {
 
 // first launch of the block engine's backward pass after a train step's head: BN_L's backward finalize, the dense-weight
 // gradient of c->tail_src and (tail_metrics) the metric update as roles of one launch
@@ -399,10 +358,6 @@ int enqueue_head_tail(mww_ctx* c, int B, const BnBwdFinalizeArgs& fin) {
   return MWW_OK;
 }
 
-}  // namespace mww
-
-namespace {
-
 int enqueue_adam(mww_ctx* c) {
   Launcher lp{c};
   AdamArgs a{c->params, c->grads, c->adam_m, c->adam_v, mail_hyper(c), (int)c->P, 0.9f, 0.999f, 1e-7f};
@@ -412,14 +367,6 @@ int enqueue_adam(mww_ctx* c) {
   return MWW_OK;
 }
 
-// the host may rewrite the current mailbox once the GPU work of its previous use has finished
-int mail_begin(mww_ctx* c) {
-  if (!c->mail_open) {
-    HIPCHK(hipEventSynchronize(c->mail_ev[c->mail_cur]));
-    c->mail_open = true;
-  }
-  return MWW_OK;
-}
 // everything enqueued so far may read the current mailbox: stamp it and move on to the next one
 int mail_commit(mww_ctx* c) {
   HIPCHK(hipEventRecord(c->mail_ev[c->mail_cur], c->stream));
@@ -428,14 +375,7 @@ int mail_commit(mww_ctx* c) {
   c->targets_in_mail = 0;
   return MWW_OK;
 }
-int push_hyper(mww_ctx* c, float alpha, float gscale) {
-  int rc = mail_begin(c);
-  if (rc) return rc;
-  float* h = reinterpret_cast<float*>(c->mail_host[c->mail_cur] + c->mail_off_hyper);
-  h[0] = alpha;
-  h[1] = gscale;
-  return MWW_OK;
-}
+
 // What every call that runs a forward opens with: the labels / weights written by mww_set_targets that no assembly kernel
 // carried to the device, and x written out where the batch is descriptor-only but its mailbox slot is no longer the current
 // one (only until then is it gathered in place)
@@ -452,159 +392,42 @@ int batch_ready(mww_ctx* c) {
   return c->lazy_slot != c->mail_cur ? materialise_x(c) : MWW_OK;
 }
 
+void drop_graphs(mww_ctx* c) {
+  for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
+  c->graphs.clear();
+}
+
+}  // namespace mww
+
+namespace {
+
+// the host may rewrite the current mailbox once the GPU work of its previous use has finished (mail_commit)
+int mail_begin(mww_ctx* c) {
+  if (!c->mail_open) {
+    HIPCHK(hipEventSynchronize(c->mail_ev[c->mail_cur]));
+    c->mail_open = true;
+  }
+  return MWW_OK;
+}
+int push_hyper(mww_ctx* c, float alpha, float gscale) {
+  int rc = mail_begin(c);
+  if (rc) return rc;
+  float* h = reinterpret_cast<float*>(c->mail_host[c->mail_cur] + c->mail_off_hyper);
+  h[0] = alpha;
+  h[1] = gscale;
+  return MWW_OK;
+}
+
 float adam_alpha(float lr, int64_t t) {
   // Keras: alpha = lr * sqrt(1 - beta2^t) / (1 - beta1^t), evaluated in float32 like the variables
   const float b1p = powf(0.9f, (float)t), b2p = powf(0.999f, (float)t);
   return lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
 }
 
-// "weight_qat": shadow = fake_quant(master), on the context's stream ahead of the first launch that reads weights (every
-// Adam update and every mww_set_params is ordered on that stream too, or joined to it before the call returns).  In a
-// non-training call under "ema_forward" the source is the weight average instead: shadow = fake_quant(ema).  A held shadow
-// (mww_evaluate_windows) is only as good as its source - the next call that reads another vector refreshes.
-int refresh_shadow(mww_ctx* c) {
-  const float* src = fwd_source(c);
-  if (!c->weight_qat || c->shadow_held == src) return MWW_OK;
-  Launcher lp{c};
-  lp.begin("weight_qat");
-  launch_weight_qat(QatArgs{src, c->shadow, c->qat_start, c->qat_elem, c->qat_copy, c->qat_channels, c->qat_n_copy}, c->stream);
-  lp.end();
-  return MWW_OK;
-}
-
-// weight averaging: what the Adam update that takes the optimizer to c->step is followed by - nothing, the copy that starts
-// the average, or one blend
-enum { EMA_NONE = 0, EMA_COPY = 1, EMA_BLEND = 2 };
-int ema_due(const mww_ctx* c) {
-  if (!c->ema || c->step % c->ema_every != 0) return EMA_NONE;
-  return c->ema_updates == 0 ? EMA_COPY : EMA_BLEND;
-}
-// ... enqueued on the context's stream directly behind that update (under "graphs": one more node of the captured chain)
-int enqueue_ema(mww_ctx* c, int mode) {
-  if (mode == EMA_NONE) return MWW_OK;
-  Launcher lp{c};
-  lp.begin("weight_ema");
-  launch_weight_ema(EmaArgs{c->params, c->ema, 1.0 - c->ema_decay, (int)c->P, 0, mode == EMA_COPY ? 1 : 0}, c->stream);
-  lp.end();
-  return MWW_OK;
-}
-
-// BN re-estimation: whatever changes what a forward at the average reads - an update of the average, mww_set_ema_state,
-// installing / removing the average, the "weight_qat" option or map - leaves the re-estimated statistics describing another
-// model: evaluations read the master's moving statistics again, and a pass in progress is closed
-void invalidate_ema_bn(mww_ctx* c) {
-  c->ema_bn_valid = false;
-  c->bnre_batches = -1;
-}
-
-void free_weight_ema(mww_ctx* c) {
-  invalidate_ema_bn(c);
-  void* bnre[] = {c->ema_bn, c->bnre_acc, c->bnre_table};
-  for (void* p : bnre) if (p) (void)hipFree(p);
-  c->ema_bn = nullptr;
-  c->bnre_acc = nullptr;
-  c->bnre_table = nullptr;
-  c->bnre_table_rows = 0;
-  c->bnre_table_host.clear();
-  if (c->ema) (void)hipFree(c->ema);
-  c->ema = nullptr;
-  c->ema_decay = 0.0;
-  c->ema_every = 1;
-  c->ema_updates = 0;
-  c->ema_forward = c->ema_src = false;
-}
-
-// a non-training call under "ema_forward" stands on the weight average once it holds a first update; for this call only
-bool ema_serves(const mww_ctx* c) { return c->ema_forward && c->ema && c->ema_updates > 0; }
-struct EmaSource {
-  mww_ctx* c;
-  EmaSource(mww_ctx* ctx, bool training) : c(ctx) { c->ema_src = !training && ema_serves(c); }
-  ~EmaSource() { c->ema_src = false; }
-};
-
-void free_weight_qat(mww_ctx* c) {
-  void* bufs[] = {c->shadow, c->qat_start, c->qat_elem, c->qat_copy};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  c->shadow = nullptr;
-  c->qat_start = c->qat_elem = c->qat_copy = nullptr;
-  c->qat_channels = c->qat_n_copy = 0;
-  c->weight_qat = false;
-}
-
-void drop_graphs(mww_ctx* c) {
-  for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
-  c->graphs.clear();
-}
-
-// ---- sharpness-aware steps and global-norm clipping (kernels_sam.hip.h; include/mww.h states the sequence)
-enum { NORM_FIRST = 0, NORM_SCALE = 1, NORM_FINAL = 2, NORM_CLIP = 3, NORM_SCALARS = 4 };
-
-void free_sharpness(mww_ctx* c) {
-  if (c->sam_w) (void)hipFree(c->sam_w);
-  if (c->norm_scalars) (void)hipFree(c->norm_scalars);
-  c->sam_w = nullptr;
-  c->norm_scalars = nullptr;
-  c->sam_rho = c->clip_norm = 0.0;
-  c->norms_valid = false;
-}
-
-// S of the gradient as it stands -> norm_scalars[slot] (and [also], if >= 0), with the scalar of `mode` behind it
-int enqueue_grad_sumsq(mww_ctx* c, int slot, int also, int mode, double value) {
-  Launcher lp{c};
-  lp.begin("grad_sumsq");
-  launch_grad_sumsq(SumsqArgs{c->grads, (int)c->P, mode, value, c->norm_scalars + slot, also >= 0 ? c->norm_scalars + also : nullptr,
-                              c->norm_scalars + slot + 1}, c->stream);
-  lp.end();
-  return MWW_OK;
-}
-
-// what stands between the gradient Adam is about to consume and Adam: its S (first: this is also the step's first-pass
-// gradient) and, with clipping installed, the scaling
-int enqueue_final_norm(mww_ctx* c, bool first) {
-  const bool clip = c->clip_norm > 0.0;
-  MWW_TRY(enqueue_grad_sumsq(c, NORM_FINAL, first ? NORM_FIRST : -1, clip ? kSumsqClip : kSumsqOnly, c->clip_norm));
-  if (clip) {
-    Launcher lp{c};
-    lp.begin("grad_clip");
-    launch_grad_scale(GradScaleArgs{c->grads, c->norm_scalars + NORM_CLIP, (int)c->P, 0}, c->stream);
-    lp.end();
-  }
-  c->norms_valid = true;
-  return MWW_OK;
-}
-
-// the applying step of a context with a sharpness-aware radius or a clipping threshold: the gradient is assembled without
-// Adam, Adam is a launch of its own
-int sharp_sequence(mww_ctx* c, int B, int flags, int ema) {
-  const bool sam = c->sam_rho > 0.0;
-  MWW_TRY(refresh_shadow(c));
-  MWW_TRY(c->model->enqueue_forward(c, B, true, true, true, !(flags & MWW_STEP_NO_METRICS)));
-  MWW_TRY(c->model->enqueue_backward(c, B, false));   // g(w)
-  if (sam) {
-    MWW_TRY(enqueue_grad_sumsq(c, NORM_FIRST, -1, kSumsqPerturb, c->sam_rho));
-    Launcher lp{c};
-    lp.begin("sam_perturb");
-    launch_sam_perturb(SamPerturbArgs{c->grads, c->params, c->sam_w, c->norm_scalars + NORM_SCALE, (int)c->P, 0}, c->stream);
-    lp.end();
-    // the second pass: the same batch (a descriptor-only one is gathered through the same mailbox slot, committed behind this
-    // call), the same dropout mask (the step's counter, or the pinned mask), batch statistics of its own that leave the moving
-    // statistics alone, no metrics; the accumulator parities flip as in a second gradient-only step
-    MWW_TRY(refresh_shadow(c));   // "weight_qat": fake_quant(w')
-    MWW_TRY(c->model->enqueue_forward(c, B, true, false, true, false));
-    MWW_TRY(c->model->enqueue_backward(c, B, false));   // g(w')
-    lp.begin("sam_restore");
-    HIPCHK(hipMemcpyAsync(c->params, c->sam_w, (size_t)c->P * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    lp.end();
-  }
-  MWW_TRY(enqueue_final_norm(c, !sam));
-  MWW_TRY(enqueue_adam(c));
-  return enqueue_ema(c, ema);
-}
-
 int step_sequence(mww_ctx* c, int B, int flags, int ema) {
   c->metric_launches = 0;
   int rc;
-  if (!(flags & MWW_STEP_NO_APPLY) && (c->sam_rho > 0.0 || c->clip_norm > 0.0)) {
+  if (!(flags & MWW_STEP_NO_APPLY) && sharp_step(c)) {
     rc = sharp_sequence(c, B, flags, ema);
     if (rc) return rc;
   } else {
@@ -725,6 +548,18 @@ void tensor_free(Tensor* t) {
   for (void* p : all) if (p) (void)hipFree(p);
 }
 
+// host <-> device copies of the getters and setters: on the context's stream, waited for
+int copy_in(mww_ctx* c, void* dst, const void* src, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return MWW_OK;
+}
+int copy_out(mww_ctx* c, void* dst, const void* src, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return MWW_OK;
+}
+
 int Model::set_dropout_mask(mww_ctx*, const uint8_t*, int) { return fail(MWW_ERR_INVALID, "context has no dropout layer"); }
 
 // plan (the caller's) -> device -> layout -> the core's buffers -> the model's -> defaults
@@ -781,163 +616,6 @@ int mww_create_convnet(const mww_convnet_desc* desc, int device, void* stream, m
   return create_context(m, desc->frames, desc->max_batch, device, stream, out);
 }
 
-int mww_set_allreduce_hook(mww_ctx* c, mww_allreduce_fn fn, void* user, int world_size, int sync_bn, int reduce_grads) {
-  if (!c) return fail(MWW_ERR_INVALID, "null context");
-  if (fn && world_size < 1) return fail(MWW_ERR_INVALID, "world size must be positive");
-  if (fn && (c->sam_rho > 0.0 || c->clip_norm > 0.0))
-    return fail(MWW_ERR_UNSUPPORTED, "sharpness-aware steps and gradient clipping are single-device: remove them before installing an exchange hook");
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->hook = fn;
-  c->hook_user = user;
-  c->world = fn ? world_size : 1;
-  c->sync_bn = fn && sync_bn;
-  c->reduce_grads = fn && reduce_grads;
-  if (c->sync_bn && !c->sync_buf) {
-    int64_t off = 0;
-    c->sync_off.clear();
-    for (int w : c->model->stat_widths()) { c->sync_off.push_back(off); off += 4 * (int64_t)w; }
-    int rc = dev_alloc(&c->sync_buf, (size_t)off);
-    if (rc) return rc;
-  }
-  return MWW_OK;
-}
-
-// ---- RCCL inside the library (mww_allreduce_init).  The exchange the caller's hook performed through
-// Python / torch.distributed (two ctypes callbacks, two dispatcher round trips and a pair of cross-stream event waits
-// per step: +38 us at W = 1 for the two-bucket schedule in round 2) is issued here, from the launching thread:
-//   MWW_EXCHANGE_IN_ORDER  ncclAllReduce on the context's stream itself
-//   MWW_EXCHANGE_DEFERRED  event on the context's stream -> the library's side stream waits for it -> ncclAllReduce there
-//   MWW_EXCHANGE_FLUSH     the context's stream waits for the side stream's last exchange
-struct RcclState {
-  RcclApi api;
-  void* comm = nullptr;
-  hipStream_t side = nullptr;
-  hipEvent_t ev_ready = nullptr, ev_done = nullptr;
-  mww_ctx* c = nullptr;
-  bool deferred = false;
-};
-
-namespace {
-int rccl_load(RcclApi* a) {
-  if (a->so) return MWW_OK;
-  const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"};
-  for (const char* n : names) {
-    a->so = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-    if (a->so) break;
-  }
-  if (!a->so) return fail(MWW_ERR_UNSUPPORTED, std::string("librccl.so not found: ") + dlerror());
-  a->GetUniqueId = reinterpret_cast<decltype(a->GetUniqueId)>(dlsym(a->so, "ncclGetUniqueId"));
-  a->CommInitRank = reinterpret_cast<decltype(a->CommInitRank)>(dlsym(a->so, "ncclCommInitRank"));
-  a->AllReduce = reinterpret_cast<decltype(a->AllReduce)>(dlsym(a->so, "ncclAllReduce"));
-  a->CommDestroy = reinterpret_cast<decltype(a->CommDestroy)>(dlsym(a->so, "ncclCommDestroy"));
-  a->GetErrorString = reinterpret_cast<decltype(a->GetErrorString)>(dlsym(a->so, "ncclGetErrorString"));
-  a->CommCount = reinterpret_cast<decltype(a->CommCount)>(dlsym(a->so, "ncclCommCount"));
-  if (!a->GetUniqueId || !a->CommInitRank || !a->AllReduce || !a->CommDestroy || !a->GetErrorString)
-    return fail(MWW_ERR_UNSUPPORTED, "librccl.so lacks an entry point");
-  return MWW_OK;
-}
-
-int rccl_exchange(void* user, float* buf, int64_t n, int flags) {
-  RcclState* r = static_cast<RcclState*>(user);
-  mww_ctx* c = r->c;
-  constexpr int kFloat = 7, kSum = 0;   // ncclFloat32, ncclSum (rccl.h)
-  if (flags == MWW_EXCHANGE_FLUSH) {
-    if (r->deferred) {
-      if (hipStreamWaitEvent(c->stream, r->ev_done, 0) != hipSuccess) return -1;
-      r->deferred = false;
-    }
-    return 0;
-  }
-  hipStream_t st = c->stream;
-  if (flags == MWW_EXCHANGE_DEFERRED) {
-    if (hipEventRecord(r->ev_ready, c->stream) != hipSuccess) return -1;
-    if (hipStreamWaitEvent(r->side, r->ev_ready, 0) != hipSuccess) return -1;
-    st = r->side;
-  }
-  const int e = r->api.AllReduce(buf, buf, (size_t)n, kFloat, kSum, r->comm, st);
-  if (e != 0) {
-    g_err = std::string("ncclAllReduce: ") + r->api.GetErrorString(e);
-    return -1;
-  }
-  if (flags == MWW_EXCHANGE_DEFERRED) {
-    if (hipEventRecord(r->ev_done, r->side) != hipSuccess) return -1;
-    r->deferred = true;
-  }
-  return 0;
-}
-}  // namespace
-
-int mww_allreduce_unique_id(void* out_id, int capacity) {
-  if (!out_id || capacity < MWW_UNIQUE_ID_BYTES) return fail(MWW_ERR_INVALID, "unique-id buffer too small");
-  static RcclApi api;
-  int rc = rccl_load(&api);
-  if (rc) return rc;
-  RcclApi::UniqueId id;
-  const int e = api.GetUniqueId(&id);
-  if (e != 0) return fail(MWW_ERR_HIP, std::string("ncclGetUniqueId: ") + api.GetErrorString(e));
-  memcpy(out_id, id.internal, sizeof(id.internal));
-  return MWW_OK;
-}
-
-int mww_allreduce_destroy(mww_ctx* c) {
-  if (!c) return fail(MWW_ERR_INVALID, "null context");
-  RcclState* r = c->rccl;
-  if (!r) return MWW_OK;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  if (r->side) (void)hipStreamSynchronize(r->side);
-  if (c->hook == rccl_exchange) {
-    c->hook = nullptr;
-    c->hook_user = nullptr;
-    c->world = 1;
-    c->sync_bn = c->reduce_grads = false;
-  }
-  if (r->comm) (void)r->api.CommDestroy(r->comm);
-  if (r->side) (void)hipStreamDestroy(r->side);
-  if (r->ev_ready) (void)hipEventDestroy(r->ev_ready);
-  if (r->ev_done) (void)hipEventDestroy(r->ev_done);
-  delete r;
-  c->rccl = nullptr;
-  return MWW_OK;
-}
-
-int mww_allreduce_world(mww_ctx* c) {
-  if (!c) return fail(MWW_ERR_INVALID, "null context");
-  if (!c->rccl || !c->rccl->comm) return 0;
-  int n = 0;
-  if (!c->rccl->api.CommCount) return fail(MWW_ERR_UNSUPPORTED, "librccl.so lacks ncclCommCount");
-  const int e = c->rccl->api.CommCount(c->rccl->comm, &n);
-  if (e != 0) return fail(MWW_ERR_HIP, std::string("ncclCommCount: ") + c->rccl->api.GetErrorString(e));
-  return n;
-}
-
-int mww_allreduce_init(mww_ctx* c, int rank, int world, const void* unique_id, int sync_bn) {
-  if (!c || !unique_id || world < 1 || rank < 0 || rank >= world) return fail(MWW_ERR_INVALID, "bad rank / world size");
-  if (c->sam_rho > 0.0 || c->clip_norm > 0.0)   // (before the communicator is touched: a refused call leaves the context as it was)
-    return fail(MWW_ERR_UNSUPPORTED, "sharpness-aware steps and gradient clipping are single-device: remove them before installing an exchange hook");
-  int rc = mww_allreduce_destroy(c);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(c->device));
-  RcclState* r = new RcclState();
-  r->c = c;
-  rc = rccl_load(&r->api);
-  if (rc) { delete r; return rc; }
-  RcclApi::UniqueId id;
-  memcpy(id.internal, unique_id, sizeof(id.internal));
-  const int e = r->api.CommInitRank(&r->comm, world, id, rank);
-  if (e != 0) {
-    const std::string msg = std::string("ncclCommInitRank: ") + r->api.GetErrorString(e);
-    delete r;
-    return fail(MWW_ERR_HIP, msg);
-  }
-  c->rccl = r;
-  HIPCHK(hipStreamCreateWithFlags(&r->side, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&r->ev_ready, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&r->ev_done, hipEventDisableTiming));
-  return mww_set_allreduce_hook(c, rccl_exchange, r, world, sync_bn, 1);
-}
-
 int mww_set_dropout_mask(mww_ctx* c, const uint8_t* keep, int B) {
   if (!c) return fail(MWW_ERR_INVALID, "context has no dropout layer");
   return c->model->set_dropout_mask(c, keep, B);
@@ -951,10 +629,10 @@ void mww_destroy(mww_ctx* c) {
   for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
   for (auto& e : c->prof) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   void* flat[] = {c->params, c->grads, c->adam_m, c->adam_v, c->mask, c->direct, c->bn_state, c->x, c->y, c->sw,
-                  c->z, c->prob, c->dz, c->loss_part, c->dwd_part, c->metrics, c->sync_buf};
+                  c->z, c->prob, c->dz, c->loss_part, c->dwd_part, c->metrics, c->xch.sync_buf};
   for (void* p : flat) if (p) (void)hipFree(p);
   free_weight_qat(c);
-  free_weight_ema(c);
+  free_weight_ema(c);   // (and the statistics re-estimated for it)
   free_sharpness(c);
   for (int i = 0; i < MWW_MAX_STORES; ++i) if (c->store[i]) (void)hipFree(c->store[i]);
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
@@ -981,17 +659,6 @@ int mww_synchronize(mww_ctx* c) {
 int64_t mww_num_params(const mww_ctx* c) { return c ? c->P : 0; }
 int64_t mww_num_bn_state(const mww_ctx* c) { return c ? c->S : 0; }
 
-static int copy_in(mww_ctx* c, void* dst, const void* src, size_t bytes) {
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return MWW_OK;
-}
-static int copy_out(mww_ctx* c, void* dst, const void* src, size_t bytes) {
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return MWW_OK;
-}
-
 int mww_set_params(mww_ctx* c, const float* h, int64_t n) {
   if (!c || !h || n != c->P) return fail(MWW_ERR_INVALID, "parameter vector size mismatch");
   return copy_in(c, c->params, h, (size_t)n * sizeof(float));
@@ -1004,136 +671,6 @@ int mww_set_bn_state(mww_ctx* c, const float* h, int64_t n) {
   if (!c || !h || n != c->S) return fail(MWW_ERR_INVALID, "BN state size mismatch");
   return copy_in(c, c->bn_state, h, (size_t)n * sizeof(float));
 }
-int mww_get_forward_params(mww_ctx* c, float* h, int64_t n) {
-  if (!c || !h || n != c->P) return fail(MWW_ERR_INVALID, "parameter vector size mismatch");
-  HIPCHK(hipSetDevice(c->device));
-  EmaSource source(c, false);
-  MWW_TRY(refresh_shadow(c));
-  HIPCHK(hipGetLastError());
-  return copy_out(c, h, fwd_params(c), (size_t)n * sizeof(float));
-}
-
-int mww_set_weight_ema(mww_ctx* c, double decay, int64_t every_steps) {
-  if (!c) return fail(MWW_ERR_INVALID, "null context");
-  // validated before anything changes: a refused call leaves the context as it was
-  if (decay != 0.0) {
-    if (!(decay > 0.0 && decay < 1.0)) return fail(MWW_ERR_INVALID, "weight_ema: decay must lie in (0, 1), or be 0 to remove the average");
-    if (every_steps < 1) return fail(MWW_ERR_INVALID, "weight_ema: every_steps must be at least 1");
-  }
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  drop_graphs(c);   // (a capture holds the average's address, the decay and whether its node copies or blends)
-  if (decay == 0.0) {
-    free_weight_ema(c);
-    return MWW_OK;
-  }
-  if (!c->ema) MWW_TRY(dev_alloc(&c->ema, (size_t)c->P));
-  c->ema_decay = decay;
-  c->ema_every = every_steps;
-  c->ema_updates = 0;
-  invalidate_ema_bn(c);
-  return MWW_OK;
-}
-int mww_get_ema_state(mww_ctx* c, float* h, int64_t n, int64_t* updates) {
-  if (!c || !c->ema) return fail(MWW_ERR_INVALID, "no weight average installed: call mww_set_weight_ema first");
-  if (n != c->P) return fail(MWW_ERR_INVALID, "weight average size mismatch");
-  if (updates) *updates = c->ema_updates;
-  return h ? copy_out(c, h, c->ema, (size_t)n * sizeof(float)) : MWW_OK;
-}
-int mww_set_ema_state(mww_ctx* c, const float* h, int64_t n, int64_t updates) {
-  if (!c || !c->ema) return fail(MWW_ERR_INVALID, "no weight average installed: call mww_set_weight_ema first");
-  if (!h || n != c->P || updates < 0) return fail(MWW_ERR_INVALID, "weight average size mismatch");
-  MWW_TRY(copy_in(c, c->ema, h, (size_t)n * sizeof(float)));
-  if ((c->ema_updates == 0) != (updates == 0)) drop_graphs(c);   // (a captured step's node copies or blends)
-  c->ema_updates = updates;
-  invalidate_ema_bn(c);
-  return MWW_OK;
-}
-
-namespace {
-// installs (value > 0) or removes (0) one of the two features; the buffers live while either is installed
-int set_sharpness(mww_ctx* c, double value, bool sam, const char* what) {
-  if (!c) return fail(MWW_ERR_INVALID, "null context");
-  // validated before anything changes: a refused call leaves the context as it was
-  if (!(value >= 0.0) || std::isinf(value)) return fail(MWW_ERR_INVALID, std::string(what) + " must be a finite number > 0, or 0 to remove it");
-  if (value > 0.0 && c->hook)
-    return fail(MWW_ERR_UNSUPPORTED, std::string(what) + " is single-device: it cannot be installed next to an exchange hook");
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  drop_graphs(c);   // (a step with either feature is not the captured sequence)
-  const double rho = sam ? value : c->sam_rho, clip = sam ? c->clip_norm : value;
-  if (rho == 0.0 && clip == 0.0) {
-    free_sharpness(c);
-    return MWW_OK;
-  }
-  if (!c->norm_scalars) MWW_TRY(dev_alloc(&c->norm_scalars, (size_t)NORM_SCALARS));
-  if (rho > 0.0 && !c->sam_w) MWW_TRY(dev_alloc(&c->sam_w, (size_t)c->P));
-  if (rho == 0.0 && c->sam_w) {
-    (void)hipFree(c->sam_w);
-    c->sam_w = nullptr;
-  }
-  c->sam_rho = rho;
-  c->clip_norm = clip;
-  return MWW_OK;
-}
-}  // namespace
-
-int mww_set_sharpness_aware(mww_ctx* c, double rho) { return set_sharpness(c, rho, true, "sharpness_aware: rho"); }
-int mww_set_grad_clip(mww_ctx* c, double global_norm) { return set_sharpness(c, global_norm, false, "grad_clip: global_norm"); }
-
-int mww_get_grad_norms(mww_ctx* c, double* first_sumsq, double* final_sumsq) {
-  if (!c) return fail(MWW_ERR_INVALID, "null context");
-  if (!c->norms_valid) return fail(MWW_ERR_STATE, "grad_norms: no sharpness-aware or clipped step has run yet");
-  double h[NORM_SCALARS];
-  MWW_TRY(copy_out(c, h, c->norm_scalars, sizeof(h)));
-  if (first_sumsq) *first_sumsq = h[NORM_FIRST];
-  if (final_sumsq) *final_sumsq = h[NORM_FINAL];
-  return MWW_OK;
-}
-
-int mww_set_weight_qat(mww_ctx* c, const int32_t* chan_start, const int32_t* chan_elem, int32_t n_channels, int64_t n_elems) {
-  if (!c || n_channels < 0 || n_elems < 0) return fail(MWW_ERR_INVALID, "bad weight_qat map arguments");
-  if (n_channels > 0 && (!chan_start || (n_elems > 0 && !chan_elem))) return fail(MWW_ERR_INVALID, "null weight_qat map");
-  // validated before anything changes: a refused map leaves the context as it was
-  std::vector<int> copy;
-  if (n_channels > 0) {
-    if (n_elems > c->P) return fail(MWW_ERR_INVALID, "weight_qat map lists more elements than the model has parameters");
-    if (chan_start[0] != 0 || chan_start[n_channels] != n_elems) return fail(MWW_ERR_INVALID, "weight_qat map: chan_start must run from 0 to n_elems");
-    for (int32_t i = 0; i < n_channels; ++i)
-      if (chan_start[i + 1] < chan_start[i]) return fail(MWW_ERR_INVALID, "weight_qat map: chan_start must be ascending");
-    std::vector<unsigned char> seen((size_t)c->P, 0);
-    for (int64_t i = 0; i < n_elems; ++i) {
-      const int32_t e = chan_elem[i];
-      if (e < 0 || e >= c->P) return fail(MWW_ERR_INVALID, "weight_qat map: element index outside the parameter vector");
-      if (seen[(size_t)e]) return fail(MWW_ERR_INVALID, "weight_qat map: an element appears in two channels");
-      seen[(size_t)e] = 1;
-    }
-    for (int64_t e = 0; e < c->P; ++e)
-      if (!seen[(size_t)e]) copy.push_back((int)e);
-  }
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  drop_graphs(c);   // (a capture holds the shadow's and the map's addresses)
-  free_weight_qat(c);
-  invalidate_ema_bn(c);
-  if (n_channels == 0) return MWW_OK;
-  auto install = [&]() -> int {
-    MWW_TRY(dev_alloc(&c->shadow, (size_t)c->P));
-    MWW_TRY(dev_alloc(&c->qat_start, (size_t)n_channels + 1));
-    MWW_TRY(dev_alloc(&c->qat_elem, (size_t)n_elems));
-    MWW_TRY(dev_alloc(&c->qat_copy, copy.size()));
-    HIPCHK(hipMemcpy(c->qat_start, chan_start, ((size_t)n_channels + 1) * sizeof(int), hipMemcpyHostToDevice));
-    if (n_elems) HIPCHK(hipMemcpy(c->qat_elem, chan_elem, (size_t)n_elems * sizeof(int), hipMemcpyHostToDevice));
-    if (!copy.empty()) HIPCHK(hipMemcpy(c->qat_copy, copy.data(), copy.size() * sizeof(int), hipMemcpyHostToDevice));
-    return MWW_OK;
-  };
-  const int rc = install();
-  if (rc) { free_weight_qat(c); return rc; }   // (no half-installed map behind a device error)
-  c->qat_channels = n_channels;
-  c->qat_n_copy = (int)copy.size();
-  return MWW_OK;
-}
-
 int mww_get_bn_state(mww_ctx* c, float* h, int64_t n) {
   if (!c || !h || n != c->S) return fail(MWW_ERR_INVALID, "BN state size mismatch");
   return copy_out(c, h, c->bn_state, (size_t)n * sizeof(float));
@@ -1309,7 +846,7 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
   const bool apply = !(flags & MWW_STEP_NO_APPLY);
   if (apply) {
     c->step += 1;
-    rc = push_hyper(c, adam_alpha(lr, c->step), (c->hook && c->reduce_grads) ? 1.0f / (float)c->world : 1.0f);
+    rc = push_hyper(c, adam_alpha(lr, c->step), (c->xch.hook && c->xch.reduce_grads) ? 1.0f / (float)c->xch.world : 1.0f);
     if (rc) return rc;
   }
   const int ema = apply ? ema_due(c) : EMA_NONE;
@@ -1324,8 +861,8 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
     h[3] = (unsigned)(counter >> 32);
   }
   // a sharpness-aware or clipped step is enqueued eagerly also under "graphs" (two walks flip the parities twice; same bytes)
-  const bool sharp = apply && (c->sam_rho > 0.0 || c->clip_norm > 0.0);
-  if (c->use_graphs && !c->profile && !c->hook && !sharp) {   // the exchange hook enqueues foreign work: no capture
+  const bool sharp = apply && sharp_step(c);
+  if (c->use_graphs && !c->profile && !c->xch.hook && !sharp) {   // the exchange hook enqueues foreign work: no capture
     // only the Adam / dropout nodes and the gather of a descriptor-only batch read the mailbox
     const int mail = (apply || gen_dropout || c->x_lazy) ? c->mail_cur : -1;
     // the accumulator parities of the statistics hand-over are baked into the captured kernel arguments
@@ -1352,13 +889,13 @@ int mww_train_step(mww_ctx* c, int B, float lr, int flags) {
       c->graphs.push_back({B, flags, mail, ckey, mkey, exec});
     }
     HIPCHK(hipGraphLaunch(exec, c->stream));
-    if (ema) { c->ema_updates += 1; invalidate_ema_bn(c); }
+    ema_enqueued(c, ema);
     return mail_commit(c);
   }
   rc = step_sequence(c, B, flags, ema);
   if (rc) return rc;
   HIPCHK(hipGetLastError());
-  if (ema) { c->ema_updates += 1; invalidate_ema_bn(c); }
+  ema_enqueued(c, ema);
   return mail_commit(c);
 }
 
@@ -1368,17 +905,15 @@ int mww_apply_gradients(mww_ctx* c, float lr, float gscale) {
   c->step += 1;
   int rc = push_hyper(c, adam_alpha(lr, c->step), gscale);
   if (rc) return rc;
-  if (c->clip_norm > 0.0) {   // the gradient as it stands in the buffer is clipped; grad_scale multiplies behind it, inside Adam
-    rc = enqueue_final_norm(c, true);
-    if (rc) return rc;
-  }
+  rc = enqueue_clip(c);   // the gradient as it stands in the buffer is clipped; grad_scale multiplies behind it, inside Adam
+  if (rc) return rc;
   rc = enqueue_adam(c);
   if (rc) return rc;
   const int ema = ema_due(c);
   rc = enqueue_ema(c, ema);
   if (rc) return rc;
   HIPCHK(hipGetLastError());
-  if (ema) { c->ema_updates += 1; invalidate_ema_bn(c); }
+  ema_enqueued(c, ema);
   return mail_commit(c);
 }
 
@@ -1400,90 +935,6 @@ int mww_forward(mww_ctx* c, int B, int training, int update_metrics) {
   return mail_commit(c);
 }
 
-// ---- BatchNorm re-estimation for the weight average (kernels_bnre.hip.h)
-int mww_bn_reestimate_begin(mww_ctx* c) {
-  if (!c) return fail(MWW_ERR_INVALID, "null context");
-  if (!c->ema || c->ema_updates == 0) return fail(MWW_ERR_INVALID, "bn_reestimate needs a weight average that has taken an update");
-  HIPCHK(hipSetDevice(c->device));
-  if (!c->ema_bn) MWW_TRY(dev_alloc(&c->ema_bn, (size_t)c->S));
-  if (!c->bnre_acc) MWW_TRY(dev_alloc(&c->bnre_acc, (size_t)c->S));
-  HIPCHK(hipMemsetAsync(c->bnre_acc, 0, (size_t)c->S * sizeof(double), c->stream));
-  c->bnre_batches = 0;
-  return MWW_OK;
-}
-
-int mww_bn_reestimate_batch(mww_ctx* c, int B) {
-  if (!c || B <= 0 || B > c->max_batch) return fail(MWW_ERR_INVALID, "bad batch size");
-  if (c->bnre_batches < 0) return fail(MWW_ERR_STATE, "bn_reestimate: no pass is open (call mww_bn_reestimate_begin; an update of the average closes a pass)");
-  if (c->have_batch < B) return fail(MWW_ERR_STATE, "forward needs a batch of at least B rows");
-  HIPCHK(hipSetDevice(c->device));
-  int rc = batch_ready(c);
-  if (rc) return rc;
-  // the forward of mww_forward(training = 1, update_metrics = 0) - batch statistics, moving statistics untouched, no loss, no
-  // metrics, no dropout - standing on the average (with "weight_qat": on its shadow); never captured
-  EmaSource source(c, true);
-  c->ema_src = true;
-  rc = refresh_shadow(c);
-  if (rc) return rc;
-  rc = c->model->enqueue_forward(c, B, true, false, false, false);
-  if (rc) return rc;
-  rc = join_side(c);
-  if (rc) return rc;
-  rc = c->model->enqueue_bn_collect(c, B);   // directly behind the forward: its accumulator parity is still the current one
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  c->bnre_batches += 1;
-  return mail_commit(c);
-}
-
-int mww_bn_reestimate_commit(mww_ctx* c) {
-  if (!c) return fail(MWW_ERR_INVALID, "null context");
-  if (c->bnre_batches <= 0) return fail(MWW_ERR_STATE, "bn_reestimate: commit without a collected batch");
-  HIPCHK(hipSetDevice(c->device));
-  Launcher lp{c};
-  lp.begin("bn_reestimate_commit");
-  launch_bnre_commit(BnreCommitArgs{c->bnre_acc, c->ema_bn, (double)c->bnre_batches, (int)c->S}, c->stream);
-  lp.end();
-  HIPCHK(hipGetLastError());
-  c->bnre_batches = -1;
-  c->ema_bn_valid = true;
-  return MWW_OK;
-}
-
-int mww_bn_reestimate_windows(mww_ctx* c, const mww_window* windows, int64_t n, int batch) {
-  if (!c || !windows || batch <= 0 || batch > c->max_batch) return fail(MWW_ERR_INVALID, "bad re-estimation arguments");
-  if (n <= 0 || n % batch != 0) return fail(MWW_ERR_INVALID, "bn_reestimate: the window count must be a positive multiple of the batch size (every batch weighs the same)");
-  if (!c->ema || c->ema_updates == 0) return fail(MWW_ERR_INVALID, "bn_reestimate needs a weight average that has taken an update");
-  // the first batch is assembled before the pass opens: windows the stores refuse leave the context as it was
-  int rc = mww_assemble_batch(c, windows, nullptr, batch, 0, 0);
-  if (!rc) rc = mww_bn_reestimate_begin(c);
-  for (int64_t s = 0; s < n && !rc; s += batch) {
-    if (s) rc = mww_assemble_batch(c, windows + s, nullptr, batch, 0, 0);
-    if (!rc) rc = mww_bn_reestimate_batch(c, batch);
-    c->shadow_held = c->ema;   // the average cannot change between the batches: the first batch's shadow serves them all
-  }
-  c->shadow_held = nullptr;
-  if (rc) { c->bnre_batches = -1; return rc; }
-  return mww_bn_reestimate_commit(c);
-}
-
-int mww_get_ema_bn_state(mww_ctx* c, float* h, int64_t n, int* valid) {
-  if (!c || !c->ema) return fail(MWW_ERR_INVALID, "no weight average installed: call mww_set_weight_ema first");
-  if (n != c->S) return fail(MWW_ERR_INVALID, "BN state size mismatch");
-  if (valid) *valid = c->ema_bn_valid ? 1 : 0;
-  return h ? copy_out(c, h, c->ema_bn_valid ? c->ema_bn : c->bn_state, (size_t)n * sizeof(float)) : MWW_OK;
-}
-int mww_set_ema_bn_state(mww_ctx* c, const float* h, int64_t n) {
-  if (!c || !c->ema) return fail(MWW_ERR_INVALID, "no weight average installed: call mww_set_weight_ema first");
-  if (!h || n != c->S) return fail(MWW_ERR_INVALID, "BN state size mismatch");
-  HIPCHK(hipSetDevice(c->device));
-  if (!c->ema_bn) MWW_TRY(dev_alloc(&c->ema_bn, (size_t)c->S));
-  MWW_TRY(copy_in(c, c->ema_bn, h, (size_t)n * sizeof(float)));
-  c->bnre_batches = -1;
-  c->ema_bn_valid = true;
-  return MWW_OK;
-}
-
 int mww_evaluate_windows(mww_ctx* c, const mww_window* windows, const float* labels, int64_t n, int batch) {
   if (!c || !windows || !labels || n < 0 || batch <= 0 || batch > c->max_batch) return fail(MWW_ERR_INVALID, "bad evaluation arguments");
   std::vector<float> ones((size_t)batch, 1.0f);
@@ -1495,10 +946,10 @@ int mww_evaluate_windows(mww_ctx* c, const mww_window* windows, const float* lab
     if (!rc) rc = mww_forward(c, b, 0, 1);
     c->bn_eval_ready = c->model->eval_fold_cached();   // the weights cannot change between the batches of this call
     // ... so the first batch's shadow serves them all (the source mww_forward chose: the master, or the weight average)
-    c->shadow_held = ema_serves(c) ? c->ema : c->params;
+    hold_shadow(c, eval_source(c));
   }
   c->bn_eval_ready = false;
-  c->shadow_held = nullptr;
+  hold_shadow(c, nullptr);
   return rc;
 }
 
@@ -1621,19 +1072,12 @@ const OptionRow kOptions[] = {
 int set_core_option(mww_ctx* c, const std::string& name, int64_t v) {
   const std::pair<const char*, bool*> flags[] = {{"graphs", &c->use_graphs}, {"profile", &c->profile}, {"side_stream", &c->use_side}, {"bn_inline", &c->bn_inline},
                                                  {"tail_roles", &c->tail_roles}, {"fused_input", &c->fused_input}};
-  const std::pair<const char*, int*> ints[] = {{"grad_buckets", &c->grad_buckets}, {"assemble_split", &c->asm_split}, {"grid_head", &c->grid_head}};
+  const std::pair<const char*, int*> ints[] = {{"grad_buckets", &c->xch.buckets}, {"assemble_split", &c->asm_split}, {"grid_head", &c->grid_head}};
   for (auto& f : flags) if (name == f.first) *f.second = v != 0;
   for (auto& f : ints) if (name == f.first) *f.second = (int)v;
   if (name == "bce_from_logits") c->bce_clipped = v == 0;
-  if (name == "weight_qat") {
-    if (v && !c->shadow) return fail(MWW_ERR_INVALID, "weight_qat needs a channel map: call mww_set_weight_qat first");
-    if (c->weight_qat != (v != 0)) invalidate_ema_bn(c);
-    c->weight_qat = v != 0;
-  }
-  if (name == "ema_forward") {
-    if (v && !c->ema) return fail(MWW_ERR_INVALID, "ema_forward needs the weight average: call mww_set_weight_ema first");
-    c->ema_forward = v != 0;
-  }
+  if (name == "weight_qat") MWW_TRY(set_weight_qat_enabled(c, v != 0));
+  if (name == "ema_forward") MWW_TRY(set_ema_forward(c, v != 0));
   if (name == "profile") {   // (the events recorded so far)
     for (auto& e : c->prof) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     c->prof.clear();

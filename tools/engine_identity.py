@@ -4,8 +4,10 @@ the probabilities / logits / loss / metric counters of those steps and of one in
 mww_evaluate_windows, the p1 / g1 / bn1 tensors of mww_debug_read, and (`sequence`) the outputs and parameters of a
 training-mode forward followed by further train steps, which leaves the accumulator parities of the statistics hand-over out of
 step with each other and, under "graphs", ends on a replayed graph.  For the cases that ask for it, `profile` is the sha256 of
-the launch NAMES one more step records under option "profile" (no times).  The kernels sum in a fixed order, so a change that
-moves no arithmetic leaves every hash as it was.
+the launch NAMES one more step records under option "profile" (no times).  The cases that install a step feature also hash what
+that feature hands back (`fwd_params`: mww_get_forward_params, `ema`: mww_get_ema_state, `ema_bn`: mww_get_ema_bn_state, `norms`:
+mww_get_grad_norms), after the three steps and again at the end.  The kernels sum in a fixed order, so a change that moves no
+arithmetic leaves every hash as it was.
 
     python tools/engine_identity.py --lib A.so > a.jsonl      # every case
     python tools/engine_identity.py --lib B.so > b.jsonl
@@ -16,7 +18,10 @@ The cases: the default MixedNet under every schedule option of either owner, the
 under the graph engine's options, the Inception variant (two stem layers, dilation, sub-spectral groups, dropout), MixedNet
 flag sets on the graph engine - generated dropout, residual branches, the attention / pooled heads, no first convolution,
 captured graphs - both engines behind a world-1 pass-through exchange hook (sync-BN + gradient exchange), and the two-bucket
-gradient exchange.  Batches come from a feature store through mww_assemble_batch (descriptor-only where the model gathers).
+gradient exchange - and the step features on the default MixedNet (block engine) and on a MixedNet of the graph engine: a
+"weight_qat" map, a weight average (every second step; "ema_forward" for the inference forward and the evaluation), a BatchNorm
+re-estimation pass in front of that evaluation, sharpness-aware steps, clipping, both, and QAT + the average in a captured
+step.  Batches come from a feature store through mww_assemble_batch (descriptor-only where the model gathers).
 No oracle is consulted: this compares builds.
 """
 import argparse
@@ -29,7 +34,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-FIELDS = ("params", "adam", "bn_state", "grads", "outputs", "metrics", "forward", "evaluate", "debug", "sequence", "profile")
+FIELDS = ("params", "adam", "bn_state", "grads", "outputs", "metrics", "forward", "evaluate", "debug", "sequence", "profile",
+          "fwd_params", "ema", "ema_bn", "norms")
+# step features a case installs -> the fields only such a case has ("-" elsewhere, like `profile`)
+FEATURE_FIELDS = {"weight_qat": ("fwd_params",), "weight_ema": ("fwd_params", "ema", "ema_bn"), "bn_reestimate": ("fwd_params", "ema", "ema_bn"),
+                  "sharpness_aware": ("norms",), "grad_clip": ("norms",)}
+FEATURE_CASES = (("weight_qat", {}), ("weight_ema", {}), ("bn_reestimate", {}), ("sharpness_aware", {}), ("grad_clip", {}),
+                 ("sharpness_aware+grad_clip", {}), ("weight_qat+weight_ema", {"graphs": 1}))
 STEPS = 3
 # train steps of `sequence`: one - or, under "graphs", one more than the mailbox ring has slots (kRing = 8), since a captured step
 # is replayed only when mailbox slot and accumulator parities recur
@@ -42,7 +53,8 @@ INCEPTION_OPTIONS = ({}, {"graph_planar": 0}, {"graph_static_shapes": 0}, {"grap
 
 
 def cases(emulator):
-    """(name, kind, flags, B, T, options, hook[, profile]) - hook: None or (sync_bn, reduce_grads); profile: hash the launch names"""
+    """(name, kind, flags, B, T, options, hook[, profile[, features]]) - hook: None or (sync_bn, reduce_grads); profile: hash the
+    launch names; features: "+"-joined keys of FEATURE_FIELDS"""
     import engine_checks as ec
     mix = (4, 60) if emulator else (6, 194)
     note = (3, 204) if emulator else (6, 204)   # (first-conv stride 3: the shortest length the emulator tests run)
@@ -66,11 +78,14 @@ def cases(emulator):
     out.append(("mixednet/hook", "mixednet", ec.DEF, mix[0], mix[1], {}, (True, True)))
     out.append(("inception/hook", "inception", ec.INC, inc[0], inc[1], {}, (True, True)))
     out.append(("mixednet/grad_buckets=2", "mixednet", ec.DEF, mix[0], mix[1], {"grad_buckets": 2}, (False, True)))
+    for kind, flags, (B, T) in (("mixednet", ec.DEF, mix), ("graph_mixednet", ec.GRAPH_MIXEDNET, gmix)):
+        for feats, o in FEATURE_CASES:
+            out.append(("%s/%s%s" % (kind, feats, "," + tag(o) if o else ""), kind, flags, B, T, o, None, False, feats))
     return out
 
 
-def run_case(lib, name, kind, flags, B, T, options, hook, profile=False):
-    from microwakeword_amd import native
+def run_case(lib, name, kind, flags, B, T, options, hook, profile=False, features=""):
+    from microwakeword_amd import native, qat
     from microwakeword_amd.layout import GraphMixedNetLayout, InceptionLayout, MixedNetLayout
     rng = np.random.default_rng(int(hashlib.sha256(name.encode()).hexdigest()[:8], 16))
     lay = {"mixednet": MixedNetLayout, "inception": InceptionLayout, "graph_mixednet": GraphMixedNetLayout}[kind](flags, T)
@@ -80,6 +95,16 @@ def run_case(lib, name, kind, flags, B, T, options, hook, profile=False):
     eng.set_params(rng.normal(0.0, 0.2, eng.n_params).astype(np.float32))
     if hook:
         eng.set_allreduce_hook(lambda ptr, n, fl: None, world_size=1, sync_bn=hook[0], reduce_grads=hook[1])
+    feats = set(features.split("+")) if features else set()
+    if "weight_qat" in feats:
+        eng.set_weight_qat_map(*qat.channel_map(lay))
+        eng.set_option("weight_qat", 1)
+    if feats & {"weight_ema", "bn_reestimate"}:
+        eng.set_weight_ema(0.9, every_steps=2)
+    if "sharpness_aware" in feats:
+        eng.set_sharpness_aware(0.05)
+    if "grad_clip" in feats:
+        eng.set_grad_clip(0.1)
     for k, v in options.items():
         eng.set_option(k, v)
     n_win = (STEPS + 1) * B + 2 * B + 1   # train steps, the inference forward, an evaluation of two batches and a part
@@ -99,6 +124,19 @@ def run_case(lib, name, kind, flags, B, T, options, hook, profile=False):
     def metrics():
         return bytes(eng.metrics_raw())
 
+    def add_features():
+        fields = {f for k in feats for f in FEATURE_FIELDS[k]}
+        if "fwd_params" in fields:
+            add("fwd_params", eng.get_forward_params())
+        if "ema" in fields:
+            ema, updates = eng.get_ema_state()
+            add("ema", ema, np.int64(updates))
+            stats, valid = eng.get_ema_bn_state()
+            add("ema_bn", stats, np.int64(valid))
+        if "norms" in fields:
+            add("norms", np.float64(eng.get_grad_norms()))
+        return fields
+
     for s in range(STEPS):
         w = slice(s * B, (s + 1) * B)
         eng.set_targets((rng.random(B) < 0.5).astype(np.float32), rng.choice([0.5, 1.0, 2.0], size=B).astype(np.float32))
@@ -114,6 +152,9 @@ def run_case(lib, name, kind, flags, B, T, options, hook, profile=False):
     add("grads", eng.get_grads())
     for tname in ("p1", "g1", "bn1"):
         add("debug", eng.debug_read(tname, B, B * T * 64))   # (capacity: no first tensor is wider than 64 channels)
+    add_features()
+    if feats & {"weight_ema", "bn_reestimate"}:   # (the average holds the copy behind the second step)
+        eng.set_option("ema_forward", 1)
     w = slice(STEPS * B, (STEPS + 1) * B)
     eng.assemble(win[w], None, 0, 0)
     eng.forward(B, training=False)
@@ -121,6 +162,9 @@ def run_case(lib, name, kind, flags, B, T, options, hook, profile=False):
     add("forward", p, z)
     eng.metrics_reset()
     ev = win[(STEPS + 1) * B:]
+    if "bn_reestimate" in feats:
+        eng.bn_reestimate_windows(ev[:2 * B], B)
+        add_features()
     eng.evaluate_windows(ev, (rng.random(ev.shape[0]) < 0.5).astype(np.float32), B)
     h["evaluate"].update(metrics())
 
@@ -143,8 +187,9 @@ def run_case(lib, name, kind, flags, B, T, options, hook, profile=False):
         eng.profile_read()   # (nothing of the calls above)
         step(0)
         h["profile"].update("\n".join(n for n, _ in eng.profile_read()).encode())
+    absent = set(FIELDS[FIELDS.index("profile") + 1:]) - add_features() | (set() if profile else {"profile"})
     eng.close()
-    return json.dumps(dict(case=name, **{f: h[f].hexdigest()[:32] if f != "profile" or profile else "-" for f in FIELDS}))
+    return json.dumps(dict(case=name, **{f: "-" if f in absent else h[f].hexdigest()[:32] for f in FIELDS}))
 
 
 def compare(path_a, path_b):
@@ -154,7 +199,7 @@ def compare(path_a, path_b):
         if name in b:
             for f in FIELDS:
                 same = a[name][f] == b[name][f]
-                print("%-36s %-9s %s %s %s" % (name, f, a[name][f], b[name][f], "equal" if same else "DIFFERENT"))
+                print("%-46s %-10s %s %s %s" % (name, f, a[name][f], b[name][f], "equal" if same else "DIFFERENT"))
                 if not same:
                     bad.append(name + " " + f)
     print("%d cases, %d hashes: %s" % (len(a), len(a) * len(FIELDS), "all equal" if not bad else "NOT equal: " + ", ".join(bad)))
