@@ -139,9 +139,10 @@ def check_forwards_own_statistics(lib, kind, inline, extra=None):
 
 
 # ---------------------------------------------------------------------------------------------- (c) the float64 oracle
-def oracle_statistics(lay, kind, vec, xs, b):
-    """batch mean / biased variance of every BN input at the weights ``vec``, averaged over the batches, in bn_state layout"""
-    om = mo.OracleModel("inception" if kind == "inception" else "mixednet", wq.flags_of(kind), T)
+def oracle_statistics(lay, kind, vec, xs, b, flags=None):
+    """batch mean / biased variance of every BN input at the weights ``vec``, averaged over the batches, in bn_state layout
+    (``flags``: of a model other than the kind's own, at the same T)"""
+    om = mo.OracleModel("inception" if kind == "inception" else "mixednet", wq.flags_of(kind) if flags is None else flags, T)
     weights = lay.unpack(vec, np.zeros(lay.n_state, np.float32))   # moving statistics zero: new = 0 * 0.99 + stat * (1 - 0.99)
     om.set_weights(weights)
     names = [v.name for v in om.vars]

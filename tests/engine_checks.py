@@ -362,6 +362,140 @@ def check_train_steps(lib, B=6, T=194, steps=2, grid=2, lr=1e-3, graphs=False, f
         eng.close()
 
 
+def mixednet_step_reads(eng, lay, B, flags, a0_shape=None):
+    """The engine half of one train step's comparison: everything compare_mixednet_step needs of an engine that has just
+    run a step on B windows.  `a0_shape`: of the first convolution's pre-activation ([B, ...] as the oracle taps it)."""
+    pr, z, loss = eng.read_outputs(B)
+    got = dict(pr=pr, z=z, loss=loss, a0=None, p=[], bn=[])
+    if a0_shape is not None and not flags.get("st_bf16"):
+        got["a0"] = eng.debug_read("a0", B, int(np.prod(a0_shape))).reshape(a0_shape)
+    for k, b in enumerate(lay.blocks):
+        got["p"].append(eng.debug_read("p%d" % (k + 1), B, B * b.tout * b.cout).reshape(B, b.tout, b.cout).astype(np.float64))
+        got["bn"].append(eng.debug_read("bn%d" % (k + 1), B, 9 * b.cout).reshape(9, b.cout).astype(np.float64))
+    got["grads"], got["params"], got["state"] = eng.get_grads(), eng.get_params(), eng.get_bn_state()
+    return got
+
+
+def merge_rank_reads(reads):
+    """The reads of W ranks of a sync-BN step (mixednet_step_reads / inception_step_reads / graph_mixednet_step_reads per rank,
+    in rank order) as ONE step on the global batch: the per-window tensors concatenated along the batch, the loss the mean of
+    the rank losses (local means over equal shares), the flat gradient the exchanged rank sum times 1 / W (what Adam consumed),
+    and gradient, parameters, BN state and the BN scale / shift rows the SAME BYTES on every rank."""
+    W = len(reads)
+    for r in range(1, W):
+        for k in ("grads", "params", "state"):
+            np.testing.assert_array_equal(reads[0][k], reads[r][k], err_msg="%s of rank %d differ from rank 0's" % (k, r))
+        for i, bn in enumerate(reads[r].get("bn", [])):
+            np.testing.assert_array_equal(reads[0]["bn"][i][:2], bn[:2], err_msg="BN scale / shift %d of rank %d" % (i + 1, r))
+    got = dict(reads[0], loss=float(np.mean([g["loss"] for g in reads])), grads=reads[0]["grads"] / np.float32(W))
+    for k in ("pr", "z"):
+        got[k] = np.concatenate([g[k] for g in reads])
+    if reads[0].get("a0") is not None:
+        got["a0"] = np.concatenate([g["a0"] for g in reads])
+    if "p" in reads[0]:
+        got["p"] = [np.concatenate([g["p"][i] for g in reads]) for i in range(len(reads[0]["p"]))]
+    return got
+
+
+def compare_mixednet_step(got, B, lay, om, taps, x, y, w, lr, flags, s, worst):
+    """The comparison half of _check_train_steps for one step: `got` (mixednet_step_reads of one engine, or merge_rank_reads of
+    the ranks of a sync-BN step) against oracle `om` on the B windows (x, y, w); `taps`: of om.logits(x, True).  Advances `om`
+    by the step and returns (the oracle's probabilities, its packed parameters, its packed BN state)."""
+    lowp = _lowp(flags)
+    loss_tol, l2_tol, el_tol, med_tol = _mixednet_tols(flags)
+    pr, loss = got["pr"], got["loss"]
+    # The engine's own ReLU decisions at the BN outputs are read back, checked to differ from the float64 oracle's only
+    # where the oracle's value is within rounding of zero, and imposed on the oracle: the gradients compared below are
+    # those of identical graphs.  (One flipped unit moves every upstream gradient by ~1/sqrt(units): a random sweep over
+    # (frames, batch) sizes hit such a unit in 13 % of the cases, each time with |value| < 2e-7.)
+    masks, flips = {}, 0
+    if "conv1.pre" in taps and not flags.get("st_bf16"):
+        # ... and the first convolution's own ReLU (no BN in front of it): the B = 600 notebook batch of the GPU suite holds
+        # one pre-activation of 2e-7 that float32 and float64 put on different sides of zero (3e-4 of conv1's gradient)
+        ref0 = taps["conv1.pre"].detach().numpy()
+        a0 = got["a0"]
+        m0 = a0 > 0
+        d0 = m0 != (ref0 > 0)
+        flips += int(d0.sum())
+        assert np.abs(ref0[d0]).max(initial=0.0) <= (2e-2 if lowp else 2e-5) * max(1.0, np.abs(ref0).max()), np.abs(ref0[d0]).max()
+        masks["conv1"] = np.ascontiguousarray(m0.transpose(0, 2, 1))
+    for k, b in enumerate(lay.blocks):
+        pk, bn = got["p"][k], got["bn"][k]
+        m = (pk * bn[0] + bn[1]) > 0
+        ref = taps["b%d.r0.bn_out" % k].detach().numpy()
+        diff = m != (ref > 0)
+        flips += int(diff.sum())
+        assert np.abs(ref[diff]).max(initial=0.0) <= (2e-2 if lowp else 2e-5) * max(1.0, np.abs(ref).max()), (k, np.abs(ref[diff]).max())
+        masks["b%d.r0" % k] = np.ascontiguousarray(m.transpose(0, 2, 1))
+    n_units = sum(B * b.tout * b.cout for b in lay.blocks)
+    assert flips <= (2e-3 * n_units if lowp else max(8, 2e-5 * n_units)), flips
+    lo, po, grads, _ = om.loss_and_grads(x, y, w, relu_masks=masks)
+    g = got["grads"]
+    gref = oracle_grads_native_order(lay, om, grads)
+    scale = max(1e-6, float(np.abs(gref).max()))
+    worst["grad"] = max(worst.get("grad", 0), float(np.abs(g - gref).max() / scale))
+    assert abs(loss - lo) <= loss_tol * max(1.0, abs(lo)), (loss, lo)
+    assert np.abs(pr - po).max() <= (5e-3 if lowp else FWD_TOL)
+    # per parameter tensor: error relative to that tensor's own gradient scale.  The depthwise
+    # biases are followed by a BatchNorm, so their true gradient is exactly zero: what any fp32
+    # implementation returns there is cancellation noise (sum of O(B*T) terms), bounded in
+    # absolute terms instead.
+    off = 0
+    for name, n in lay.segments():
+        a, r = g[off:off + n], gref[off:off + n]
+        off += n
+        if name.endswith("dw.bias"):
+            assert np.abs(a - r).max() <= (2e-2 if lowp else 2e-3) * scale, (s, name, np.abs(a - r).max(), scale)
+        else:
+            # fp32 (engine) vs fp64 (oracle): an activation within ~1e-7 of zero can take the other
+            # side of the ReLU in one of them (expected ~once per 1e6 activations); such a flip moves a
+            # handful of weight gradients by that element's contribution.  Hence a tight bound on the
+            # relative L2 error of the tensor and a looser one on any single element.
+            seg_scale = max(float(np.abs(r).max()), 1e-3 * scale)
+            l2 = float(np.linalg.norm(a - r) / max(np.linalg.norm(r), 1e-3 * scale * np.sqrt(n)))
+            # measured: 1e-6 typical.  The BN gamma / beta and dense-bias gradients are short signed sums that may nearly
+            # cancel: float32 summation noise reaches a few 1e-4 of their norm in ~1 % of random cases
+            loose = name == "dense.bias" or name.endswith((".bn.gamma", ".bn.beta"))
+            assert l2 <= (max(l2_tol, 1e-3) if loose else l2_tol), (s, name, l2)
+            assert np.abs(a - r).max() <= el_tol * seg_scale, (s, name, np.abs(a - r).max(), seg_scale)
+            worst["grad"] = max(worst.get("grad", 0), l2)
+            worst.setdefault("l2s", []).append(l2)
+            worst["ratio"] = max(worst.get("ratio", 0), l2 / (max(l2_tol, 1e-3) if loose else l2_tol), float(np.abs(a - r).max() / (el_tol * seg_scale)))
+    om.train_step(x, y, w, lr, relu_masks=masks)
+    p_ref, s_ref = lay.pack(om.get_weights())
+    p_got, s_got = got["params"], got["state"]
+    # Adam normalises every step to ~lr, so compare in units of lr.  Parameters whose true gradient
+    # is (mathematically) zero — the depthwise biases, cancelled by the BatchNorm that follows —
+    # carry only fp32 rounding noise that Adam amplifies to O(lr) in ANY fp32 implementation:
+    # they are excluded here and bounded by 2*lr instead.
+    well = np.abs(gref) > (1e-2 if lowp else 1e-4) * scale
+    assert np.abs(p_got - p_ref)[well].max() <= (0.2 if lowp else 0.05) * lr, (s, np.abs(p_got - p_ref)[well].max())
+    assert np.abs(p_got - p_ref).max() <= 2.0 * lr
+    assert np.abs(s_got - s_ref).max() <= (1e-4 if lowp else 1e-5) * max(1.0, np.abs(s_ref).max())
+    worst["param"] = max(worst.get("param", 0), float(np.abs(p_got - p_ref)[well].max()))
+    worst["ratio"] = max(worst.get("ratio", 0), abs(loss - lo) / (loss_tol * max(1.0, abs(lo))), float(np.abs(pr - po).max()) / (5e-3 if lowp else FWD_TOL),
+                         worst["param"] / ((0.2 if lowp else 0.05) * lr),
+                         float(np.abs(s_got - s_ref).max() / ((1e-4 if lowp else 1e-5) * max(1.0, np.abs(s_ref).max()))))
+    return po, p_ref, s_ref
+
+
+def _mixednet_tols(flags):
+    """(loss, per-tensor relative L2, per-element, median L2) bounds of a MixedNet train step against the float64 oracle."""
+    # bf16-operand mode: the oracle rounds the same operands, but an fp32 value (engine) and its fp64 twin
+    # (oracle) within 1e-7 of a bf16 rounding boundary round apart (a few per 1e5 operands, each a 0.4 %
+    # operand error), so the bounds are those of that noise instead of fp32 rounding
+    # In that mode a ReLU network's gradient is also far more exposed to decision flips (an operand error
+    # eps flips ~0.4*eps of the units, moving the gradient by ~sqrt of that), so the engine's own ReLU
+    # decisions are read back, checked to differ from the oracle's only at near-zero values, and imposed
+    # on the oracle (as in the Inception check): what is compared are identical graphs.
+    loss_tol, l2_tol, el_tol, med_tol = (1e-3, 2e-2, 6e-2, 6e-3) if _lowp(flags) else (1e-5, 1e-4, 1e-3, 2e-5)
+    if flags.get("st_bf16"):
+        # two more rounded tensors per block; the float32 and the float64 oracle differ from each other by as much
+        # (median 3e-3, worst 1e-2 per tensor on the default topology: the noise is that of the mode, not of the engine)
+        l2_tol, med_tol = 3e-2, 1.2e-2
+    return loss_tol, l2_tol, el_tol, med_tol
+
+
 def _check_train_steps(eng, lay, om, B, T, steps, grid, lr, graphs, flags, raw_u16_range):
     if grid:
         for k in ("grid_fwd", "grid_bwd", "grid_head"):
@@ -372,19 +506,8 @@ def _check_train_steps(eng, lay, om, B, T, steps, grid, lr, graphs, flags, raw_u
     worst = {}
     engine_outputs = []   # (probabilities, logits, labels) of every step as the engine produced them
     oracle_probs = []     # the float64 oracle's probabilities of every step
-    # bf16-operand mode: the oracle rounds the same operands, but an fp32 value (engine) and its fp64 twin
-    # (oracle) within 1e-7 of a bf16 rounding boundary round apart (a few per 1e5 operands, each a 0.4 %
-    # operand error), so the bounds are those of that noise instead of fp32 rounding
-    # In that mode a ReLU network's gradient is also far more exposed to decision flips (an operand error
-    # eps flips ~0.4*eps of the units, moving the gradient by ~sqrt of that), so the engine's own ReLU
-    # decisions are read back, checked to differ from the oracle's only at near-zero values, and imposed
-    # on the oracle (as in the Inception check): what is compared are identical graphs.
     lowp = _lowp(flags)
-    loss_tol, l2_tol, el_tol, med_tol = (1e-3, 2e-2, 6e-2, 6e-3) if lowp else (1e-5, 1e-4, 1e-3, 2e-5)
-    if flags.get("st_bf16"):
-        # two more rounded tensors per block; the float32 and the float64 oracle differ from each other by as much
-        # (median 3e-3, worst 1e-2 per tensor on the default topology: the noise is that of the mode, not of the engine)
-        l2_tol, med_tol = 3e-2, 1.2e-2
+    loss_tol, l2_tol, el_tol, med_tol = _mixednet_tols(flags)
     for s in range(steps):
         x = synth_x(rng, B, T, raw_u16_range)
         y = (rng.random(B) < 0.5).astype(np.float32)
@@ -392,79 +515,12 @@ def _check_train_steps(eng, lay, om, B, T, steps, grid, lr, graphs, flags, raw_u
         eng.set_batch(x)
         eng.set_targets(y, w)
         eng.train_step(B, lr)
-        pr, z, loss = eng.read_outputs(B)
-        engine_outputs.append((pr.copy(), z.copy(), y.copy()))
-        # The engine's own ReLU decisions at the BN outputs are read back, checked to differ from the float64 oracle's only
-        # where the oracle's value is within rounding of zero, and imposed on the oracle: the gradients compared below are
-        # those of identical graphs.  (One flipped unit moves every upstream gradient by ~1/sqrt(units): a random sweep over
-        # (frames, batch) sizes hit such a unit in 13 % of the cases, each time with |value| < 2e-7.)
-        taps, masks, flips = {}, {}, 0
+        taps = {}
         om.logits(x, True, taps=taps)
-        if "conv1.pre" in taps and not flags.get("st_bf16"):
-            # ... and the first convolution's own ReLU (no BN in front of it): the B = 600 notebook batch of the GPU suite holds
-            # one pre-activation of 2e-7 that float32 and float64 put on different sides of zero (3e-4 of conv1's gradient)
-            ref0 = taps["conv1.pre"].detach().numpy()
-            a0 = eng.debug_read("a0", B, ref0.size).reshape(ref0.shape)
-            m0 = a0 > 0
-            d0 = m0 != (ref0 > 0)
-            flips += int(d0.sum())
-            assert np.abs(ref0[d0]).max(initial=0.0) <= (2e-2 if lowp else 2e-5) * max(1.0, np.abs(ref0).max()), np.abs(ref0[d0]).max()
-            masks["conv1"] = np.ascontiguousarray(m0.transpose(0, 2, 1))
-        for k, b in enumerate(lay.blocks):
-            pk = eng.debug_read("p%d" % (k + 1), B, B * b.tout * b.cout).reshape(B, b.tout, b.cout).astype(np.float64)
-            bn = eng.debug_read("bn%d" % (k + 1), B, 9 * b.cout).reshape(9, b.cout).astype(np.float64)
-            m = (pk * bn[0] + bn[1]) > 0
-            ref = taps["b%d.r0.bn_out" % k].detach().numpy()
-            diff = m != (ref > 0)
-            flips += int(diff.sum())
-            assert np.abs(ref[diff]).max(initial=0.0) <= (2e-2 if lowp else 2e-5) * max(1.0, np.abs(ref).max()), (k, np.abs(ref[diff]).max())
-            masks["b%d.r0" % k] = np.ascontiguousarray(m.transpose(0, 2, 1))
-        n_units = sum(B * b.tout * b.cout for b in lay.blocks)
-        assert flips <= (2e-3 * n_units if lowp else max(8, 2e-5 * n_units)), flips
-        lo, po, grads, _ = om.loss_and_grads(x, y, w, relu_masks=masks)
+        got = mixednet_step_reads(eng, lay, B, flags, a0_shape=taps["conv1.pre"].shape if "conv1.pre" in taps else None)
+        engine_outputs.append((got["pr"].copy(), got["z"].copy(), y.copy()))
+        po, p_ref, s_ref = compare_mixednet_step(got, B, lay, om, taps, x, y, w, lr, flags, s, worst)
         oracle_probs.append(np.asarray(po, np.float64).copy())
-        g = eng.get_grads()
-        gref = oracle_grads_native_order(lay, om, grads)
-        scale = max(1e-6, float(np.abs(gref).max()))
-        worst["grad"] = max(worst.get("grad", 0), float(np.abs(g - gref).max() / scale))
-        assert abs(loss - lo) <= loss_tol * max(1.0, abs(lo)), (loss, lo)
-        assert np.abs(pr - po).max() <= (5e-3 if lowp else FWD_TOL)
-        # per parameter tensor: error relative to that tensor's own gradient scale.  The depthwise
-        # biases are followed by a BatchNorm, so their true gradient is exactly zero: what any fp32
-        # implementation returns there is cancellation noise (sum of O(B*T) terms), bounded in
-        # absolute terms instead.
-        off = 0
-        for name, n in lay.segments():
-            a, r = g[off:off + n], gref[off:off + n]
-            off += n
-            if name.endswith("dw.bias"):
-                assert np.abs(a - r).max() <= (2e-2 if lowp else 2e-3) * scale, (s, name, np.abs(a - r).max(), scale)
-            else:
-                # fp32 (engine) vs fp64 (oracle): an activation within ~1e-7 of zero can take the other
-                # side of the ReLU in one of them (expected ~once per 1e6 activations); such a flip moves a
-                # handful of weight gradients by that element's contribution.  Hence a tight bound on the
-                # relative L2 error of the tensor and a looser one on any single element.
-                seg_scale = max(float(np.abs(r).max()), 1e-3 * scale)
-                l2 = float(np.linalg.norm(a - r) / max(np.linalg.norm(r), 1e-3 * scale * np.sqrt(n)))
-                # measured: 1e-6 typical.  The BN gamma / beta and dense-bias gradients are short signed sums that may nearly
-                # cancel: float32 summation noise reaches a few 1e-4 of their norm in ~1 % of random cases
-                loose = name == "dense.bias" or name.endswith((".bn.gamma", ".bn.beta"))
-                assert l2 <= (max(l2_tol, 1e-3) if loose else l2_tol), (s, name, l2)
-                assert np.abs(a - r).max() <= el_tol * seg_scale, (s, name, np.abs(a - r).max(), seg_scale)
-                worst["grad"] = max(worst.get("grad", 0), l2)
-                worst.setdefault("l2s", []).append(l2)
-        om.train_step(x, y, w, lr, relu_masks=masks)
-        p_ref, s_ref = lay.pack(om.get_weights())
-        p_got, s_got = eng.get_params(), eng.get_bn_state()
-        # Adam normalises every step to ~lr, so compare in units of lr.  Parameters whose true gradient
-        # is (mathematically) zero — the depthwise biases, cancelled by the BatchNorm that follows —
-        # carry only fp32 rounding noise that Adam amplifies to O(lr) in ANY fp32 implementation:
-        # they are excluded here and bounded by 2*lr instead.
-        well = np.abs(gref) > (1e-2 if lowp else 1e-4) * scale
-        assert np.abs(p_got - p_ref)[well].max() <= (0.2 if lowp else 0.05) * lr, (s, np.abs(p_got - p_ref)[well].max())
-        assert np.abs(p_got - p_ref).max() <= 2.0 * lr
-        assert np.abs(s_got - s_ref).max() <= (1e-4 if lowp else 1e-5) * max(1.0, np.abs(s_ref).max())
-        worst["param"] = max(worst.get("param", 0), float(np.abs(p_got - p_ref)[well].max()))
         # keep both sides on identical weights so that errors do not compound between steps
         eng.set_params(p_ref)
         eng.set_bn_state(s_ref)
@@ -675,6 +731,71 @@ def check_inception_forward(lib, B=3, T=194, training=False, grid=None, flags=IN
     return float(np.abs(pr - po).max())
 
 
+def inception_step_reads(eng, lay, B):
+    """The engine half of one Inception train step's comparison (see mixednet_step_reads)."""
+    pr, z, loss = eng.read_outputs(B)
+    got = dict(pr=pr, z=z, loss=loss, p=[], bn=[])
+    for k, op in enumerate(lay.ops):
+        n_el = B * op["tout"] * op["filters"]
+        got["p"].append(eng.debug_read("p%d" % (k + 1), B, n_el).reshape(B, op["tout"], op["filters"]).astype(np.float64))
+        got["bn"].append(eng.debug_read("bn%d" % (k + 1), B, 9 * op["filters"]).reshape(9, op["filters"]).astype(np.float64))
+    got["grads"], got["params"], got["state"] = eng.get_grads(), eng.get_params(), eng.get_bn_state()
+    return got
+
+
+def compare_inception_step(got, B, lay, om, x, y, w, keep, lr, s, l2s):
+    """The comparison half of check_inception_train_steps for one step: `got` (inception_step_reads of one engine, or
+    merge_rank_reads of the ranks of a sync-BN step) against oracle `om` on the B windows (x, y, w) under dropout mask `keep`.
+    Advances `om` by the step, appends the tensors' relative L2 errors to `l2s` and returns the oracle's packed (parameters, BN state)."""
+    pr, loss = got["pr"], got["loss"]
+    # fp32 (engine) vs fp64 (oracle): a BN output within float32 rounding of zero can land on the other
+    # side of the ReLU (a few per million activations).  The decisions the engine took are read back
+    # (exact sign of fma(p, scale, shift)), checked to differ from the oracle's only at such near-zero
+    # values, and then imposed on the oracle so that the gradient comparison is between identical graphs.
+    taps = {}
+    om.logits(x, True, dropout_mask=keep, taps=taps)
+    masks, flips = {}, 0
+    for k, (members, op) in enumerate(zip(lay.op_members, lay.ops)):
+        pk, bn = got["p"][k], got["bn"][k]
+        m_all = (pk * bn[0] + bn[1]) > 0
+        for name, c0, cn in members:
+            m = m_all[:, :, c0:c0 + cn]
+            ref = taps[name + ".bn_out"].detach().numpy()
+            diff = m != (ref > 0)
+            flips += int(diff.sum())
+            assert np.abs(ref[diff]).max(initial=0.0) <= 2e-5 * max(1.0, np.abs(ref).max()), (name, np.abs(ref[diff]).max())
+            masks[name] = np.ascontiguousarray(m.transpose(0, 2, 1))
+    n_units = sum(B * op["tout"] * op["filters"] for op in lay.ops)
+    assert flips <= max(8, 2e-5 * n_units), (flips, n_units)   # 21 of 5e7 units at B = 1024, each within 2e-5 of zero
+    lo, po, grads, _ = om.loss_and_grads(x, y, w, dropout_mask=keep, relu_masks=masks)
+    g = got["grads"]
+    gref = lay.pack([grads[n].numpy().astype(np.float32) if kind == "param" else np.zeros(shape, np.float32)
+                     for n, shape, kind in lay.keras_vars])[0]
+    assert abs(loss - lo) <= 1e-5 * max(1.0, abs(lo)), (loss, lo)
+    assert np.abs(pr - po).max() <= FWD_TOL
+    scale = max(1e-6, float(np.abs(gref).max()))
+    off = 0
+    for name, n in lay.segments():
+        a, r = g[off:off + n], gref[off:off + n]
+        off += n
+        seg_scale = max(float(np.abs(r).max()), 1e-3 * scale)
+        l2 = float(np.linalg.norm(a - r) / max(np.linalg.norm(r), 1e-3 * scale * np.sqrt(n)))
+        # dense.bias and the BN / sub-spectral gamma, beta gradients are signed sums that may nearly cancel (and have as
+        # few as 1-4 entries): float32 summation noise reaches a few 1e-4 of their norm in ~1 % of random topologies
+        loose = name == "dense.bias" or name.endswith((".bn.gamma", ".bn.beta"))
+        assert l2 <= (1e-3 if loose else 1e-4), (s, name, l2)
+        assert np.abs(a - r).max() <= 1e-3 * seg_scale, (s, name, np.abs(a - r).max(), seg_scale)
+        l2s.append(l2)
+    om.train_step(x, y, w, lr, dropout_mask=keep, relu_masks=masks)
+    p_ref, s_ref = lay.pack(om.get_weights())
+    p_got, s_got = got["params"], got["state"]
+    well = np.abs(gref) > 1e-4 * scale
+    assert np.abs(p_got - p_ref)[well].max() <= 0.05 * lr, (s, np.abs(p_got - p_ref)[well].max())
+    assert np.abs(p_got - p_ref).max() <= 2.0 * lr
+    assert np.abs(s_got - s_ref).max() <= 1e-5 * max(1.0, np.abs(s_ref).max())
+    return p_ref, s_ref
+
+
 def check_inception_train_steps(lib, B=4, T=194, steps=2, grid=2, lr=1e-3, graphs=False, flags=INC, fuse_heads=True, options=None):
     om = perturbed_inception_oracle(T, flags)
     lay, eng = make_inception_engine(lib, T, B, om, flags, fuse_heads)
@@ -696,54 +817,8 @@ def check_inception_train_steps(lib, B=4, T=194, steps=2, grid=2, lr=1e-3, graph
         eng.set_targets(y, w)
         eng.set_dropout_mask(keep)
         eng.train_step(B, lr)
-        pr, z, loss = eng.read_outputs(B)
-        # fp32 (engine) vs fp64 (oracle): a BN output within float32 rounding of zero can land on the other
-        # side of the ReLU (a few per million activations).  The decisions the engine took are read back
-        # (exact sign of fma(p, scale, shift)), checked to differ from the oracle's only at such near-zero
-        # values, and then imposed on the oracle so that the gradient comparison is between identical graphs.
-        taps = {}
-        om.logits(x, True, dropout_mask=keep, taps=taps)
-        masks, flips = {}, 0
-        for k, (members, op) in enumerate(zip(lay.op_members, lay.ops)):
-            n_el = B * op["tout"] * op["filters"]
-            pk = eng.debug_read("p%d" % (k + 1), B, n_el).reshape(B, op["tout"], op["filters"]).astype(np.float64)
-            bn = eng.debug_read("bn%d" % (k + 1), B, 9 * op["filters"]).reshape(9, op["filters"]).astype(np.float64)
-            m_all = (pk * bn[0] + bn[1]) > 0
-            for name, c0, cn in members:
-                m = m_all[:, :, c0:c0 + cn]
-                ref = taps[name + ".bn_out"].detach().numpy()
-                diff = m != (ref > 0)
-                flips += int(diff.sum())
-                assert np.abs(ref[diff]).max(initial=0.0) <= 2e-5 * max(1.0, np.abs(ref).max()), (name, np.abs(ref[diff]).max())
-                masks[name] = np.ascontiguousarray(m.transpose(0, 2, 1))
-        n_units = sum(B * op["tout"] * op["filters"] for op in lay.ops)
-        assert flips <= max(8, 2e-5 * n_units), (flips, n_units)   # 21 of 5e7 units at B = 1024, each within 2e-5 of zero
-        lo, po, grads, _ = om.loss_and_grads(x, y, w, dropout_mask=keep, relu_masks=masks)
-        g = eng.get_grads()
-        gref = lay.pack([grads[n].numpy().astype(np.float32) if kind == "param" else np.zeros(shape, np.float32)
-                         for n, shape, kind in lay.keras_vars])[0]
-        assert abs(loss - lo) <= 1e-5 * max(1.0, abs(lo)), (loss, lo)
-        assert np.abs(pr - po).max() <= FWD_TOL
-        scale = max(1e-6, float(np.abs(gref).max()))
-        off = 0
-        for name, n in lay.segments():
-            a, r = g[off:off + n], gref[off:off + n]
-            off += n
-            seg_scale = max(float(np.abs(r).max()), 1e-3 * scale)
-            l2 = float(np.linalg.norm(a - r) / max(np.linalg.norm(r), 1e-3 * scale * np.sqrt(n)))
-            # dense.bias and the BN / sub-spectral gamma, beta gradients are signed sums that may nearly cancel (and have as
-            # few as 1-4 entries): float32 summation noise reaches a few 1e-4 of their norm in ~1 % of random topologies
-            loose = name == "dense.bias" or name.endswith((".bn.gamma", ".bn.beta"))
-            assert l2 <= (1e-3 if loose else 1e-4), (s, name, l2)
-            assert np.abs(a - r).max() <= 1e-3 * seg_scale, (s, name, np.abs(a - r).max(), seg_scale)
-            l2s.append(l2)
-        om.train_step(x, y, w, lr, dropout_mask=keep, relu_masks=masks)
-        p_ref, s_ref = lay.pack(om.get_weights())
-        p_got, s_got = eng.get_params(), eng.get_bn_state()
-        well = np.abs(gref) > 1e-4 * scale
-        assert np.abs(p_got - p_ref)[well].max() <= 0.05 * lr, (s, np.abs(p_got - p_ref)[well].max())
-        assert np.abs(p_got - p_ref).max() <= 2.0 * lr
-        assert np.abs(s_got - s_ref).max() <= 1e-5 * max(1.0, np.abs(s_ref).max())
+        got = inception_step_reads(eng, lay, B)
+        p_ref, s_ref = compare_inception_step(got, B, lay, om, x, y, w, keep, lr, s, l2s)
         eng.set_params(p_ref)
         eng.set_bn_state(s_ref)
     m = native.metrics_from_raw(eng.metrics_raw())
@@ -981,6 +1056,49 @@ def count_graph_mixednet_near_zero(flags, B, T, steps=1, lr=1e-3, seed=42):
     return total
 
 
+def graph_mixednet_step_reads(eng, B):
+    """The engine half of one graph-MixedNet train step's comparison (see mixednet_step_reads)."""
+    pr, z, loss = eng.read_outputs(B)
+    return dict(pr=pr, z=z, loss=loss, grads=eng.get_grads(), params=eng.get_params(), state=eng.get_bn_state())
+
+
+def compare_graph_mixednet_step(got, B, lay, om, x, y, w, lr, st, l2s, near_zero, loss_slack):
+    """The comparison half of check_graph_mixednet for one train step: `got` (graph_mixednet_step_reads of one engine, or
+    merge_rank_reads of the ranks of a sync-BN step) against oracle `om` on the B windows (x, y, w).  `near_zero`, `loss_slack`:
+    of graph_mixednet_near_zero on that batch.  Advances `om` by the step and returns its packed (parameters, BN state)."""
+    grad_tol = 1e-3 if near_zero == 0 else 5e-2
+    pr, loss = got["pr"], got["loss"]
+    lo, po, grads, _ = om.loss_and_grads(x, y, w)
+    g = got["grads"]
+    gref = lay.pack([grads[n].numpy().astype(np.float32) if kind == "param" else np.zeros(shape, np.float32)
+                     for n, shape, kind in lay.keras_vars])[0]
+    assert abs(loss - lo) <= 1e-5 * max(1.0, abs(lo)) + loss_slack, (loss, lo, loss_slack)
+    assert np.abs(pr - po).max() <= FWD_TOL
+    scale = max(1e-6, float(np.abs(gref).max()))
+    off = 0
+    for name, n in lay.segments():
+        a, r = g[off:off + n], gref[off:off + n]
+        off += n
+        if name.endswith(".dw.bias"):   # followed by a BatchNorm: the true gradient is zero, what remains is cancellation noise
+            assert np.abs(a - r).max() <= 2e-3 * scale, (st, name, np.abs(a - r).max())
+            continue
+        l2 = float(np.linalg.norm(a - r) / max(np.linalg.norm(r), 1e-3 * scale * np.sqrt(n)))
+        assert l2 <= grad_tol, (st, name, l2, near_zero)
+        if near_zero == 0:
+            l2s.append(l2)
+    # structural zero taps of fused MixConv groups stay exactly zero in the gradient
+    assert np.all(g[lay.grad_mask() == 0] == 0)
+    om.train_step(x, y, w, lr)
+    p_ref, s_ref = lay.pack(om.get_weights())
+    well = np.abs(gref) > (1e-4 if near_zero == 0 else 0.2) * scale
+    # every step starts from the oracle's weights, moving statistics AND Adam moments (installed below), so a step in
+    # which a one-unit decision went the other way does not loosen the steps after it: the update is always held to
+    # 5 % of an Adam step (a flagged step itself: only where the gradient is well away from the flipped unit's share)
+    assert np.abs(got["params"] - p_ref)[well].max() <= 0.05 * lr, (st, near_zero)
+    assert np.abs(got["state"] - s_ref).max() <= 1e-5 * max(1.0, np.abs(s_ref).max())
+    return p_ref, s_ref
+
+
 def check_graph_mixednet(lib, flags=GRAPH_MIXEDNET, B=3, T=100, steps=1, grid=2, graphs=False, lr=1e-3, bn_inline=None, options=None,
                          seed=42, strict=False):
     """Forward intermediates and train step of a MixedNet running on the generic conv/BN graph kernels.  bn_inline: None =
@@ -1038,38 +1156,11 @@ def check_graph_mixednet(lib, flags=GRAPH_MIXEDNET, B=3, T=100, steps=1, grid=2,
         near_zero, zabs = graph_mixednet_near_zero(om, flags, x)
         loss_slack = float(np.sum(w * 1.2e-7 * np.exp(np.minimum(zabs, 16.0))) / B)
         assert not (strict and near_zero), "step %d: %d units within float32 rounding of a ReLU zero / an attention tie" % (st, near_zero)
-        grad_tol = 1e-3 if near_zero == 0 else 5e-2
         eng.set_batch(x)
         eng.set_targets(y, w)
         eng.train_step(B, lr)
-        pr, z, loss = eng.read_outputs(B)
-        lo, po, grads, _ = om.loss_and_grads(x, y, w)
-        g = eng.get_grads()
-        gref = lay.pack([grads[n].numpy().astype(np.float32) if kind == "param" else np.zeros(shape, np.float32)
-                         for n, shape, kind in lay.keras_vars])[0]
-        assert abs(loss - lo) <= 1e-5 * max(1.0, abs(lo)) + loss_slack, (loss, lo, loss_slack)
-        scale = max(1e-6, float(np.abs(gref).max()))
-        off = 0
-        for name, n in lay.segments():
-            a, r = g[off:off + n], gref[off:off + n]
-            off += n
-            if name.endswith(".dw.bias"):   # followed by a BatchNorm: the true gradient is zero, what remains is cancellation noise
-                assert np.abs(a - r).max() <= 2e-3 * scale, (st, name, np.abs(a - r).max())
-                continue
-            l2 = float(np.linalg.norm(a - r) / max(np.linalg.norm(r), 1e-3 * scale * np.sqrt(n)))
-            assert l2 <= grad_tol, (st, name, l2, near_zero)
-            if near_zero == 0:
-                l2s.append(l2)
-        # structural zero taps of fused MixConv groups stay exactly zero in the gradient
-        assert np.all(g[lay.grad_mask() == 0] == 0)
-        om.train_step(x, y, w, lr)
-        p_ref, s_ref = lay.pack(om.get_weights())
-        well = np.abs(gref) > (1e-4 if near_zero == 0 else 0.2) * scale
-        # every step starts from the oracle's weights, moving statistics AND Adam moments (installed below), so a step in
-        # which a one-unit decision went the other way does not loosen the steps after it: the update is always held to
-        # 5 % of an Adam step (a flagged step itself: only where the gradient is well away from the flipped unit's share)
-        assert np.abs(eng.get_params() - p_ref)[well].max() <= 0.05 * lr, (st, near_zero)
-        assert np.abs(eng.get_bn_state() - s_ref).max() <= 1e-5 * max(1.0, np.abs(s_ref).max())
+        got = graph_mixednet_step_reads(eng, B)
+        p_ref, s_ref = compare_graph_mixednet_step(got, B, lay, om, x, y, w, lr, st, l2s, near_zero, loss_slack)
         eng.set_params(p_ref)
         eng.set_bn_state(s_ref)
         tr = [v.name for v in om.vars if v.trainable]

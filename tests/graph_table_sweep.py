@@ -84,8 +84,8 @@ UNREACHABLE = {
     "gconv_bwd2_kernel<24, 24>": "as gconv_fwd2_kernel<24>",
     "gconv_fwd2_kernel<32>": "as width 24: the concatenation would hold 96 channels",
     "gconv_bwd2_kernel<32, 32>": "as gconv_fwd2_kernel<32>",
-    "gconv_bwd_kernel<10, 10, GSh3>": "shape 3 (a 10-channel slice of the fused, row-stored heads) belongs to a block's two second-level convolutions, which always form a twin; they run singly only under sync-BN data parallelism, or under \"profile_split\", which also splits the backward launch",
-    "gconv_bwd_kernel<16, 16, GSh7>": "as gconv_bwd_kernel<10, 10, GSh3>, for the 16-channel block",
+    "gconv_bwd_kernel<10, 10, GSh3>": "shape 3 (a 10-channel slice of the fused, row-stored heads) belongs to a block's two second-level convolutions, which always form a twin; they run singly only under sync-BN data parallelism, or under \"profile_split\", which also splits the backward launch; it runs in the INC cases of tests/exchange_checks.py (sync-BN ranks replayed on one device), which no plan of this sweep can express",
+    "gconv_bwd_kernel<16, 16, GSh7>": "as gconv_bwd_kernel<10, 10, GSh3>, for the 16-channel block (the same cases of tests/exchange_checks.py)",
     ("dw-taps", 1): "a MixedNet block of kernel size 1 has no depthwise op (mixednet.py); a 1-tap group of a MixConv is covered as (\"dw-mix1\",)",
     ("dw-bias", False): "every depthwise op of a MixedNet has a bias (layout.GraphMixedNetLayout: norm \"bias\")",
 }
@@ -590,21 +590,28 @@ def case_layout(case):
     return InceptionLayout(case["flags"], case["T"], fuse_heads=case["fuse_heads"])
 
 
-def case_ctx(case, tabs=None):
+def case_ctx(case, tabs=None, sync_bn=False):
+    """`sync_bn`: the case as a rank of a sync-BN data-parallel step (GWalk of graph_engine.hip with an exchange hook that
+    reduces the statistics): no statistics hand-over - every BatchNorm takes its finalize launches, behind the exchange - and
+    "pairing off" - twin ops launch singly, forward and backward."""
     lay = case_layout(case)
     model = build_graph(lay.ops, case["T"], getattr(lay, "head_attention", False), getattr(lay, "head_pool", 0), tabs)
     lazy = case["kind"] == "gather"
-    return make_ctx(model, case["options"], tabs, lazy=lazy, B=case["B"], grid=case["grid"])
+    options = case["options"]
+    if sync_bn:
+        options = dict(options, bn_inline=0)
+        model = dict(model, G=[dict(o, twin_next=False) for o in model["G"]])
+    return make_ctx(model, options, tabs, lazy=lazy, B=case["B"], grid=case["grid"])
 
 
-def case_route(case, tabs=None):
+def case_route(case, tabs=None, sync_bn=False):
     """The graph engine's launch names of the case's train step, as option "profile" records them."""
-    return [name for name, _, _, _ in train_step_launches(case_ctx(case, tabs))]
+    return [name for name, _, _, _ in train_step_launches(case_ctx(case, tabs, sync_bn))]
 
 
-def case_kernels(case, tabs=None):
+def case_kernels(case, tabs=None, sync_bn=False):
     """The instantiations the case's train step launches, in launch order."""
-    return [k for _, ks, _, _ in train_step_launches(case_ctx(case, tabs)) for k in ks]
+    return [k for _, ks, _, _ in train_step_launches(case_ctx(case, tabs, sync_bn)) for k in ks]
 
 
 ROUTE_PREFIXES = ("conv_fwd", "conv_bwd", "conv_wgrad", "conv_dgrad", "dw_fwd", "dw_wgrad", "dw_dgrad", "bn_fwd_finalize", "bn_bwd_finalize",
